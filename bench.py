@@ -10,9 +10,12 @@ int8 weights) are resident in HBM when the timed region starts.  Multi-GPU: prom
 over ranks (weak scaling, one prompt in flight per GPU as the reference's batch_size=1), packed
 weights are broadcast once from rank 0, no collective inside a step.
 
-Besides the headline (`value`: BASELINE.json's metric, W8A8) the line carries, at N = 1, `extras`: short legs of the
-other single-GPU configurations of BASELINE.json on the same build - W4A8 timestep-aware, W4A8 mixed precision
-(20-step schedule) and PixArt-Sigma 1024^2 W4A8 - each with its own steps/s and GEMM fraction (`--no-extras` skips them).
+A plain run sets up, warms up, times K steps, writes the last timed step's outputs (`--dump-outputs DIR`) and prints the
+headline (`value`: BASELINE.json's metric, W8A8; `ms_per_step`).  `--full` adds everything else the line can carry:
+telemetry, the live GEMM roofline, the host's graph launch cost, the hoisted-prompt re-run, the CPU baseline and, at
+N = 1, `extras`: short legs of the other single-GPU configurations of BASELINE.json on the same build - W4A8
+timestep-aware, W4A8 mixed precision (20-step schedule) and PixArt-Sigma 1024^2 W4A8 - each with its own steps/s and GEMM
+fraction (`--no-extras` skips them).
 """
 import argparse
 import json
@@ -305,6 +308,13 @@ def parse():
                     help="w8a8 = BASELINE metric (w8a8_dynamic.yaml); w4a8 = ViDiT-Q W4A8 timestep-aware channel "
                          "balancing, synthetic calibration; w4a8_mp = the same with the per-layer mixed-precision "
                          "config on the 20-step schedule")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: telemetry, the live GEMM roofline, the idle-queue graph launch and "
+                         "node census, the hoisted-prompt re-run, the extras legs and the CPU baseline (the --no-* switches "
+                         "below drop single parts of it); without it a run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (latent, cond / uncond model "
+                         "outputs; float32) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline-events", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the W4A8 / W4A8-MP / PixArt-Sigma legs")
@@ -509,6 +519,7 @@ def _measure_plan(a, dev, rank, world, qnn, cfg, plan, steps, warmup, dist, even
     embeds, lens = synth.synthetic_prompts(n_prompts, dev)
     idx = list(range(sch.num_timesteps))[::-1]
     gs = None
+    last = {}                                           # the model outputs of the latest step (references, no copy)
 
     def inputs(pi):
         x = synth.synthetic_latent(pi, device=dev).float()
@@ -527,6 +538,7 @@ def _measure_plan(a, dev, rank, world, qnn, cfg, plan, steps, warmup, dist, even
             cond = qnn(x, t, y_c, mask=mask, timestep_id=t_id)
             unc = qnn(x, t, y_u, mask=mask, timestep_id=t_id)
         out = sch.ddim_step(x, cond, unc, i, sch.cfg_scale, 0.0, out=buf)
+        last["cond"], last["uncond"] = cond, unc
         return out, x
 
     el = 0.0
@@ -565,7 +577,11 @@ def _measure_plan(a, dev, rank, world, qnn, cfg, plan, steps, warmup, dist, even
             torch.cuda.synchronize()
         el += time.perf_counter() - t0
         host_enqueue += t_enq
-        if gs is not None and n_done == len(mine) - 1:
+        if a.dump_outputs and n_done == len(mine) - 1:
+            # copied now: the probes below step the same buffers further
+            res["outputs"] = {name: t.detach().float().cpu() for name, t in
+                              (("latent", x), ("model_out_cond", last["cond"]), ("model_out_uncond", last["uncond"]))}
+        if a.full and gs is not None and n_done == len(mine) - 1:
             # What a replay costs the HOST, measured with an EMPTY queue (a synchronize before every launch).  The figure above
             # (host_enqueue_ms_per_step) is the time until the loop's last replay call returned: with more than ~7 steps in
             # flight hipGraphLaunch blocks on the full hardware queue, so over 20 steps it reads ~GPU time per step
@@ -750,6 +766,21 @@ def check_line(line, a):
         assert wb and wb["bytes"] > 0, "N > 1 run without a weight broadcast: %r" % (wb,)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: the last timed step's arrays as <out_dir>/<name>.npy (float32).  The inputs are seeded (model,
+    latents, prompts), so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    arrays = {name: t.numpy() for name, t in outputs.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the dump limit of %d" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -785,10 +816,11 @@ def main():
     if a.gemm_variant is not None:
         ops.DEFAULT_GEMM_VARIANT = a.gemm_variant
     global TEL
-    if rank == 0 and not a.no_telemetry:
+    if rank == 0 and a.full and not a.no_telemetry:
         TEL = Telemetry(local)
 
-    head = stdit_legs(a, dev, rank, world, [a.plan], a.steps, a.warmup, dist=dist, events=not a.no_roofline_events)[0]
+    head = stdit_legs(a, dev, rank, world, [a.plan], a.steps, a.warmup, dist=dist, events=a.full and not a.no_roofline_events,
+                      hoisted=a.full)[0]
     el = head["el"]
     el_t = torch.tensor([el], device=dev, dtype=torch.float64)
     per_rank = [el]
@@ -809,7 +841,7 @@ def main():
         bc_rank = [float(t.item()) for t in every]
 
     extras = None
-    if rank == 0 and world == 1 and a.plan == "w8a8" and not a.no_extras and a.depth == 28 and not a.prompts:
+    if rank == 0 and world == 1 and a.plan == "w8a8" and a.full and not a.no_extras and a.depth == 28 and not a.prompts:
         extras = {}
         # a leg that fails reports its error; the headline line above is already measured and is printed regardless
         try:
@@ -877,13 +909,15 @@ def main():
                 "extras": extras}
         if rehearsal:
             line["rehearsal"] = "ranks share devices, gloo backend: control-flow dry run, NOT a measurement"
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # noqa: BLE001  (a reported side measurement: its failure must not lose the GPU line)
                 line["cpu_baseline"] = {"value": None, "unit": "denoising steps/s", "cores": 0, "kind": "port",
                                         "sample": "failed: %s: %s" % (type(e).__name__, e)}
         check_line(line, a)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, head["outputs"])
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -53,3 +53,23 @@ def test_line_check_rejects_a_one_rank_line_for_a_multi_gpu_request():
     with pytest.raises(AssertionError):
         bench.check_line({"n_gpus": 2, "per_rank_steps_per_s": [1.0, 1.0], "weights_broadcast": None}, A)
     bench.check_line({"n_gpus": 2, "per_rank_steps_per_s": [1.0, 1.0], "weights_broadcast": {"bytes": 5}}, A)
+
+
+def test_plain_run_is_the_default_and_dump_outputs_writes_float32_arrays(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import importlib
+    import numpy as np
+    import pytest
+    import torch
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"])
+    a = bench.parse()
+    assert a.steps == 4 and not a.full and a.dump_outputs is None
+    x = torch.randn(1, 4, 2, 3, 3)
+    bench.dump_outputs(str(tmp_path / "d"), {"latent": x, "model_out_cond": x * 2})
+    got = np.load(tmp_path / "d" / "latent.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    assert np.array_equal(np.load(tmp_path / "d" / "model_out_cond.npy"), (x * 2).numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", x.numel() * 4 - 1)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"latent": x})

@@ -4,7 +4,7 @@
 set -u
 OUT=$1; R=$2; shift 2
 mkdir -p $OUT
-FLAGS="--steps 20 --warmup 3 --no-extras --no-cpu-baseline ${AB_FLAGS:-}"
+FLAGS="--full --steps 20 --warmup 3 --no-extras --no-cpu-baseline ${AB_FLAGS:-}"
 for r in $(seq 1 $R); do
   for spec in "$@"; do
     name=${spec%%:*}; envs=${spec#*:}

@@ -13,7 +13,7 @@ shift || true
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 EXTRA="$@"
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-extras $EXTRA > $O/stats.log 2>&1)
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-extras $EXTRA > $O/stats.log 2>&1)
 pass() {  # name, counters...
   n=$1; shift
   (cd /tmp && timeout 400 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$n -o p -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-graph --no-roofline-events --no-telemetry $EXTRA > $O/$n.log 2>&1)
@@ -31,7 +31,7 @@ done
 python tools/summarize_round.py $TAG > $O/summary.log 2>&1
 # the traffic figure just measured becomes the one bench.py reports (same sources: the hash matches)
 cp $R/gpurun_out/${TAG}_summary/${TAG}_gemm_traffic.json $R/profiles/ 2>/dev/null
-python bench.py $EXTRA > $O/bench_line.json 2> $O/bench.err
+python bench.py --full $EXTRA > $O/bench_line.json 2> $O/bench.err
 cp $O/bench_line.json $R/gpurun_out/${TAG}_summary/${TAG}_bench_line.json
 # the raw per-dispatch counter tables are tens of MB: only the summaries (and the kernel stats) travel back
 for d in FETCH_SIZE WRITE_SIZE SQ1 SQ2 GRBM cal_FETCH_SIZE cal_WRITE_SIZE; do rm -rf $O/$d; done

@@ -8,7 +8,7 @@ TAG=$1; shift
 O=$R/gpurun_out/sk_$TAG
 mkdir -p $O
 for n in 2 6; do
-  (cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s$n -o b -- python $R/bench.py --steps $n --warmup 2 --no-cpu-baseline --no-extras --no-roofline-events "$@" > $O/s$n.log 2>&1)
+  (cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s$n -o b -- python $R/bench.py --full --steps $n --warmup 2 --no-cpu-baseline --no-extras --no-roofline-events "$@" > $O/s$n.log 2>&1)
 done
 python tools/stats_diff.py $(find $O/s2 -name "b_kernel_stats.csv") $(find $O/s6 -name "b_kernel_stats.csv") 4 > $O/${TAG}_step_kernels.txt
 find $O -type f ! -name "*step_kernels.txt" -delete
