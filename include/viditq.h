@@ -264,6 +264,19 @@ int vq_attn_temporal_rowquant(const void* q, const void* k, const void* v, const
                               int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o, int B, int T,
                               int S, int H, int D, long ld_in, int Kp, float scale, void* stream);
 
+/* Temporal attention for up to 64 frames (OpenSORA 64x512x512; STDiTBlock's temporal branch, stdit.py:112-118), with
+ * the per-token 8-bit dynamic quantizer of attn_temp.proj (QuantTemporalAttnLinear.forward, stdit_quant_layer.py:161-166)
+ * optionally fused.  Rows [B][T][S] as in vq_attn_temporal; 1 <= T <= 64, H <= 16 (one workgroup per spatial position
+ * and all heads), D in {16, 32, 64, 72}, H*D % 16 == 0, q / k / v 16-byte aligned, ld_in % 8 == 0.
+ * o: nullable fp16 output [B*T*S] rows of stride ld_out (% 8 == 0), rounded as vq_attn_temporal stores it.
+ * xq: nullable; when set, sx, zx and R are required, B == 1 (per-token grids are shared over the batch) and
+ * Kp % 128 == 0, and xq / sx / zx / R / status are what vq_rowquant(n_bits = 8, s, s_rcp) produces from the fp16
+ * output (see vq_attn_temporal_rowquant).  At least one of o and xq.  s / s_rcp: both null or both set, 16-byte
+ * aligned. */
+int vq_attn_temporal_long(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
+                          int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o, int B, int T,
+                          int S, int H, int D, long ld_in, long ld_out, int Kp, float scale, void* stream);
+
 /* ---- small fused elementwise helpers ---------------------------------------
  * mod[j, b, c] = table[j, c] + t0[b, j*C + c]  (stdit.py:100-102), fp32 out, chunk-major. */
 int vq_adaln_table(const void* table, const void* t0, float* mod, int B, int J, int C, void* stream);

@@ -20,6 +20,7 @@
 // coalesced loads, one wave per head, 32x32 MFMA over the 2x16 token rows with a
 // block-diagonal mask.
 #include <stdlib.h>
+#include <mutex>
 #include <type_traits>
 #include "vq_common.h"
 
@@ -939,6 +940,262 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(TempQArgs a)
             a.sx[grow] = delta;
             a.zx[grow] = izx;
             a.R[grow] = rs - 128 * C - C * izx;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// attn_temporal_long_kernel: temporal attention for 17 <= T <= 64 frames (OpenSORA 64x512x512: stdit.py:112-118), with the
+// optional per-token 8-bit quantizer of attn_temp.proj (stdit_quant_layer.py:161-166) fused as in the kernels above.
+// One persistent workgroup walks spatial positions (b, s); one wave per head (H <= 16), 64 * H threads.
+//   * LDS: at T = 64 one position's q | k | v is 442 KB, so nothing is staged for the whole workgroup.  Each wave stages its
+//     OWN head's V rows [64 t][D] (row stride 2 D bytes, rows t >= T zeroed) for the ds_read_b64_tr_b16 transpose read of
+//     the V^T operand; no other wave reads them, so no barrier guards the tile.  H * 64 * 2 D bytes (147 456 B at H = 16,
+//     D = 72) + 64 B of zeroed tail (the dims 72..79 of the last transpose read at D = 72, which land in O^T rows >= D that
+//     are discarded) + 3 KB of cross-wave row statistics = 150 592 B:
+//     one workgroup per CU.
+//   * Q and K operands of S^T = K Q^T come straight from global memory in 16x16x32 operand form (16-byte loads of the
+//     head's 2 D-byte row slice), both per 16-query tile: K of the 4 key tiles is 48 VGPRs at D = 72 and is read again
+//     for every query tile (from L2 after the first) - kept for the whole position it made the kernel spill.
+//   * queries in tiles of 16 (registers: a full 64 x 64 score tile plus O^T for 64 queries does not fit 128 VGPRs):
+//     S^T [64 keys][16 queries] in 4 accumulators, keys >= T masked, softmax lane-local over 16 keys + the permlane row
+//     reductions, O^T = V^T P^T over 4 key steps, rounded to fp16 as the stored tensor.  Query tiles wholly past T are
+//     skipped, so are key tiles.
+//   * with codes (B == 1): the tile's row min / max and code sums are combined over the waves through LDS (two barriers
+//     per tile), grid and codes are the vq_row_grid / rq_round_group arithmetic of vq_rowquant (bit-identical to it on
+//     the kernel's own fp16 output), and the codes leave straight from registers: 4 bytes per lane, 16 contiguous bytes
+//     per row and 16-lane group.
+// ---------------------------------------------------------------------------
+struct TempLArgs {
+    const half_t* q;
+    const half_t* k;
+    const half_t* v;
+    int8_t* xq;                                    // nullable: no quantizer (plain fp16 output)
+    float* sx;
+    int32_t* zx;
+    int32_t* R;
+    int32_t* status;
+    half_t* o;                                     // nullable when xq is set
+    const float* s;                                // nullable [H*D] smoothing vector of the consuming Linear
+    const float* s_rcp;
+    long ld_in, ld_out;
+    int B, T, S, H, Kp;
+    float c;
+};
+
+template <int D>
+__global__ __launch_bounds__(1024) void attn_temporal_long_kernel(TempLArgs a) {
+    constexpr int KS = (D + 15) / 16, KS2 = (D + 31) / 32, CHD = D / 8;
+    constexpr int RSV = D * 2, VT = 64 * RSV;      // V tile of one head: row stride, bytes
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // = head
+    const int tq = lane & 15, g4 = lane >> 4;
+    const int H = a.H, C = H * D, T = a.T, nthr = 64 * H;
+    uint8_t* vs = smem + wave * VT;
+    float* ex_min = reinterpret_cast<float*>(smem + H * VT + 64);
+    float* ex_max = ex_min + 256;
+    int* ex_sum = reinterpret_cast<int*>(ex_max + 256);
+    const int npos = a.S * a.B;
+    const int nt = (T + 15) >> 4;                  // 16-row tiles holding rows < T (keys and queries)
+    const unsigned tstride = (unsigned)a.S * (unsigned)a.ld_in * 2u;          // bytes between the rows t, t + 1 of a position
+    const bool quant = a.xq != nullptr;
+    const int npad = a.Kp / 16 - C / 16;           // 16-byte pad chunks [C, Kp) of a code row
+    const unsigned vtro = (unsigned)((4 * g4 + (tq >> 2)) * RSV + 4 * (tq & 3) * 2);   // transpose-read lane offset
+    const unsigned kqo = (unsigned)(wave * D + 8 * g4) * 2u;                           // + 64 bytes per k-step
+    // the LDS tail behind the last head's V tile: the dt = 4 transpose read at D = 72 covers dims 72..79, which for the
+    // last key row of the last head lie in it.  Those values only reach O^T rows >= D (never stored, never counted);
+    // zeroed once so that they are defined.
+    if (tid < 4) *reinterpret_cast<int4v*>(smem + H * VT + 16 * tid) = int4v{0, 0, 0, 0};
+    __syncthreads();
+
+    for (int pos = blockIdx.x; pos < npos; pos += gridDim.x) {
+        const int s = pos % a.S, b = pos / a.S;
+        const size_t row0 = (size_t)b * T * a.S + s;                          // row (b, t = 0, s)
+        const size_t bo = row0 * (size_t)a.ld_in * 2;
+        const uint8_t* qb = reinterpret_cast<const uint8_t*>(a.q) + bo;
+        const uint8_t* kb = reinterpret_cast<const uint8_t*>(a.k) + bo;
+        const uint8_t* vb = reinterpret_cast<const uint8_t*>(a.v) + bo + wave * D * 2;
+
+        // ---- this head's V rows (chunk c = row c / CHD, 16-byte piece c % CHD)
+        // (lx: an opaque per-position copy of the lane id, so that the chunk offsets are recomputed per position instead
+        //  of being hoisted out of the loop - nine 64-bit offsets kept live made the D = 72 kernel spill)
+        int lx = lane;
+        asm volatile("" : "+v"(lx));
+        int4v vals[CHD];
+#pragma unroll
+        for (int i = 0; i < CHD; ++i) {
+            const int c = lx + 64 * i, t = c / CHD, ch = c - t * CHD;
+            vals[i] = int4v{0, 0, 0, 0};
+            if (t < T) vals[i] = *reinterpret_cast<const int4v*>(vb + (unsigned)t * tstride + ch * 16);
+        }
+        // (the wave's transpose reads of the previous position were consumed by MFMAs before this point; LDS operations of
+        //  one wave complete in order)
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < CHD; ++i) *reinterpret_cast<int4v*>(vs + (lane + 64 * i) * 16) = vals[i];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+
+        for (int qt = 0; qt < nt; ++qt) {          // workgroup-uniform
+            const int tr = 16 * qt + tq;           // this lane's query row
+            const bool qrow = tr < T;
+            half8 qf[KS2];
+#pragma unroll
+            for (int ks = 0; ks < KS2; ++ks) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) qf[ks][e] = (half_t)0.f;
+                if (qrow && ks * 32 + 8 * g4 < D)
+                    qf[ks] = *reinterpret_cast<const half8*>(qb + (unsigned)tr * tstride + kqo + ks * 64);
+            }
+            // ---- S^T[key 16 kt + 4 g4 + r][query tq] = K Q^T; the K operands are read per query tile (from L2 after the
+            //      first): held for the whole position, 48 VGPRs at D = 72, they made the kernel spill
+            float4v sc[4];
+            float mloc = -INFINITY;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) {
+                sc[kt] = float4v{0.f, 0.f, 0.f, 0.f};
+                if (kt < nt) {
+                    const int t = 16 * kt + tq;
+                    half8 kf[KS2];
+#pragma unroll
+                    for (int ks = 0; ks < KS2; ++ks) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) kf[ks][e] = (half_t)0.f;
+                        if (t < T && ks * 32 + 8 * g4 < D)
+                            kf[ks] = *reinterpret_cast<const half8*>(kb + (unsigned)t * tstride + kqo + ks * 64);
+                    }
+#pragma unroll
+                    for (int ks = 0; ks < KS2; ++ks)
+                        sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[ks], qf[ks], sc[kt], 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (16 * kt + 4 * g4 + r >= T) sc[kt][r] = -INFINITY;
+                    mloc = fmaxf(mloc, sc[kt][r]);
+                }
+            }
+            mloc = tq_xor32(tq_xor16(mloc, true), true);
+            const float m_use = (mloc == -INFINITY) ? 0.f : mloc;
+            float psum = 0.f;
+            half4 pf[4];
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float p = __builtin_amdgcn_exp2f((sc[kt][r] - m_use) * a.c);
+                    psum += p;
+                    pf[kt][r] = (half_t)p;
+                }
+            psum = tq_sum4rows(psum);
+            const float inv_p = psum > 0.f ? __builtin_amdgcn_rcpf(psum) : 0.f;
+
+            // ---- O^T[dim 16 dt + 4 g4 + r][query tq] = V^T P^T over the key tiles, rounded to fp16 as the stored tensor
+            half4 ov[KS];                          // (fp16: the quantizer's x / s is recomputed where it is needed)
+#pragma unroll
+            for (int dt = 0; dt < KS; ++dt) {
+                float4v o4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt)
+                    if (kt < nt) {
+                        const h4t_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                            (__attribute__((address_space(3))) h4t_t*)(vs + kt * 16 * RSV + vtro + dt * 32));
+                        const half4 vf = {(half_t)vt[0], (half_t)vt[1], (half_t)vt[2], (half_t)vt[3]};
+                        o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[kt], o4, 0, 0, 0);
+                    }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ov[dt][r] = (half_t)(o4[r] * inv_p);
+            }
+            const size_t grow = row0 + (size_t)tr * a.S;
+            if (a.o && qrow) {
+                half_t* orow = a.o + grow * a.ld_out + wave * D;
+#pragma unroll
+                for (int dt = 0; dt < KS; ++dt) {
+                    const int d0 = dt * 16 + 4 * g4;
+                    if (d0 < D) *reinterpret_cast<half4*>(orow + d0) = ov[dt];
+                }
+            }
+            if (!quant) continue;                  // kernel-uniform
+
+            // ---- quantizer of the consuming Linear on the fp16 output (x / s first when it has a smoothing vector)
+            auto qin = [&](int dt, float (&x4)[4]) {
+                const int d0 = dt * 16 + 4 * g4;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x4[r] = (float)ov[dt][r];
+                if (a.s) {                         // kernel-uniform
+                    const float4v s4 = *reinterpret_cast<const float4v*>(a.s + wave * D + d0);
+                    const float4v r4 = *reinterpret_cast<const float4v*>(a.s_rcp + wave * D + d0);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) x4[r] = rq_div_rcp(x4[r], s4[r], r4[r]);
+                }
+            };
+            float vmin = INFINITY, vmax = -INFINITY;
+#pragma unroll
+            for (int dt = 0; dt < KS; ++dt)
+                if (dt * 16 + 4 * g4 < D) {
+                    float x4[4];
+                    qin(dt, x4);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        vmin = fminf(vmin, x4[r]);
+                        vmax = fmaxf(vmax, x4[r]);
+                    }
+                }
+            vmin = tq_xor32(tq_xor16(vmin, false), false);
+            vmax = tq_xor32(tq_xor16(vmax, true), true);
+            if (lane < 16) {
+                ex_min[wave * 16 + tq] = vmin;
+                ex_max[wave * 16 + tq] = vmax;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (raw barrier: __syncthreads() would also wait for the loads in flight)
+            __builtin_amdgcn_s_barrier();                        // the tile's per-head row statistics are visible
+            vmin = INFINITY;
+            vmax = -INFINITY;
+            for (int w = 0; w < H; ++w) {
+                vmin = fminf(vmin, ex_min[w * 16 + tq]);
+                vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
+            }
+            float delta, zp, inv;
+            bool small;
+            vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
+            if (small && tid < 16 && qrow && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
+            const int izx = (int)zp - 128;
+            uint8_t* xrow = reinterpret_cast<uint8_t*>(a.xq) + grow * (size_t)a.Kp + wave * D;
+            uint32_t csum = 0;
+#pragma unroll
+            for (int dt = 0; dt < KS; ++dt) {
+                const int d0 = dt * 16 + 4 * g4;
+                if (d0 < D) {
+                    uint32_t pk = 0;
+                    float x4[4], c4[4];
+                    qin(dt, x4);
+                    rq_round_group<4>(x4, inv, delta, zp, c4);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
+                    csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
+                    if (qrow) *reinterpret_cast<uint32_t*>(xrow + d0) = pk ^ 0x80808080u;
+                }
+            }
+            const int cs = tq_isum4rows((int)csum);
+            if (lane < 16) ex_sum[wave * 16 + tq] = cs;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();        // code sums visible; every wave has read ex_min / ex_max of this tile
+            if (tid < 16 && qrow) {
+                int rs = 0;
+                for (int w = 0; w < H; ++w) rs += ex_sum[w * 16 + tq];
+                a.sx[grow] = delta;
+                a.zx[grow] = izx;
+                a.R[grow] = rs - 128 * C - C * izx;
+            }
+            for (int c = tid; c < 16 * npad; c += nthr) {       // pad columns [C, Kp) zeroed like the row quantizers do
+                const int t = c / npad, ch = c - t * npad;
+                if (16 * qt + t < T) {
+                    int8_t* prow = a.xq + (row0 + (size_t)(16 * qt + t) * a.S) * (size_t)a.Kp + C;
+                    *reinterpret_cast<int4v*>(prow + ch * 16) = int4v{0, 0, 0, 0};
+                }
+            }
+            // (the next tile writes ex_min / ex_max only after this barrier and ex_sum only after its first one, which
+            //  the lanes reading ex_sum above reach after reading it)
         }
     }
 }
@@ -2583,6 +2840,70 @@ extern "C" int vq_attn_temporal_rowquant(const void* q, const void* k, const voi
         case 64: return launch_temporal_quant<64>(a, st);
         case 32: return launch_temporal_quant<32>(a, st);
         case 16: return launch_temporal_quant<16>(a, st);
+        default: return VQ_ESHAPE;
+    }
+}
+
+// Per-device launch state of attn_temporal_long_kernel: the dynamic-LDS attribute is set on (and the CU count read from)
+// the device current at the call, once per device.
+#define VQ_TL_MAX_DEV 64
+template <int D>
+static int launch_temporal_long(const TempLArgs& a, hipStream_t st) {
+    constexpr int LDS_MAX = 16 * 64 * D * 2 + 64 + 3 * 1024;
+    const int LDS = a.H * 64 * D * 2 + 64 + 3 * 1024;
+    auto k = attn_temporal_long_kernel<D>;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && (dev < 0 || dev >= VQ_TL_MAX_DEV)) e = hipErrorInvalidDevice;
+    if (e != hipSuccess) {
+        g_vq_last_hip_error = (int)e;
+        return VQ_ELAUNCH;
+    }
+    static std::once_flag once[VQ_TL_MAX_DEV];
+    static hipError_t attr[VQ_TL_MAX_DEV];
+    static int ncu[VQ_TL_MAX_DEV];
+    std::call_once(once[dev], [&] {
+        attr[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+        int v = 0;
+        ncu[dev] = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256;
+    });
+    if (attr[dev] != hipSuccess) {
+        g_vq_last_hip_error = (int)attr[dev];
+        return VQ_ELAUNCH;
+    }
+    // persistent: 16 heads x 150 KB of LDS own a CU; small head counts fit two workgroups
+    const int npos = a.S * a.B;
+    const int per_cu = (a.H <= 8 && 2 * LDS <= 160 * 1024) ? 2 : 1;
+    const int grid = npos < ncu[dev] * per_cu ? npos : ncu[dev] * per_cu;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * a.H), LDS, st, a);
+    return vq_check_launch();
+}
+
+extern "C" int vq_attn_temporal_long(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
+                                     int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o, int B,
+                                     int T, int S, int H, int D, long ld_in, long ld_out, int Kp, float scale,
+                                     void* stream) {
+    if (!q || !k || !v || (!o && !xq)) return VQ_EINVAL;
+    if (xq && (!sx || !zx || !R)) return VQ_EINVAL;
+    if ((s != nullptr) != (s_rcp != nullptr)) return VQ_EINVAL;     // the division exists in reciprocal form only
+    if (B <= 0 || T <= 0 || S <= 0 || H <= 0) return VQ_EINVAL;
+    const long C = (long)H * D;
+    if (T > 64 || H > 16 || B > 65535 || C % 16 != 0 || ld_in % 8 != 0) return VQ_ESHAPE;
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 != 0) return VQ_ESHAPE;
+    if (o && (ld_out % 8 != 0 || ld_out < C || (uintptr_t)o % 16 != 0)) return VQ_ESHAPE;
+    if (((uintptr_t)s | (uintptr_t)s_rcp) % 16 != 0) return VQ_ESHAPE;    // read as float4 per 4 channels
+    // per-token grids: one row statistic per (t, s), shared over the batch by the caller's contract
+    if (xq && (B != 1 || Kp % 128 != 0 || Kp < C || (uintptr_t)xq % 16 != 0)) return VQ_ESHAPE;
+    // 32-bit byte offsets of a position's rows
+    if ((long)T * S * ld_in * 2 >= (1l << 31) || (xq && (long)T * S * Kp >= (1l << 31))) return VQ_ESHAPE;
+    TempLArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, xq, sx, zx, R, status, (half_t*)o, s, s_rcp, ld_in,
+                ld_out, B, T, S, H, Kp, scale * ATT_LOG2E};
+    hipStream_t st = (hipStream_t)stream;
+    switch (D) {
+        case 72: return launch_temporal_long<72>(a, st);
+        case 64: return launch_temporal_long<64>(a, st);
+        case 32: return launch_temporal_long<32>(a, st);
+        case 16: return launch_temporal_long<16>(a, st);
         default: return VQ_ESHAPE;
     }
 }

@@ -553,6 +553,49 @@ def attn_temporal_rowquant(q, k, v, B, T, S, H, D, ld_in, scale: Optional[float]
     return QAct(xq, sx, zx, R, Cc, 8)
 
 
+def attn_temporal_long(q, k, v, B, T, S, H, D, ld_in, o: Optional[torch.Tensor] = None, quant: bool = False,
+                       scale: Optional[float] = None, status: Optional[torch.Tensor] = None,
+                       s: Optional[torch.Tensor] = None):
+    """Temporal attention for T <= 64 frames (one kernel; rows [B][T][S] as in :func:`attn_temporal`).
+    ``quant=False``: writes and returns ``o`` [B*T*S, H*D] fp16 (row stride ``o.stride(0)``).
+    ``quant=True`` (B == 1): returns the ``QAct`` of the consuming Linear's per-token 8-bit quantizer (behind its
+    smoothing vector ``s``), bit-identical to ``rowquant`` of the fp16 output, and also writes ``o`` when given; None when
+    ``s`` has no exact reciprocal form (the caller then runs attention and the quantizer separately)."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise VQError("%s must be a GPU fp16 tensor" % n)
+    Cc = H * D
+    rows = B * T * S
+    if o is not None:
+        _req(o, torch.float16, "o")
+        if o.shape != (rows, Cc):
+            raise VQError("attn_temporal_long: o must be [B*T*S, H*D]")
+    elif not quant:
+        raise VQError("attn_temporal_long: o is required without quant")
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    ld_out = o.stride(0) if o is not None else 0
+    if not quant:
+        check(_L().vq_attn_temporal_long(_p(q), _p(k), _p(v), None, None, None, None, None, None, None, _p(o), B, T, S,
+                                         H, D, ld_in, ld_out, 0, scale, _stream()), "vq_attn_temporal_long")
+        return o
+    if B != 1:
+        raise VQError("attn_temporal_long: per-token scales are shared over the batch; B must be 1")
+    s_rcp = None
+    if s is not None:
+        s_rcp = smooth_rcp(s)
+        if s_rcp is None:
+            return None
+    Kp = pad128(Cc)
+    dev = q.device
+    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
+    sx = torch.empty(rows, dtype=torch.float32, device=dev)
+    zx = torch.empty(rows, dtype=torch.int32, device=dev)
+    R = torch.empty(rows, dtype=torch.int32, device=dev)
+    check(_L().vq_attn_temporal_long(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(xq), _p(sx), _p(zx), _p(R), _p(status),
+                                     _p(o), B, T, S, H, D, ld_in, ld_out, Kp, scale, _stream()), "vq_attn_temporal_long")
+    return QAct(xq, sx, zx, R, Cc, 8)
+
+
 # --------------------------------------------------------------------------- misc
 def adaln_table(table: torch.Tensor, t0: torch.Tensor) -> torch.Tensor:
     """mod[J, B, C] fp32 = table[J, C] + t0[B, J*C]  (fp16 inputs); mod[j] is a contiguous [B, C]."""

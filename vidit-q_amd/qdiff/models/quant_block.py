@@ -71,6 +71,9 @@ class QuantAttention(nn.Module):
         if T <= 16:
             ops.attn_temporal(qkv, qkv[:, C:], qkv[:, 2 * C:], out, B, T, S, self.num_heads, self.head_dim,
                               ld, out.stride(0), scale=self.scale)
+        elif self._long_ok(T):
+            ops.attn_temporal_long(qkv, qkv[:, C:], qkv[:, 2 * C:], B, T, S, self.num_heads, self.head_dim, ld, o=out,
+                                   scale=self.scale)
         else:  # general T: the flash kernel over strided sequences, one launch per sample
             for b in range(B):
                 base = qkv[b * T * S:]
@@ -79,13 +82,21 @@ class QuantAttention(nn.Module):
                              ld, S * ld, ld, S * ld, out.stride(0), S * out.stride(0), scale=self.scale)
         return out
 
+    def _long_ok(self, T: int) -> bool:
+        """16 < T <= 64 runs the long-video temporal kernel (one workgroup per spatial position and all heads)."""
+        C = self.num_heads * self.head_dim
+        return 16 < T <= 64 and self.num_heads <= 16 and C % 16 == 0 and self.head_dim in (16, 32, 64, 72)
+
     def temporal_quantized(self, qkv: torch.Tensor, B: int, T: int, S: int, status=None, s=None):
         """:meth:`temporal` + the 8-bit dynamic per-token quantizer of the next Linear (behind its smoothing vector
         ``s`` when it has one), one kernel; None when that kernel does not apply (then call :meth:`temporal` and the
         layer's own quantizer)."""
         C = self.num_heads * self.head_dim
-        if B != 1 or T > 16 or self.num_heads > 16 or C % 16 != 0 or self.head_dim not in (16, 32, 64, 72):
+        if B != 1 or T > 64 or self.num_heads > 16 or C % 16 != 0 or self.head_dim not in (16, 32, 64, 72):
             return None
+        if T > 16:
+            return ops.attn_temporal_long(qkv, qkv[:, C:], qkv[:, 2 * C:], B, T, S, self.num_heads, self.head_dim,
+                                          qkv.stride(0), quant=True, scale=self.scale, status=status, s=s)
         return ops.attn_temporal_rowquant(qkv, qkv[:, C:], qkv[:, 2 * C:], B, T, S, self.num_heads, self.head_dim,
                                           qkv.stride(0), scale=self.scale, status=status, s=s)
 

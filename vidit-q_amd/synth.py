@@ -97,10 +97,12 @@ def redraw_zero_init(model: torch.nn.Module, seed: int = 1, std: float = 0.02):
 
 
 def build_stdit(device, depth=28, hidden_size=1152, num_heads=16, input_size=(16, 64, 64), model_max_length=120,
-                caption_channels=4096, seed=0) -> STDiT:
+                caption_channels=4096, seed=0, time_scale=1.0) -> STDiT:
+    """``time_scale``: the temporal position-embedding scale of the reference config (2/3 for 64x512x512)."""
     torch.manual_seed(seed)
     m = STDiT(input_size=input_size, depth=depth, hidden_size=hidden_size, num_heads=num_heads,
-              model_max_length=model_max_length, caption_channels=caption_channels, dtype=torch.float16)
+              model_max_length=model_max_length, caption_channels=caption_channels, dtype=torch.float16,
+              time_scale=time_scale)
     redraw_zero_init(m, seed + 1)
     return m.half().to(device).eval()
 
