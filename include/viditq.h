@@ -236,7 +236,8 @@ int vq_gemm_i8_grouped(int ngroups, const int8_t* const* xq, const float* const*
  * attention), kv_seq_stride is ignored and Lk is an upper bound on every sequence's
  * kv length if the caller knows one (0 = unknown): D = 72 with a bound <= 128 (the
  * <= 120 prompt tokens of STDiT) runs a kernel that keeps K and V^T of a head in
- * registers.  D in {16, 32, 64, 72}.
+ * registers.  D in {16, 32, 64, 72}.  q, k, v and o are 16-byte aligned (VQ_ESHAPE
+ * otherwise): the kernels move 16 bytes per access.
  */
 int vq_attn_fwd(const void* q, const void* k, const void* v, void* o,
                 int n_seq, int Lq, int Lk, int H, int D,
@@ -244,9 +245,31 @@ int vq_attn_fwd(const void* q, const void* k, const void* v, void* o,
                 long o_seq_stride, long o_tok_stride, const int32_t* kv_off,
                 float scale, void* stream);
 
+/* Kernels behind vq_attn_fwd (ids returned by vq_attn_fwd_route). */
+#define VQ_ATTN_K_FWD 0         /* attn_fwd_kernel: the general kernel (kv_off with an unknown bound, short queries)   */
+#define VQ_ATTN_K_FWD8_NW4 1    /* attn_fwd8_kernel, 4 waves: no kv_off, Lk > 128, 96 <= Lq < 192                      */
+#define VQ_ATTN_K_FWD8_NW8 2    /* attn_fwd8_kernel, 8 waves: Lq >= 192 with a K / V byte extent of 2^31 or more       */
+#define VQ_ATTN_K_FWD32D 3      /* attn_fwd32d_kernel: no kv_off, Lk > 128, Lq >= 192                                  */
+#define VQ_ATTN_K_FWD32D_NW4 4  /* attn_fwd32d_kernel, 4 waves (measurement switch VQ_ATTN_NW=4, D = 72 only)         */
+#define VQ_ATTN_K_FWD64D 5      /* attn_fwd64d_kernel: Lq >= 2048 and Lk >= 2048                                       */
+#define VQ_ATTN_K_CROSS32_2 6   /* attn_cross32_kernel, 2 tile images: known Lk <= 128, Lq >= 256                      */
+#define VQ_ATTN_K_CROSS32_3 7   /* attn_cross32_kernel, 3 / 4 / 5 tile images: kv_off, Lk bound 129-192 / 193-256 /    */
+#define VQ_ATTN_K_CROSS32_4 8   /*   257-320, Lq >= 256, D >= 64                                                       */
+#define VQ_ATTN_K_CROSS32_5 9
+#define VQ_ATTN_K_CROSS_REG 10  /* attn_cross_reg_kernel: D = 72, known Lk <= 128, H % 8 == 0, 64 <= Lq < 256          */
+
+/* Test hook: the VQ_ATTN_K_* kernel vq_attn_fwd would launch for exactly these arguments (same checks, same
+ * negative code on a bad argument).  Launches nothing and makes no HIP call; pointers are not dereferenced. */
+int vq_attn_fwd_route(const void* q, const void* k, const void* v, void* o,
+                      int n_seq, int Lq, int Lk, int H, int D,
+                      long q_seq_stride, long q_tok_stride, long kv_seq_stride, long kv_tok_stride,
+                      long o_seq_stride, long o_tok_stride, const int32_t* kv_off,
+                      float scale, void* stream);
+
 /* Temporal attention of STDiTBlock (stdit.py:112-118): rows are laid out
  * [B][T][S] (row = (b*T + t)*S + s, row strides ld_in / ld_out elements) and
- * attention runs over t for every (b, s, head).  T <= 16. */
+ * attention runs over t for every (b, s, head).  T <= 16.  q, k, v and o are
+ * 16-byte aligned (VQ_ESHAPE otherwise). */
 int vq_attn_temporal(const void* q, const void* k, const void* v, void* o,
                      int B, int T, int S, int H, int D, long ld_in, long ld_out,
                      float scale, void* stream);
@@ -259,7 +282,8 @@ int vq_attn_temporal(const void* q, const void* k, const void* v, void* o,
  * s / s_rcp: both null, or the consuming Linear's smooth-quant channel scale [H*D] and its reciprocal from
  * vq_smooth_reciprocal (the division x / s of quant_layer.py:140 exists in reciprocal form only in this kernel).
  * o: nullable, dense [B*T*S, H*D] fp16 copy of the attention output for callers that need both.
- * H <= 16, T <= 16, H*D % 16 == 0, Kp % 128 == 0. */
+ * H <= 16, T <= 16, H*D % 16 == 0, Kp % 128 == 0.  q, k, v, xq and, when set, s, s_rcp and o are 16-byte
+ * aligned (VQ_ESHAPE otherwise). */
 int vq_attn_temporal_rowquant(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
                               int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o, int B, int T,
                               int S, int H, int D, long ld_in, int Kp, float scale, void* stream);

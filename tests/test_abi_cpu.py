@@ -112,7 +112,7 @@ def test_every_entry_point_rejects_null_and_bad_shapes_without_gpu():
     zero_size = {"vq_rowquant": 15, "vq_gelu_rowquant": 8, "vq_ln_modulate_rowquant": 13, "vq_rowquant_smooth_multi": 8,
                  "vq_smooth_reciprocal": 2, "vq_fakequant_act": 9, "vq_epsfill_fixup": 7, "vq_pack_weight": 8,
                  "vq_weight_minmax": 4, "vq_gemm_i8": 14, "vq_gemm_i8_stamped": 11, "vq_gemm_i8_batched": 11, "vq_gemm_i8_grouped": 12,
-                 "vq_attn_fwd": 5, "vq_attn_temporal": 6, "vq_attn_temporal_rowquant": 13, "vq_adaln_table": 4,
+                 "vq_attn_fwd": 5, "vq_attn_fwd_route": 5, "vq_attn_temporal": 6, "vq_attn_temporal_rowquant": 13, "vq_adaln_table": 4,
                  "vq_linear_f16": 4, "vq_cfg_ddim_step": 4}
     for name, pos in zero_size.items():
         assert getattr(lib, name)(*_args(name, one, ints={pos: 0})) == -1, name
@@ -159,6 +159,38 @@ def test_every_entry_point_rejects_null_and_bad_shapes_without_gpu():
         assert getattr(lib, name)(*_args(name, one, ints=ints, longs=longs)) == -4, name
     for code in (0, -1, -2, -3, -4, -99):
         assert lib.vq_strerror(code)
+
+
+def test_attention_entry_points_reject_pointers_off_16_bytes_without_gpu():
+    """q, k, v, o (and the fused quantizer's xq, s, s_rcp) are accessed 16 bytes at a time: a base pointer that is
+    8 mod 16 returns VQ_ESHAPE before anything is launched.  With 16-aligned dummies the route hook names a kernel."""
+    import viditq_amd  # noqa: F401
+    from viditq_amd import _lib
+    lib = _lib.load()
+    good, bad = ctypes.c_void_p(1 << 20), ctypes.c_void_p((1 << 20) + 8)
+    fwd = dict(ints={4: 1, 5: 300, 6: 333, 7: 2, 8: 72}, longs={9: 300 * 144, 10: 144, 11: 333 * 288, 12: 288,
+                                                                13: 300 * 144, 14: 144})
+    for name in ("vq_attn_fwd", "vq_attn_fwd_route"):
+        args = _args(name, good, **fwd)
+        args[15] = None                                                         # no kv_off
+        for pos in range(4):                                                    # q, k, v, o
+            a = list(args)
+            a[pos] = bad
+            assert getattr(lib, name)(*a) == -2, (name, pos)
+    args = _args("vq_attn_fwd_route", good, **fwd)
+    args[15] = None
+    assert lib.vq_attn_fwd_route(*args) == 3                                    # VQ_ATTN_K_FWD32D
+    tmp = _args("vq_attn_temporal", good, ints={4: 1, 5: 16, 6: 4, 7: 4, 8: 72}, longs={9: 864, 10: 288})
+    for pos in range(4):
+        a = list(tmp)
+        a[pos] = bad
+        assert lib.vq_attn_temporal(*a) == -2, pos
+    # q k v s s_rcp xq sx zx R status o | B T S H D ld_in Kp scale stream
+    tq = _args("vq_attn_temporal_rowquant", good, ints={11: 1, 12: 16, 13: 4, 14: 4, 15: 72, 17: 384}, longs={16: 864})
+    for pos in (0, 1, 2, 3, 4, 5, 10):
+        a = list(tq)
+        a[pos] = bad
+        assert lib.vq_attn_temporal_rowquant(*a) == -2, pos
 
 
 def test_product_ops_refuse_cpu_tensors():

@@ -2643,8 +2643,20 @@ static int launch_attn8(const AttnArgs& a, hipStream_t st) {
     return vq_check_launch();
 }
 
+#if defined(VQ_ATTN_64) && VQ_ATTN_64 > 0   // lab builds only: routes of the round-6 A/B kernels (never returned by the product library)
+#define VQ_ATTN_K_LAB_64D_128 100            // attn_fwd64d_kernel<D, 8, 128>
+#define VQ_ATTN_K_LAB_64D_NW4 101            // attn_fwd64d_kernel<D, 4, 64>
+#define VQ_ATTN_K_LAB_64P 102                // attn_fwd64p_kernel (tools/lab/attn_phased.h)
+#endif
+#ifdef VQ_ATTN_STREAM_LAB
+#define VQ_ATTN_K_LAB_64S 103                // attn_fwd64s_kernel (tools/lab/attn_stream.h)
+#endif
+
+// The kernel vq_attn_fwd runs for these (checked) arguments: a VQ_ATTN_K_* id of include/viditq.h.  The one place the
+// dispatch is decided - launch_attn switches on it and vq_attn_fwd_route returns it - so the test hook cannot disagree
+// with the launch.  No HIP call.
 template <int D>
-static int launch_attn(const AttnArgs& a, hipStream_t st) {
+static int attn_route(const AttnArgs& a) {
     // second-generation kernel for long key sequences; short ones (cross attention: <= 2 key tiles, where the
     // per-workgroup prologue dominates) and short query sequences keep the first kernel.  VQ_ATTN_V1 forces it.
     static const bool old_kernel = getenv("VQ_ATTN_V1") != nullptr;
@@ -2654,16 +2666,16 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
     static const bool cross_reg = getenv("VQ_ATTN_CROSS") && getenv("VQ_ATTN_CROSS")[0] == 'r';
     if (!old_kernel && !no_reg && !cross_reg && a.Lk > 0 && a.Lk <= 128 && a.Lq >= 256 &&
         (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31))
-        return launch_cross32<D>(a, st);
+        return VQ_ATTN_K_CROSS32_2;
     // round 6: prompts of up to 320 tokens (PixArt-Sigma: 300) with every sample's keys given by offsets - K / V of a
     // (sequence, head) pair resident in 3 ... 5 tile images, one workgroup per CU.  VQ_ATTN_CROSS_LONG=0: the generic kernel (A/B)
     static const bool no_long = getenv("VQ_ATTN_CROSS_LONG") && atoi(getenv("VQ_ATTN_CROSS_LONG")) == 0;
     if constexpr (D >= 64) {
         if (!old_kernel && !no_reg && !cross_reg && !no_long && a.kv_off && a.Lk > 128 && a.Lk <= 320 && a.Lq >= 256 &&
             (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31))
-            return a.Lk <= 192 ? launch_cross32<D, 3>(a, st) : a.Lk <= 256 ? launch_cross32<D, 4>(a, st) : launch_cross32<D, 5>(a, st);
+            return a.Lk <= 192 ? VQ_ATTN_K_CROSS32_3 : a.Lk <= 256 ? VQ_ATTN_K_CROSS32_4 : VQ_ATTN_K_CROSS32_5;
     }
-    if (D == 72 && !old_kernel && !no_reg && a.Lk > 0 && a.Lk <= 128 && a.H % 8 == 0 && a.Lq >= 64) return launch_cross_reg(a, st);
+    if (D == 72 && !old_kernel && !no_reg && a.Lk > 0 && a.Lk <= 128 && a.H % 8 == 0 && a.Lq >= 64) return VQ_ATTN_K_CROSS_REG;
     if (!old_kernel && !a.kv_off && a.Lk > 128 && a.Lq >= 96)
     {
         // long query sequences: 32 queries per wave, LDS-DMA tiles, four waves per SIMD (attn_fwd32d_kernel; its buffer
@@ -2674,13 +2686,13 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
         static const bool nw4 = getenv("VQ_ATTN_NW") && atoi(getenv("VQ_ATTN_NW")) == 4;
 #if defined(VQ_ATTN_64) && VQ_ATTN_64 > 0   // round-6 A/B builds: 64 queries per wave everywhere (1: 64-key tiles, 2: 128-key tiles,
         if (!gen8 && a.Lq >= 512 && (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31)) {  // 3: four waves per workgroup, two workgroups per CU; 4 / 5: opposite phases)
-            if constexpr (D >= 64 && (VQ_ATTN_64 == 4 || VQ_ATTN_64 == 5)) return launch_attn64p<D, VQ_ATTN_64 == 4 ? 3 : 4>(a, st);
-            else return VQ_ATTN_64 == 2 ? launch_attn64d<D, 8, 128>(a, st) : VQ_ATTN_64 == 3 ? launch_attn64d<D, 4, 64>(a, st) : launch_attn64d<D>(a, st);
+            if (D >= 64 && (VQ_ATTN_64 == 4 || VQ_ATTN_64 == 5)) return VQ_ATTN_K_LAB_64P;
+            return VQ_ATTN_64 == 2 ? VQ_ATTN_K_LAB_64D_128 : VQ_ATTN_64 == 3 ? VQ_ATTN_K_LAB_64D_NW4 : VQ_ATTN_K_FWD64D;
         }
 #else
         // 64 queries per wave (attn_fwd64d_kernel) where a workgroup walks MANY key tiles (PixArt-Sigma's 4096-token images:
         // 181.4 vs 188.1 us, round 6); at 1024 keys the two forms tie (111.7 vs 111.6 us) and the 32-query form stays
-        if (!gen8 && a.Lq >= 2048 && a.Lk >= 2048 && (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31)) return launch_attn64d<D>(a, st);
+        if (!gen8 && a.Lq >= 2048 && a.Lk >= 2048 && (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31)) return VQ_ATTN_K_FWD64D;
 #ifdef VQ_ATTN_STREAM_LAB
         // the two query tiles of a pair as one tile stream (attn_fwd64s_kernel) where the plain launch would be SEVERAL generations
         // of short-lived workgroups: >= 512 tiles of 512 queries (STDiT's spatial attention: 256 pairs x 2 tiles, 16 key tiles each).
@@ -2692,25 +2704,54 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
             // (>= 64 D / 512 key tiles per query tile: that many tiles carry the parked O rows out; >= 4 for the Q prefetch)
             if (!gen8 && !no_stream && !nw4 && a.Lq > 512 && a.Lk >= 64 * (64 * D * 2 / 1024) && tiles64 >= 512 && (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31) &&
                 (long)a.Lq * a.q_tok_stride * 2 < (1l << 31))
-                return launch_attn64s<D>(a, st);
+                return VQ_ATTN_K_LAB_64S;
         }
 #endif
 #endif
         if (!gen8 && a.Lq >= 192 && (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31))
-            return (nw4 && D == 72) ? launch_attn32d<D, 4>(a, st) : launch_attn32d<D>(a, st);
-        return a.Lq >= 192 ? launch_attn8<D, 8>(a, st) : launch_attn8<D, 4>(a, st);
+            return (nw4 && D == 72) ? VQ_ATTN_K_FWD32D_NW4 : VQ_ATTN_K_FWD32D;
+        return a.Lq >= 192 ? VQ_ATTN_K_FWD8_NW8 : VQ_ATTN_K_FWD8_NW4;
     }
-    using C = AttCfg<D>;
-    auto k = attn_fwd_kernel<D>;
-    static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);  // once
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
+    return VQ_ATTN_K_FWD;
+}
+
+template <int D>
+static int launch_attn(const AttnArgs& a, hipStream_t st) {
+    switch (attn_route<D>(a)) {
+        case VQ_ATTN_K_CROSS32_2: return launch_cross32<D>(a, st);
+        case VQ_ATTN_K_CROSS32_3: if constexpr (D >= 64) return launch_cross32<D, 3>(a, st); break;
+        case VQ_ATTN_K_CROSS32_4: if constexpr (D >= 64) return launch_cross32<D, 4>(a, st); break;
+        case VQ_ATTN_K_CROSS32_5: if constexpr (D >= 64) return launch_cross32<D, 5>(a, st); break;
+        case VQ_ATTN_K_CROSS_REG: return launch_cross_reg(a, st);
+        case VQ_ATTN_K_FWD64D: return launch_attn64d<D>(a, st);
+#if defined(VQ_ATTN_64) && VQ_ATTN_64 > 0
+        case VQ_ATTN_K_LAB_64D_128: return launch_attn64d<D, 8, 128>(a, st);
+        case VQ_ATTN_K_LAB_64D_NW4: return launch_attn64d<D, 4, 64>(a, st);
+        case VQ_ATTN_K_LAB_64P: if constexpr (D >= 64) return launch_attn64p<D, VQ_ATTN_64 == 4 ? 3 : 4>(a, st); break;
+#endif
+#ifdef VQ_ATTN_STREAM_LAB
+        case VQ_ATTN_K_LAB_64S: if constexpr (D % 8 == 0 && D >= 64) return launch_attn64s<D>(a, st); break;
+#endif
+        case VQ_ATTN_K_FWD32D: return launch_attn32d<D>(a, st);
+        case VQ_ATTN_K_FWD32D_NW4: if constexpr (D == 72) return launch_attn32d<D, 4>(a, st); break;
+        case VQ_ATTN_K_FWD8_NW8: return launch_attn8<D, 8>(a, st);
+        case VQ_ATTN_K_FWD8_NW4: return launch_attn8<D, 4>(a, st);
+        case VQ_ATTN_K_FWD: {
+            using C = AttCfg<D>;
+            auto k = attn_fwd_kernel<D>;
+            static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);  // once
+            if (e != hipSuccess) {
+                g_vq_last_hip_error = (int)e;
+                return VQ_ELAUNCH;
+            }
+            dim3 grid((a.Lq + 127) / 128, a.H, a.n_seq);
+            hipLaunchKernelGGL(k, grid, dim3(256), C::LDS, st, a);
+            return vq_check_launch();
+        }
+        default: break;
     }
-    dim3 grid((a.Lq + 127) / 128, a.H, a.n_seq);
-    hipLaunchKernelGGL(k, grid, dim3(256), C::LDS, st, a);
-    return vq_check_launch();
+    return VQ_EUNSUP;     // (a route without a kernel for this head dim: attn_route never returns one)
 }
 
 #ifdef VQ_ATTN_STAMPS   // lab builds only: the phased kernel with cycle stamps (D = 72): stamps = uint32[workgroups][8 waves][16]
@@ -2729,23 +2770,52 @@ extern "C" int vq_lab_attn64p_stamped(const void* q, const void* k, const void* 
 }
 #endif
 
-extern "C" int vq_attn_fwd(const void* q, const void* k, const void* v, void* o, int n_seq, int Lq, int Lk, int H,
-                           int D, long q_seq_stride, long q_tok_stride, long kv_seq_stride, long kv_tok_stride,
-                           long o_seq_stride, long o_tok_stride, const int32_t* kv_off, float scale, void* stream) {
+// Argument checks of vq_attn_fwd / vq_attn_fwd_route (no dereference, no HIP call): VQ_OK with *a filled, or the error code.
+static int attn_fwd_args(const void* q, const void* k, const void* v, void* o, int n_seq, int Lq, int Lk, int H,
+                         long q_seq_stride, long q_tok_stride, long kv_seq_stride, long kv_tok_stride,
+                         long o_seq_stride, long o_tok_stride, const int32_t* kv_off, float scale, AttnArgs* a) {
     if (!q || !k || !v || !o) return VQ_EINVAL;
     if (n_seq <= 0 || Lq <= 0 || H <= 0 || (Lk <= 0 && !kv_off)) return VQ_EINVAL;
     if ((q_tok_stride | kv_tok_stride | o_tok_stride | q_seq_stride | kv_seq_stride | o_seq_stride) % 8 != 0)
         return VQ_ESHAPE;  // 16-byte alignment of every row
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 != 0) return VQ_ESHAPE;   // ... and of its base
     if (n_seq > 65535 || H > 65535) return VQ_ESHAPE;
-    AttnArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, (half_t*)o, q_seq_stride, q_tok_stride,
-               kv_seq_stride, kv_tok_stride, o_seq_stride, o_tok_stride, kv_off, n_seq, Lq, Lk, H,
-               scale * ATT_LOG2E};
+    *a = AttnArgs{(const half_t*)q, (const half_t*)k, (const half_t*)v, (half_t*)o, q_seq_stride, q_tok_stride,
+                  kv_seq_stride, kv_tok_stride, o_seq_stride, o_tok_stride, kv_off, n_seq, Lq, Lk, H,
+                  scale * ATT_LOG2E};
+    return VQ_OK;
+}
+
+extern "C" int vq_attn_fwd(const void* q, const void* k, const void* v, void* o, int n_seq, int Lq, int Lk, int H,
+                           int D, long q_seq_stride, long q_tok_stride, long kv_seq_stride, long kv_tok_stride,
+                           long o_seq_stride, long o_tok_stride, const int32_t* kv_off, float scale, void* stream) {
+    AttnArgs a;
+    const int rc = attn_fwd_args(q, k, v, o, n_seq, Lq, Lk, H, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride,
+                                 o_seq_stride, o_tok_stride, kv_off, scale, &a);
+    if (rc != VQ_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     switch (D) {
         case 72: return launch_attn<72>(a, st);
         case 64: return launch_attn<64>(a, st);
         case 32: return launch_attn<32>(a, st);
         case 16: return launch_attn<16>(a, st);
+        default: return VQ_ESHAPE;
+    }
+}
+
+extern "C" int vq_attn_fwd_route(const void* q, const void* k, const void* v, void* o, int n_seq, int Lq, int Lk, int H,
+                                 int D, long q_seq_stride, long q_tok_stride, long kv_seq_stride, long kv_tok_stride,
+                                 long o_seq_stride, long o_tok_stride, const int32_t* kv_off, float scale, void* stream) {
+    (void)stream;
+    AttnArgs a;
+    const int rc = attn_fwd_args(q, k, v, o, n_seq, Lq, Lk, H, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride,
+                                 o_seq_stride, o_tok_stride, kv_off, scale, &a);
+    if (rc != VQ_OK) return rc;
+    switch (D) {
+        case 72: return attn_route<72>(a);
+        case 64: return attn_route<64>(a);
+        case 32: return attn_route<32>(a);
+        case 16: return attn_route<16>(a);
         default: return VQ_ESHAPE;
     }
 }
@@ -2770,6 +2840,7 @@ extern "C" int vq_attn_temporal(const void* q, const void* k, const void* v, voi
     if (!q || !k || !v || !o) return VQ_EINVAL;
     if (B <= 0 || T <= 0 || S <= 0 || H <= 0) return VQ_EINVAL;
     if (T > 16 || ld_in % 8 != 0 || ld_out % 8 != 0 || B > 65535) return VQ_ESHAPE;
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 != 0) return VQ_ESHAPE;   // 16-byte loads (o: as vq_attn_temporal_long)
     TempArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, (half_t*)o, ld_in, ld_out, B, T, S, H,
                scale * ATT_LOG2E};
     hipStream_t st = (hipStream_t)stream;
@@ -2832,6 +2903,9 @@ extern "C" int vq_attn_temporal_rowquant(const void* q, const void* k, const voi
     const int C = H * D;
     if (T > 16 || H > 16 || ld_in % 8 != 0 || B > 65535 || C % 16 != 0 || Kp % 128 != 0 || Kp < C) return VQ_ESHAPE;
     if (16 * (C / 8) > 3 * 64 * H || D % 4 != 0) return VQ_ESHAPE;   // V staging registers of the kernel
+    // 16-byte loads of q / k / v, float4 reads of s / s_rcp, 16-byte code stores; o: 16 bytes as everywhere else
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)xq | (uintptr_t)s | (uintptr_t)s_rcp | (uintptr_t)o) % 16 != 0)
+        return VQ_ESHAPE;
     TempQArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, xq, sx, zx, R, status, (half_t*)o, s, s_rcp, ld_in, B, T, S, H, Kp,
                 scale * ATT_LOG2E};
     hipStream_t st = (hipStream_t)stream;
