@@ -105,6 +105,9 @@ __device__ __forceinline__ float rq_round_div(float x, float inv, float delta) {
 //   with v_max3_f32 and tested ONCE (a wave-level branch per group instead of one per element: the per-element branches
 //   were ~40 % of the quantizers' issue slots); a group with a value that close to a tie (2e-4 of all values) redoes
 //   those values with the division.  ``inv`` may be the 1-ulp v_rcp_f32 of delta (vq_row_grid): the bound becomes 5.3e-5.
+//   Exact ties (where rint(q + zp) and rint(q) + zp differ for an odd zp: only the fallback makes them agree) and
+//   quotients 1e-6 .. 1e-3 to either side of a tie run in tests/test_quantizer_edges_gpu.py (families Q1, Q2 of
+//   tests/quant_rows.py) through every kernel that calls this.
 typedef float float2v __attribute__((ext_vector_type(2)));
 template <int N>
 __device__ __forceinline__ void rq_round_group(const float (&x)[N], float inv, float delta, float zp, float (&r)[N]) {
@@ -142,9 +145,12 @@ __device__ __forceinline__ void vq_minmax_to_params(float xmin, float xmax, floa
 // ~12 VALU instructions that all 64 lanes execute; three of them were a tenth of a C = 1152 row's instructions):
 //   delta = RN((max - min) / qmax): for qmax = 255 by Markstein's correction with the constant RN(1/255) (255's
 //     significand is not all ones; exact for every dividend whose residual cannot underflow - checked against the IEEE
-//     quotient on 3 x 10^7 values and every fp16 magnitude), else the division;
+//     quotient on 3 x 10^7 values and every fp16 magnitude, and held to the oracle's delta bit for bit on every 7th fp16
+//     magnitude, +-65504, subnormal rows and the 1e-6 threshold to the ulp by tests/test_quantizer_edges_gpu.py, families
+//     Q3 - Q5), else the division;
 //   inv = v_rcp_f32(delta), 1 ulp: it only feeds the tie-guarded product form of rq_round_group;
-//   zp = rint(-min / delta) through the same guarded product form (exact division when within 1e-4 of a tie).
+//   zp = rint(-min / delta) through the same guarded product form (exact division when within 1e-4 of a tie: every
+//     symmetric row max = -min has -min / delta = qmax / 2, family Q3 of the same test).
 // Bit-identical results to vq_minmax_to_params + __fdiv_rn(1, delta) wherever they are used.
 __device__ __forceinline__ void vq_row_grid(float xmin, float xmax, float qmax, float& delta, float& zp, bool& small,
                                             float& inv) {
