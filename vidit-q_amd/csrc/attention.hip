@@ -19,10 +19,16 @@
 // workgroup = 2 spatial positions x 4 heads, rows staged once through LDS with full-width
 // coalesced loads, one wave per head, 32x32 MFMA over the 2x16 token rows with a
 // block-diagonal mask.
+//
+// attn_temporal_quant_kernel / attn_temporal_quant2_kernel (T <= 16) and attn_temporal_long_kernel (T <= 64): temporal
+// attention with the consuming Linear's per-token quantizer fused in; one argument struct (TempQArgs), lane layout,
+// LDS exchange contract and row reductions in attn_rowquant.h.
+//
+// Host side: every launcher goes through vq_prepare_kernel (dynamic-LDS limit and CU count once per device, vq_common.h)
+// and every entry point picks the head dim with vq_dispatch_head_dim.
 #include <stdlib.h>
-#include <mutex>
-#include <type_traits>
 #include "vq_common.h"
+#include "attn_rowquant.h"
 
 #define ATT_LOG2E 1.4426950408889634f
 
@@ -407,15 +413,15 @@ struct TempQArgs {
     const half_t* q;
     const half_t* k;
     const half_t* v;
-    int8_t* xq;
+    int8_t* xq;                                    // nullable in attn_temporal_long_kernel: no quantizer (plain fp16 output)
     float* sx;
     int32_t* zx;
     int32_t* R;
     int32_t* status;
-    half_t* o;                                     // nullable: also store the fp16 attention output [B*T*S, H*D]
+    half_t* o;                                     // nullable (not when xq is null): also store the fp16 attention output [B*T*S, ld_out]
     const float* s;                                // nullable [H*D]: smooth-quant channel scale of the consuming Linear
     const float* s_rcp;                            //                 and its reciprocal (vq_smooth_reciprocal)
-    long ld_in;
+    long ld_in, ld_out;                            // row strides in elements (the T <= 16 kernels store o densely: ld_out = H*D)
     int B, T, S, H, Kp;
     float c;
 };
@@ -681,43 +687,6 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(TempQArgs a) 
 // Codes / grids / row sums remain exact functions of the kernel's own fp16 output (bit-identical to vq_rowquant of it: same
 // vq_row_grid / rq_round_group arithmetic, tested).
 // ---------------------------------------------------------------------------
-// (the swap builtins return a 2-vector: its elements are copied into scalars before any __builtin_bit_cast - written on the
-//  vector elements directly, hipcc of ROCm 7.2 reads element 0 for both)
-__device__ __forceinline__ float tq_xor16(float x, bool is_max) {     // combine rows (0,1) and (2,3) of the wave
-    const unsigned b = __builtin_bit_cast(unsigned, x);
-    const auto r = __builtin_amdgcn_permlane16_swap(b, b, false, false);
-    const unsigned r0 = r[0], r1 = r[1];
-    float m;      // (asm: fmaxf / fminf would canonicalise both operands first - two more instructions per reduction step)
-    if (is_max) asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(r0), "v"(r1));
-    else asm("v_min_f32 %0, %1, %2" : "=v"(m) : "v"(r0), "v"(r1));
-    return m;
-}
-__device__ __forceinline__ float tq_xor32(float x, bool is_max) {     // combine the two halves of the wave
-    const unsigned b = __builtin_bit_cast(unsigned, x);
-    const auto r = __builtin_amdgcn_permlane32_swap(b, b, false, false);
-    const unsigned r0 = r[0], r1 = r[1];
-    float m;      // (asm: fmaxf / fminf would canonicalise both operands first - two more instructions per reduction step)
-    if (is_max) asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(r0), "v"(r1));
-    else asm("v_min_f32 %0, %1, %2" : "=v"(m) : "v"(r0), "v"(r1));
-    return m;
-}
-__device__ __forceinline__ float tq_sum4rows(float x) {
-    unsigned b = __builtin_bit_cast(unsigned, x);
-    auto r = __builtin_amdgcn_permlane16_swap(b, b, false, false);
-    unsigned r0 = r[0], r1 = r[1];
-    x = __builtin_bit_cast(float, r0) + __builtin_bit_cast(float, r1);
-    b = __builtin_bit_cast(unsigned, x);
-    r = __builtin_amdgcn_permlane32_swap(b, b, false, false);
-    r0 = r[0], r1 = r[1];
-    return __builtin_bit_cast(float, r0) + __builtin_bit_cast(float, r1);
-}
-__device__ __forceinline__ int tq_isum4rows(int x) {
-    auto r = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);
-    x = (int)r[0] + (int)r[1];
-    r = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false);
-    return (int)r[0] + (int)r[1];
-}
-
 template <int D>
 __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(TempQArgs a) {
     constexpr int H = 16, C = H * D, NTHR = 64 * H;
@@ -966,25 +935,8 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(TempQArgs a)
 //     the kernel's own fp16 output), and the codes leave straight from registers: 4 bytes per lane, 16 contiguous bytes
 //     per row and 16-lane group.
 // ---------------------------------------------------------------------------
-struct TempLArgs {
-    const half_t* q;
-    const half_t* k;
-    const half_t* v;
-    int8_t* xq;                                    // nullable: no quantizer (plain fp16 output)
-    float* sx;
-    int32_t* zx;
-    int32_t* R;
-    int32_t* status;
-    half_t* o;                                     // nullable when xq is set
-    const float* s;                                // nullable [H*D] smoothing vector of the consuming Linear
-    const float* s_rcp;
-    long ld_in, ld_out;
-    int B, T, S, H, Kp;
-    float c;
-};
-
 template <int D>
-__global__ __launch_bounds__(1024) void attn_temporal_long_kernel(TempLArgs a) {
+__global__ __launch_bounds__(1024) void attn_temporal_long_kernel(TempQArgs a) {
     constexpr int KS = (D + 15) / 16, KS2 = (D + 31) / 32, CHD = D / 8;
     constexpr int RSV = D * 2, VT = 64 * RSV;      // V tile of one head: row stride, bytes
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1851,7 +1803,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A
 template <int D, int NW = 8, int KT = 64>
 static int launch_attn32d(const AttnArgs& a, hipStream_t st) {
     constexpr int LDS = 2 * (KT / 64) * Att8Cfg<D, 8>::KTILE + 2 * KT * 192;
-    auto k = attn_fwd32d_kernel<D, 0, NW, KT>;
+    constexpr auto k = attn_fwd32d_kernel<D, 0, NW, KT>;
     const int nqt = (a.Lq + 32 * NW - 1) / (32 * NW), G = a.n_seq * a.H;
 #ifdef VQ_LAB_ABLATIONS   // profiling builds only (wrong results by design); never defined for the product library
     if (D == 72 && NW == 8) {
@@ -1865,12 +1817,7 @@ static int launch_attn32d(const AttnArgs& a, hipStream_t st) {
         }
     }
 #endif
-    static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS);  // once
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
-    }
+    if (const int rc = vq_prepare_kernel<k>(LDS)) return rc;
     hipLaunchKernelGGL(k, dim3(8 * ((G + 7) / 8) * nqt), dim3(64 * NW), LDS, st, a);
     return vq_check_launch();
 }
@@ -2118,14 +2065,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
 template <int D, int NW = 8, int KT = 64>
 static int launch_attn64d(const AttnArgs& a, hipStream_t st) {
     constexpr int LDS = 2 * (KT / 64) * Att8Cfg<D, 8>::KTILE + 2 * KT * 192;
-    auto k = attn_fwd64d_kernel<D, NW, KT>;
+    constexpr auto k = attn_fwd64d_kernel<D, NW, KT>;
     const int nqt = (a.Lq + 64 * NW - 1) / (64 * NW), G = a.n_seq * a.H;
-    static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS);  // once
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
-    }
+    if (const int rc = vq_prepare_kernel<k>(LDS)) return rc;
     hipLaunchKernelGGL(k, dim3(8 * ((G + 7) / 8) * nqt), dim3(64 * NW), LDS, st, a);
     return vq_check_launch();
 }
@@ -2392,18 +2334,9 @@ static int launch_cross32(const AttnArgs& a, hipStream_t st) {
     constexpr int NW = 8;
     constexpr int LDS = NT * Att8Cfg<D, 8>::KTILE + NT * 64 * 192 + NW * 32 * Att8Cfg<D, 8>::KROW;
     static_assert(LDS <= 163840, "LDS budget of one CU");
-    auto k = attn_cross32_kernel<D, NW, NT>;
-    static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
-    }
-    static int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-        return v;
-    }();
+    constexpr auto k = attn_cross32_kernel<D, NW, NT>;
+    int ncu = 0;
+    if (const int rc = vq_prepare_kernel<k>(LDS, &ncu)) return rc;
     // NT == 2: two 8-wave workgroups per CU (four waves per SIMD; 1 / 3 / 4 measured slower, round 6); more tile images: one (LDS).
     // The (sequence, head) pairs share the chip, every workgroup walks >= 1 query tile of 256
     const int G = a.n_seq * a.H, nqt = (a.Lq + 32 * NW - 1) / (32 * NW);
@@ -2589,18 +2522,9 @@ __global__ __launch_bounds__(512) void attn_cross_reg_kernel(AttnArgs a) {
 
 static int launch_cross_reg(const AttnArgs& a, hipStream_t st) {
     constexpr int LDS = 8 * 128 * 152;
-    auto k = attn_cross_reg_kernel;
-    static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
-    }
-    static int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-        return v;
-    }();
+    constexpr auto k = attn_cross_reg_kernel;
+    int ncu = 0;
+    if (const int rc = vq_prepare_kernel<k>(LDS, &ncu)) return rc;
     const int groups = a.n_seq * (a.H / 8);            // (sequence, 8-head group) pairs share the CUs
     const int nsub = (a.Lq + 15) / 16;
     int gx = ncu / groups;
@@ -2615,7 +2539,7 @@ static int launch_cross_reg(const AttnArgs& a, hipStream_t st) {
 template <int D, int NW, int NQ = 1>
 static int launch_attn8(const AttnArgs& a, hipStream_t st) {
     using C = Att8Cfg<D, NW>;
-    auto k = attn_fwd8_kernel<D, NW, 0, NQ>;
+    constexpr auto k = attn_fwd8_kernel<D, NW, 0, NQ>;
 #ifdef VQ_LAB_ABLATIONS   // profiling builds only (wrong results by design); never defined for the product library
     if (D == 72 && NW == 8 && NQ == 1) {               // profiling ablations (VQ_ATTN_ABL)
         static const int abl = getenv("VQ_ATTN_ABL") ? atoi(getenv("VQ_ATTN_ABL")) : 0;
@@ -2631,12 +2555,7 @@ static int launch_attn8(const AttnArgs& a, hipStream_t st) {
         }
     }
 #endif
-    static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);  // once
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
-    }
+    if (const int rc = vq_prepare_kernel<k>(C::LDS)) return rc;
     const int nqt = (a.Lq + 32 * NW * NQ - 1) / (32 * NW * NQ), G = a.n_seq * a.H;
     dim3 grid(8 * ((G + 7) / 8) * nqt);
     hipLaunchKernelGGL(k, grid, dim3(64 * NW), C::LDS, st, a);
@@ -2738,13 +2657,8 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
         case VQ_ATTN_K_FWD8_NW4: return launch_attn8<D, 4>(a, st);
         case VQ_ATTN_K_FWD: {
             using C = AttCfg<D>;
-            auto k = attn_fwd_kernel<D>;
-            static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);  // once
-            if (e != hipSuccess) {
-                g_vq_last_hip_error = (int)e;
-                return VQ_ELAUNCH;
-            }
+            constexpr auto k = attn_fwd_kernel<D>;
+            if (const int rc = vq_prepare_kernel<k>(C::LDS)) return rc;
             dim3 grid((a.Lq + 127) / 128, a.H, a.n_seq);
             hipLaunchKernelGGL(k, grid, dim3(256), C::LDS, st, a);
             return vq_check_launch();
@@ -2794,13 +2708,7 @@ extern "C" int vq_attn_fwd(const void* q, const void* k, const void* v, void* o,
                                  o_seq_stride, o_tok_stride, kv_off, scale, &a);
     if (rc != VQ_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 72: return launch_attn<72>(a, st);
-        case 64: return launch_attn<64>(a, st);
-        case 32: return launch_attn<32>(a, st);
-        case 16: return launch_attn<16>(a, st);
-        default: return VQ_ESHAPE;
-    }
+    return vq_dispatch_head_dim(D, [&](auto d) { return launch_attn<d()>(a, st); });
 }
 
 extern "C" int vq_attn_fwd_route(const void* q, const void* k, const void* v, void* o, int n_seq, int Lq, int Lk, int H,
@@ -2811,25 +2719,14 @@ extern "C" int vq_attn_fwd_route(const void* q, const void* k, const void* v, vo
     const int rc = attn_fwd_args(q, k, v, o, n_seq, Lq, Lk, H, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride,
                                  o_seq_stride, o_tok_stride, kv_off, scale, &a);
     if (rc != VQ_OK) return rc;
-    switch (D) {
-        case 72: return attn_route<72>(a);
-        case 64: return attn_route<64>(a);
-        case 32: return attn_route<32>(a);
-        case 16: return attn_route<16>(a);
-        default: return VQ_ESHAPE;
-    }
+    return vq_dispatch_head_dim(D, [&](auto d) { return attn_route<d()>(a); });
 }
 
 template <int D>
 static int launch_temporal(const TempArgs& a, hipStream_t st) {
     constexpr int LDS = 3 * 32 * (4 * D * 2 + 16);
-    auto k = attn_temporal_kernel<D>;
-    static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS);  // once
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
-    }
+    constexpr auto k = attn_temporal_kernel<D>;
+    if (const int rc = vq_prepare_kernel<k>(LDS)) return rc;
     dim3 grid((a.S + 1) / 2, (a.H + 3) / 4, a.B);
     hipLaunchKernelGGL(k, grid, dim3(256), LDS, st, a);
     return vq_check_launch();
@@ -2844,53 +2741,32 @@ extern "C" int vq_attn_temporal(const void* q, const void* k, const void* v, voi
     TempArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, (half_t*)o, ld_in, ld_out, B, T, S, H,
                scale * ATT_LOG2E};
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 72: return launch_temporal<72>(a, st);
-        case 64: return launch_temporal<64>(a, st);
-        case 32: return launch_temporal<32>(a, st);
-        case 16: return launch_temporal<16>(a, st);
-        default: return VQ_ESHAPE;
-    }
+    return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal<d()>(a, st); });
 }
 
 template <int D>
 static int launch_temporal_quant(const TempQArgs& a, hipStream_t st) {
     const int C = a.H * D;
     const int LDS = 16 * (C * 2 + 16) + 16 * (C + 16) + 3 * 1024;
-    auto k = a.H == 16 ? attn_temporal_quant_kernel<D, 16> : attn_temporal_quant_kernel<D, 0>;
     constexpr int LDS_MAX = 16 * (16 * 72 * 2 + 16) + 16 * (16 * 72 + 16) + 3 * 1024;
-    static hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_temporal_quant_kernel<D, 0>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    static hipError_t e = e0 != hipSuccess ? e0 : hipFuncSetAttribute(reinterpret_cast<const void*>(attn_temporal_quant_kernel<D, 16>),
-                                                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
-    }
-    // persistent: a 1024-thread workgroup at up to 128 VGPRs owns its CU; small problems get one position each
-    const int npos = a.S * a.B;
-    static int ncu = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 256;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-        return v;
-    }();
-    const int per_cu = a.H > 8 ? 1 : (LDS > 80 * 1024 ? 1 : (LDS > 52 * 1024 ? 2 : 3));
-    const int grid = npos < ncu * per_cu ? npos : ncu * per_cu;
+    constexpr auto k2 = attn_temporal_quant2_kernel<D>;
+    constexpr auto k16 = attn_temporal_quant_kernel<D, 16>;
+    constexpr auto k0 = attn_temporal_quant_kernel<D, 0>;
 #ifndef VQ_TEMPORAL_V1   // (A/B builds: -DVQ_TEMPORAL_V1 keeps the round-3 kernel everywhere)
     // H = 16 heads, 32-bit byte offsets inside a position's rows: the instruction-trimmed kernel (round 6)
-    if (a.H == 16 && a.Kp <= 2048 && (long)a.T * a.S * a.ld_in * 2 < (1l << 31) && (long)a.T * a.S * a.Kp < (1l << 31)) {
-        auto k2 = attn_temporal_quant2_kernel<D>;
-        static hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-        if (e2 != hipSuccess) {
-            g_vq_last_hip_error = (int)e2;
-            return VQ_ELAUNCH;
-        }
-        hipLaunchKernelGGL(k2, dim3(grid), dim3(1024), LDS, st, a);
-        return vq_check_launch();
-    }
+    const bool trimmed = a.H == 16 && a.Kp <= 2048 && (long)a.T * a.S * a.ld_in * 2 < (1l << 31) && (long)a.T * a.S * a.Kp < (1l << 31);
+#else
+    const bool trimmed = false;
 #endif
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * a.H), LDS, st, a);
+    int ncu = 0;
+    if (const int rc = trimmed ? vq_prepare_kernel<k2>(LDS_MAX, &ncu)
+                               : a.H == 16 ? vq_prepare_kernel<k16>(LDS_MAX, &ncu) : vq_prepare_kernel<k0>(LDS_MAX, &ncu))
+        return rc;
+    // persistent: a 1024-thread workgroup at up to 128 VGPRs owns its CU; small problems get one position each
+    const int npos = a.S * a.B;
+    const int per_cu = a.H > 8 ? 1 : (LDS > 80 * 1024 ? 1 : (LDS > 52 * 1024 ? 2 : 3));
+    const int grid = npos < ncu * per_cu ? npos : ncu * per_cu;
+    hipLaunchKernelGGL(trimmed ? k2 : a.H == 16 ? k16 : k0, dim3(grid), dim3(64 * a.H), LDS, st, a);
     return vq_check_launch();
 }
 
@@ -2906,49 +2782,23 @@ extern "C" int vq_attn_temporal_rowquant(const void* q, const void* k, const voi
     // 16-byte loads of q / k / v, float4 reads of s / s_rcp, 16-byte code stores; o: 16 bytes as everywhere else
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)xq | (uintptr_t)s | (uintptr_t)s_rcp | (uintptr_t)o) % 16 != 0)
         return VQ_ESHAPE;
-    TempQArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, xq, sx, zx, R, status, (half_t*)o, s, s_rcp, ld_in, B, T, S, H, Kp,
-                scale * ATT_LOG2E};
+    TempQArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, xq, sx, zx, R, status, (half_t*)o, s, s_rcp, ld_in, /*ld_out*/ C,
+                B, T, S, H, Kp, scale * ATT_LOG2E};
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 72: return launch_temporal_quant<72>(a, st);
-        case 64: return launch_temporal_quant<64>(a, st);
-        case 32: return launch_temporal_quant<32>(a, st);
-        case 16: return launch_temporal_quant<16>(a, st);
-        default: return VQ_ESHAPE;
-    }
+    return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_quant<d()>(a, st); });
 }
 
-// Per-device launch state of attn_temporal_long_kernel: the dynamic-LDS attribute is set on (and the CU count read from)
-// the device current at the call, once per device.
-#define VQ_TL_MAX_DEV 64
 template <int D>
-static int launch_temporal_long(const TempLArgs& a, hipStream_t st) {
+static int launch_temporal_long(const TempQArgs& a, hipStream_t st) {
     constexpr int LDS_MAX = 16 * 64 * D * 2 + 64 + 3 * 1024;
     const int LDS = a.H * 64 * D * 2 + 64 + 3 * 1024;
-    auto k = attn_temporal_long_kernel<D>;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess && (dev < 0 || dev >= VQ_TL_MAX_DEV)) e = hipErrorInvalidDevice;
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
-    }
-    static std::once_flag once[VQ_TL_MAX_DEV];
-    static hipError_t attr[VQ_TL_MAX_DEV];
-    static int ncu[VQ_TL_MAX_DEV];
-    std::call_once(once[dev], [&] {
-        attr[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-        int v = 0;
-        ncu[dev] = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256;
-    });
-    if (attr[dev] != hipSuccess) {
-        g_vq_last_hip_error = (int)attr[dev];
-        return VQ_ELAUNCH;
-    }
+    constexpr auto k = attn_temporal_long_kernel<D>;
+    int ncu = 0;
+    if (const int rc = vq_prepare_kernel<k>(LDS_MAX, &ncu)) return rc;
     // persistent: 16 heads x 150 KB of LDS own a CU; small head counts fit two workgroups
     const int npos = a.S * a.B;
     const int per_cu = (a.H <= 8 && 2 * LDS <= 160 * 1024) ? 2 : 1;
-    const int grid = npos < ncu[dev] * per_cu ? npos : ncu[dev] * per_cu;
+    const int grid = npos < ncu * per_cu ? npos : ncu * per_cu;
     hipLaunchKernelGGL(k, dim3(grid), dim3(64 * a.H), LDS, st, a);
     return vq_check_launch();
 }
@@ -2970,14 +2820,8 @@ extern "C" int vq_attn_temporal_long(const void* q, const void* k, const void* v
     if (xq && (B != 1 || Kp % 128 != 0 || Kp < C || (uintptr_t)xq % 16 != 0)) return VQ_ESHAPE;
     // 32-bit byte offsets of a position's rows
     if ((long)T * S * ld_in * 2 >= (1l << 31) || (xq && (long)T * S * Kp >= (1l << 31))) return VQ_ESHAPE;
-    TempLArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, xq, sx, zx, R, status, (half_t*)o, s, s_rcp, ld_in,
+    TempQArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, xq, sx, zx, R, status, (half_t*)o, s, s_rcp, ld_in,
                 ld_out, B, T, S, H, Kp, scale * ATT_LOG2E};
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 72: return launch_temporal_long<72>(a, st);
-        case 64: return launch_temporal_long<64>(a, st);
-        case 32: return launch_temporal_long<32>(a, st);
-        case 16: return launch_temporal_long<16>(a, st);
-        default: return VQ_ESHAPE;
-    }
+    return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_long<d()>(a, st); });
 }

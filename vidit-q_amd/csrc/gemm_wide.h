@@ -329,13 +329,8 @@ static int launch_gemm_wide_e(const GemmArgs& a, hipStream_t st) {
     if (INT != 0 && (a.M % BM != 0 || a.N % BN != 0 || (a.N & 7) != 0 || (a.ldo & 7) != 0 ||
                      (EPI == VQ_EPI_GATE_RESID && a.rows_per_gate % BM != 0)))
         return VQ_ESHAPE;
-    auto k = gemm_i8_wide_kernel<BM, BN, WAVES_M, WAVES_N, EPI, W4, false, INT>;
-    static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);  // once
-    if (e != hipSuccess) {
-        g_vq_last_hip_error = (int)e;
-        return VQ_ELAUNCH;
-    }
+    constexpr auto k = gemm_i8_wide_kernel<BM, BN, WAVES_M, WAVES_N, EPI, W4, false, INT>;
+    if (const int rc = vq_prepare_kernel<k>((int)LDS)) return rc;
     hipLaunchKernelGGL(k, dim3(tiles), dim3(NT), LDS, st, a);
     return vq_check_launch();
 }

@@ -477,10 +477,8 @@ static bool launch_rq_smooth_lds(const half_t* x, const float* s, const float* s
                                  int32_t* R, int n_tok, int C, int Kp, int n_bits, int32_t* status, hipStream_t st) {
     if (C % 8 != 0 || C <= 1536 || C > 4608) return false;
     const int lds = 2 * C * (int)sizeof(float);
-    auto k = rowquant_smooth_lds_kernel<9, GELU, PAIR>;
-    static hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              2 * 4608 * (int)sizeof(float));
-    if (e != hipSuccess) return false;
+    constexpr auto k = rowquant_smooth_lds_kernel<9, GELU, PAIR>;
+    if (vq_prepare_kernel<k>(2 * 4608 * (int)sizeof(float)) != VQ_OK) return false;
     constexpr int PER = PAIR ? RQF_WAVES / 2 : RQF_WAVES;  // tokens per workgroup and walk step
     int grid = (n_tok + PER - 1) / PER;
     if (grid > 1024) grid = 1024;                          // 4 workgroups of 36.9 KB LDS per CU; rows grid-stride

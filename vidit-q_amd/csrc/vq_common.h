@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <mutex>
+#include <type_traits>
 #include "../../include/viditq.h"
 
 #define VQ_EPS 1.0e-6f  // reference eps, qdiff/quantizer/base_quantizer.py:219
@@ -24,6 +26,50 @@ static inline int vq_check_launch() {
         return VQ_ELAUNCH;
     }
     return VQ_OK;
+}
+
+// ---- host side: launch preparation ------------------------------------------
+// Before the first launch of kernel K on a device: raise its dynamic LDS limit to lds_max, once per device (the attribute
+// is per device; the device is the one current at the call).  ncu_out, if given, receives that device's CU count (256
+// when it cannot be read) for the persistent kernels' grids.  One instantiation - one set of per-device flags - per
+// kernel.  VQ_OK, or VQ_ELAUNCH with g_vq_last_hip_error set.
+#define VQ_MAX_DEV 64
+template <auto K>
+static int vq_prepare_kernel(int lds_max, int* ncu_out = nullptr) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && (dev < 0 || dev >= VQ_MAX_DEV)) e = hipErrorInvalidDevice;
+    if (e != hipSuccess) {
+        g_vq_last_hip_error = (int)e;
+        return VQ_ELAUNCH;
+    }
+    static std::once_flag once[VQ_MAX_DEV];
+    static hipError_t attr[VQ_MAX_DEV];
+    static int ncu[VQ_MAX_DEV];
+    std::call_once(once[dev], [&] {
+        attr[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        int v = 0;
+        if (ncu_out)                                    // (a call site either always asks or never does)
+            ncu[dev] = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256;
+    });
+    if (attr[dev] != hipSuccess) {
+        g_vq_last_hip_error = (int)attr[dev];
+        return VQ_ELAUNCH;
+    }
+    if (ncu_out) *ncu_out = ncu[dev];
+    return VQ_OK;
+}
+
+// The head dims the attention kernels are compiled for: f(std::integral_constant<int, D>) for a supported D.
+template <class F>
+static int vq_dispatch_head_dim(int D, F&& f) {
+    switch (D) {
+        case 72: return f(std::integral_constant<int, 72>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        default: return VQ_ESHAPE;
+    }
 }
 
 // ---- wave64 reductions (all 64 lanes receive the result) --------------------
