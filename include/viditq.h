@@ -250,7 +250,7 @@ int vq_attn_fwd(const void* q, const void* k, const void* v, void* o,
 #define VQ_ATTN_K_FWD8_NW4 1    /* attn_fwd8_kernel, 4 waves: no kv_off, Lk > 128, 96 <= Lq < 192                      */
 #define VQ_ATTN_K_FWD8_NW8 2    /* attn_fwd8_kernel, 8 waves: Lq >= 192 with a K / V byte extent of 2^31 or more       */
 #define VQ_ATTN_K_FWD32D 3      /* attn_fwd32d_kernel: no kv_off, Lk > 128, Lq >= 192                                  */
-#define VQ_ATTN_K_FWD32D_NW4 4  /* attn_fwd32d_kernel, 4 waves (measurement switch VQ_ATTN_NW=4, D = 72 only)         */
+/* (value 4 is retired, never reused: the four-wave arm of attn_fwd32d_kernel, a lab kernel in tools/lab/attn_lab.hip) */
 #define VQ_ATTN_K_FWD64D 5      /* attn_fwd64d_kernel: Lq >= 2048 and Lk >= 2048                                       */
 #define VQ_ATTN_K_CROSS32_2 6   /* attn_cross32_kernel, 2 tile images: known Lk <= 128, Lq >= 256                      */
 #define VQ_ATTN_K_CROSS32_3 7   /* attn_cross32_kernel, 3 / 4 / 5 tile images: kv_off, Lk bound 129-192 / 193-256 /    */

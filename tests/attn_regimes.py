@@ -171,7 +171,7 @@ def kernel_ids():
     return {m.group(1): int(m.group(2)) for m in re.finditer(r"#define (VQ_ATTN_K_\w+) (\d+)", hdr)}
 
 
-# kernels of the product dispatch (the VQ_ATTN_K_FWD32D_NW4 measurement arm is not one) and the temporal entry points
+# kernels of the product dispatch (every VQ_ATTN_K_* id of include/viditq.h) and the temporal entry points
 FWD_KERNELS = ["VQ_ATTN_K_FWD", "VQ_ATTN_K_FWD8_NW4", "VQ_ATTN_K_FWD8_NW8", "VQ_ATTN_K_FWD32D", "VQ_ATTN_K_FWD64D",
                "VQ_ATTN_K_CROSS32_2", "VQ_ATTN_K_CROSS32_3", "VQ_ATTN_K_CROSS32_4", "VQ_ATTN_K_CROSS32_5",
                "VQ_ATTN_K_CROSS_REG"]

@@ -42,7 +42,7 @@ def test_every_case_reaches_the_kernel_it_names():
 
 def test_every_kernel_of_the_table_is_covered_by_each_regime():
     kernels = ar.FWD_KERNELS + ar.TEMPORAL_KERNELS
-    assert set(ar.FWD_KERNELS) == set(IDS) - {"VQ_ATTN_K_FWD32D_NW4"}     # the measurement arm is not a product route
+    assert set(ar.FWD_KERNELS) == set(IDS)
     for reg in ("R1", "R2", "R3"):
         for kern in kernels:
             dims = {c["D"] for c in CASES if c["kernel"] == kern and c["regime"][0] == reg}

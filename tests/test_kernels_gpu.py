@@ -5,6 +5,7 @@ tolerance written next to each assert (fp16 output rounding is 2^-11 relative).
 """
 
 import os
+import re
 
 import pytest
 import torch
@@ -840,21 +841,19 @@ def test_attn_cross_lds_kernel_every_head_dim(ops, dev, D, H, Lk):
     assert _cross_case(ops, dev, D, H, 2, 300, [Lk], False) < 1e-3
 
 
-def test_attn_cross_register_kernel_still_covered():
-    """The round-1 register-resident cross kernel (attn_cross_reg_kernel) stays selectable (VQ_ATTN_CROSS=reg, read once
-    per process) and tested at Nq >= 256 - in a child process, since the default process binds the LDS kernel."""
-    import subprocess
-    import sys
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    code = ("import sys, os; sys.path.insert(0, %r); sys.path.insert(0, %r); import torch; import viditq_amd; "
-            "from viditq_amd import ops; import test_kernels_gpu as t; dev = torch.device('cuda:0'); "
-            "e = [t._cross_case(ops, dev, 72, 16, 1, 1000, [L], True) for L in (120, 80, 17, 128)]; "
-            "e.append(t._cross_case(ops, dev, 72, 16, 3, 300, [17, 120, 1], True)); print('ERRS', e); "
-            "assert max(e) < 1e-3" % (ROOT, os.path.join(ROOT, "tests")))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, VQ_ATTN_CROSS="reg"), capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0 and "ERRS" in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
+def test_attn_cross_register_kernel_still_covered(ops, dev):
+    """The round-1 register-resident cross kernel (attn_cross_reg_kernel) at Lq = 200, where the product dispatch itself
+    picks it (D = 72, H % 8 == 0, a known bound <= 128, 64 <= Lq < 256 - checked through vq_attn_fwd_route): the key counts at
+    and off its 16-key sub-tile edges, one sequence and three ragged ones, against the fp32 softmax."""
+    import ctypes
+    from viditq_amd import _lib
+    lib, D, H, Lq = _lib.load(), 72, 16, 200
+    Cc, p = H * D, ctypes.c_void_p(1 << 20)
+    reg = int(re.search(r"#define VQ_ATTN_K_CROSS_REG (\d+)", open(os.path.join(ROOT, "include", "viditq.h")).read()).group(1))
+    for B, lens in ((1, [120]), (1, [80]), (1, [17]), (1, [128]), (3, [17, 120, 1])):
+        # the arguments _cross_case gives ops.attn_fwd for a varlen launch (pointers are not dereferenced by the hook)
+        assert lib.vq_attn_fwd_route(p, p, p, p, B, Lq, max(lens), H, D, Lq * Cc, Cc, 0, 2 * Cc, Lq * Cc, Cc, p, D ** -0.5, None) == reg
+        assert _cross_case(ops, dev, D, H, B, Lq, lens, True) < 1e-3, lens
 
 
 @pytest.mark.parametrize("B,T,S,H,D", [(1, 16, 64, 16, 72), (2, 4, 9, 4, 16), (1, 16, 1024, 16, 72)])

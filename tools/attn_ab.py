@@ -1,5 +1,6 @@
-"""Round 6: attention kernels timed from graph replays (GPU box only).  One process = one library (VIDITQ_LIB selects another
-build of the same C ABI); run it alternately over the arms from a shell loop.  Prints one line per shape:
+"""Round 6: attention kernels timed from graph replays (GPU box only).  One process = one arm: VIDITQ_LIB selects another
+build of the same C ABI, --lab-kernel=<id> a retired spatial / image kernel of tools/lab/attn_lab.hip (ids in tools/lab/lab.py);
+run it alternately over the arms from a shell loop.  Prints one line per shape:
 spatial 16 x 1024 (STDiT), image 2 x 4096 (PixArt-Sigma, B = 2), cross 16384 x 120, temporal + quantizer 1024 x 16."""
 import os
 import sys
@@ -13,7 +14,16 @@ from viditq_amd import ops, _lib
 dev = torch.device("cuda:0")
 H, D = 16, 72
 g = torch.Generator().manual_seed(0)
-WHICH = sys.argv[1:] or ["spatial", "image", "cross", "temporal"]
+LAB_KERNEL = next((int(w[13:]) for w in sys.argv[1:] if w.startswith("--lab-kernel=")), None)
+WHICH = [w for w in sys.argv[1:] if not w.startswith("--lab-kernel=")] or ["spatial", "image", "cross", "temporal"]
+if LAB_KERNEL is None:
+    self_attn = ops.attn_fwd
+else:
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "lab"))
+    import lab  # noqa: E402
+
+    def self_attn(*a):
+        return lab.attn_fwd(LAB_KERNEL, *a)
 
 
 def timeit(fn, n=8, reps=10):
@@ -37,7 +47,7 @@ def timeit(fn, n=8, reps=10):
     return e0.elapsed_time(e1) / (n * reps) * 1e3
 
 
-tag = os.path.basename(os.path.dirname(_lib.LIB_PATH))
+tag = os.path.basename(os.path.dirname(_lib.LIB_PATH)) if LAB_KERNEL is None else "lab kernel %d" % LAB_KERNEL
 out = []
 # --dump=<file> / --cmp=<file>: the spatial / image outputs of a fixed input, saved by one library and compared bit for bit by another
 DUMP = next((w[7:] for w in WHICH if w.startswith("--dump=")), None)
@@ -48,7 +58,7 @@ if DUMP or CMP:
         M = n_seq * L
         q = (torch.randn(M, 3 * 1152, generator=torch.Generator().manual_seed(7)) * 1.3).half().to(dev)
         o = torch.zeros((M, 1152), dtype=torch.float16, device=dev)
-        ops.attn_fwd(q, q[:, 1152:], q[:, 2304:], o, n_seq, L, L, H, D, L * 3456, 3456, L * 3456, 3456, L * 1152, 1152)
+        self_attn(q, q[:, 1152:], q[:, 2304:], o, n_seq, L, L, H, D, L * 3456, 3456, L * 3456, 3456, L * 1152, 1152)
         res[name] = o.cpu()
     if DUMP:
         torch.save(res, DUMP)
@@ -70,7 +80,7 @@ for name, n_seq, L in (("spatial", 16, 1024), ("image", 2, 4096)):
     def f():
         i[0] = (i[0] + 1) % len(bufs)
         q = bufs[i[0]]
-        ops.attn_fwd(q, q[:, 1152:], q[:, 2304:], o, n_seq, L, L, H, D, L * ld, ld, L * ld, ld, L * 1152, 1152)
+        self_attn(q, q[:, 1152:], q[:, 2304:], o, n_seq, L, L, H, D, L * ld, ld, L * ld, ld, L * 1152, 1152)
     t = timeit(f)
     fl = 4.0 * n_seq * L * L * H * D
     out.append("%s %dx%d %.1f us (%.0f TF)" % (name, n_seq, L, t, fl / t / 1e6))

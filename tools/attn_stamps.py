@@ -1,14 +1,15 @@
-"""Round 6: cycle stamps of the phased spatial-attention kernel (attn_fwd64p_kernel, lab build with -DVQ_ATTN_STAMPS=<NB>).
-GPU box only.  VIDITQ_LIB must point at the stamped build.  Prints, per wave half (0: leads, 1: one slot behind), the median
+"""Round 6: cycle stamps of the phased spatial-attention kernel (attn_fwd64p_kernel, ring of 3 tile images) through
+vq_lab_attn64p_stamped of tools/lab/attn_lab.hip.  GPU box only.  Prints, per wave half (0: leads, 1: one slot behind), the median
 length of each phase of tile 1 and of the barrier waits between them, plus the whole loop per slot."""
-import ctypes
 import os
 import sys
 
 import numpy as np
 import torch
 
-lib = ctypes.CDLL(os.environ["VIDITQ_LIB"])
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "lab"))
+import lab  # noqa: E402
+
 dev = torch.device("cuda:0")
 H, D = 16, 72
 n_seq, L = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (16, 1024)
@@ -17,9 +18,7 @@ q = (torch.randn(M, 3 * 1152, generator=torch.Generator().manual_seed(7)) * 1.3)
 o = torch.zeros((M, 1152), dtype=torch.float16, device=dev)
 nwg = 8 * ((n_seq * H + 7) // 8) * ((L + 511) // 512)
 st = torch.zeros((nwg, 8, 16), dtype=torch.int32, device=dev)
-f = lib.vq_lab_attn64p_stamped
-f.restype = ctypes.c_int
-f.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_long] * 6 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
+f = lab.lib().vq_lab_attn64p_stamped
 k, v = q[:, 1152:], q[:, 2304:]
 for _ in range(5):
     rc = f(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), n_seq, L, L, H, L * 3456, 3456, L * 3456, 3456, L * 1152, 1152,

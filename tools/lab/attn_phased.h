@@ -1,8 +1,8 @@
 // attn_phased.h - LAB ONLY (round 6): the spatial-attention kernel with the two waves of a SIMD in explicit opposite phases.
 // Built bit-identical to attn_fwd32d / 64d and measured SLOWER than the product kernels (profiles/r06_attention_phases.md):
-// not part of libviditq_hip.so.  csrc/attention.hip includes this file only in lab builds (-DVQ_ATTN_64=4|5 routes
-// vq_attn_fwd to it, -DVQ_ATTN_STAMPS=<NB> exports vq_lab_attn64p_stamped for tools/attn_stamps.py); it uses attention.hip's
-// AttnArgs, Att8Cfg, attn_store_rows and vector types.
+// not part of libviditq_hip.so.  Included by tools/lab/attn_lab.hip behind csrc/attention.hip (kernel ids 102 / 104 of
+// vq_lab_attn_fwd; vq_lab_attn64p_stamped for tools/attn_stamps.py); it uses attention.hip's AttnArgs, Att8Cfg,
+// attn_store_rows and vector types.
 #pragma once
 // ---------------------------------------------------------------------------
 // attn_fwd64p_kernel (round 6): attn_fwd64d_kernel's 64 queries per wave, with the two waves of a SIMD in EXPLICIT OPPOSITE

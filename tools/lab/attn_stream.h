@@ -2,8 +2,7 @@
 // pair (persistent workgroup, Q of the second tile prefetched into an LDS park, O of the first parked there and stored under the
 // second tile's loop).  Built bit-identical to attn_fwd32d_kernel (five shapes incl. ragged / odd tile counts / D = 64) and
 // measured EQUAL to it (107.4-107.9 vs 108.5-109.4 us back to back, 26.9 vs 26.8 steps/s): not part of libviditq_hip.so.
-// csrc/attention.hip includes this file only with -DVQ_ATTN_STREAM_LAB (VQ_ATTN_STREAM=0 then selects the product kernel per
-// call).  Uses attention.hip's AttnArgs, Att8Cfg, attn_store_rows and vector types.  profiles/r06_attention_phases.md.
+// Included by tools/lab/attn_lab.hip behind csrc/attention.hip (kernel id 103 of vq_lab_attn_fwd).  Uses attention.hip's AttnArgs, Att8Cfg, attn_store_rows and vector types.  profiles/r06_attention_phases.md.
 #pragma once
 // ---------------------------------------------------------------------------
 // attn_fwd64s_kernel (round 6): attn_fwd64d_kernel as ONE TILE STREAM over the two query tiles of a (sequence, head) pair.

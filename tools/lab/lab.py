@@ -1,5 +1,6 @@
-"""ctypes binding of tools/lab/libviditq_lab.so (retired GEMM variants, ablations, probes) for the measurement
-scripts in tools/.  ``gemm_i8`` has the signature of viditq_amd.ops.gemm_i8 with a mandatory ``variant``."""
+"""ctypes binding of tools/lab/libviditq_lab.so (retired GEMM and attention variants, ablations, probes) for the measurement
+scripts in tools/.  ``gemm_i8`` has the signature of viditq_amd.ops.gemm_i8 with a mandatory ``variant``, ``attn_fwd`` that
+of viditq_amd.ops.attn_fwd behind a mandatory kernel id."""
 import ctypes as C
 import os
 import sys
@@ -38,6 +39,10 @@ def lib():
         _lib.vq_lab_gemm_persist6.argtypes = [_vp] * 10 + [_i, _vp, _vp] + [_i] * 8 + [_vp]
         _lib.vq_lab_gemm_sp.restype = _i
         _lib.vq_lab_gemm_sp.argtypes = [_vp] * 10 + [_i, _vp, _vp] + [_i] * 8 + [_vp]
+        _lib.vq_lab_attn_fwd.restype = _i
+        _lib.vq_lab_attn_fwd.argtypes = [_i] + [_vp] * 4 + [_i] * 5 + [C.c_long] * 6 + [_vp, C.c_float, _vp]
+        _lib.vq_lab_attn64p_stamped.restype = _i
+        _lib.vq_lab_attn64p_stamped.argtypes = [_vp] * 4 + [_i] * 4 + [C.c_long] * 6 + [C.c_float, _vp, _vp]
         _lib.vq_probe_mfma_i8.argtypes = [_vp, _vp, _vp, _vp]
         _lib.vq_probe_stage_rate.argtypes = [_i, _vp, _i, _i, _i, _vp, _vp]
         _lib.vq_probe_mfma_rate.argtypes = [_i, _i, _i, _vp, _vp]
@@ -113,6 +118,22 @@ def gemm_sp(a, w, bias=None, out=None, epilogue=0, resid=None, gate=None, rows_p
     if rc != 0:
         raise RuntimeError("vq_lab_gemm_sp variant %d: error %d" % (variant, rc))
     return out
+
+
+# kernel ids of vq_lab_attn_fwd (tools/lab/attn_lab.hip); ATTN_ABL32D / ATTN_ABL8 + the ablation mask (wrong results by design)
+ATTN_PRODUCT, ATTN_FWD32D_NW4, ATTN_64D_128, ATTN_64D_NW4, ATTN_64P, ATTN_64S, ATTN_64P_NB4 = -1, 4, 100, 101, 102, 103, 104
+ATTN_ABL32D, ATTN_ABL8 = 1000, 2000
+
+
+def attn_fwd(kernel, q, k, v, o, n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride, o_seq_stride,
+             o_tok_stride, kv_off=None, scale=None):
+    """viditq_amd.ops.attn_fwd on the kernel the caller names (ATTN_PRODUCT: the product's choice, built from the same sources)"""
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    rc = lib().vq_lab_attn_fwd(kernel, _p(q), _p(k), _p(v), _p(o), n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_stride, kv_seq_stride,
+                               kv_tok_stride, o_seq_stride, o_tok_stride, _p(kv_off), scale, torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        raise RuntimeError("vq_lab_attn_fwd kernel %d: error %d" % (kernel, rc))
+    return o
 
 
 def probe_mfma_i8(a, b):

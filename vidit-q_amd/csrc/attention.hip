@@ -25,8 +25,8 @@
 // LDS exchange contract and row reductions in attn_rowquant.h.
 //
 // Host side: every launcher goes through vq_prepare_kernel (dynamic-LDS limit and CU count once per device, vq_common.h)
-// and every entry point picks the head dim with vq_dispatch_head_dim.
-#include <stdlib.h>
+// and every entry point picks the head dim with vq_dispatch_head_dim.  Nothing here reads the environment or depends on a
+// build flag; the retired kernels, profiling ablations and A/B arms are the lab's attn_lab.hip, which includes this file.
 #include "vq_common.h"
 #include "attn_rowquant.h"
 
@@ -1805,18 +1805,6 @@ static int launch_attn32d(const AttnArgs& a, hipStream_t st) {
     constexpr int LDS = 2 * (KT / 64) * Att8Cfg<D, 8>::KTILE + 2 * KT * 192;
     constexpr auto k = attn_fwd32d_kernel<D, 0, NW, KT>;
     const int nqt = (a.Lq + 32 * NW - 1) / (32 * NW), G = a.n_seq * a.H;
-#ifdef VQ_LAB_ABLATIONS   // profiling builds only (wrong results by design); never defined for the product library
-    if (D == 72 && NW == 8) {
-        static const int abl = getenv("VQ_ATTN32_ABL") ? atoi(getenv("VQ_ATTN32_ABL")) : 0;
-        if (abl) {
-            auto ka = abl == 1 ? attn_fwd32d_kernel<72, 1> : abl == 4 ? attn_fwd32d_kernel<72, 4> : abl == 8 ? attn_fwd32d_kernel<72, 8>
-                      : abl == 16 ? attn_fwd32d_kernel<72, 16> : abl == 24 ? attn_fwd32d_kernel<72, 24> : attn_fwd32d_kernel<72, 5>;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ka), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            hipLaunchKernelGGL(ka, dim3(8 * ((G + 7) / 8) * nqt), dim3(512), LDS, st, a);
-            return vq_check_launch();
-        }
-    }
-#endif
     if (const int rc = vq_prepare_kernel<k>(LDS)) return rc;
     hipLaunchKernelGGL(k, dim3(8 * ((G + 7) / 8) * nqt), dim3(64 * NW), LDS, st, a);
     return vq_check_launch();
@@ -2071,13 +2059,6 @@ static int launch_attn64d(const AttnArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k, dim3(8 * ((G + 7) / 8) * nqt), dim3(64 * NW), LDS, st, a);
     return vq_check_launch();
 }
-
-#ifdef VQ_ATTN_STREAM_LAB   // lab builds only: the two-query-tile stream form (measured equal to the product kernel, round 6)
-#include "../../tools/lab/attn_stream.h"
-#endif
-#if defined(VQ_ATTN_64) || defined(VQ_ATTN_STAMPS)   // lab builds only: the opposite-phase kernel (measured slower, round 6)
-#include "../../tools/lab/attn_phased.h"
-#endif
 
 // ---------------------------------------------------------------------------
 // attn_cross32_kernel (round 4): cross attention against a SHORT key/value sequence (<= 128 keys) as attn_fwd32d_kernel
@@ -2540,21 +2521,6 @@ template <int D, int NW, int NQ = 1>
 static int launch_attn8(const AttnArgs& a, hipStream_t st) {
     using C = Att8Cfg<D, NW>;
     constexpr auto k = attn_fwd8_kernel<D, NW, 0, NQ>;
-#ifdef VQ_LAB_ABLATIONS   // profiling builds only (wrong results by design); never defined for the product library
-    if (D == 72 && NW == 8 && NQ == 1) {               // profiling ablations (VQ_ATTN_ABL)
-        static const int abl = getenv("VQ_ATTN_ABL") ? atoi(getenv("VQ_ATTN_ABL")) : 0;
-        if (abl) {
-            auto ka = abl == 1 ? attn_fwd8_kernel<72, 8, 1> : abl == 2 ? attn_fwd8_kernel<72, 8, 2>
-                    : abl == 4 ? attn_fwd8_kernel<72, 8, 4> : abl == 8 ? attn_fwd8_kernel<72, 8, 8>
-                    : abl == 6 ? attn_fwd8_kernel<72, 8, 6> : abl == 16 ? attn_fwd8_kernel<72, 8, 16>
-                    : abl == 32 ? attn_fwd8_kernel<72, 8, 32> : abl == 64 ? attn_fwd8_kernel<72, 8, 64>
-                    : abl == 96 ? attn_fwd8_kernel<72, 8, 96> : abl == 128 ? attn_fwd8_kernel<72, 8, 128> : attn_fwd8_kernel<72, 8, 15>;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ka), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-            hipLaunchKernelGGL(ka, dim3(8 * ((a.n_seq * a.H + 7) / 8) * ((a.Lq + 255) / 256)), dim3(512), C::LDS, st, a);
-            return vq_check_launch();
-        }
-    }
-#endif
     if (const int rc = vq_prepare_kernel<k>(C::LDS)) return rc;
     const int nqt = (a.Lq + 32 * NW * NQ - 1) / (32 * NW * NQ), G = a.n_seq * a.H;
     dim3 grid(8 * ((G + 7) / 8) * nqt);
@@ -2562,73 +2528,30 @@ static int launch_attn8(const AttnArgs& a, hipStream_t st) {
     return vq_check_launch();
 }
 
-#if defined(VQ_ATTN_64) && VQ_ATTN_64 > 0   // lab builds only: routes of the round-6 A/B kernels (never returned by the product library)
-#define VQ_ATTN_K_LAB_64D_128 100            // attn_fwd64d_kernel<D, 8, 128>
-#define VQ_ATTN_K_LAB_64D_NW4 101            // attn_fwd64d_kernel<D, 4, 64>
-#define VQ_ATTN_K_LAB_64P 102                // attn_fwd64p_kernel (tools/lab/attn_phased.h)
-#endif
-#ifdef VQ_ATTN_STREAM_LAB
-#define VQ_ATTN_K_LAB_64S 103                // attn_fwd64s_kernel (tools/lab/attn_stream.h)
-#endif
-
-// The kernel vq_attn_fwd runs for these (checked) arguments: a VQ_ATTN_K_* id of include/viditq.h.  The one place the
-// dispatch is decided - launch_attn switches on it and vq_attn_fwd_route returns it - so the test hook cannot disagree
-// with the launch.  No HIP call.
+// The kernel vq_attn_fwd runs for these (checked) arguments: a VQ_ATTN_K_* id of include/viditq.h, whose comments give the
+// same table.  The one place the dispatch is decided - launch_attn switches on it and vq_attn_fwd_route returns it - so the
+// test hook cannot disagree with the launch.  No HIP call, no switch: the retired arms live in the lab's attn_lab.hip.
 template <int D>
 static int attn_route(const AttnArgs& a) {
-    // second-generation kernel for long key sequences; short ones (cross attention: <= 2 key tiles, where the
-    // per-workgroup prologue dominates) and short query sequences keep the first kernel.  VQ_ATTN_V1 forces it.
-    static const bool old_kernel = getenv("VQ_ATTN_V1") != nullptr;
-    // short key/value sequences with a known bound (cross attention over <= 128 prompt tokens): K, V^T in registers
-    static const bool no_reg = getenv("VQ_ATTN_CROSS_REG") && atoi(getenv("VQ_ATTN_CROSS_REG")) == 0;   // measurement switch
-    // VQ_ATTN_CROSS=reg keeps the round-1 register-resident kernel (A/B measurements); default: K / V resident in LDS
-    static const bool cross_reg = getenv("VQ_ATTN_CROSS") && getenv("VQ_ATTN_CROSS")[0] == 'r';
-    if (!old_kernel && !no_reg && !cross_reg && a.Lk > 0 && a.Lk <= 128 && a.Lq >= 256 &&
-        (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31))
-        return VQ_ATTN_K_CROSS32_2;
-    // round 6: prompts of up to 320 tokens (PixArt-Sigma: 300) with every sample's keys given by offsets - K / V of a
-    // (sequence, head) pair resident in 3 ... 5 tile images, one workgroup per CU.  VQ_ATTN_CROSS_LONG=0: the generic kernel (A/B)
-    static const bool no_long = getenv("VQ_ATTN_CROSS_LONG") && atoi(getenv("VQ_ATTN_CROSS_LONG")) == 0;
+    const bool off32 = (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31);     // K / V addressed with 32-bit byte offsets
+    // cross attention, Lq >= 256: K / V of a (sequence, head) pair resident in LDS - two 64-key tile images for a known
+    // bound of <= 128 prompt tokens, 3 ... 5 (one workgroup per CU) for bounds up to 320 with per-sample offsets
+    // (PixArt-Sigma: 300)
+    if (a.Lk > 0 && a.Lk <= 128 && a.Lq >= 256 && off32) return VQ_ATTN_K_CROSS32_2;
     if constexpr (D >= 64) {
-        if (!old_kernel && !no_reg && !cross_reg && !no_long && a.kv_off && a.Lk > 128 && a.Lk <= 320 && a.Lq >= 256 &&
-            (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31))
+        if (a.kv_off && a.Lk > 128 && a.Lk <= 320 && a.Lq >= 256 && off32)
             return a.Lk <= 192 ? VQ_ATTN_K_CROSS32_3 : a.Lk <= 256 ? VQ_ATTN_K_CROSS32_4 : VQ_ATTN_K_CROSS32_5;
     }
-    if (D == 72 && !old_kernel && !no_reg && a.Lk > 0 && a.Lk <= 128 && a.H % 8 == 0 && a.Lq >= 64) return VQ_ATTN_K_CROSS_REG;
-    if (!old_kernel && !a.kv_off && a.Lk > 128 && a.Lq >= 96)
-    {
-        // long query sequences: 32 queries per wave, LDS-DMA tiles, four waves per SIMD (attn_fwd32d_kernel; its buffer
-        // loads carry 32-bit byte offsets).  VQ_ATTN_LONG=8 keeps the previous generation for A/B measurements.
-        static const bool gen8 = getenv("VQ_ATTN_LONG") && atoi(getenv("VQ_ATTN_LONG")) == 8;
-        // VQ_ATTN_NW=4 (measurement arm, round 5): four waves per workgroup - three independent workgroups per CU by LDS
-        // instead of two lock-stepped groups of eight
-        static const bool nw4 = getenv("VQ_ATTN_NW") && atoi(getenv("VQ_ATTN_NW")) == 4;
-#if defined(VQ_ATTN_64) && VQ_ATTN_64 > 0   // round-6 A/B builds: 64 queries per wave everywhere (1: 64-key tiles, 2: 128-key tiles,
-        if (!gen8 && a.Lq >= 512 && (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31)) {  // 3: four waves per workgroup, two workgroups per CU; 4 / 5: opposite phases)
-            if (D >= 64 && (VQ_ATTN_64 == 4 || VQ_ATTN_64 == 5)) return VQ_ATTN_K_LAB_64P;
-            return VQ_ATTN_64 == 2 ? VQ_ATTN_K_LAB_64D_128 : VQ_ATTN_64 == 3 ? VQ_ATTN_K_LAB_64D_NW4 : VQ_ATTN_K_FWD64D;
-        }
-#else
+    // ... and shorter query sequences: K, V^T in registers
+    if (D == 72 && a.Lk > 0 && a.Lk <= 128 && a.H % 8 == 0 && a.Lq >= 64) return VQ_ATTN_K_CROSS_REG;
+    // long key sequences of one length: the LDS-DMA kernels.  Short ones (<= 2 key tiles, where the per-workgroup
+    // prologue dominates), short query sequences and offsets with an unknown bound keep the first kernel.
+    if (!a.kv_off && a.Lk > 128 && a.Lq >= 96) {
         // 64 queries per wave (attn_fwd64d_kernel) where a workgroup walks MANY key tiles (PixArt-Sigma's 4096-token images:
         // 181.4 vs 188.1 us, round 6); at 1024 keys the two forms tie (111.7 vs 111.6 us) and the 32-query form stays
-        if (!gen8 && a.Lq >= 2048 && a.Lk >= 2048 && (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31)) return VQ_ATTN_K_FWD64D;
-#ifdef VQ_ATTN_STREAM_LAB
-        // the two query tiles of a pair as one tile stream (attn_fwd64s_kernel) where the plain launch would be SEVERAL generations
-        // of short-lived workgroups: >= 512 tiles of 512 queries (STDiT's spatial attention: 256 pairs x 2 tiles, 16 key tiles each).
-        // VQ_ATTN_STREAM=0 keeps the 32-query form (A/B measurements).
-        const char* se = getenv("VQ_ATTN_STREAM");      // (read per call: the bit-identity test flips it inside one process)
-        const bool no_stream = se && atoi(se) == 0;
-        if constexpr (D % 8 == 0 && D >= 64) {
-            const long tiles64 = (long)a.n_seq * a.H * ((a.Lq + 511) / 512);
-            // (>= 64 D / 512 key tiles per query tile: that many tiles carry the parked O rows out; >= 4 for the Q prefetch)
-            if (!gen8 && !no_stream && !nw4 && a.Lq > 512 && a.Lk >= 64 * (64 * D * 2 / 1024) && tiles64 >= 512 && (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31) &&
-                (long)a.Lq * a.q_tok_stride * 2 < (1l << 31))
-                return VQ_ATTN_K_LAB_64S;
-        }
-#endif
-#endif
-        if (!gen8 && a.Lq >= 192 && (long)a.Lk * a.kv_tok_stride * 2 < (1l << 31))
-            return (nw4 && D == 72) ? VQ_ATTN_K_FWD32D_NW4 : VQ_ATTN_K_FWD32D;
+        if (off32 && a.Lq >= 2048 && a.Lk >= 2048) return VQ_ATTN_K_FWD64D;
+        // 32 queries per wave, four waves per SIMD (attn_fwd32d_kernel)
+        if (off32 && a.Lq >= 192) return VQ_ATTN_K_FWD32D;
         return a.Lq >= 192 ? VQ_ATTN_K_FWD8_NW8 : VQ_ATTN_K_FWD8_NW4;
     }
     return VQ_ATTN_K_FWD;
@@ -2643,16 +2566,7 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
         case VQ_ATTN_K_CROSS32_5: if constexpr (D >= 64) return launch_cross32<D, 5>(a, st); break;
         case VQ_ATTN_K_CROSS_REG: return launch_cross_reg(a, st);
         case VQ_ATTN_K_FWD64D: return launch_attn64d<D>(a, st);
-#if defined(VQ_ATTN_64) && VQ_ATTN_64 > 0
-        case VQ_ATTN_K_LAB_64D_128: return launch_attn64d<D, 8, 128>(a, st);
-        case VQ_ATTN_K_LAB_64D_NW4: return launch_attn64d<D, 4, 64>(a, st);
-        case VQ_ATTN_K_LAB_64P: if constexpr (D >= 64) return launch_attn64p<D, VQ_ATTN_64 == 4 ? 3 : 4>(a, st); break;
-#endif
-#ifdef VQ_ATTN_STREAM_LAB
-        case VQ_ATTN_K_LAB_64S: if constexpr (D % 8 == 0 && D >= 64) return launch_attn64s<D>(a, st); break;
-#endif
         case VQ_ATTN_K_FWD32D: return launch_attn32d<D>(a, st);
-        case VQ_ATTN_K_FWD32D_NW4: if constexpr (D == 72) return launch_attn32d<D, 4>(a, st); break;
         case VQ_ATTN_K_FWD8_NW8: return launch_attn8<D, 8>(a, st);
         case VQ_ATTN_K_FWD8_NW4: return launch_attn8<D, 4>(a, st);
         case VQ_ATTN_K_FWD: {
@@ -2667,22 +2581,6 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
     }
     return VQ_EUNSUP;     // (a route without a kernel for this head dim: attn_route never returns one)
 }
-
-#ifdef VQ_ATTN_STAMPS   // lab builds only: the phased kernel with cycle stamps (D = 72): stamps = uint32[workgroups][8 waves][16]
-extern "C" int vq_lab_attn64p_stamped(const void* q, const void* k, const void* v, void* o, int n_seq, int Lq, int Lk, int H,
-                                      long q_seq_stride, long q_tok_stride, long kv_seq_stride, long kv_tok_stride,
-                                      long o_seq_stride, long o_tok_stride, float scale, void* stamps, void* stream) {
-    AttnArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, (half_t*)o, q_seq_stride, q_tok_stride,
-               kv_seq_stride, kv_tok_stride, o_seq_stride, o_tok_stride, nullptr, n_seq, Lq, Lk, H, scale * ATT_LOG2E};
-    constexpr int NB = VQ_ATTN_STAMPS;
-    constexpr int LDS = NB * (Att8Cfg<72, 8>::KTILE + 64 * 192);
-    auto kern = attn_fwd64p_kernel<72, NB, 1>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    const int nqt = (Lq + 511) / 512, G = n_seq * H;
-    hipLaunchKernelGGL(kern, dim3(8 * ((G + 7) / 8) * nqt), dim3(512), LDS, (hipStream_t)stream, a, (long long*)stamps);
-    return vq_check_launch();
-}
-#endif
 
 // Argument checks of vq_attn_fwd / vq_attn_fwd_route (no dereference, no HIP call): VQ_OK with *a filled, or the error code.
 static int attn_fwd_args(const void* q, const void* k, const void* v, void* o, int n_seq, int Lq, int Lk, int H,
@@ -2744,20 +2642,19 @@ extern "C" int vq_attn_temporal(const void* q, const void* k, const void* v, voi
     return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal<d()>(a, st); });
 }
 
+// H = 16 heads, 32-bit byte offsets inside a position's rows: the instruction-trimmed kernel (round 6)
+static bool temporal_quant_trimmed(const TempQArgs& a) {
+    return a.H == 16 && a.Kp <= 2048 && (long)a.T * a.S * a.ld_in * 2 < (1l << 31) && (long)a.T * a.S * a.Kp < (1l << 31);
+}
+
 template <int D>
-static int launch_temporal_quant(const TempQArgs& a, hipStream_t st) {
+static int launch_temporal_quant(const TempQArgs& a, hipStream_t st, bool trimmed) {
     const int C = a.H * D;
     const int LDS = 16 * (C * 2 + 16) + 16 * (C + 16) + 3 * 1024;
     constexpr int LDS_MAX = 16 * (16 * 72 * 2 + 16) + 16 * (16 * 72 + 16) + 3 * 1024;
     constexpr auto k2 = attn_temporal_quant2_kernel<D>;
     constexpr auto k16 = attn_temporal_quant_kernel<D, 16>;
     constexpr auto k0 = attn_temporal_quant_kernel<D, 0>;
-#ifndef VQ_TEMPORAL_V1   // (A/B builds: -DVQ_TEMPORAL_V1 keeps the round-3 kernel everywhere)
-    // H = 16 heads, 32-bit byte offsets inside a position's rows: the instruction-trimmed kernel (round 6)
-    const bool trimmed = a.H == 16 && a.Kp <= 2048 && (long)a.T * a.S * a.ld_in * 2 < (1l << 31) && (long)a.T * a.S * a.Kp < (1l << 31);
-#else
-    const bool trimmed = false;
-#endif
     int ncu = 0;
     if (const int rc = trimmed ? vq_prepare_kernel<k2>(LDS_MAX, &ncu)
                                : a.H == 16 ? vq_prepare_kernel<k16>(LDS_MAX, &ncu) : vq_prepare_kernel<k0>(LDS_MAX, &ncu))
@@ -2770,9 +2667,10 @@ static int launch_temporal_quant(const TempQArgs& a, hipStream_t st) {
     return vq_check_launch();
 }
 
-extern "C" int vq_attn_temporal_rowquant(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
-                                         int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o, int B,
-                                         int T, int S, int H, int D, long ld_in, int Kp, float scale, void* stream) {
+// Argument checks of vq_attn_temporal_rowquant (no dereference, no HIP call): VQ_OK with *a filled, or the error code.
+static int temporal_quant_args(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
+                               int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o, int B,
+                               int T, int S, int H, int D, long ld_in, int Kp, float scale, TempQArgs* a) {
     if (!q || !k || !v || !xq || !sx || !zx || !R) return VQ_EINVAL;
     if ((s != nullptr) != (s_rcp != nullptr)) return VQ_EINVAL;     // the division exists in reciprocal form only here
     if (B <= 0 || T <= 0 || S <= 0 || H <= 0) return VQ_EINVAL;
@@ -2782,10 +2680,18 @@ extern "C" int vq_attn_temporal_rowquant(const void* q, const void* k, const voi
     // 16-byte loads of q / k / v, float4 reads of s / s_rcp, 16-byte code stores; o: 16 bytes as everywhere else
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)xq | (uintptr_t)s | (uintptr_t)s_rcp | (uintptr_t)o) % 16 != 0)
         return VQ_ESHAPE;
-    TempQArgs a{(const half_t*)q, (const half_t*)k, (const half_t*)v, xq, sx, zx, R, status, (half_t*)o, s, s_rcp, ld_in, /*ld_out*/ C,
-                B, T, S, H, Kp, scale * ATT_LOG2E};
+    *a = TempQArgs{(const half_t*)q, (const half_t*)k, (const half_t*)v, xq, sx, zx, R, status, (half_t*)o, s, s_rcp, ld_in, /*ld_out*/ C,
+                   B, T, S, H, Kp, scale * ATT_LOG2E};
+    return VQ_OK;
+}
+
+extern "C" int vq_attn_temporal_rowquant(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
+                                         int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o, int B,
+                                         int T, int S, int H, int D, long ld_in, int Kp, float scale, void* stream) {
+    TempQArgs a;
+    if (const int rc = temporal_quant_args(q, k, v, s, s_rcp, xq, sx, zx, R, status, o, B, T, S, H, D, ld_in, Kp, scale, &a)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_quant<d()>(a, st); });
+    return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_quant<d()>(a, st, temporal_quant_trimmed(a)); });
 }
 
 template <int D>

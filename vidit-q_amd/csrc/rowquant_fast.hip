@@ -17,6 +17,62 @@
 #define RQF_WAVES 4
 #define RQF_THREADS (RQF_WAVES * 64)
 
+// ---- host side: the dispatch every entry point below shares -----------------
+// The half-wave kernels are compiled for rows of C = 128 * NIT channels, NIT in {6, 8, 9, 10}: the hidden sizes 768, 1024,
+// 1152 and 1280.  (The sources used to spell this set in two ways; the second, C % 128 == 0 && 768 <= C <= 1280, also let
+// 896 through to a width switch that had no kernel for it and fell back - the assert below pins exactly that.)
+constexpr bool rq_block_width(int C) { return C % 128 == 0 && (C / 128 == 6 || C / 128 == 8 || C / 128 == 9 || C / 128 == 10); }
+constexpr bool rq_block_width_is_both_spellings() {
+    for (int C = 0; C <= 8192; ++C) {
+        const bool named = C == 1152 || C == 1024 || C == 1280 || C == 768;
+        const bool range = C % 128 == 0 && C >= 768 && C <= 1280;
+        if (rq_block_width(C) != named || rq_block_width(C) != (range && C != 896)) return false;
+    }
+    return true;
+}
+static_assert(rq_block_width_is_both_spellings(), "one predicate for the widths of the half-wave kernels");
+
+// f(std::integral_constant<int, NIT>) and true at a block width, false (nothing launched) at any other C
+template <class F>
+static bool vq_dispatch_nit(int C, F&& f) {
+    const int nit = rq_block_width(C) ? C / 128 : 0;
+    switch (nit) {
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        case 9: f(std::integral_constant<int, 9>{}); break;
+        case 10: f(std::integral_constant<int, 10>{}); break;
+        default: return false;
+    }
+    return true;
+}
+
+// f(std::integral_constant<int, MAXCH>): the 16-byte chunks per lane the one-row-per-wave kernels hold for a padded row of Kp
+template <class F>
+static void vq_dispatch_maxch(int Kp, F&& f) {
+    if (Kp <= 512) f(std::integral_constant<int, 1>{});
+    else if (Kp <= 1536) f(std::integral_constant<int, 3>{});
+    else f(std::integral_constant<int, 9>{});
+}
+
+template <class F>
+static void vq_dispatch_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// The two environment variables this file reads, each here and nowhere else, once per process.  They are TEST ARMS, not
+// tuning knobs: tests/test_kernels_gpu.py and tests/test_quantizer_edges_gpu.py start a child process with VQ_RQ_SPLIT=0 /
+// VQ_RQ_SM1=0 to obtain the kernel the default one must match bit for bit (one row per wave at C = 4608;
+// smooth_rowquant_half_kernel for one smoothed output).
+static bool rq_split_enabled() {
+    static const bool on = !(getenv("VQ_RQ_SPLIT") && atoi(getenv("VQ_RQ_SPLIT")) == 0);
+    return on;
+}
+static int vq_sm1_mode() {
+    static const int mode = getenv("VQ_RQ_SM1") ? atoi(getenv("VQ_RQ_SM1")) : 1;
+    return mode;
+}
+
 // VALU is what bounds these kernels at C = 1152 (~11 us of ~17 at 16384 rows), so the per-element sequence is
 // kept minimal: the row's own min/max defines delta, hence |x/delta| <= 255 (no magnitude guard needed here),
 // the rounding-boundary guard is one subtract + one compare, and for 8-bit codes v_cvt_pk_u8_f32 itself
@@ -598,6 +654,18 @@ struct LnqFastOut {
     int32_t* zx[3];
     int32_t* R[3];
 };
+static LnqFastOut lnq_many(int n_out, const float* const* s, const float* const* r, int8_t* const* xq, float* const* sx,
+                           int32_t* const* zx, int32_t* const* R) {   // s, r: may be null; outputs >= n_out stay null
+    LnqFastOut o{};
+    for (int j = 0; j < n_out; ++j) {
+        o.s[j] = s ? s[j] : nullptr, o.r[j] = r ? r[j] : nullptr;
+        o.xq[j] = xq[j], o.sx[j] = sx[j], o.zx[j] = zx[j], o.R[j] = R[j];
+    }
+    return o;
+}
+static LnqFastOut lnq_one(const float* s, const float* r, int8_t* xq, float* sx, int32_t* zx, int32_t* R) {
+    return lnq_many(1, &s, &r, &xq, &sx, &zx, &R);
+}
 
 template <int MAXCH, int NOUT>
 __global__ __launch_bounds__(RQF_THREADS) void ln_modulate_rowquant_fast_kernel(
@@ -962,18 +1030,10 @@ static bool launch_smooth_half(const half_t* x, const float* shift, const float*
                                int n_out, half_t* xm, int n_tok, int C, int n_bits, int32_t* status, hipStream_t st) {
     constexpr int PER = (PAIR ? 1 : 2) * RQF_WAVES * RPW;   // rows (PAIR: tokens) per workgroup
     dim3 grid((n_tok + PER - 1) / PER, n_out);
-#define SMH_GO(N_)                                                                                                  \
-    hipLaunchKernelGGL((smooth_rowquant_half_kernel<N_, LN, RPW, PAIR>), grid, dim3(RQF_THREADS), 0, st, x, shift, scale, eps, \
-                       o, xm, n_tok, n_bits, status)
-    switch (C / 128) {
-        case 6: SMH_GO(6); break;
-        case 8: SMH_GO(8); break;
-        case 9: SMH_GO(9); break;
-        case 10: SMH_GO(10); break;
-        default: return false;
-    }
-#undef SMH_GO
-    return true;
+    return vq_dispatch_nit(C, [&](auto nit) {
+        hipLaunchKernelGGL((smooth_rowquant_half_kernel<nit(), LN, RPW, PAIR>), grid, dim3(RQF_THREADS), 0, st, x, shift, scale,
+                           eps, o, xm, n_tok, n_bits, status);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -988,28 +1048,9 @@ static bool launch_smooth_half(const half_t* x, const float* shift, const float*
 // ---------------------------------------------------------------------------
 // One smoothed output through the same kernel (round 5; VQ_RQ_SM1=0 keeps smooth_rowquant_half_kernel): with the vectors in
 // LDS a wave needs ~80 registers instead of 167 (LN: 248), i.e. every wave of a launch is resident at once.
-#ifndef VQ_SM1_MINW
-#define VQ_SM1_MINW 6
-#endif
-#ifndef VQ_SM1_RPW
-#define VQ_SM1_RPW 1
-#endif
-#ifndef VQ_SM1_NWV
-#define VQ_SM1_NWV 8
-#endif
-#ifndef VQ_SMM_RPW       // the two- / three-output launches: row pairs per wave, waves per workgroup, waves per SIMD asked of the compiler
-#define VQ_SMM_RPW 1
-#endif
-#ifndef VQ_SMM_NWV
-#define VQ_SMM_NWV 8
-#endif
-#ifndef VQ_SMM_MINW
-#define VQ_SMM_MINW 4
-#endif
-static int vq_sm1_mode() {
-    static const int mode = getenv("VQ_RQ_SM1") ? atoi(getenv("VQ_RQ_SM1")) : 1;
-    return mode;
-}
+// waves per SIMD asked of the compiler, row pairs per wave, waves per workgroup: one output / two or three
+constexpr int VQ_SM1_MINW = 6, VQ_SM1_RPW = 1, VQ_SM1_NWV = 8;
+constexpr int VQ_SMM_MINW = 4, VQ_SMM_RPW = 1, VQ_SMM_NWV = 8;
 template <int NIT, bool LN, int NOUT, int RPW, int NWV>
 __global__ __launch_bounds__(64 * NWV, NOUT == 1 ? VQ_SM1_MINW : VQ_SMM_MINW) void smooth_rowquant_multi_kernel(
     const half_t* __restrict__ x, const float* __restrict__ shift, const float* __restrict__ scale, float ln_eps,
@@ -1143,36 +1184,33 @@ static bool launch_smooth_multi(const half_t* x, const float* shift, const float
     constexpr int RPW = NOUT == 1 ? VQ_SM1_RPW : VQ_SMM_RPW, NWV = NOUT == 1 ? VQ_SM1_NWV : VQ_SMM_NWV;
     const size_t lds = (size_t)(2 * NOUT + (LN ? 2 : 0)) * C * sizeof(float);
     dim3 grid((n_tok + 2 * NWV * RPW - 1) / (2 * NWV * RPW));
-#define SMM_GO(N_)                                                                                                   \
-    hipLaunchKernelGGL((smooth_rowquant_multi_kernel<N_, LN, NOUT, RPW, NWV>), grid, dim3(64 * NWV), lds, st, x, shift, \
-                       scale, eps, o, xm, n_tok, n_bits, status)
-    switch (C / 128) {                                     // <= 8 x 5 KB of LDS: inside the 64 KB every kernel may use
-        case 6: SMM_GO(6); break;
-        case 8: SMM_GO(8); break;
-        case 9: SMM_GO(9); break;
-        case 10: SMM_GO(10); break;
-        default: return false;
-    }
-#undef SMM_GO
-    return true;
+    return vq_dispatch_nit(C, [&](auto nit) {              // <= 8 x 5 KB of LDS: inside the 64 KB every kernel may use
+        hipLaunchKernelGGL((smooth_rowquant_multi_kernel<nit(), LN, NOUT, RPW, NWV>), grid, dim3(64 * NWV), lds, st, x, shift,
+                           scale, eps, o, xm, n_tok, n_bits, status);
+    });
 }
 
 // ---------------------------------------------------------------------------
 // host dispatch (called from the C ABI entry points in rowquant.hip)
 // ---------------------------------------------------------------------------
-template <int MAXCH>
-static void launch_rq(bool has_s, bool has_add, dim3 grid, hipStream_t st, const half_t* x, const half_t* add_rows,
-                      int add_div, const float* s, const float* s_rcp, int8_t* xq, float* sx, int32_t* zx, int32_t* R, float* zpf,
-                      int n_tok, int C, int Kp, int n_bits, int32_t* status) {
-    dim3 block(RQF_THREADS);
-#define RQ_GO(S_, A_)                                                                                              \
-    hipLaunchKernelGGL((rowquant_fast_kernel<MAXCH, S_, A_>), grid, block, 0, st, x, add_rows, add_div, s, s_rcp, xq, \
-                       sx, zx, R, zpf, n_tok, C, Kp, n_bits, status)
-    if (has_s && has_add) RQ_GO(true, true);
-    else if (has_s) RQ_GO(true, false);
-    else if (has_add) RQ_GO(false, true);
-    else RQ_GO(false, false);
-#undef RQ_GO
+// rowquant_fast_kernel<MAXCH, HAS_S, HAS_ADD, GELU, PAIR>, one row per wave (PAIR: per partner wave), for these operands.
+// Only the forms an entry point can ask for are compiled: added rows exist for the plain quantizer alone, and the plain
+// pair quantizer takes no smoothing vector.
+template <bool GELU, bool PAIR>
+static void launch_rq(const half_t* x, const half_t* add_rows, int add_div, const float* s, const float* s_rcp, int8_t* xq,
+                      float* sx, int32_t* zx, int32_t* R, float* zpf, int n_tok, int C, int Kp, int n_bits, int32_t* status,
+                      hipStream_t st) {
+    constexpr int PER = PAIR ? RQF_WAVES / 2 : RQF_WAVES;   // tokens per workgroup
+    dim3 grid((n_tok + PER - 1) / PER);
+    vq_dispatch_maxch(Kp, [&](auto m) {
+        vq_dispatch_bool(s != nullptr, [&](auto hs) {
+            vq_dispatch_bool(add_rows != nullptr, [&](auto ha) {
+                if constexpr ((!ha() || (!GELU && !PAIR)) && (!hs() || GELU || !PAIR))
+                    hipLaunchKernelGGL((rowquant_fast_kernel<m(), hs(), ha(), GELU, PAIR>), grid, dim3(RQF_THREADS), 0, st, x, add_rows,
+                                       add_div, s, s_rcp, xq, sx, zx, R, zpf, n_tok, C, Kp, n_bits, status);
+            });
+        });
+    });
 }
 
 bool vq_rowquant_fast(const half_t* x, const half_t* add_rows, int add_div, const float* s, const float* s_rcp,
@@ -1183,28 +1221,19 @@ bool vq_rowquant_fast(const half_t* x, const half_t* add_rows, int add_div, cons
     if (hs && s_rcp && !ha && !zpf && C > 1536 && n_tok >= 64 &&
         launch_rq_smooth_lds<false>(x, s, s_rcp, xq, sx, zx, R, n_tok, C, Kp, n_bits, status, st))
         return true;
-    if (hs && s_rcp && !ha && !zpf && C % 128 == 0 && Kp == C && C >= 768 && C <= 1280 && n_tok >= 2) {
-        LnqFastOut o{};
-        o.s[0] = s, o.r[0] = s_rcp, o.xq[0] = xq, o.sx[0] = sx, o.zx[0] = zx, o.R[0] = R;
+    const bool half_wave = rq_block_width(C) && Kp == C && n_tok >= 2;
+    if (hs && s_rcp && !ha && !zpf && half_wave) {
+        const LnqFastOut o = lnq_one(s, s_rcp, xq, sx, zx, R);
         if (vq_sm1_mode() && launch_smooth_multi<false, 1>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;
         if (launch_smooth_half<false, 2>(x, nullptr, nullptr, 0.f, o, 1, nullptr, n_tok, C, n_bits, status, st)) return true;
     }
-    if (!hs && !ha && C % 128 == 0 && Kp == C && (C == 1152 || C == 1024 || C == 1280 || C == 768) && n_tok >= 2) {
+    if (!hs && !ha && half_wave) {
         dim3 g2((n_tok + 2 * RQF_WAVES - 1) / (2 * RQF_WAVES));
-#define RQH_GO(N_) hipLaunchKernelGGL((rowquant_half_kernel<N_>), g2, dim3(RQF_THREADS), 0, st, x, xq, sx, zx, R, zpf, n_tok, n_bits, status)
-        switch (C / 128) {
-            case 6: RQH_GO(6); break;
-            case 8: RQH_GO(8); break;
-            case 9: RQH_GO(9); break;
-            default: RQH_GO(10); break;
-        }
-#undef RQH_GO
-        return true;
+        return vq_dispatch_nit(C, [&](auto nit) {
+            hipLaunchKernelGGL((rowquant_half_kernel<nit()>), g2, dim3(RQF_THREADS), 0, st, x, xq, sx, zx, R, zpf, n_tok, n_bits, status);
+        });
     }
-    dim3 grid((n_tok + RQF_WAVES - 1) / RQF_WAVES);
-    if (Kp <= 512) launch_rq<1>(hs, ha, grid, st, x, add_rows, add_div, s, s_rcp, xq, sx, zx, R, zpf, n_tok, C, Kp, n_bits, status);
-    else if (Kp <= 1536) launch_rq<3>(hs, ha, grid, st, x, add_rows, add_div, s, s_rcp, xq, sx, zx, R, zpf, n_tok, C, Kp, n_bits, status);
-    else launch_rq<9>(hs, ha, grid, st, x, add_rows, add_div, s, s_rcp, xq, sx, zx, R, zpf, n_tok, C, Kp, n_bits, status);
+    launch_rq<false, false>(x, add_rows, add_div, s, s_rcp, xq, sx, zx, R, zpf, n_tok, C, Kp, n_bits, status, st);
     return true;
 }
 
@@ -1213,26 +1242,13 @@ bool vq_rowquant_fast(const half_t* x, const half_t* add_rows, int add_div, cons
 bool vq_rowquant_pair_fast(const half_t* x, int8_t* xq, float* sx, int32_t* zx, int32_t* R, float* zpf, int n_tok, int C,
                            int Kp, int n_bits, int32_t* status, hipStream_t st) {
     if (C > 4608 || Kp > 4608) return false;
-    if (C % 128 == 0 && Kp == C && (C == 1152 || C == 1024 || C == 1280 || C == 768)) {
+    if (rq_block_width(C) && Kp == C) {
         dim3 g2((n_tok + RQF_WAVES - 1) / RQF_WAVES);
-#define RQP_GO(N_) hipLaunchKernelGGL((rowquant_half_kernel<N_, true>), g2, dim3(RQF_THREADS), 0, st, x, xq, sx, zx, R, zpf, n_tok, n_bits, status)
-        switch (C / 128) {
-            case 6: RQP_GO(6); break;
-            case 8: RQP_GO(8); break;
-            case 9: RQP_GO(9); break;
-            default: RQP_GO(10); break;
-        }
-#undef RQP_GO
-        return true;
+        return vq_dispatch_nit(C, [&](auto nit) {
+            hipLaunchKernelGGL((rowquant_half_kernel<nit(), true>), g2, dim3(RQF_THREADS), 0, st, x, xq, sx, zx, R, zpf, n_tok, n_bits, status);
+        });
     }
-    dim3 grid((n_tok + RQF_WAVES / 2 - 1) / (RQF_WAVES / 2)), block(RQF_THREADS);
-#define RQP_GO(M_)                                                                                                   \
-    hipLaunchKernelGGL((rowquant_fast_kernel<M_, false, false, false, true>), grid, block, 0, st, x, (const half_t*)nullptr, \
-                       1, (const float*)nullptr, (const float*)nullptr, xq, sx, zx, R, zpf, n_tok, C, Kp, n_bits, status)
-    if (Kp <= 512) RQP_GO(1);
-    else if (Kp <= 1536) RQP_GO(3);
-    else RQP_GO(9);
-#undef RQP_GO
+    launch_rq<false, true>(x, nullptr, 1, nullptr, nullptr, xq, sx, zx, R, zpf, n_tok, C, Kp, n_bits, status, st);
     return true;
 }
 
@@ -1241,82 +1257,60 @@ bool vq_rowquant_pair_smooth_fast(const half_t* x, const float* s, const float* 
                                   int32_t* R, int n_tok, int C, int Kp, int n_bits, int32_t* status, hipStream_t st) {
     if (C > 1536)
         return n_tok >= 2 && launch_rq_smooth_lds<false, true>(x, s, s_rcp, xq, sx, zx, R, n_tok, C, Kp, n_bits, status, st);
-    if (C % 128 != 0 || Kp != C || C < 768 || C > 1280) return false;
-    LnqFastOut o{};
-    o.s[0] = s, o.r[0] = s_rcp, o.xq[0] = xq, o.sx[0] = sx, o.zx[0] = zx, o.R[0] = R;
-    return launch_smooth_half<false, 2, true>(x, nullptr, nullptr, 0.f, o, 1, nullptr, n_tok, C, n_bits, status, st);
+    if (!rq_block_width(C) || Kp != C) return false;
+    return launch_smooth_half<false, 2, true>(x, nullptr, nullptr, 0.f, lnq_one(s, s_rcp, xq, sx, zx, R), 1, nullptr, n_tok, C, n_bits,
+                                              status, st);
 }
 
 bool vq_lnq_pair_fast(const half_t* x, const float* shift, const float* scale, float eps, const float* s, const float* s_rcp,
                       int8_t* xq, float* sx,
                       int32_t* zx, int32_t* R, half_t* xm, int n_tok, int C, int Kp, int n_bits, int32_t* status, hipStream_t st) {
-    if (Kp != C || !(C == 1152 || C == 1024 || C == 1280 || C == 768)) return false;
+    if (Kp != C || !rq_block_width(C)) return false;
     if (s) {
         if (!s_rcp || xm) return false;
-        LnqFastOut o{};
-        o.s[0] = s, o.r[0] = s_rcp, o.xq[0] = xq, o.sx[0] = sx, o.zx[0] = zx, o.R[0] = R;
-        return launch_smooth_half<true, 2, true>(x, shift, scale, eps, o, 1, nullptr, n_tok, C, n_bits, status, st);
+        return launch_smooth_half<true, 2, true>(x, shift, scale, eps, lnq_one(s, s_rcp, xq, sx, zx, R), 1, nullptr, n_tok, C, n_bits,
+                                                 status, st);
     }
     dim3 g2((n_tok + RQF_WAVES - 1) / RQF_WAVES);
-#define LNP_GO(N_)                                                                                                    \
-    if (xm)                                                                                                           \
-        hipLaunchKernelGGL((ln_modulate_rowquant_half_kernel<N_, true, true>), g2, dim3(RQF_THREADS), 0, st, x, shift,   \
-                           scale, eps, xq, sx, zx, R, n_tok, n_bits, status, xm);                                     \
-    else                                                                                                              \
-        hipLaunchKernelGGL((ln_modulate_rowquant_half_kernel<N_, true>), g2, dim3(RQF_THREADS), 0, st, x, shift, scale, eps, \
-                           xq, sx, zx, R, n_tok, n_bits, status, (half_t*)nullptr)
-    switch (C / 128) {
-        case 6: LNP_GO(6); break;
-        case 8: LNP_GO(8); break;
-        case 9: LNP_GO(9); break;
-        default: LNP_GO(10); break;
-    }
-#undef LNP_GO
-    return true;
+    return vq_dispatch_nit(C, [&](auto nit) {
+        vq_dispatch_bool(xm != nullptr, [&](auto has_xm) {
+            hipLaunchKernelGGL((ln_modulate_rowquant_half_kernel<nit(), true, has_xm()>), g2, dim3(RQF_THREADS), 0, st, x, shift,
+                               scale, eps, xq, sx, zx, R, n_tok, n_bits, status, xm);
+        });
+    });
 }
 
 template <int MAXCH>
 static void launch_lnq(int n_out, dim3 grid, hipStream_t st, const half_t* x, const float* shift, const float* scale,
                        float eps, const LnqFastOut& o, half_t* xm, int n_tok, int C, int Kp, int n_bits,
                        int32_t* status) {
-    dim3 block(RQF_THREADS);
-    if (n_out == 1)
-        hipLaunchKernelGGL((ln_modulate_rowquant_fast_kernel<MAXCH, 1>), grid, block, 0, st, x, shift, scale, eps, o,
+    auto go = [&](auto nout) {
+        hipLaunchKernelGGL((ln_modulate_rowquant_fast_kernel<MAXCH, nout()>), grid, dim3(RQF_THREADS), 0, st, x, shift, scale, eps, o,
                            xm, n_tok, C, Kp, n_bits, status);
-    else if (n_out == 2)
-        hipLaunchKernelGGL((ln_modulate_rowquant_fast_kernel<MAXCH, 2>), grid, block, 0, st, x, shift, scale, eps, o,
-                           xm, n_tok, C, Kp, n_bits, status);
-    else
-        hipLaunchKernelGGL((ln_modulate_rowquant_fast_kernel<MAXCH, 3>), grid, block, 0, st, x, shift, scale, eps, o,
-                           xm, n_tok, C, Kp, n_bits, status);
+    };
+    if (n_out == 1) go(std::integral_constant<int, 1>{});
+    else if (n_out == 2) go(std::integral_constant<int, 2>{});
+    else go(std::integral_constant<int, 3>{});
 }
 
 // GELU(tanh) + (x / s) + per-token quantizer: mlp.act + the activation quantizer of mlp.fc2 in one pass
 bool vq_gelu_rowquant_fast(const half_t* x, const float* s, const float* s_rcp, int8_t* xq, float* sx, int32_t* zx,
                            int32_t* R, int n_tok, int C, int Kp, int n_bits, int32_t* status, hipStream_t st) {
     if (C > 4608 || Kp > 4608) return false;
-    // C = 4608 (the fc2 input of the XL models), no smoothing: the row split over two partner waves.  VQ_RQ_SPLIT=0 keeps the
-    // one-row-per-wave kernel (A/B measurements; bit-identical outputs).  (The SMOOTHED long-row kernel below - persistent
-    // workgroups, vectors in LDS, next row in flight - was also built in the split form, bit-identical, and the W4A8 step
-    // lost 0.8 % with it in an A/B on one box (23.75 vs 23.56 steps/s, profiles/r05_experiments.md): it already overlaps its
-    // loads with its arithmetic, the split only added a barrier per row.  Not kept.)
-    static const bool no_split = getenv("VQ_RQ_SPLIT") && atoi(getenv("VQ_RQ_SPLIT")) == 0;
     if (s && s_rcp && C > 1536 && n_tok >= 64 &&
         launch_rq_smooth_lds<true>(x, s, s_rcp, xq, sx, zx, R, n_tok, C, Kp, n_bits, status, st))
         return true;
-    if (!s && !no_split && C == 4608 && Kp == C && n_tok >= 2) {
+    // C = 4608 (the fc2 input of the XL models), no smoothing: the row split over two partner waves (bit-identical to the
+    // one-row-per-wave kernel below, rq_split_enabled).  (The SMOOTHED long-row kernel above - persistent workgroups,
+    // vectors in LDS, next row in flight - was also built in the split form, bit-identical, and the W4A8 step lost 0.8 % with
+    // it in an A/B on one box (23.75 vs 23.56 steps/s, profiles/r05_experiments.md): it already overlaps its loads with its
+    // arithmetic, the split only added a barrier per row.  Not kept.)
+    if (!s && rq_split_enabled() && C == 4608 && Kp == C && n_tok >= 2) {
         hipLaunchKernelGGL((rowquant_split_kernel<4, true, true>), dim3((n_tok + RQF_WAVES / 2 - 1) / (RQF_WAVES / 2)),
                            dim3(RQF_THREADS), 0, st, x, xq, sx, zx, R, n_tok, n_bits, status);
         return true;
     }
-    dim3 grid((n_tok + RQF_WAVES - 1) / RQF_WAVES), block(RQF_THREADS);
-#define RQG_GO(M_, S_)                                                                                            \
-    hipLaunchKernelGGL((rowquant_fast_kernel<M_, S_, false, true>), grid, block, 0, st, x, (const half_t*)nullptr, 1, s, \
-                       s_rcp, xq, sx, zx, R, (float*)nullptr, n_tok, C, Kp, n_bits, status)
-    if (Kp <= 512) { if (s) RQG_GO(1, true); else RQG_GO(1, false); }
-    else if (Kp <= 1536) { if (s) RQG_GO(3, true); else RQG_GO(3, false); }
-    else { if (s) RQG_GO(9, true); else RQG_GO(9, false); }
-#undef RQG_GO
+    launch_rq<true, false>(x, nullptr, 1, s, s_rcp, xq, sx, zx, R, nullptr, n_tok, C, Kp, n_bits, status, st);
     return true;
 }
 
@@ -1329,9 +1323,8 @@ bool vq_gelu_rowquant_pair_fast(const half_t* x, const float* s, const float* s_
     if (s && s_rcp && C > 1536 && n_tok >= 2 &&
         launch_rq_smooth_lds<true, true>(x, s, s_rcp, xq, sx, zx, R, n_tok, C, Kp, n_bits, status, st))
         return true;
-    // C = 4608 without smoothing: the (sample, half) split - four waves per token (VQ_RQ_SPLIT=0: one row per wave)
-    static const bool no_split = getenv("VQ_RQ_SPLIT") && atoi(getenv("VQ_RQ_SPLIT")) == 0;
-    if (!s && !no_split && C == 4608 && Kp == C) {
+    // C = 4608 without smoothing: the (sample, half) split - four waves per token
+    if (!s && rq_split_enabled() && C == 4608 && Kp == C) {
         hipLaunchKernelGGL((rowquant_split_kernel<4, true, true, true>), dim3(n_tok), dim3(RQF_THREADS), 0, st, x, xq, sx, zx, R, n_tok,
                            n_bits, status);
         return true;
@@ -1339,14 +1332,7 @@ bool vq_gelu_rowquant_pair_fast(const half_t* x, const float* s, const float* s_
     // every other smoothed case - a vector without a usable reciprocal (vq_smooth_reciprocal flagged a channel, or an
     // unseen vector under graph capture: s_rcp == nullptr -> IEEE division, as B = 1 falls back), short rows - takes the
     // register kernel with the smoothing operands from global memory, like the un-smoothed pair
-    dim3 grid((n_tok + RQF_WAVES / 2 - 1) / (RQF_WAVES / 2)), block(RQF_THREADS);
-#define RQGP_GO(M_, S_)                                                                                              \
-    hipLaunchKernelGGL((rowquant_fast_kernel<M_, S_, false, true, true>), grid, block, 0, st, x, (const half_t*)nullptr, \
-                       1, s, s_rcp, xq, sx, zx, R, (float*)nullptr, n_tok, C, Kp, n_bits, status)
-    if (Kp <= 512) { if (s) RQGP_GO(1, true); else RQGP_GO(1, false); }
-    else if (Kp <= 1536) { if (s) RQGP_GO(3, true); else RQGP_GO(3, false); }
-    else { if (s) RQGP_GO(9, true); else RQGP_GO(9, false); }
-#undef RQGP_GO
+    launch_rq<true, true>(x, nullptr, 1, s, s_rcp, xq, sx, zx, R, nullptr, n_tok, C, Kp, n_bits, status, st);
     return true;
 }
 
@@ -1355,46 +1341,31 @@ bool vq_lnq_fast(const half_t* x, const float* shift, const float* scale, float 
                  int32_t* const* zx, int32_t* const* R, half_t* xm, int n_tok, int C, int Kp, int n_bits, int32_t* status,
                  hipStream_t st) {
     if (Kp > 1536) return false;
+    const bool half_wave = rq_block_width(C) && Kp == C && n_tok >= 2;
     {
-        bool all = s && s_rcp && Kp == C && C % 128 == 0 && C >= 768 && C <= 1280 && n_tok >= 2;
+        bool all = s && s_rcp && half_wave;
         for (int j = 0; all && j < n_out; ++j) all = s[j] && s_rcp[j];
         if (all) {
-            LnqFastOut o{};
-            for (int j = 0; j < n_out; ++j)
-                o.s[j] = s[j], o.r[j] = s_rcp[j], o.xq[j] = xq[j], o.sx[j] = sx[j], o.zx[j] = zx[j], o.R[j] = R[j];
+            const LnqFastOut o = lnq_many(n_out, s, s_rcp, xq, sx, zx, R);
             if (n_out == 3 && launch_smooth_multi<true, 3>(x, shift, scale, eps, o, xm, n_tok, C, n_bits, status, st)) return true;
             if (n_out == 2 && launch_smooth_multi<true, 2>(x, shift, scale, eps, o, xm, n_tok, C, n_bits, status, st)) return true;
             if (n_out == 1 && vq_sm1_mode() && launch_smooth_multi<true, 1>(x, shift, scale, eps, o, xm, n_tok, C, n_bits, status, st)) return true;
             if (launch_smooth_half<true, 4>(x, shift, scale, eps, o, n_out, xm, n_tok, C, n_bits, status, st)) return true;
         }
     }
-    if (n_out == 1 && !(s && s[0]) && !xm && Kp == C && (C == 1152 || C == 1024 || C == 1280 || C == 768) && n_tok >= 2) {
+    if (n_out == 1 && !(s && s[0]) && !xm && half_wave) {
         dim3 g2((n_tok + 2 * RQF_WAVES - 1) / (2 * RQF_WAVES));
-#define LNH_GO(N_)                                                                                              \
-    hipLaunchKernelGGL((ln_modulate_rowquant_half_kernel<N_>), g2, dim3(RQF_THREADS), 0, st, x, shift, scale, eps,  \
-                       xq[0], sx[0], zx[0], R[0], n_tok, n_bits, status)
-        switch (C / 128) {
-            case 6: LNH_GO(6); break;
-            case 8: LNH_GO(8); break;
-            case 9: LNH_GO(9); break;
-            default: LNH_GO(10); break;
-        }
-#undef LNH_GO
-        return true;
+        return vq_dispatch_nit(C, [&](auto nit) {
+            hipLaunchKernelGGL((ln_modulate_rowquant_half_kernel<nit()>), g2, dim3(RQF_THREADS), 0, st, x, shift, scale, eps,
+                               xq[0], sx[0], zx[0], R[0], n_tok, n_bits, status);
+        });
     }
-    LnqFastOut o;
-    for (int j = 0; j < 3; ++j) {
-        const bool on = j < n_out;
-        o.s[j] = (on && s) ? s[j] : nullptr;
-        o.r[j] = nullptr;
-        o.xq[j] = on ? xq[j] : nullptr;
-        o.sx[j] = on ? sx[j] : nullptr;
-        o.zx[j] = on ? zx[j] : nullptr;
-        o.R[j] = on ? R[j] : nullptr;
-    }
+    const LnqFastOut o = lnq_many(n_out, s, nullptr, xq, sx, zx, R);       // (IEEE division: no reciprocals)
     dim3 grid((n_tok + RQF_WAVES - 1) / RQF_WAVES);
-    if (Kp <= 512) launch_lnq<1>(n_out, grid, st, x, shift, scale, eps, o, xm, n_tok, C, Kp, n_bits, status);
-    else launch_lnq<3>(n_out, grid, st, x, shift, scale, eps, o, xm, n_tok, C, Kp, n_bits, status);
+    vq_dispatch_maxch(Kp, [&](auto m) {
+        if constexpr (m() <= 3)                               // (Kp <= 1536 here: no MAXCH = 9 form of this kernel exists)
+            launch_lnq<m()>(n_out, grid, st, x, shift, scale, eps, o, xm, n_tok, C, Kp, n_bits, status);
+    });
     return true;
 }
 
@@ -1402,10 +1373,8 @@ bool vq_lnq_fast(const half_t* x, const float* shift, const float* scale, float 
 bool vq_rowquant_smooth_multi_fast(const half_t* x, int n_out, const float* const* s, const float* const* s_rcp,
                                    int8_t* const* xq, float* const* sx, int32_t* const* zx, int32_t* const* R, int n_tok,
                                    int C, int Kp, int n_bits, int32_t* status, hipStream_t st) {
-    if (Kp != C || C % 128 != 0 || C < 768 || C > 1280 || n_tok < 2) return false;
-    LnqFastOut o{};
-    for (int j = 0; j < n_out; ++j)
-        o.s[j] = s[j], o.r[j] = s_rcp[j], o.xq[j] = xq[j], o.sx[j] = sx[j], o.zx[j] = zx[j], o.R[j] = R[j];
+    if (Kp != C || !rq_block_width(C) || n_tok < 2) return false;
+    const LnqFastOut o = lnq_many(n_out, s, s_rcp, xq, sx, zx, R);
     if (n_out == 3 && launch_smooth_multi<false, 3>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;
     if (n_out == 2 && launch_smooth_multi<false, 2>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;
     if (n_out == 1 && vq_sm1_mode() && launch_smooth_multi<false, 1>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;
