@@ -120,6 +120,32 @@ int vq_rowquant_smooth_multi(const void* x, int n_out, const float* const* s, co
                              int8_t* const* xq, float* const* sx, int32_t* const* zx, int32_t* const* R,
                              int n_tok, int C, int Kp, int n_bits, int32_t* status, void* stream);
 
+/* One pass over x [B, n_tok, C] fp16 -> n_out (1..3) quantized copies on STATIC calibrated grids: ActQuantizer.forward
+ * after init_done (qdiff/quantizer/base_quantizer.py:129-144) for Linears that share an input (q / k / v), with what
+ * precedes them in a block in the same pass.  Input arm, one of:
+ *   plain;
+ *   + add_rows[(r % n_tok) / add_div] (fp16 [n_add, C]: the temporal position embedding, stdit.py:112-114);
+ *   LayerNorm(ln_eps, no affine) + (1 + scale[b]) * y + shift[b] (shift / scale fp32 [B, C], both set; stdit.py:103,124,
+ *   layers/blocks.py:51), rounded to fp16 - the activation the reference stores - before it is quantized; xm_out
+ *   (nullable, [B*n_tok, C] fp16) receives it, bit-identical to vq_ln_modulate_rowquant(n_out = 1, s = NULL, xm_out).
+ * Output j: u = v / s[j][c] when s[j] is set (quant_layer.py:140; the reciprocal form only when s_rcp[j] is given too),
+ *   code = clamp(rint(u / delta_j) + zp_j, 0, 2^n_bits - 1)   (base_quantizer.py:134-140),
+ * with the grid (delta[j], zp[j]) of n_param entries (1 = tensor-wise, or n_tok: entry tok serves every b) read on the
+ * device - no host synchronisation.  xq / sx / zx / R as vq_rowquant writes them (sx[r] = delta, zx[r] = (int)zp - cx,
+ * R[r] = sum(xq) - C * zx[r], pad columns [C, Kp) zero).  There is no status word: a static grid has no eps fill.
+ * s, s_rcp, delta, zp, xq, sx, zx, R are HOST arrays of n_out device pointers (s / s_rcp nullable, as may be their
+ * entries).  Precondition: zp integer-valued and delta > 0, as every calibrated grid is.
+ * Errors, all before anything is dereferenced or launched: VQ_EINVAL for a null pointer, a non-positive extent, n_out
+ * outside 1..3, n_param not in {1, n_tok}; VQ_ESHAPE for C % 8, Kp % 128, Kp < C or a pointer off 16 bytes (x, add_rows,
+ * shift, scale, xm_out, s[j], s_rcp[j], xq[j]); VQ_EUNSUP for add_rows together with LayerNorm, n_bits outside 2..8 or
+ * Kp > 4608. */
+int vq_rowquant_static(const void* x, const void* add_rows, int n_add, int add_div,
+                       const float* shift, const float* scale, float ln_eps,
+                       int n_out, const float* const* s, const float* const* s_rcp,
+                       const float* const* delta, const float* const* zp, int n_param,
+                       int8_t* const* xq, float* const* sx, int32_t* const* zx, int32_t* const* R,
+                       void* xm_out, int B, int n_tok, int C, int Kp, int n_bits, void* stream);
+
 /* Reciprocal of a smooth-quant channel scale for the s_rcp arguments above: r[c] = RN(1 / s[c]); *n_bad (device int32,
  * zeroed by the caller) counts the channels for which the reciprocal form of x / s is not guaranteed bit-exact
  * (s not a positive normal number, significand all ones, reciprocal not normal): pass s_rcp only when it stays 0.

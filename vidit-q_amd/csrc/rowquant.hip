@@ -31,6 +31,11 @@ bool vq_lnq_fast(const half_t* x, const float* shift, const float* scale, float 
                  int32_t* const* zx, int32_t* const* R, half_t* xm, int n_tok, int C, int Kp, int n_bits, int32_t* status,
                  hipStream_t st);
 
+// one-pass kernels for a static grid (rowquant_static.hip); false when the shape is not covered, else *rc = the result
+bool vq_rowquant_static_one(const half_t* x, const half_t* add_rows, int n_add, int add_div, const float* s, const float* s_rcp,
+                            int8_t* xq, float* sx, int32_t* zx, int32_t* R, const float* delta, const float* zp, int n_param,
+                            int B, int n_tok, int C, int Kp, int n_bits, hipStream_t st, int* rc);
+
 __device__ __forceinline__ void store_codes8(int8_t* dst, const int q[8]) {
     uint32_t lo = (uint32_t)(q[0] & 0xff) | ((uint32_t)(q[1] & 0xff) << 8) | ((uint32_t)(q[2] & 0xff) << 16) |
                   ((uint32_t)(q[3] & 0xff) << 24);
@@ -448,6 +453,11 @@ extern "C" int vq_rowquant(const void* x, const void* add_rows, int n_add, int a
         vq_rowquant_pair_smooth_fast((const half_t*)x, s, s_rcp, xq, sx, zx, R, n_tok, C, Kp, n_bits, status,
                                      (hipStream_t)stream))
         return vq_check_launch();
+    int rc;
+    if (delta_in && !zpf &&
+        vq_rowquant_static_one((const half_t*)x, (const half_t*)add_rows, n_add, add_div, s, s_rcp, xq, sx, zx, R, delta_in, zp_in,
+                               n_param, B, n_tok, C, Kp, n_bits, (hipStream_t)stream, &rc))
+        return rc;
     dim3 grid((n_tok + RQ_WAVES - 1) / RQ_WAVES);
     hipLaunchKernelGGL(rowquant_kernel, grid, dim3(RQ_THREADS), 0, (hipStream_t)stream, (const half_t*)x,
                        (const half_t*)add_rows, add_div > 0 ? add_div : 1, s, xq, sx, zx, R, zpf, delta_in, zp_in,

@@ -1,7 +1,7 @@
 // rowquant_fast.hip - register-resident per-token quantizers (the per-step hot variants).
 //
 // Same arithmetic and C ABI semantics as the generic kernels in rowquant.hip (which remain the
-// fallback for batch-shared scales B > 1, static grids and rows longer than 4608), but:
+// fallback for batch-shared scales B > 1 and rows longer than 4608; static grids: rowquant_static.hip), but:
 //   - the token's row is loaded ONCE into registers (16 B / lane coalesced), nothing is re-read;
 //   - min/max of the plain quantizer runs on packed fp16 (v_pk_min/max_f16: exact, fp16 inputs);
 //   - round(x/delta) is computed as rint(x * (1/delta)) with an exact-division fallback for the
@@ -13,52 +13,10 @@
 // HBM-bound: algorithmic bytes per row = 2*C read + Kp written.
 #include <stdlib.h>
 #include "vq_common.h"
+#include "rowquant_shared.h"
 
 #define RQF_WAVES 4
 #define RQF_THREADS (RQF_WAVES * 64)
-
-// ---- host side: the dispatch every entry point below shares -----------------
-// The half-wave kernels are compiled for rows of C = 128 * NIT channels, NIT in {6, 8, 9, 10}: the hidden sizes 768, 1024,
-// 1152 and 1280.  (The sources used to spell this set in two ways; the second, C % 128 == 0 && 768 <= C <= 1280, also let
-// 896 through to a width switch that had no kernel for it and fell back - the assert below pins exactly that.)
-constexpr bool rq_block_width(int C) { return C % 128 == 0 && (C / 128 == 6 || C / 128 == 8 || C / 128 == 9 || C / 128 == 10); }
-constexpr bool rq_block_width_is_both_spellings() {
-    for (int C = 0; C <= 8192; ++C) {
-        const bool named = C == 1152 || C == 1024 || C == 1280 || C == 768;
-        const bool range = C % 128 == 0 && C >= 768 && C <= 1280;
-        if (rq_block_width(C) != named || rq_block_width(C) != (range && C != 896)) return false;
-    }
-    return true;
-}
-static_assert(rq_block_width_is_both_spellings(), "one predicate for the widths of the half-wave kernels");
-
-// f(std::integral_constant<int, NIT>) and true at a block width, false (nothing launched) at any other C
-template <class F>
-static bool vq_dispatch_nit(int C, F&& f) {
-    const int nit = rq_block_width(C) ? C / 128 : 0;
-    switch (nit) {
-        case 6: f(std::integral_constant<int, 6>{}); break;
-        case 8: f(std::integral_constant<int, 8>{}); break;
-        case 9: f(std::integral_constant<int, 9>{}); break;
-        case 10: f(std::integral_constant<int, 10>{}); break;
-        default: return false;
-    }
-    return true;
-}
-
-// f(std::integral_constant<int, MAXCH>): the 16-byte chunks per lane the one-row-per-wave kernels hold for a padded row of Kp
-template <class F>
-static void vq_dispatch_maxch(int Kp, F&& f) {
-    if (Kp <= 512) f(std::integral_constant<int, 1>{});
-    else if (Kp <= 1536) f(std::integral_constant<int, 3>{});
-    else f(std::integral_constant<int, 9>{});
-}
-
-template <class F>
-static void vq_dispatch_bool(bool b, F&& f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
 
 // The two environment variables this file reads, each here and nowhere else, once per process.  They are TEST ARMS, not
 // tuning knobs: tests/test_kernels_gpu.py and tests/test_quantizer_edges_gpu.py start a child process with VQ_RQ_SPLIT=0 /
@@ -158,15 +116,6 @@ __device__ __forceinline__ uint32_t rq_quant4(const float (&v)[4], float inv, fl
     }
     return pk;
 }
-#define RQ_BY_WIDTH(qmax_, ...)                                       \
-    if ((qmax_) == 255.0f) {                                          \
-        constexpr bool SAT8_ = true;                                  \
-        __VA_ARGS__                                                   \
-    } else {                                                          \
-        constexpr bool SAT8_ = false;                                 \
-        __VA_ARGS__                                                   \
-    }
-
 // ---------------------------------------------------------------------------
 // plain per-token quantizer, B == 1
 // ---------------------------------------------------------------------------
@@ -775,19 +724,6 @@ __global__ __launch_bounds__(RQF_THREADS) void ln_modulate_rowquant_fast_kernel(
 
 // LN + modulate + ONE un-smoothed quantizer, two rows per wave (same reasoning as rowquant_half_kernel; this
 // kernel has five per-row reductions and four IEEE divisions / a square root per row).
-#define RQH_REDUCE2(T_, OP_, v_)                                                                        \
-    {                                                                                                   \
-        VQ_DPP_STEP(T_, OP_, v_, 0xB1);                                                                 \
-        VQ_DPP_STEP(T_, OP_, v_, 0x4E);                                                                 \
-        VQ_DPP_STEP(T_, OP_, v_, 0x141);                                                                \
-        VQ_DPP_STEP(T_, OP_, v_, 0x140);                                                                \
-        const int b_ = __builtin_bit_cast(int, v_);                                                     \
-        const T_ r0_ = __builtin_bit_cast(T_, __builtin_amdgcn_readlane(b_, 0));                        \
-        const T_ r1_ = __builtin_bit_cast(T_, __builtin_amdgcn_readlane(b_, 16));                       \
-        const T_ r2_ = __builtin_bit_cast(T_, __builtin_amdgcn_readlane(b_, 32));                       \
-        const T_ r3_ = __builtin_bit_cast(T_, __builtin_amdgcn_readlane(b_, 48));                       \
-        v_ = hi ? OP_(r2_, r3_) : OP_(r0_, r1_);                                                        \
-    }
 // XM: also store the modulated activation as fp16 (the t2i final layer's LayerNorm + modulate in front of a Linear that
 // quantizes its own input: for B = 2 that call used to fall to the generic kernel, 74 us per PixArt-Sigma step)
 template <int NIT, bool PAIR = false, bool XM = false>   // PAIR: see rowquant_half_kernel; shift / scale [2, C], one row per sample

@@ -184,6 +184,72 @@ def rowquant_multi(x: torch.Tensor, smooth: Sequence[torch.Tensor], n_bits: int 
     return outs
 
 
+STATIC_MAX_KP = 4608        # rows the one-pass static-grid kernels hold (csrc/rowquant_static.hip)
+
+
+def rowquant_static_ok(Cc: int, Kp: int, n_bits: int, n_out: int, add_rows: bool = False, ln: bool = False) -> bool:
+    """Whether vq_rowquant_static takes this launch: the entry point's refusals (include/viditq.h), mirrored for callers
+    that choose a route BEFORE they launch - a refused shape takes the layerwise quantizers, it does not raise."""
+    if not (1 <= n_out <= 3) or Cc <= 0 or Kp <= 0:
+        return False
+    if Cc % 8 or Kp % 128 or Kp < Cc:
+        return False
+    return not (add_rows and ln) and 2 <= n_bits <= 8 and Kp <= STATIC_MAX_KP
+
+
+def rowquant_static(x: torch.Tensor, delta: Sequence[torch.Tensor], zp: Sequence[torch.Tensor], n_bits: int = 8,
+                    smooth: Optional[Sequence[Optional[torch.Tensor]]] = None, add_rows: Optional[torch.Tensor] = None,
+                    add_div: int = 1, shift: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                    eps: float = 1e-6, want_xm: bool = False, fast_div: bool = True, Kp: Optional[int] = None):
+    """One pass over x [B, n_tok, C] fp16 -> one QAct per calibrated grid (delta[j], zp[j]) (1 or n_tok entries each, read
+    on the device), behind ``smooth[j]`` when given.  Input arm: plain, ``+ add_rows[(r % n_tok) // add_div]``, or - with
+    ``shift`` / ``scale`` [B, C] fp32 - LayerNorm + modulate rounded to fp16 (returned too with ``want_xm``).
+    ``Kp``: row stride of the codes when it is to be more than C rounded up to 128."""
+    _req(x, torch.float16, "x")
+    assert x.dim() == 3
+    B, n_tok, Cc = x.shape
+    n_out = len(delta)
+    assert len(zp) == n_out and 1 <= n_out <= 3
+    Kp = pad128(Cc) if Kp is None else int(Kp)
+    rows = B * n_tok
+    dev = x.device
+    ds = [_req(d.reshape(-1).contiguous(), torch.float32, "delta") for d in delta]
+    zs = [_req(z.reshape(-1).contiguous(), torch.float32, "zp") for z in zp]
+    n_param = ds[0].numel()
+    assert all(d.numel() == n_param for d in ds) and all(z.numel() == n_param for z in zs)
+    smooth = [None] * n_out if smooth is None else list(smooth)
+    assert len(smooth) == n_out
+    for sm in smooth:
+        if sm is not None:
+            _req(sm, torch.float32, "smooth")
+            assert sm.numel() == Cc
+    rcps = [smooth_rcp(sm) if fast_div else None for sm in smooth]     # kept alive until the launch is enqueued
+    n_add = 0
+    if add_rows is not None:
+        _req(add_rows, torch.float16, "add_rows")
+        assert add_rows.shape[-1] == Cc
+        n_add = add_rows.shape[0]
+    ln = shift is not None or scale is not None
+    if ln:
+        _req(shift, torch.float32, "shift")
+        _req(scale, torch.float32, "scale")
+        assert shift.numel() == B * Cc and scale.numel() == B * Cc
+    elif want_xm:
+        raise VQError("rowquant_static: xm exists behind LayerNorm + modulate only")
+    outs = [QAct(torch.empty((rows, Kp), dtype=torch.int8, device=dev), torch.empty(rows, dtype=torch.float32, device=dev),
+                 torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
+                 Cc, n_bits) for _ in range(n_out)]
+    xm = torch.empty_like(x) if want_xm else None
+    keep = [_ptr_array([_p(sm) for sm in smooth]), _ptr_array([_p(r) for r in rcps]),
+            _ptr_array([_p(d) for d in ds]), _ptr_array([_p(z) for z in zs])] + \
+           [_ptr_array([getattr(o, f).data_ptr() for o in outs]) for f in ("xq", "sx", "zx", "R")]
+    kp = [C.cast(k, C.c_void_p) for k in keep]
+    check(_L().vq_rowquant_static(_p(x), _p(add_rows), n_add, add_div, _p(shift), _p(scale), float(eps), n_out, kp[0], kp[1],
+                                  kp[2], kp[3], n_param, kp[4], kp[5], kp[6], kp[7], _p(xm), B, n_tok, Cc, Kp, n_bits,
+                                  _stream()), "vq_rowquant_static")
+    return (outs, xm) if want_xm else outs
+
+
 def gelu_rowquant(x: torch.Tensor, n_bits: int = 8, s: Optional[torch.Tensor] = None,
                   status: Optional[torch.Tensor] = None, fast_div: bool = True) -> QAct:
     """GELU(tanh) then the per-token quantizer of x [B, n_tok, C] fp16 (the fc1 -> act -> fc2-quantizer hand-over);

@@ -339,6 +339,25 @@ class MultiHeadCrossAttention(nn.Module):
 # gets ~20 % shorter.  On by default since round 3; VQ_GELU_QUANT=0 restores the GELU epilogue.
 _ATTN_QUANT = __import__("os").environ.get("VQ_ATTN_QUANT", "1") != "0"   # attention kernels that also run the next quantizer
 _GELU_QUANT = __import__('os').environ.get('VQ_GELU_QUANT', '1') != '0'
+# static (calibrated) tensor-wise grids: the quantizers of Linears that share an input, and what precedes them
+# (LayerNorm + modulate, the temporal position embedding), in ONE pass (ops.rowquant_static) instead of one generic
+# pass per Linear behind a LayerNorm launch.  Bit-identical; False restores that route (tests compare the two).
+_STATIC_FUSED = True
+
+
+def _static_one_pass(layers, C, add_rows=False, ln=False) -> bool:
+    """Whether ONE ops.rowquant_static launch serves the calibrated quantizers of ``layers`` (which share an input):
+    the route switch, tensor-wise grids of one bit width, and nothing the entry point would refuse."""
+    aqs = [l.act_quantizer for l in layers]
+    if not _STATIC_FUSED or any(isinstance(a, DynamicActQuantizer) for a in aqs):
+        return False
+    if len({a.n_bits for a in aqs}) != 1 or any(a.delta.numel() != 1 or a.zero_point.numel() != 1 for a in aqs):
+        return False
+    return ops.rowquant_static_ok(C, ops.pad128(C), aqs[0].n_bits, len(aqs), add_rows=add_rows, ln=ln)
+
+
+def _static_grids(layers):
+    return [l.act_quantizer.delta.float() for l in layers], [l.act_quantizer.zero_point.float() for l in layers]
 
 
 # The one activation of the block that no LayerNorm precedes is the prompt (cross_attn.kv_linear): a (near-)constant
@@ -417,6 +436,10 @@ class STDiTBlock(nn.Module):
             smooth = [None] if all(s is None for s in svs) else list(svs)
             return ops.ln_modulate_rowquant(x3, shift, scale, 1e-6, smooth=smooth, n_bits=l0.act_quantizer.n_bits,
                                             status=status)
+        if _static_one_pass(layers, x3.shape[-1], ln=True):
+            delta, zp = _static_grids(layers)
+            return ops.rowquant_static(x3, delta, zp, n_bits=l0.act_quantizer.n_bits, smooth=svs, shift=shift, scale=scale,
+                                       eps=1e-6)
         _, xm = ops.ln_modulate_rowquant(x3, shift, scale, 1e-6, smooth=[None], n_bits=8, want_xm=True)
         # one pass per layer: each has its own calibrated grid tensor (comparing them would be a host sync)
         return [l.quantize_input(xm, s) for l, s in zip(layers, svs)]
@@ -543,6 +566,9 @@ class STDiTBlock(nn.Module):
                 isinstance(l.act_quantizer, DynamicActQuantizer) for l in (a2.q, a2.k, a2.v)) and len(
                 {l.act_quantizer.n_bits for l in (a2.q, a2.k, a2.v)}) == 1:
             qas = ops.rowquant_multi(x3, svs, n_bits=a2.q.act_quantizer.n_bits, status=a2.q.status)   # one launch
+        elif _static_one_pass((a2.q, a2.k, a2.v), C, add_rows=tpe2 is not None):
+            delta, zp = _static_grids((a2.q, a2.k, a2.v))
+            qas = ops.rowquant_static(x3, delta, zp, n_bits=a2.q.act_quantizer.n_bits, smooth=svs, add_rows=tpe2, add_div=S)
         else:
             qas = [l.quantize_input(x3, s, add_rows=tpe2, add_div=S) for l, s in zip((a2.q, a2.k, a2.v), svs)]
         qkv = qkv_proj(a2, qas)
