@@ -73,14 +73,17 @@ def test_rowquant_full_size_bit_exact(ops, dev, C):
     assert torch.equal(qa.R.cpu(), (codes.int().reshape(n_tok, C) - 128).sum(-1) - C * zx)
 
 
-def test_rowquant_smooth_and_add(ops, dev):
-    B, T, S, C = 2, 4, 8, 96
+@pytest.mark.parametrize("smooth", [True, False])
+@pytest.mark.parametrize("B", [2, 1])                            # B == 1: rowquant_fast_kernel<1, HAS_S, HAS_ADD>; B == 2: rowquant_kernel
+def test_rowquant_smooth_and_add(ops, dev, B, smooth):
+    T, S, C = 4, 8, 96
     x = h16(B, T * S, C, scale=2.0, seed=3)
     tpe = h16(T, C, scale=0.5, seed=4)
-    s = (torch.rand(C, generator=torch.Generator().manual_seed(5)) + 0.5).float()
-    xin = (x.float().reshape(B, T, S, C) + tpe.float().reshape(1, T, 1, C)).reshape(B, T * S, C) / s
+    s = (torch.rand(C, generator=torch.Generator().manual_seed(5)) + 0.5).float() if smooth else None
+    xin = (x.float().reshape(B, T, S, C) + tpe.float().reshape(1, T, 1, C)).reshape(B, T * S, C)
+    xin = xin / s if smooth else xin
     codes, dq, delta, zp, _ = fq.dyn_act_quant(xin, 8)
-    qa = ops.rowquant(x.to(dev), s=s.to(dev), add_rows=tpe.to(dev), add_div=S, want_zp=True)
+    qa = ops.rowquant(x.to(dev), s=s.to(dev) if smooth else None, add_rows=tpe.to(dev), add_div=S, want_zp=True)
     assert torch.equal(qa.xq[:, :C].cpu().int().reshape(B, T * S, C) + 128, codes.int())
     assert torch.equal(qa.sx.cpu().reshape(B, -1)[0], delta.reshape(-1))
 

@@ -70,10 +70,12 @@ def _check_exact(qa, st, x, n_bits, s, what, delta=None, zp=None):
 
 def _dynamic(ops, dev, B, C, n_bits, launch, s=None, fixed=False, small=True, ulp=False):
     """One route: the exact launch (every family, an odd row count that fills many workgroups), 131 and 257 rows thinned
-    from it, and the flagged launches.  ``launch(x_dev, status) -> [(QAct, s or None), ...]``."""
+    from it, 65 rows (the first count the LDS-staged smooth kernel takes) and 3 rows (one full pair and an odd tail: the
+    upper half-wave or the partner wave re-does the last row and must write nothing), and the flagged launches.
+    ``launch(x_dev, status) -> [(QAct, s or None), ...]``."""
     exact, flagged, names = qr.launch_sets(B, C, n_bits, s=s, q3_stride=7 if (B, C) == (1, 1152) else 49, fixed=fixed,
                                            ulp=ulp)
-    sets = [exact] + ([qr.thin(exact, 131), qr.thin(exact, 257)] if small else [])
+    sets = [exact] + ([qr.thin(exact, 131), qr.thin(exact, 257)] if small else []) + [qr.thin(exact, 65), qr.thin(exact, 3)]
     for x in sets:
         st = ops.new_status(dev)
         for j, (qa, sj) in enumerate(launch(x.to(dev), st)):
@@ -93,8 +95,9 @@ def _dynamic(ops, dev, B, C, n_bits, launch, s=None, fixed=False, small=True, ul
 #   B = 2, C = 768 .. 1280       rowquant_half_kernel<.., PAIR>     B = 2, C = 4608   rowquant_fast_kernel<9, .., PAIR>
 #   B = 2, C = 96                rowquant_fast_kernel<1, .., PAIR>
 # (rowquant_split_kernel - a C = 4608 row over two partner waves - is built behind GELU only: see the GELU test below)
+#   B = 1 / 2, C = 1408          rowquant_fast_kernel<3> / <3, .., PAIR>
 PLAIN = [(3, 64), (3, 96), (1, 64), (1, 96), (1, 320), (1, 768), (1, 1024), (1, 1152), (1, 1280), (1, 4608), (2, 96),
-         (2, 1152), (2, 768), (2, 4608)]
+         (2, 1152), (2, 768), (2, 4608), (2, 1024), (2, 1280), (1, 1408), (2, 1408)]
 
 
 @pytest.mark.parametrize("n_bits", [8, 6])
@@ -141,9 +144,10 @@ def test_smoothed_one_output_vectors_in_registers_edges(ops, dev):
 # B = 1, C = 4608 (n_tok >= 64)  rowquant_smooth_lds_kernel; with the zero point output or under 64 rows
 #                                rowquant_fast_kernel<9, HAS_S> (reciprocal form from global memory)
 # B = 2, C = 1152                smooth_rowquant_half_kernel<.., PAIR>      B = 2, C = 4608   rowquant_smooth_lds_kernel<.., PAIR>
+# C = 1544 (Kp = 1664)           the same two LDS-staged kernels with a masked last chunk and pad columns [C, Kp) to zero
 # fast_div=False                 the same kernels' IEEE-division branch (B = 1) / rowquant_kernel (B = 2)
 @pytest.mark.parametrize("n_bits", [8, 6])
-@pytest.mark.parametrize("B,C", [(1, 4608), (2, 1152), (2, 4608), (1, 1152)])
+@pytest.mark.parametrize("B,C", [(1, 4608), (2, 1152), (2, 4608), (1, 1152), (1, 1544), (2, 1544), (2, 768)])
 def test_smoothed_rowquant_edges(ops, dev, B, C, n_bits):
     for s, sd, fixed in _svecs(C, dev, n_bits):
         assert ops.smooth_rcp(sd) is not None
@@ -322,8 +326,10 @@ GELU_SPLIT = ((1, 8), (1, 6), (2, 8), (2, 6))
 def _gelu_split_outputs(ops, dev):
     out = {}
     for B, bits in GELU_SPLIT:
-        q = ops.gelu_rowquant(_gelu_input(B, 4608).to(dev), n_bits=bits)
-        out[(B, bits)] = [t.cpu() for t in (q.xq, q.sx, q.zx, q.R)]
+        x = _gelu_input(B, 4608)
+        for n in (x.shape[1], 3):                          # 3 rows: the partner waves of the odd tail write nothing
+            q = ops.gelu_rowquant(qr.thin(x, n).to(dev), n_bits=bits)
+            out[(B, bits, n)] = [t.cpu() for t in (q.xq, q.sx, q.zx, q.R)]
     return out
 
 
@@ -341,16 +347,16 @@ def test_gelu_rowquant_split_rows_edges(ops, dev, tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     ref = torch.load(f)
     got = _gelu_split_outputs(ops, dev)
-    assert len(ref) == len(GELU_SPLIT)
+    assert len(ref) == 2 * len(GELU_SPLIT)
     for key, want in ref.items():
         for name, g_, w_ in zip(FIELDS, got[key], want):
             assert torch.equal(g_, w_), (key, name)
         assert bool(torch.isfinite(got[key][1]).all())
 
 
-@pytest.mark.parametrize("B,C", [(1, 4608), (1, 1152), (2, 4608), (2, 1152), (1, 320)])
+@pytest.mark.parametrize("B,C", [(1, 4608), (1, 1152), (2, 4608), (2, 1152), (1, 320), (1, 1544), (2, 1544)])
 def test_gelu_rowquant_fast_division_edges(ops, dev, B, C):
-    """Smoothed GELU quantizers (C = 4608: rowquant_smooth_lds_kernel<GELU>; else rowquant_fast_kernel<.., GELU>) with the
+    """Smoothed GELU quantizers (C = 4608, 1544: rowquant_smooth_lds_kernel<GELU>, at 1544 with pad columns; else rowquant_fast_kernel<.., GELU>) with the
     reciprocal form against the same call with the IEEE division, on Q3 / Q5 / Q6: bit-identical, status included."""
     x = _gelu_input(B, C).to(dev)
     s = torch.exp(torch.randn(C, generator=torch.Generator().manual_seed(C + B)) * 0.7).float().to(dev)
@@ -363,13 +369,17 @@ def test_gelu_rowquant_fast_division_edges(ops, dev, B, C):
             assert torch.equal(getattr(a, f), getattr(b, f)), (f, bits)
         assert int(sa.item()) == int(sb.item()) == 1            # the sweep holds rows under 1e-6
         assert bool(torch.isfinite(a.sx).all())
+        assert bool((a.xq[:, C:] == 0).all())                    # pad columns [C, Kp)
 
 
 # ----------------------------------------------------------------------------- LayerNorm + modulate in front of the quantizer
 # B, C, outputs -> kernel: (1, 64, plain) ln_modulate_rowquant_fast_kernel<1>; (1, 1152, plain) ln_modulate_rowquant_half_kernel;
-# (2, 1152, plain) its PAIR form; (1, 1152, one vector) smooth_rowquant_multi_kernel<LN, 1>; three vectors <LN, 3>
+# (2, 1152, plain) its PAIR form; (1, 1152, one vector) smooth_rowquant_multi_kernel<LN, 1>; three vectors <LN, 3>;
+# (1, 768, plain) / (2, 768, plain) the half-wave kernels at NIT = 6; (1, 64, two vectors) ln_modulate_rowquant_fast_kernel<1, 2>;
+# (1, 1408, plain / three vectors) ln_modulate_rowquant_fast_kernel<3, 1> / <3, 3> (vectors without reciprocals in registers)
 @pytest.mark.parametrize("name", qr.LN_FAMILIES)
-@pytest.mark.parametrize("B,C,nout", [(1, 64, 0), (1, 1152, 0), (2, 1152, 0), (1, 1152, 1), (1, 1152, 3)])
+@pytest.mark.parametrize("B,C,nout", [(1, 64, 0), (1, 1152, 0), (2, 1152, 0), (1, 1152, 1), (1, 1152, 3), (1, 768, 0), (2, 768, 0),
+                                      (1, 64, 2), (1, 1408, 0), (1, 1408, 3)])
 def test_ln_modulate_rowquant_edges(ops, dev, B, C, nout, name):
     """Q3 / Q5 / Q6 behind LayerNorm + modulate, against the oracle at the bounds of test_ln_modulate_rowquant (LN statistics
     differ from torch's in the last ulp: <= 1 code step on < 0.5 % of the elements, tight dequant parity, delta to 1e-5).

@@ -11,30 +11,17 @@
 // nn.LayerNorm + t2i_modulate (opensora/models/stdit/stdit.py:103,124;
 // layers/blocks.py:51) and the smooth-quant division (qdiff/models/quant_layer.py:140).
 #include "vq_common.h"
+#include "rowquant_shared.h"
 
 #define RQ_WAVES 4
 #define RQ_THREADS (RQ_WAVES * 64)
 
-// register-resident hot variants (rowquant_fast.hip); return false when the shape is not covered
-bool vq_rowquant_fast(const half_t* x, const half_t* add_rows, int add_div, const float* s, const float* s_rcp,
-                      int8_t* xq, float* sx, int32_t* zx, int32_t* R, float* zpf, int n_tok, int C, int Kp, int n_bits,
-                      int32_t* status, hipStream_t st);
-bool vq_rowquant_pair_fast(const half_t* x, int8_t* xq, float* sx, int32_t* zx, int32_t* R, float* zpf, int n_tok, int C,
-                           int Kp, int n_bits, int32_t* status, hipStream_t st);
-bool vq_rowquant_pair_smooth_fast(const half_t* x, const float* s, const float* s_rcp, int8_t* xq, float* sx, int32_t* zx,
-                                  int32_t* R, int n_tok, int C, int Kp, int n_bits, int32_t* status, hipStream_t st);
-bool vq_lnq_pair_fast(const half_t* x, const float* shift, const float* scale, float eps, const float* s, const float* s_rcp,
-                      int8_t* xq, float* sx,
-                      int32_t* zx, int32_t* R, half_t* xm, int n_tok, int C, int Kp, int n_bits, int32_t* status, hipStream_t st);
-bool vq_lnq_fast(const half_t* x, const float* shift, const float* scale, float eps, int n_out,
-                 const float* const* s, const float* const* s_rcp, int8_t* const* xq, float* const* sx,
-                 int32_t* const* zx, int32_t* const* R, half_t* xm, int n_tok, int C, int Kp, int n_bits, int32_t* status,
-                 hipStream_t st);
-
-// one-pass kernels for a static grid (rowquant_static.hip); false when the shape is not covered, else *rc = the result
-bool vq_rowquant_static_one(const half_t* x, const half_t* add_rows, int n_add, int add_div, const float* s, const float* s_rcp,
-                            int8_t* xq, float* sx, int32_t* zx, int32_t* R, const float* delta, const float* zp, int n_param,
-                            int B, int n_tok, int C, int Kp, int n_bits, hipStream_t st, int* rc);
+// the shape and code-width check of the quantizer entry points: rows of C channels padded to Kp, codes of n_bits
+static int rq_check_shape(int C, int Kp, int n_bits) {
+    if (C % 8 != 0 || Kp % 128 != 0 || Kp < C) return VQ_ESHAPE;
+    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    return VQ_OK;
+}
 
 __device__ __forceinline__ void store_codes8(int8_t* dst, const int q[8]) {
     uint32_t lo = (uint32_t)(q[0] & 0xff) | ((uint32_t)(q[1] & 0xff) << 8) | ((uint32_t)(q[2] & 0xff) << 16) |
@@ -130,13 +117,6 @@ __global__ __launch_bounds__(RQ_THREADS) void rowquant_kernel(
 // LayerNorm(no affine) + AdaLN modulate + up to 3 smoothed per-token quantizers
 // ---------------------------------------------------------------------------
 #define LNQ_MAXB 8
-struct LnqOut {
-    const float* s[3];
-    int8_t* xq[3];
-    float* sx[3];
-    int32_t* zx[3];
-    int32_t* R[3];
-};
 
 template <int NOUT>
 __global__ __launch_bounds__(RQ_THREADS) void ln_modulate_rowquant_kernel(
@@ -439,8 +419,7 @@ extern "C" int vq_rowquant(const void* x, const void* add_rows, int n_add, int a
     if (!x || !xq || !sx || !zx || !R) return VQ_EINVAL;
     if (delta_in && (!zp_in || (n_param != 1 && n_param != n_tok))) return VQ_EINVAL;
     if (B <= 0 || n_tok <= 0 || C <= 0) return VQ_EINVAL;
-    if (C % 8 != 0 || Kp % 128 != 0 || Kp < C) return VQ_ESHAPE;
-    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    if (const int e = rq_check_shape(C, Kp, n_bits)) return e;
     if (add_rows && (add_div <= 0 || n_add <= 0 || (n_tok + add_div - 1) / add_div > n_add)) return VQ_EINVAL;
     if (B == 1 && !delta_in &&
         vq_rowquant_fast((const half_t*)x, (const half_t*)add_rows, add_div > 0 ? add_div : 1, s, s_rcp, xq, sx, zx, R, zpf,
@@ -465,17 +444,11 @@ extern "C" int vq_rowquant(const void* x, const void* add_rows, int n_add, int a
     return vq_check_launch();
 }
 
-bool vq_gelu_rowquant_fast(const half_t* x, const float* s, const float* s_rcp, int8_t* xq, float* sx, int32_t* zx,
-                           int32_t* R, int n_tok, int C, int Kp, int n_bits, int32_t* status, hipStream_t st);
-bool vq_gelu_rowquant_pair_fast(const half_t* x, const float* s, const float* s_rcp, int8_t* xq, float* sx, int32_t* zx,
-                                int32_t* R, int n_tok, int C, int Kp, int n_bits, int32_t* status, hipStream_t st);
-
 extern "C" int vq_gelu_rowquant(const void* x, const float* s, const float* s_rcp, int8_t* xq, float* sx, int32_t* zx,
                                 int32_t* R, int B, int n_tok, int C, int Kp, int n_bits, int32_t* status, void* stream) {
     if (!x || !xq || !sx || !zx || !R) return VQ_EINVAL;
     if (B <= 0 || n_tok <= 0 || C <= 0) return VQ_EINVAL;
-    if (C % 8 != 0 || Kp % 128 != 0 || Kp < C) return VQ_ESHAPE;
-    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    if (const int e = rq_check_shape(C, Kp, n_bits)) return e;
     if (B > 2) return VQ_EUNSUP;    // larger batches with shared token scales: use the GEMM's GELU epilogue + vq_rowquant
     if (B == 2) {                   // uncond | cond pair, grids shared over the two samples of a token
         if (!vq_gelu_rowquant_pair_fast((const half_t*)x, s, s_rcp, xq, sx, zx, R, n_tok, C, Kp, n_bits, status,
@@ -495,8 +468,8 @@ extern "C" int vq_ln_modulate_rowquant(const void* x, const float* shift, const 
                                        int Kp, int n_bits, int32_t* status, void* stream) {
     if (!x || !shift || !scale || !xq || !sx || !zx || !R) return VQ_EINVAL;
     if (n_out < 1 || n_out > 3 || B <= 0 || n_tok <= 0 || C <= 0) return VQ_EINVAL;
-    if (B > LNQ_MAXB || C % 8 != 0 || Kp % 128 != 0 || Kp < C) return VQ_ESHAPE;
-    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    if (B > LNQ_MAXB) return VQ_ESHAPE;
+    if (const int e = rq_check_shape(C, Kp, n_bits)) return e;
     for (int j = 0; j < n_out; ++j)
         if (!xq[j] || !sx[j] || !zx[j] || !R[j]) return VQ_EINVAL;
     if (B == 1 && vq_lnq_fast((const half_t*)x, shift, scale, ln_eps, n_out, s, s_rcp, xq, sx, zx, R, (half_t*)xm_out, n_tok,
@@ -506,16 +479,7 @@ extern "C" int vq_ln_modulate_rowquant(const void* x, const float* shift, const 
         vq_lnq_pair_fast((const half_t*)x, shift, scale, ln_eps, s ? s[0] : nullptr, (s && s[0] && s_rcp) ? s_rcp[0] : nullptr,
                          xq[0], sx[0], zx[0], R[0], (half_t*)xm_out, n_tok, C, Kp, n_bits, status, (hipStream_t)stream))
         return vq_check_launch();
-    LnqOut o;
-    for (int j = 0; j < 3; ++j) {
-        const bool on = j < n_out;
-        o.s[j] = (on && s) ? s[j] : nullptr;
-        o.xq[j] = on ? xq[j] : nullptr;
-        o.sx[j] = on ? sx[j] : nullptr;
-        o.zx[j] = on ? zx[j] : nullptr;
-        o.R[j] = on ? R[j] : nullptr;
-        if (on && (!o.xq[j] || !o.sx[j] || !o.zx[j] || !o.R[j])) return VQ_EINVAL;
-    }
+    const LnqOut o = lnq_many(n_out, s, nullptr, xq, sx, zx, R);   // (outputs checked above; IEEE division: no reciprocals)
     dim3 grid((n_tok + RQ_WAVES - 1) / RQ_WAVES), block(RQ_THREADS);
     hipStream_t st = (hipStream_t)stream;
     const half_t* xh = (const half_t*)x;
@@ -598,17 +562,12 @@ extern "C" int vq_smooth_div_check(const float* a, const float* b, float* fast, 
     return vq_check_launch();
 }
 
-bool vq_rowquant_smooth_multi_fast(const half_t* x, int n_out, const float* const* s, const float* const* s_rcp,
-                                   int8_t* const* xq, float* const* sx, int32_t* const* zx, int32_t* const* R, int n_tok,
-                                   int C, int Kp, int n_bits, int32_t* status, hipStream_t st);
-
 extern "C" int vq_rowquant_smooth_multi(const void* x, int n_out, const float* const* s, const float* const* s_rcp,
                                         int8_t* const* xq, float* const* sx, int32_t* const* zx, int32_t* const* R,
                                         int n_tok, int C, int Kp, int n_bits, int32_t* status, void* stream) {
     if (!x || !s || !s_rcp || !xq || !sx || !zx || !R) return VQ_EINVAL;
     if (n_out < 1 || n_out > 3 || n_tok <= 0 || C <= 0) return VQ_EINVAL;
-    if (C % 8 != 0 || Kp % 128 != 0 || Kp < C) return VQ_ESHAPE;
-    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    if (const int e = rq_check_shape(C, Kp, n_bits)) return e;
     for (int j = 0; j < n_out; ++j)
         if (!s[j] || !s_rcp[j] || !xq[j] || !sx[j] || !zx[j] || !R[j]) return VQ_EINVAL;
     if (!vq_rowquant_smooth_multi_fast((const half_t*)x, n_out, s, s_rcp, xq, sx, zx, R, n_tok, C, Kp, n_bits, status,

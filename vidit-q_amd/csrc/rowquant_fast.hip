@@ -11,6 +11,9 @@
 //   - LN + modulate keeps the modulated row in fp32 registers between the min/max and the
 //     quantize pass and reads shift/scale as 16-byte vectors.
 // HBM-bound: algorithmic bytes per row = 2*C read + Kp written.
+// The per-row steps (lane maps, reductions, row load, LayerNorm statistics, modulate, the quantize / store / row-sum
+// tail) are in rowquant_shared.h; a kernel here is what is its own: which rows a wave takes, where its vectors live,
+// how min / max are collected and exchanged.
 #include <stdlib.h>
 #include "vq_common.h"
 #include "rowquant_shared.h"
@@ -31,91 +34,29 @@ static int vq_sm1_mode() {
     return mode;
 }
 
-// VALU is what bounds these kernels at C = 1152 (~11 us of ~17 at 16384 rows), so the per-element sequence is
-// kept minimal: the row's own min/max defines delta, hence |x/delta| <= 255 (no magnitude guard needed here),
-// the rounding-boundary guard is one subtract + one compare, and for 8-bit codes v_cvt_pk_u8_f32 itself
-// saturates to [0, 255] (no clamp instruction).
-__device__ __forceinline__ float rq_gelu_tanh(float x) {
-    // nn.GELU(approximate='tanh') = x * sigmoid(2u), u = sqrt(2/pi)(x + 0.044715 x^3)  (same form as gemm_i8.hip)
-    const float w = x * fmaf(x * x, -0.044715f * 2.302208198f, -2.302208198f);
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(w));
-}
-// the same expression on a pair of values as packed fp32 math (v_pk_mul / v_pk_fma / v_pk_add: IEEE-identical to the
-// scalar forms, two elements per issue slot; exp2 and rcp stay per element), result rounded to fp16 like the activation
-// the reference stores between the two Linears
-__device__ __forceinline__ void rq_gelu_tanh8(half8& h) {
-    const float2v c1 = {-0.044715f * 2.302208198f, -0.044715f * 2.302208198f}, c2 = {-2.302208198f, -2.302208198f};
-    const float2v one = {1.0f, 1.0f};
+// smooth-quant division of one chunk, w = u / s in the reciprocal form, and the lane's running min / max of the quotients
+template <int W>
+__device__ __forceinline__ void rq_smooth_chunk(const float (&u)[W], const float (&s)[W], const float (&r)[W], float (&w)[W],
+                                                float& vmin, float& vmax) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float2v x = {(float)h[2 * j], (float)h[2 * j + 1]};
-        const float2v w = x * __builtin_elementwise_fma(x * x, c1, c2);
-        const float2v d = float2v{__builtin_amdgcn_exp2f(w[0]), __builtin_amdgcn_exp2f(w[1])} + one;
-        const float2v g = x * float2v{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-        h[2 * j] = (half_t)g[0];
-        h[2 * j + 1] = (half_t)g[1];
+    for (int e = 0; e < W; ++e) {
+        w[e] = rq_div_rcp(u[e], s[e], r[e]);
+        vmin = fminf(vmin, w[e]);
+        vmax = fmaxf(vmax, w[e]);
+    }
+}
+// min / max over the lanes' packed fp16 running values
+template <class V>
+__device__ __forceinline__ void rq_minmax_h(const V& mn, const V& mx, float& vmin, float& vmax) {
+    vmin = (float)mn[0];
+    vmax = (float)mx[0];
+#pragma unroll
+    for (int e = 1; e < (int)(sizeof(V) / sizeof(half_t)); ++e) {
+        vmin = fminf(vmin, (float)mn[e]);
+        vmax = fmaxf(vmax, (float)mx[e]);
     }
 }
 
-
-__device__ __forceinline__ void rq_gelu_tanh4(half4& h) {      // the same expression on four values (the 8-byte tail of a split row)
-    const float2v c1 = {-0.044715f * 2.302208198f, -0.044715f * 2.302208198f}, c2 = {-2.302208198f, -2.302208198f};
-    const float2v one = {1.0f, 1.0f};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const float2v x = {(float)h[2 * j], (float)h[2 * j + 1]};
-        const float2v w = x * __builtin_elementwise_fma(x * x, c1, c2);
-        const float2v d = float2v{__builtin_amdgcn_exp2f(w[0]), __builtin_amdgcn_exp2f(w[1])} + one;
-        const float2v g = x * float2v{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-        h[2 * j] = (half_t)g[0];
-        h[2 * j + 1] = (half_t)g[1];
-    }
-}
-
-// quantize 8 values -> two packed dwords of (code - cx); returns sum of raw codes
-template <bool SAT8>
-__device__ __forceinline__ uint32_t rq_quant8_t(const float (&v)[8], float inv, float delta, float zp, float qmax,
-                                                uint32_t flip, uint2& packed) {
-    float r[8];
-    rq_round_group<8>(v, inv, delta, zp, r);
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float q0 = r[i], q1 = r[4 + i];
-        if constexpr (!SAT8) {
-            q0 = __builtin_amdgcn_fmed3f(q0, 0.0f, qmax);
-            q1 = __builtin_amdgcn_fmed3f(q1, 0.0f, qmax);
-        }
-        lo = __builtin_amdgcn_cvt_pk_u8_f32(q0, i, lo);    // integer-valued input; saturates to [0, 255]
-        hi = __builtin_amdgcn_cvt_pk_u8_f32(q1, i, hi);
-    }
-    const uint32_t sum = __builtin_amdgcn_sad_u8(hi, 0u, __builtin_amdgcn_sad_u8(lo, 0u, 0u));
-    packed = make_uint2(lo ^ flip, hi ^ flip);
-    return sum;
-}
-__device__ __forceinline__ uint32_t rq_quant8(const float (&v)[8], float inv, float delta, float zp, float qmax,
-                                              uint32_t flip, uint2& packed) {
-    if (qmax == 255.0f) return rq_quant8_t<true>(v, inv, delta, zp, qmax, flip, packed);   // wave-uniform
-    return rq_quant8_t<false>(v, inv, delta, zp, qmax, flip, packed);
-}
-
-// quantize 4 values of one lane -> one dword of raw codes (tie test shared by the four, see rq_round_group)
-// SAT8 (8-bit codes): v_cvt_pk_u8_f32 saturates to [0, 255] by itself; other widths clamp first.  The callers pick the
-// instantiation with ONE kernel-uniform branch around their whole store loop (RQ_BY_WIDTH) - as a per-element select it
-// cost a v_med3 + v_cndmask per code.
-template <bool SAT8>
-__device__ __forceinline__ uint32_t rq_quant4(const float (&v)[4], float inv, float delta, float zp, float qmax) {
-    float r[4];
-    rq_round_group<4>(v, inv, delta, zp, r);
-    uint32_t pk = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float q = r[e];
-        if constexpr (!SAT8) q = __builtin_amdgcn_fmed3f(q, 0.0f, qmax);
-        pk = __builtin_amdgcn_cvt_pk_u8_f32(q, e, pk);
-    }
-    return pk;
-}
 // ---------------------------------------------------------------------------
 // plain per-token quantizer, B == 1
 // ---------------------------------------------------------------------------
@@ -129,7 +70,8 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_fast_kernel(
     const float* __restrict__ s_rcp, int8_t* __restrict__ xq, float* __restrict__ sx, int32_t* __restrict__ zx,
     int32_t* __restrict__ R, float* __restrict__ zpf, int n_tok, int C, int Kp, int n_bits, int32_t* status) {
     static_assert(!PAIR || (!HAS_ADD && RQF_WAVES % 2 == 0), "pairs of waves; added rows are per token");
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    using L = RqWave<MAXCH>;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lc = L::lane_col(lane);
     int tok = PAIR ? blockIdx.x * (RQF_WAVES / 2) + (wv >> 1) : blockIdx.x * RQF_WAVES + wv;
     const bool live = tok < n_tok;
     if (!live) {
@@ -137,21 +79,12 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_fast_kernel(
         tok = n_tok - 1;                                // stays for the workgroup barrier below, writes nothing
     }
     if (PAIR && (wv & 1)) tok += n_tok;                 // row index of (sample 1, token)
-    const float qmax = (float)((1 << n_bits) - 1);
-    const int cx = (n_bits == 8) ? 128 : 0;
-    const uint32_t flip = (n_bits == 8) ? 0x80808080u : 0u;
-    const half_t* row = x + (size_t)tok * C;
+    const RqWidth wd = rq_width(n_bits);
 
     half8 h[MAXCH];
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-        const int c0 = lane * 8 + i * 512;
-        if (c0 < C) {
-            h[i] = *reinterpret_cast<const half8*>(row + c0);
-            // act(fc1 output) applied here, under the HBM stream, instead of in the GEMM epilogue
-            if constexpr (GELU) rq_gelu_tanh8(h[i]);
-        }
-    }
+    // act(fc1 output) applied here, under the HBM stream, instead of in the GEMM epilogue
+    if constexpr (GELU) rq_load_row<L>(x + (size_t)tok * C, lc, C, h, [](half8& v) { rq_gelu_tanh<8>(v); });
+    else rq_load_row<L>(x + (size_t)tok * C, lc, C, h);
     float vmin, vmax;
     float w[(HAS_S || HAS_ADD) ? MAXCH : 1][8];     // the quantizer's input when it is not the row itself
     if constexpr (!HAS_S && !HAS_ADD) {
@@ -163,33 +96,23 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_fast_kernel(
         }
 #pragma unroll
         for (int i = 0; i < MAXCH; ++i)
-            if (lane * 8 + i * 512 < C) {
+            if (lc + i * 512 < C) {
                 mn = __builtin_elementwise_min(mn, h[i]);
                 mx = __builtin_elementwise_max(mx, h[i]);
             }
-        vmin = (float)mn[0];
-        vmax = (float)mx[0];
-#pragma unroll
-        for (int e = 1; e < 8; ++e) {
-            vmin = fminf(vmin, (float)mn[e]);
-            vmax = fmaxf(vmax, (float)mx[e]);
-        }
+        rq_minmax_h(mn, mx, vmin, vmax);
     } else {
         const half_t* addp = HAS_ADD ? add_rows + (size_t)(tok / add_div) * C : nullptr;
         vmin = INFINITY;
         vmax = -INFINITY;
 #pragma unroll
         for (int i = 0; i < MAXCH; ++i) {
-            const int c0 = lane * 8 + i * 512;
+            const int c0 = lc + i * 512;
             if (c0 < C) {
                 float sv[8], rv[8];
                 if constexpr (HAS_S) {
-                    *reinterpret_cast<float4v*>(sv) = *reinterpret_cast<const float4v*>(s + c0);
-                    *reinterpret_cast<float4v*>(sv + 4) = *reinterpret_cast<const float4v*>(s + c0 + 4);
-                    if (s_rcp) {   // kernel-uniform
-                        *reinterpret_cast<float4v*>(rv) = *reinterpret_cast<const float4v*>(s_rcp + c0);
-                        *reinterpret_cast<float4v*>(rv + 4) = *reinterpret_cast<const float4v*>(s_rcp + c0 + 4);
-                    }
+                    rq_load_f<8>(s + c0, sv);
+                    if (s_rcp) rq_load_f<8>(s_rcp + c0, rv);   // kernel-uniform
                 }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -203,8 +126,8 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_fast_kernel(
             }
         }
     }
-    vmin = wave_min_f(vmin);
-    vmax = wave_max_f(vmax);
+    vmin = rq_min_f<L::HALF>(vmin, false);
+    vmax = rq_max_f<L::HALF>(vmax, false);
     if constexpr (PAIR) {
         __shared__ float pm[RQF_WAVES][2];
         if (lane == 0) {
@@ -215,36 +138,16 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_fast_kernel(
         vmin = fminf(vmin, pm[wv ^ 1][0]);
         vmax = fmaxf(vmax, pm[wv ^ 1][1]);
     }
-    float delta, zp;
+    float delta, zp, inv;
     bool small;
-    float inv;
-    vq_row_grid(vmin, vmax, qmax, delta, zp, small, inv);
+    vq_row_grid(vmin, vmax, wd.qmax, delta, zp, small, inv);
     if (small && lane == 0 && live && status) atomicOr(status, VQ_ST_EPSFILL);
-    const int izx = (int)zp - cx;
 
     int8_t* qrow = xq + (size_t)tok * Kp;
-    uint32_t csum = 0;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-        const int c0 = lane * 8 + i * 512;
-        if (c0 < C) {
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (HAS_S || HAS_ADD) ? w[i][e] : (float)h[i][e];
-            uint2 p;
-            csum += rq_quant8(v, inv, delta, zp, qmax, flip, p);
-            if (live) *reinterpret_cast<uint2*>(qrow + c0) = p;
-        } else if (c0 < Kp) {
-            if (live) *reinterpret_cast<uint2*>(qrow + c0) = make_uint2(0u, 0u);
-        }
-    }
-    const int rs = wave_sum_i((int)csum) - cx * C;
-    if (lane == 0 && live) {
-        sx[tok] = delta;
-        zx[tok] = izx;
-        R[tok] = rs - C * izx;
-        if (zpf) zpf[tok] = zp;
-    }
+    int cs;
+    if constexpr (HAS_S || HAS_ADD) cs = rq_quant_row<L>(w, lc, C, Kp, delta, zp, inv, wd, qrow, live, false);
+    else cs = rq_quant_row<L>(h, lc, C, Kp, delta, zp, inv, wd, qrow, live, false);
+    if (lane == 0 && live) rq_write_row(sx, zx, R, zpf, tok, delta, zp, cs, C, wd.cx);
 }
 
 // ---------------------------------------------------------------------------
@@ -257,54 +160,55 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_fast_kernel(
 // fastest quantizers of the step - and exchange min / max and the code sums through LDS: half the instruction stream per
 // wave, half the registers (8 resident waves per SIMD), twice the wave generations, so loads, arithmetic and stores of
 // different waves interleave instead of alternating chip-wide.  Same per-element expressions as rowquant_fast_kernel
-// (rq_gelu_tanh8, packed fp16 min / max, vq_row_grid, rq_round_group): bit-identical outputs (tested).
+// (rq_gelu_tanh, packed fp16 min / max, vq_row_grid, rq_quant): bit-identical outputs (tested).
 // C / 2 = NF * 512 + (TAIL8 ? 256 : 0) channels per wave: NF 16-byte loads per lane + one 8-byte load.
 // ---------------------------------------------------------------------------
 // PAIR: x [2, n_tok, C] with the grid of a token shared by its two samples (the t2i uncond | cond forward): the four waves of a
 // workgroup are (sample, half) of ONE token - min / max over all four, code sums per sample.
+struct RqTail4 {             // one unmasked chunk of four channels for each of the 64 lanes (loaded and quantized, never reduced by this map)
+    static constexpr bool HALF = true;
+    static constexpr int NCH = 1, W = 4, STEP = 0;
+    typedef half4 hvec;
+    static __device__ __forceinline__ int lane_col(int lane) { return lane * 4; }
+};
 template <int NF, bool TAIL8, bool GELU, bool PAIR = false>
 __global__ __launch_bounds__(RQF_THREADS) void rowquant_split_kernel(const half_t* __restrict__ x, int8_t* __restrict__ xq,
                                                                      float* __restrict__ sx, int32_t* __restrict__ zx,
                                                                      int32_t* __restrict__ R, int n_tok, int n_bits,
                                                                      int32_t* status) {
     static_assert(!PAIR || RQF_WAVES == 4, "(sample, half) = the four waves of a workgroup");
+    using L = RqWave<NF>;        // the NF full chunks of the wave's half row (HC is a constant: no chunk is masked)
+    using LT = RqTail4;          // its 8-byte tail
     constexpr int HC = NF * 512 + (TAIL8 ? 256 : 0), C = 2 * HC;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, half = wv & 1;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, half = wv & 1, lc = L::lane_col(lane);
     int tok = PAIR ? blockIdx.x : blockIdx.x * (RQF_WAVES / 2) + (wv >> 1);
     const bool live = tok < n_tok;
     if (!live) tok = n_tok - 1;                        // stays for the workgroup barriers, writes nothing
     if (PAIR && (wv >> 1)) tok += n_tok;               // row index of (sample 1, token)
-    const float qmax = (float)((1 << n_bits) - 1);
-    const int cx = (n_bits == 8) ? 128 : 0;
-    const uint32_t flip = (n_bits == 8) ? 0x80808080u : 0u;
+    const RqWidth wd = rq_width(n_bits);
     const half_t* row = x + (size_t)tok * C + half * HC;
 
     half8 h[NF];
-    half4 ht;
-#pragma unroll
-    for (int i = 0; i < NF; ++i) h[i] = *reinterpret_cast<const half8*>(row + lane * 8 + i * 512);
-    if constexpr (TAIL8) ht = *reinterpret_cast<const half4*>(row + NF * 512 + lane * 4);
+    half4 ht[1];
+    rq_load_row<L>(row, lc, HC, h);
+    if constexpr (TAIL8) rq_load_row<LT>(row + NF * 512, LT::lane_col(lane), 256, ht);
     half8 mn, mx;
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
-        if constexpr (GELU) rq_gelu_tanh8(h[i]);
+        if constexpr (GELU) rq_gelu_tanh<8>(h[i]);
         mn = i == 0 ? h[0] : __builtin_elementwise_min(mn, h[i]);
         mx = i == 0 ? h[0] : __builtin_elementwise_max(mx, h[i]);
     }
     if constexpr (TAIL8) {
-        if constexpr (GELU) rq_gelu_tanh4(ht);
-        const half8 t8 = {ht[0], ht[1], ht[2], ht[3], ht[0], ht[1], ht[2], ht[3]};
+        if constexpr (GELU) rq_gelu_tanh<4>(ht[0]);
+        const half8 t8 = {ht[0][0], ht[0][1], ht[0][2], ht[0][3], ht[0][0], ht[0][1], ht[0][2], ht[0][3]};
         mn = NF == 0 ? t8 : __builtin_elementwise_min(mn, t8);
         mx = NF == 0 ? t8 : __builtin_elementwise_max(mx, t8);
     }
-    float vmin = (float)mn[0], vmax = (float)mx[0];
-#pragma unroll
-    for (int e = 1; e < 8; ++e) {
-        vmin = fminf(vmin, (float)mn[e]);
-        vmax = fmaxf(vmax, (float)mx[e]);
-    }
-    vmin = wave_min_f(vmin);
-    vmax = wave_max_f(vmax);
+    float vmin, vmax;
+    rq_minmax_h(mn, mx, vmin, vmax);
+    vmin = rq_min_f<L::HALF>(vmin, false);
+    vmax = rq_max_f<L::HALF>(vmax, false);
     __shared__ float pm[RQF_WAVES][2];
     __shared__ int ps[RQF_WAVES];
     if (lane == 0) {
@@ -322,40 +226,18 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_split_kernel(const half_
         vmin = fminf(vmin, pm[wv ^ 1][0]);
         vmax = fmaxf(vmax, pm[wv ^ 1][1]);
     }
-    float delta, zp;
+    float delta, zp, inv;
     bool small;
-    float inv;
-    vq_row_grid(vmin, vmax, qmax, delta, zp, small, inv);
+    vq_row_grid(vmin, vmax, wd.qmax, delta, zp, small, inv);
     if (small && lane == 0 && (PAIR ? wv == 0 : half == 0) && live && status) atomicOr(status, VQ_ST_EPSFILL);
-    const int izx = (int)zp - cx;
 
     int8_t* qrow = xq + (size_t)tok * C + half * HC;
-    uint32_t csum = 0;
-#pragma unroll
-    for (int i = 0; i < NF; ++i) {
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (float)h[i][e];
-        uint2 p;
-        csum += rq_quant8(v, inv, delta, zp, qmax, flip, p);
-        if (live) *reinterpret_cast<uint2*>(qrow + lane * 8 + i * 512) = p;
-    }
-    if constexpr (TAIL8) {
-        const float x4[4] = {(float)ht[0], (float)ht[1], (float)ht[2], (float)ht[3]};
-        uint32_t pk;
-        if (qmax == 255.0f) pk = rq_quant4<true>(x4, inv, delta, zp, qmax);
-        else pk = rq_quant4<false>(x4, inv, delta, zp, qmax);
-        csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-        if (live) *reinterpret_cast<uint32_t*>(qrow + NF * 512 + lane * 4) = pk ^ flip;
-    }
-    const int rs_half = wave_sum_i((int)csum);
+    uint32_t csum = rq_quant_lane<L>(h, lc, HC, HC, delta, zp, inv, wd, qrow, live);
+    if constexpr (TAIL8) csum = rq_quant_lane<LT>(ht, LT::lane_col(lane), 256, 256, delta, zp, inv, wd, qrow + NF * 512, live, csum);
+    const int rs_half = rq_sum_i<L::HALF>((int)csum, false);
     if (lane == 0) ps[wv] = rs_half;
     __syncthreads();
-    if (lane == 0 && half == 0 && live) {
-        sx[tok] = delta;
-        zx[tok] = izx;
-        R[tok] = rs_half + ps[wv ^ 1] - cx * C - C * izx;
-    }
+    if (lane == 0 && half == 0 && live) rq_write_row(sx, zx, R, nullptr, tok, delta, zp, rs_half + ps[wv ^ 1], C, wd.cx);
 }
 
 // ---------------------------------------------------------------------------
@@ -373,6 +255,7 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_smooth_lds_kernel(
     const half_t* __restrict__ x, const float* __restrict__ s, const float* __restrict__ s_rcp, int8_t* __restrict__ xq,
     float* __restrict__ sx, int32_t* __restrict__ zx, int32_t* __restrict__ R, int n_tok, int C, int Kp, int n_bits,
     int32_t* status) {
+    using L = RqWave<MAXCH>;
     extern __shared__ __attribute__((aligned(16))) float rq_lds[];
     float* ls = rq_lds;
     float* lr = rq_lds + C;
@@ -381,11 +264,8 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_smooth_lds_kernel(
         *reinterpret_cast<float4v*>(lr + c) = *reinterpret_cast<const float4v*>(s_rcp + c);
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const float qmax = (float)((1 << n_bits) - 1);
-    const int cx = (n_bits == 8) ? 128 : 0;
-    const uint32_t flip = (n_bits == 8) ? 0x80808080u : 0u;
-    const int wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lc = L::lane_col(lane);
+    const RqWidth wd = rq_width(n_bits);
     const int stride = PAIR ? gridDim.x * (RQF_WAVES / 2) : gridDim.x * RQF_WAVES;
     const int tok0 = PAIR ? blockIdx.x * (RQF_WAVES / 2) + (wv >> 1) : blockIdx.x * RQF_WAVES + wv;
     const size_t roff = (PAIR && (wv & 1)) ? (size_t)n_tok : 0;   // row = token + roff
@@ -394,12 +274,7 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_smooth_lds_kernel(
     const int n_it = base < n_tok ? (n_tok - base + stride - 1) / stride : 0;
     __shared__ float pm[2][RQF_WAVES][2];
     half8 hn[MAXCH];
-    if (n_it > 0) {
-        const half_t* row = x + ((size_t)(tok0 < n_tok ? tok0 : n_tok - 1) + roff) * C;
-#pragma unroll
-        for (int i = 0; i < MAXCH; ++i)
-            if (lane * 8 + i * 512 < C) hn[i] = *reinterpret_cast<const half8*>(row + lane * 8 + i * 512);
-    }
+    if (n_it > 0) rq_load_row<L>(x + ((size_t)(tok0 < n_tok ? tok0 : n_tok - 1) + roff) * C, lc, C, hn);
     for (int it = 0; it < n_it; ++it) {
         const int tk = tok0 + it * stride;
         const bool live = tk < n_tok;
@@ -407,39 +282,28 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_smooth_lds_kernel(
         float w[MAXCH][8];
 #pragma unroll
         for (int i = 0; i < MAXCH; ++i)
-            if (lane * 8 + i * 512 < C) {
+            if (lc + i * 512 < C) {
                 half8 g = hn[i];
-                if constexpr (GELU) rq_gelu_tanh8(g);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) w[i][e] = (float)g[e];
+                if constexpr (GELU) rq_gelu_tanh<8>(g);
+                rq_widen(g, w[i]);
             }
         if (it + 1 < n_it) {                               // next row in flight under this row's arithmetic
             const int tn = tk + stride;
-            const half_t* row = x + ((size_t)(tn < n_tok ? tn : n_tok - 1) + roff) * C;
-#pragma unroll
-            for (int i = 0; i < MAXCH; ++i)
-                if (lane * 8 + i * 512 < C) hn[i] = *reinterpret_cast<const half8*>(row + lane * 8 + i * 512);
+            rq_load_row<L>(x + ((size_t)(tn < n_tok ? tn : n_tok - 1) + roff) * C, lc, C, hn);
         }
         float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
         for (int i = 0; i < MAXCH; ++i) {
-            const int c0 = lane * 8 + i * 512;
+            const int c0 = lc + i * 512;
             if (c0 < C) {
                 float sv[8], rv[8];
-                *reinterpret_cast<float4v*>(sv) = *reinterpret_cast<const float4v*>(ls + c0);
-                *reinterpret_cast<float4v*>(sv + 4) = *reinterpret_cast<const float4v*>(ls + c0 + 4);
-                *reinterpret_cast<float4v*>(rv) = *reinterpret_cast<const float4v*>(lr + c0);
-                *reinterpret_cast<float4v*>(rv + 4) = *reinterpret_cast<const float4v*>(lr + c0 + 4);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    w[i][e] = rq_div_rcp(w[i][e], sv[e], rv[e]);
-                    vmin = fminf(vmin, w[i][e]);
-                    vmax = fmaxf(vmax, w[i][e]);
-                }
+                rq_load_f<8>(ls + c0, sv);
+                rq_load_f<8>(lr + c0, rv);
+                rq_smooth_chunk<8>(w[i], sv, rv, w[i], vmin, vmax);
             }
         }
-        vmin = wave_min_f(vmin);
-        vmax = wave_max_f(vmax);
+        vmin = rq_min_f<L::HALF>(vmin, false);
+        vmax = rq_max_f<L::HALF>(vmax, false);
         if constexpr (PAIR) {
             if (lane == 0) {
                 pm[it & 1][wv][0] = vmin;
@@ -449,31 +313,12 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_smooth_lds_kernel(
             vmin = fminf(vmin, pm[it & 1][wv ^ 1][0]);
             vmax = fmaxf(vmax, pm[it & 1][wv ^ 1][1]);
         }
-        float delta, zp;
+        float delta, zp, inv;
         bool small;
-        float inv;
-        vq_row_grid(vmin, vmax, qmax, delta, zp, small, inv);
+        vq_row_grid(vmin, vmax, wd.qmax, delta, zp, small, inv);
         if (small && lane == 0 && live && status) atomicOr(status, VQ_ST_EPSFILL);
-        const int izx = (int)zp - cx;
-        int8_t* qrow = xq + tok * Kp;
-        uint32_t csum = 0;
-#pragma unroll
-        for (int i = 0; i < MAXCH; ++i) {
-            const int c0 = lane * 8 + i * 512;
-            if (c0 < C) {
-                uint2 p;
-                csum += rq_quant8(w[i], inv, delta, zp, qmax, flip, p);
-                if (live) *reinterpret_cast<uint2*>(qrow + c0) = p;
-            } else if (c0 < Kp) {
-                if (live) *reinterpret_cast<uint2*>(qrow + c0) = make_uint2(0u, 0u);
-            }
-        }
-        const int rs = wave_sum_i((int)csum) - cx * C;
-        if (lane == 0 && live) {
-            sx[tok] = delta;
-            zx[tok] = izx;
-            R[tok] = rs - C * izx;
-        }
+        const int cs = rq_quant_row<L>(w, lc, C, Kp, delta, zp, inv, wd, xq + tok * Kp, live, false);
+        if (lane == 0 && live) rq_write_row(sx, zx, R, nullptr, tok, delta, zp, cs, C, wd.cx);
     }
 }
 
@@ -503,27 +348,40 @@ static bool launch_rq_smooth_lds(const half_t* x, const float* s, const float* s
 // uncond | cond forward), whose quantization grid the reference shares over the batch (base_quantizer.py:185): the
 // min / max of the two half-waves are combined, everything else stays per row.  The generic B > 1 kernel this
 // replaces for B == 2 took 24 us per launch at 2 x 4096 rows (13.5 % of a PixArt-Sigma step).
+// The row of this half-wave when its wave takes pair p: two consecutive rows, or (PAIR) the two samples of token p.
+// Odd tail: the upper half re-does the last row and writes nothing (``live``).
+template <bool PAIR>
+__device__ __forceinline__ int rqh_row(int p, bool hi, int n_tok, bool& live) {
+    const int t = PAIR ? p : p * 2 + (hi ? 1 : 0);
+    live = t < n_tok;
+    return (live ? t : n_tok - 1) + ((PAIR && hi) ? n_tok : 0);
+}
+// min / max of a half-wave's row; PAIR: one grid for the token's two samples
+template <bool PAIR>
+__device__ __forceinline__ void rqh_minmax(float& vmin, float& vmax, bool hi) {
+    vmin = rq_min_f<true>(vmin, hi);
+    vmax = rq_max_f<true>(vmax, hi);
+    if constexpr (PAIR) {
+        vmin = fminf(vmin, __shfl_xor(vmin, 32));
+        vmax = fmaxf(vmax, __shfl_xor(vmax, 32));
+    }
+}
+
 template <int NIT, bool PAIR = false>   // C = 128 * NIT
 __global__ __launch_bounds__(RQF_THREADS) void rowquant_half_kernel(const half_t* __restrict__ x, int8_t* __restrict__ xq,
                                                                     float* __restrict__ sx, int32_t* __restrict__ zx,
                                                                     int32_t* __restrict__ R, float* __restrict__ zpf,
                                                                     int n_tok, int n_bits, int32_t* status) {
+    using L = RqHalf<NIT>;
     constexpr int C = 128 * NIT;
-    const int lane = threadIdx.x & 63, hl = lane & 31;
+    const int lane = threadIdx.x & 63, hl = lane & 31, lc = L::lane_col(lane);
     const bool hi = lane >= 32;
-    int tok = PAIR ? blockIdx.x * RQF_WAVES + (threadIdx.x >> 6)
-                   : (blockIdx.x * RQF_WAVES + (threadIdx.x >> 6)) * 2 + (hi ? 1 : 0);
-    const bool live = tok < n_tok;
-    if (!live) tok = n_tok - 1;                       // odd tail: the upper half re-does the last row, writes nothing
-    if (PAIR && hi) tok += n_tok;                     // row index of (sample 1, token)
-    const float qmax = (float)((1 << n_bits) - 1);
-    const int cx = (n_bits == 8) ? 128 : 0;
-    const uint32_t flip = (n_bits == 8) ? 0x80808080u : 0u;
-    const half_t* row = x + (size_t)tok * C + hl * 4;
+    bool live;
+    const int tok = rqh_row<PAIR>(blockIdx.x * RQF_WAVES + (threadIdx.x >> 6), hi, n_tok, live);
+    const RqWidth wd = rq_width(n_bits);
 
     half4 h[NIT];
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) h[i] = *reinterpret_cast<const half4*>(row + i * 128);
+    rq_load_row<L>(x + (size_t)tok * C, lc, C, h);
     half4 mn = h[0], mx = h[0];
 #pragma unroll
     for (int i = 1; i < NIT; ++i) {
@@ -532,62 +390,13 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_half_kernel(const half_t
     }
     float vmin = fminf(fminf((float)mn[0], (float)mn[1]), fminf((float)mn[2], (float)mn[3]));
     float vmax = fmaxf(fmaxf((float)mx[0], (float)mx[1]), fmaxf((float)mx[2], (float)mx[3]));
-    // reduce inside each row of 16 lanes by DPP, then combine the two rows of this half
-    VQ_DPP_STEP(float, fminf, vmin, 0xB1);
-    VQ_DPP_STEP(float, fminf, vmin, 0x4E);
-    VQ_DPP_STEP(float, fminf, vmin, 0x141);
-    VQ_DPP_STEP(float, fminf, vmin, 0x140);
-    VQ_DPP_STEP(float, fmaxf, vmax, 0xB1);
-    VQ_DPP_STEP(float, fmaxf, vmax, 0x4E);
-    VQ_DPP_STEP(float, fmaxf, vmax, 0x141);
-    VQ_DPP_STEP(float, fmaxf, vmax, 0x140);
-    {
-        const int bmin = __builtin_bit_cast(int, vmin), bmax = __builtin_bit_cast(int, vmax);
-        const float n0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bmin, 0));
-        const float n1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bmin, 16));
-        const float n2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bmin, 32));
-        const float n3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bmin, 48));
-        const float m0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bmax, 0));
-        const float m1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bmax, 16));
-        const float m2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bmax, 32));
-        const float m3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(bmax, 48));
-        if constexpr (PAIR) {
-            vmin = fminf(fminf(n0, n1), fminf(n2, n3));
-            vmax = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
-        } else {
-            vmin = hi ? fminf(n2, n3) : fminf(n0, n1);
-            vmax = hi ? fmaxf(m2, m3) : fmaxf(m0, m1);
-        }
-    }
-    float delta, zp;
+    rqh_minmax<PAIR>(vmin, vmax, hi);
+    float delta, zp, inv;
     bool small;
-    float inv;
-    vq_row_grid(vmin, vmax, qmax, delta, zp, small, inv);
+    vq_row_grid(vmin, vmax, wd.qmax, delta, zp, small, inv);
     if (small && hl == 0 && live && status) atomicOr(status, VQ_ST_EPSFILL);
-    const int izx = (int)zp - cx;
-
-    int8_t* qrow = xq + (size_t)tok * C + hl * 4;
-    uint32_t csum = 0;
-    RQ_BY_WIDTH(qmax, _Pragma("unroll") for (int i = 0; i < NIT; ++i) {
-        const float x4[4] = {(float)h[i][0], (float)h[i][1], (float)h[i][2], (float)h[i][3]};
-        const uint32_t pk = rq_quant4<SAT8_>(x4, inv, delta, zp, qmax);
-        csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-        if (live) *reinterpret_cast<uint32_t*>(qrow + i * 128) = pk ^ flip;
-    })
-    int cs = (int)csum;
-    VQ_DPP_STEP(int, vq_addi, cs, 0xB1);
-    VQ_DPP_STEP(int, vq_addi, cs, 0x4E);
-    VQ_DPP_STEP(int, vq_addi, cs, 0x141);
-    VQ_DPP_STEP(int, vq_addi, cs, 0x140);
-    const int c0 = __builtin_amdgcn_readlane(cs, 0), c1 = __builtin_amdgcn_readlane(cs, 16);
-    const int c2 = __builtin_amdgcn_readlane(cs, 32), c3 = __builtin_amdgcn_readlane(cs, 48);
-    const int rs = (hi ? c2 + c3 : c0 + c1) - cx * C;
-    if (hl == 0 && live) {
-        sx[tok] = delta;
-        zx[tok] = izx;
-        R[tok] = rs - C * izx;
-        if (zpf) zpf[tok] = zp;
-    }
+    const int cs = rq_quant_row<L>(h, lc, C, C, delta, zp, inv, wd, xq + (size_t)tok * C, live, hi);
+    if (hl == 0 && live) rq_write_row(sx, zx, R, zpf, tok, delta, zp, cs, C, wd.cx);
 }
 
 // ---------------------------------------------------------------------------
@@ -595,66 +404,22 @@ __global__ __launch_bounds__(RQF_THREADS) void rowquant_half_kernel(const half_t
 // (rows of different batch samples are independent here because every row gets its own scale
 //  only when B == 1; the host dispatches B > 1 to the generic kernel)
 // ---------------------------------------------------------------------------
-struct LnqFastOut {
-    const float* s[3];
-    const float* r[3];     // RN(1 / s) per channel (smooth_rowquant_half_kernel only)
-    int8_t* xq[3];
-    float* sx[3];
-    int32_t* zx[3];
-    int32_t* R[3];
-};
-static LnqFastOut lnq_many(int n_out, const float* const* s, const float* const* r, int8_t* const* xq, float* const* sx,
-                           int32_t* const* zx, int32_t* const* R) {   // s, r: may be null; outputs >= n_out stay null
-    LnqFastOut o{};
-    for (int j = 0; j < n_out; ++j) {
-        o.s[j] = s ? s[j] : nullptr, o.r[j] = r ? r[j] : nullptr;
-        o.xq[j] = xq[j], o.sx[j] = sx[j], o.zx[j] = zx[j], o.R[j] = R[j];
-    }
-    return o;
-}
-static LnqFastOut lnq_one(const float* s, const float* r, int8_t* xq, float* sx, int32_t* zx, int32_t* R) {
-    return lnq_many(1, &s, &r, &xq, &sx, &zx, &R);
-}
-
 template <int MAXCH, int NOUT>
 __global__ __launch_bounds__(RQF_THREADS) void ln_modulate_rowquant_fast_kernel(
     const half_t* __restrict__ x, const float* __restrict__ shift, const float* __restrict__ scale, float ln_eps,
-    LnqFastOut o, half_t* __restrict__ xm_out, int n_tok, int C, int Kp, int n_bits, int32_t* status) {
-    const int lane = threadIdx.x & 63;
+    LnqOut o, half_t* __restrict__ xm_out, int n_tok, int C, int Kp, int n_bits, int32_t* status) {
+    using L = RqWave<MAXCH>;
+    const int lane = threadIdx.x & 63, lc = L::lane_col(lane);
     const int tok = blockIdx.x * RQF_WAVES + (threadIdx.x >> 6);
     if (tok >= n_tok) return;
-    const float qmax = (float)((1 << n_bits) - 1);
-    const int cx = (n_bits == 8) ? 128 : 0;
-    const uint32_t flip = (n_bits == 8) ? 0x80808080u : 0u;
-    const float invC = 1.0f / (float)C;
-    const half_t* row = x + (size_t)tok * C;
+    const RqWidth wd = rq_width(n_bits);
 
+    half8 h[MAXCH];
     float v[MAXCH][8];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-        const int c0 = lane * 8 + i * 512;
-        if (c0 < C) {
-            const half8 h = *reinterpret_cast<const half8*>(row + c0);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                v[i][e] = (float)h[e];
-                sum += v[i][e];
-            }
-        }
-    }
-    const float mu = wave_sum_f(sum) * invC;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i)
-        if (lane * 8 + i * 512 < C)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float d = v[i][e] - mu;
-                sq += d * d;
-            }
-    const float var = wave_sum_f(sq) * invC;
-    const float rstd = __fdiv_rn(1.0f, __fsqrt_rn(var + ln_eps));
+    rq_load_row<L>(x + (size_t)tok * C, lc, C, h);
+    rq_widen_row<L>(h, lc, C, v);
+    float mu, rstd;
+    rq_ln_stats<L>(v, lc, C, ln_eps, false, mu, rstd);
 
     float vmin[NOUT], vmax[NOUT];
 #pragma unroll
@@ -664,61 +429,36 @@ __global__ __launch_bounds__(RQF_THREADS) void ln_modulate_rowquant_fast_kernel(
     }
 #pragma unroll
     for (int i = 0; i < MAXCH; ++i) {
-        const int c0 = lane * 8 + i * 512;
+        const int c0 = lc + i * 512;
         if (c0 < C) {
-            const float4v s0 = *reinterpret_cast<const float4v*>(scale + c0);
-            const float4v s1 = *reinterpret_cast<const float4v*>(scale + c0 + 4);
-            const float4v h0 = *reinterpret_cast<const float4v*>(shift + c0);
-            const float4v h1 = *reinterpret_cast<const float4v*>(shift + c0 + 4);
-            half8 hm;
+            float sc1[8], sh[8];
+            rq_load_mod<8>(scale + c0, shift + c0, sc1, sh);
+            rq_modulate<8>(v[i], mu, rstd, sc1, sh, xm_out != nullptr, xm_out, (size_t)tok * C + c0);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float sc = e < 4 ? s0[e] : s1[e - 4];
-                const float sh = e < 4 ? h0[e] : h1[e - 4];
-                const float y = (v[i][e] - mu) * rstd;
-                const float u = y * (1.0f + sc) + sh;
-                v[i][e] = u;
-                hm[e] = (half_t)u;
+            for (int e = 0; e < 8; ++e)
 #pragma unroll
                 for (int j = 0; j < NOUT; ++j) {
-                    const float w = o.s[j] ? __fdiv_rn(u, o.s[j][c0 + e]) : u;
+                    const float w = o.s[j] ? __fdiv_rn(v[i][e], o.s[j][c0 + e]) : v[i][e];
                     vmin[j] = fminf(vmin[j], w);
                     vmax[j] = fmaxf(vmax[j], w);
                 }
-            }
-            if (xm_out) *reinterpret_cast<half8*>(xm_out + (size_t)tok * C + c0) = hm;
         }
     }
 #pragma unroll
     for (int j = 0; j < NOUT; ++j) {
-        float delta, zp;
+        float delta, zp, inv;
         bool small;
-        float inv;
-        vq_row_grid(wave_min_f(vmin[j]), wave_max_f(vmax[j]), qmax, delta, zp, small, inv);
+        vq_row_grid(rq_min_f<L::HALF>(vmin[j], false), rq_max_f<L::HALF>(vmax[j], false), wd.qmax, delta, zp, small, inv);
         if (small && lane == 0 && status) atomicOr(status, VQ_ST_EPSFILL);
-        const int izx = (int)zp - cx;
-        int8_t* qrow = o.xq[j] + (size_t)tok * Kp;
-        uint32_t csum = 0;
+        const float* sj = o.s[j];                          // (IEEE division again: the quotients are not kept, NOUT x 72 registers)
+        const int cs = rq_quant_row<L>(v, lc, C, Kp, delta, zp, inv, wd, o.xq[j] + (size_t)tok * Kp, true, false,
+                                       [&](int, int c0, float (&w)[8]) {
+                                           if (sj) {
 #pragma unroll
-        for (int i = 0; i < MAXCH; ++i) {
-            const int c0 = lane * 8 + i * 512;
-            if (c0 < C) {
-                float w[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) w[e] = o.s[j] ? __fdiv_rn(v[i][e], o.s[j][c0 + e]) : v[i][e];
-                uint2 p;
-                csum += rq_quant8(w, inv, delta, zp, qmax, flip, p);
-                *reinterpret_cast<uint2*>(qrow + c0) = p;
-            } else if (c0 < Kp) {
-                *reinterpret_cast<uint2*>(qrow + c0) = make_uint2(0u, 0u);
-            }
-        }
-        const int rs = wave_sum_i((int)csum) - cx * C;
-        if (lane == 0) {
-            o.sx[j][tok] = delta;
-            o.zx[j][tok] = izx;
-            o.R[j][tok] = rs - C * izx;
-        }
+                                               for (int e = 0; e < 8; ++e) w[e] = __fdiv_rn(w[e], sj[c0 + e]);
+                                           }
+                                       });
+        if (lane == 0) rq_write_row(o.sx[j], o.zx[j], o.R[j], nullptr, tok, delta, zp, cs, C, wd.cx);
     }
 }
 
@@ -731,47 +471,24 @@ __global__ __launch_bounds__(RQF_THREADS) void ln_modulate_rowquant_half_kernel(
     const half_t* __restrict__ x, const float* __restrict__ shift, const float* __restrict__ scale, float ln_eps,
     int8_t* __restrict__ xq, float* __restrict__ sx, int32_t* __restrict__ zx, int32_t* __restrict__ R, int n_tok,
     int n_bits, int32_t* status, half_t* __restrict__ xm = nullptr) {
+    using L = RqHalf<NIT>;
     constexpr int C = 128 * NIT;
-    const int lane = threadIdx.x & 63, hl = lane & 31;
+    const int lane = threadIdx.x & 63, hl = lane & 31, lc = L::lane_col(lane);
     const bool hi = lane >= 32;
-    int tok = PAIR ? blockIdx.x * RQF_WAVES + (threadIdx.x >> 6)
-                   : (blockIdx.x * RQF_WAVES + (threadIdx.x >> 6)) * 2 + (hi ? 1 : 0);
-    const bool live = tok < n_tok;
-    if (!live) tok = n_tok - 1;
+    bool live;
+    const int tok = rqh_row<PAIR>(blockIdx.x * RQF_WAVES + (threadIdx.x >> 6), hi, n_tok, live);
     if (PAIR && hi) {
-        tok += n_tok;
         shift += C;
         scale += C;
     }
-    const float qmax = (float)((1 << n_bits) - 1);
-    const int cx = (n_bits == 8) ? 128 : 0;
-    const uint32_t flip = (n_bits == 8) ? 0x80808080u : 0u;
-    const float invC = 1.0f / (float)C;
-    const half_t* row = x + (size_t)tok * C + hl * 4;
+    const RqWidth wd = rq_width(n_bits);
 
+    half4 h[NIT];
     float v[NIT][4];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-        const half4 h = *reinterpret_cast<const half4*>(row + i * 128);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[i][e] = (float)h[e];
-            sum += v[i][e];
-        }
-    }
-    RQH_REDUCE2(float, vq_addf, sum)
-    const float mu = sum * invC;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < NIT; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = v[i][e] - mu;
-            sq += d * d;
-        }
-    RQH_REDUCE2(float, vq_addf, sq)
-    const float rstd = __fdiv_rn(1.0f, __fsqrt_rn(sq * invC + ln_eps));
+    rq_load_row<L>(x + (size_t)tok * C, lc, C, h);
+    rq_widen_row<L>(h, lc, C, v);
+    float mu, rstd;
+    rq_ln_stats<L>(v, lc, C, ln_eps, hi, mu, rstd);
 
     float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
@@ -793,32 +510,22 @@ __global__ __launch_bounds__(RQF_THREADS) void ln_modulate_rowquant_half_kernel(
             }
         }
     }
-    RQH_REDUCE2(float, fminf, vmin)
-    RQH_REDUCE2(float, fmaxf, vmax)
-    if constexpr (PAIR) {                             // one grid for the token's two samples
-        vmin = fminf(vmin, __shfl_xor(vmin, 32));
-        vmax = fmaxf(vmax, __shfl_xor(vmax, 32));
-    }
-    float delta, zp;
+    rqh_minmax<PAIR>(vmin, vmax, hi);
+    float delta, zp, inv;
     bool small;
-    float inv;
-    vq_row_grid(vmin, vmax, qmax, delta, zp, small, inv);
+    vq_row_grid(vmin, vmax, wd.qmax, delta, zp, small, inv);
     if (small && hl == 0 && live && status) atomicOr(status, VQ_ST_EPSFILL);
-    const int izx = (int)zp - cx;
     int8_t* qrow = xq + (size_t)tok * C + hl * 4;
     uint32_t csum = 0;
-    RQ_BY_WIDTH(qmax, _Pragma("unroll") for (int i = 0; i < NIT; ++i) {
-        const uint32_t pk = rq_quant4<SAT8_>(v[i], inv, delta, zp, qmax);
-        csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-        if (live) *reinterpret_cast<uint32_t*>(qrow + i * 128) = pk ^ flip;
+    RQ_BY_WIDTH(wd.qmax, _Pragma("unroll") for (int i = 0; i < NIT; ++i) {
+        uint32_t pk[1];
+        rq_quant<4, SAT8_>(v[i], inv, delta, zp, wd.qmax, pk);
+        csum = __builtin_amdgcn_sad_u8(pk[0], 0u, csum);
+        if (live) *reinterpret_cast<uint32_t*>(qrow + i * 128) = pk[0] ^ wd.flip;
     })
     int cs = (int)csum;
     RQH_REDUCE2(int, vq_addi, cs)
-    if (hl == 0 && live) {
-        sx[tok] = delta;
-        zx[tok] = izx;
-        R[tok] = cs - cx * C - C * izx;
-    }
+    if (hl == 0 && live) rq_write_row(sx, zx, R, nullptr, tok, delta, zp, cs, C, wd.cx);
 }
 
 // ---------------------------------------------------------------------------
@@ -836,133 +543,60 @@ __global__ __launch_bounds__(RQF_THREADS) void ln_modulate_rowquant_half_kernel(
 template <int NIT, bool LN, int RPW, bool PAIR = false>   // PAIR: the wave's two rows are ONE token of a batch of two (see rowquant_half_kernel)
 __global__ __launch_bounds__(RQF_THREADS) void smooth_rowquant_half_kernel(
     const half_t* __restrict__ x, const float* __restrict__ shift, const float* __restrict__ scale, float ln_eps,
-    LnqFastOut o, half_t* __restrict__ xm_out, int n_tok, int n_bits, int32_t* status) {
+    LnqOut o, half_t* __restrict__ xm_out, int n_tok, int n_bits, int32_t* status) {
+    using L = RqHalf<NIT>;
     constexpr int C = 128 * NIT;
-    const int lane = threadIdx.x & 63, hl = lane & 31;
+    const int lane = threadIdx.x & 63, hl = lane & 31, lc = L::lane_col(lane);
     const bool hi = lane >= 32;
     const int j = blockIdx.y;
-    const float qmax = (float)((1 << n_bits) - 1);
-    const int cx = (n_bits == 8) ? 128 : 0;
-    const uint32_t flip = (n_bits == 8) ? 0x80808080u : 0u;
-    const float invC = 1.0f / (float)C;
+    const RqWidth wd = rq_width(n_bits);
     const float* __restrict__ sp = o.s[j];
     const float* __restrict__ rp = o.r[j];
-    int8_t* __restrict__ xq = o.xq[j];
-    float4v s4[NIT], r4[NIT], sc4[LN ? NIT : 1], sh4[LN ? NIT : 1];
+    float s4[NIT][4], r4[NIT][4], sc1[LN ? NIT : 1][4], sh[LN ? NIT : 1][4];
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
-        s4[i] = *reinterpret_cast<const float4v*>(sp + i * 128 + hl * 4);
-        r4[i] = *reinterpret_cast<const float4v*>(rp + i * 128 + hl * 4);
+        rq_load_f<4>(sp + lc + i * 128, s4[i]);
+        rq_load_f<4>(rp + lc + i * 128, r4[i]);
         if constexpr (LN) {
             const int bo = (PAIR && hi) ? C : 0;           // modulation vectors of the upper half's sample
-            sc4[i] = *reinterpret_cast<const float4v*>(scale + bo + i * 128 + hl * 4);
-            sh4[i] = *reinterpret_cast<const float4v*>(shift + bo + i * 128 + hl * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sc4[i][e] = 1.0f + sc4[i][e];
+            rq_load_mod<4>(scale + bo + lc + i * 128, shift + bo + lc + i * 128, sc1[i], sh[i]);
         }
     }
     const int pair0 = (blockIdx.x * RQF_WAVES + (threadIdx.x >> 6)) * RPW;
-    // row of this half-wave in walk step p: two consecutive rows, or (PAIR) the two samples of token p
-    auto row_of = [&](int p) {
-        if constexpr (PAIR) return (p < n_tok ? p : n_tok - 1) + (hi ? n_tok : 0);
-        else {
-            const int t = p * 2 + (hi ? 1 : 0);
-            return t < n_tok ? t : n_tok - 1;
-        }
-    };
+    bool live;
     half4 hn[NIT];
-    {
-        const int t = row_of(pair0);
-        const half_t* row = x + (size_t)t * C + hl * 4;
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) hn[i] = *reinterpret_cast<const half4*>(row + i * 128);
-    }
+    rq_load_row<L>(x + (size_t)rqh_row<PAIR>(pair0, hi, n_tok, live) * C, lc, C, hn);
     for (int it = 0; it < RPW; ++it) {
         if ((PAIR ? pair0 + it : (pair0 + it) * 2) >= n_tok) break;   // wave-uniform
-        const bool live = PAIR || (pair0 + it) * 2 + (hi ? 1 : 0) < n_tok;
-        const int tok = row_of(pair0 + it);                // odd tail: the upper half re-does the last row, writes nothing
+        const int tok = rqh_row<PAIR>(pair0 + it, hi, n_tok, live);
         float w[NIT][4];
-#pragma unroll
-        for (int i = 0; i < NIT; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[i][e] = (float)hn[i][e];
+        rq_widen_row<L>(hn, lc, C, w);
         if (it + 1 < RPW) {                                // next pair's rows fly under this pair's arithmetic
-            const int t = row_of(pair0 + it + 1);
-            const half_t* row = x + (size_t)t * C + hl * 4;
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) hn[i] = *reinterpret_cast<const half4*>(row + i * 128);
+            bool unused;
+            rq_load_row<L>(x + (size_t)rqh_row<PAIR>(pair0 + it + 1, hi, n_tok, unused) * C, lc, C, hn);
         }
         if constexpr (LN) {
-            float sum = 0.f;
+            float mu, rstd;
+            rq_ln_stats<L>(w, lc, C, ln_eps, hi, mu, rstd);
 #pragma unroll
             for (int i = 0; i < NIT; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sum += w[i][e];
-            RQH_REDUCE2(float, vq_addf, sum)
-            const float mu = sum * invC;
-            float sq = 0.f;
-#pragma unroll
-            for (int i = 0; i < NIT; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float d = w[i][e] - mu;
-                    sq += d * d;
-                }
-            RQH_REDUCE2(float, vq_addf, sq)
-            const float rstd = __fdiv_rn(1.0f, __fsqrt_rn(sq * invC + ln_eps));
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) {
-                half4 hm;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float y = (w[i][e] - mu) * rstd;
-                    const float u = y * sc4[i][e] + sh4[i][e];
-                    hm[e] = (half_t)u;
-                    w[i][e] = u;
-                }
-                if (xm_out && j == 0 && live) *reinterpret_cast<half4*>(xm_out + (size_t)tok * C + hl * 4 + i * 128) = hm;
-            }
+                rq_modulate<4>(w[i], mu, rstd, sc1[i], sh[i], xm_out && j == 0 && live, xm_out, (size_t)tok * C + lc + i * 128);
         }
         float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
-        for (int i = 0; i < NIT; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                w[i][e] = rq_div_rcp(w[i][e], s4[i][e], r4[i][e]);
-                vmin = fminf(vmin, w[i][e]);
-                vmax = fmaxf(vmax, w[i][e]);
-            }
-        RQH_REDUCE2(float, fminf, vmin)
-        RQH_REDUCE2(float, fmaxf, vmax)
-        if constexpr (PAIR) {                              // one grid for the token's two samples
-            vmin = fminf(vmin, __shfl_xor(vmin, 32));
-            vmax = fmaxf(vmax, __shfl_xor(vmax, 32));
-        }
-        float delta, zp;
+        for (int i = 0; i < NIT; ++i) rq_smooth_chunk<4>(w[i], s4[i], r4[i], w[i], vmin, vmax);
+        rqh_minmax<PAIR>(vmin, vmax, hi);
+        float delta, zp, inv;
         bool small;
-        float inv;
-        vq_row_grid(vmin, vmax, qmax, delta, zp, small, inv);
+        vq_row_grid(vmin, vmax, wd.qmax, delta, zp, small, inv);
         if (small && hl == 0 && live && status) atomicOr(status, VQ_ST_EPSFILL);
-        const int izx = (int)zp - cx;
-        int8_t* qrow = xq + (size_t)tok * C + hl * 4;
-        uint32_t csum = 0;
-        RQ_BY_WIDTH(qmax, _Pragma("unroll") for (int i = 0; i < NIT; ++i) {
-            const uint32_t pk = rq_quant4<SAT8_>(w[i], inv, delta, zp, qmax);
-            csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-            if (live) *reinterpret_cast<uint32_t*>(qrow + i * 128) = pk ^ flip;
-        })
-        int cs = (int)csum;
-        RQH_REDUCE2(int, vq_addi, cs)
-        if (hl == 0 && live) {
-            o.sx[j][tok] = delta;
-            o.zx[j][tok] = izx;
-            o.R[j][tok] = cs - cx * C - C * izx;
-        }
+        const int cs = rq_quant_row<L>(w, lc, C, C, delta, zp, inv, wd, o.xq[j] + (size_t)tok * C, live, hi);
+        if (hl == 0 && live) rq_write_row(o.sx[j], o.zx[j], o.R[j], nullptr, tok, delta, zp, cs, C, wd.cx);
     }
 }
 
 template <bool LN, int RPW, bool PAIR = false>
-static bool launch_smooth_half(const half_t* x, const float* shift, const float* scale, float eps, const LnqFastOut& o,
+static bool launch_smooth_half(const half_t* x, const float* shift, const float* scale, float eps, const LnqOut& o,
                                int n_out, half_t* xm, int n_tok, int C, int n_bits, int32_t* status, hipStream_t st) {
     constexpr int PER = (PAIR ? 1 : 2) * RQF_WAVES * RPW;   // rows (PAIR: tokens) per workgroup
     dim3 grid((n_tok + PER - 1) / PER, n_out);
@@ -990,24 +624,17 @@ constexpr int VQ_SMM_MINW = 4, VQ_SMM_RPW = 1, VQ_SMM_NWV = 8;
 template <int NIT, bool LN, int NOUT, int RPW, int NWV>
 __global__ __launch_bounds__(64 * NWV, NOUT == 1 ? VQ_SM1_MINW : VQ_SMM_MINW) void smooth_rowquant_multi_kernel(
     const half_t* __restrict__ x, const float* __restrict__ shift, const float* __restrict__ scale, float ln_eps,
-    LnqFastOut o, half_t* __restrict__ xm_out, int n_tok, int n_bits, int32_t* status) {
+    LnqOut o, half_t* __restrict__ xm_out, int n_tok, int n_bits, int32_t* status) {
+    using L = RqHalf<NIT>;
     constexpr int C = 128 * NIT;
     extern __shared__ __attribute__((aligned(16))) float smq_lds[];   // [NOUT][s | r][C], then (LN) [1 + scale | shift][C]
-    const int lane = threadIdx.x & 63, hl = lane & 31;
+    const int lane = threadIdx.x & 63, hl = lane & 31, lc = L::lane_col(lane);
     const bool hi = lane >= 32;
-    const float qmax = (float)((1 << n_bits) - 1);
-    const int cx = (n_bits == 8) ? 128 : 0;
-    const uint32_t flip = (n_bits == 8) ? 0x80808080u : 0u;
-    const float invC = 1.0f / (float)C;
+    const RqWidth wd = rq_width(n_bits);
     const int pair0 = (blockIdx.x * NWV + (threadIdx.x >> 6)) * RPW;
-    half4 hn[NIT];
-    {                                                      // the first rows are requested before the staging loads
-        int t = pair0 * 2 + (hi ? 1 : 0);
-        t = t < n_tok ? t : n_tok - 1;
-        const half_t* row = x + (size_t)t * C + hl * 4;
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) hn[i] = *reinterpret_cast<const half4*>(row + i * 128);
-    }
+    bool live;
+    half4 hn[NIT];                                         // the first rows are requested before the staging loads
+    rq_load_row<L>(x + (size_t)rqh_row<false>(pair0, hi, n_tok, live) * C, lc, C, hn);
     for (int i = threadIdx.x; i < C / 4; i += 64 * NWV) {
 #pragma unroll
         for (int j = 0; j < NOUT; ++j) {
@@ -1015,62 +642,31 @@ __global__ __launch_bounds__(64 * NWV, NOUT == 1 ? VQ_SM1_MINW : VQ_SMM_MINW) vo
             reinterpret_cast<float4v*>(smq_lds + (2 * j + 1) * C)[i] = reinterpret_cast<const float4v*>(o.r[j])[i];
         }
         if constexpr (LN) {
-            float4v sc = reinterpret_cast<const float4v*>(scale)[i];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sc[e] = 1.0f + sc[e];
-            reinterpret_cast<float4v*>(smq_lds + (2 * NOUT) * C)[i] = sc;
-            reinterpret_cast<float4v*>(smq_lds + (2 * NOUT + 1) * C)[i] = reinterpret_cast<const float4v*>(shift)[i];
+            float sc1[4], sh[4];
+            rq_load_mod<4>(scale + 4 * i, shift + 4 * i, sc1, sh);
+            reinterpret_cast<float4v*>(smq_lds + (2 * NOUT) * C)[i] = *reinterpret_cast<const float4v*>(sc1);
+            reinterpret_cast<float4v*>(smq_lds + (2 * NOUT + 1) * C)[i] = *reinterpret_cast<const float4v*>(sh);
         }
     }
     __syncthreads();
     for (int it = 0; it < RPW; ++it) {
         if ((pair0 + it) * 2 >= n_tok) break;              // wave-uniform
-        int tok = (pair0 + it) * 2 + (hi ? 1 : 0);
-        const bool live = tok < n_tok;
-        if (!live) tok = n_tok - 1;                        // odd tail: the upper half re-does the last row, writes nothing
+        const int tok = rqh_row<false>(pair0 + it, hi, n_tok, live);
         float w[NIT][4];
-#pragma unroll
-        for (int i = 0; i < NIT; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[i][e] = (float)hn[i][e];
+        rq_widen_row<L>(hn, lc, C, w);
         if (it + 1 < RPW) {                                // next pair's rows fly under this pair's arithmetic
-            int t = (pair0 + it + 1) * 2 + (hi ? 1 : 0);
-            t = t < n_tok ? t : n_tok - 1;
-            const half_t* row = x + (size_t)t * C + hl * 4;
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) hn[i] = *reinterpret_cast<const half4*>(row + i * 128);
+            bool unused;
+            rq_load_row<L>(x + (size_t)rqh_row<false>(pair0 + it + 1, hi, n_tok, unused) * C, lc, C, hn);
         }
         if constexpr (LN) {
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < NIT; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sum += w[i][e];
-            RQH_REDUCE2(float, vq_addf, sum)
-            const float mu = sum * invC;
-            float sq = 0.f;
-#pragma unroll
-            for (int i = 0; i < NIT; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float d = w[i][e] - mu;
-                    sq += d * d;
-                }
-            RQH_REDUCE2(float, vq_addf, sq)
-            const float rstd = __fdiv_rn(1.0f, __fsqrt_rn(sq * invC + ln_eps));
+            float mu, rstd;
+            rq_ln_stats<L>(w, lc, C, ln_eps, hi, mu, rstd);
 #pragma unroll
             for (int i = 0; i < NIT; ++i) {
-                const float4v sc4 = *reinterpret_cast<const float4v*>(smq_lds + (2 * NOUT) * C + i * 128 + hl * 4);
-                const float4v sh4 = *reinterpret_cast<const float4v*>(smq_lds + (2 * NOUT + 1) * C + i * 128 + hl * 4);
-                half4 hm;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float y = (w[i][e] - mu) * rstd;
-                    const float u = y * sc4[e] + sh4[e];
-                    hm[e] = (half_t)u;
-                    w[i][e] = u;
-                }
-                if (xm_out && live) *reinterpret_cast<half4*>(xm_out + (size_t)tok * C + hl * 4 + i * 128) = hm;
+                float sc1[4], sh[4];
+                rq_load_f<4>(smq_lds + (2 * NOUT) * C + lc + i * 128, sc1);
+                rq_load_f<4>(smq_lds + (2 * NOUT + 1) * C + lc + i * 128, sh);
+                rq_modulate<4>(w[i], mu, rstd, sc1, sh, xm_out && live, xm_out, (size_t)tok * C + lc + i * 128);
             }
         }
 #pragma unroll
@@ -1079,43 +675,24 @@ __global__ __launch_bounds__(64 * NWV, NOUT == 1 ? VQ_SM1_MINW : VQ_SMM_MINW) vo
             float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
             for (int i = 0; i < NIT; ++i) {
-                const float4v s4 = *reinterpret_cast<const float4v*>(smq_lds + (2 * j) * C + i * 128 + hl * 4);
-                const float4v r4 = *reinterpret_cast<const float4v*>(smq_lds + (2 * j + 1) * C + i * 128 + hl * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    q[i][e] = rq_div_rcp(w[i][e], s4[e], r4[e]);
-                    vmin = fminf(vmin, q[i][e]);
-                    vmax = fmaxf(vmax, q[i][e]);
-                }
+                float s4[4], r4[4];
+                rq_load_f<4>(smq_lds + (2 * j) * C + lc + i * 128, s4);
+                rq_load_f<4>(smq_lds + (2 * j + 1) * C + lc + i * 128, r4);
+                rq_smooth_chunk<4>(w[i], s4, r4, q[i], vmin, vmax);
             }
-            RQH_REDUCE2(float, fminf, vmin)
-            RQH_REDUCE2(float, fmaxf, vmax)
-            float delta, zp;
+            rqh_minmax<false>(vmin, vmax, hi);
+            float delta, zp, inv;
             bool small;
-            float inv;
-            vq_row_grid(vmin, vmax, qmax, delta, zp, small, inv);
+            vq_row_grid(vmin, vmax, wd.qmax, delta, zp, small, inv);
             if (small && hl == 0 && live && status) atomicOr(status, VQ_ST_EPSFILL);
-            const int izx = (int)zp - cx;
-            int8_t* qrow = o.xq[j] + (size_t)tok * C + hl * 4;
-            uint32_t csum = 0;
-            RQ_BY_WIDTH(qmax, _Pragma("unroll") for (int i = 0; i < NIT; ++i) {
-                const uint32_t pk = rq_quant4<SAT8_>(q[i], inv, delta, zp, qmax);
-                csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-                if (live) *reinterpret_cast<uint32_t*>(qrow + i * 128) = pk ^ flip;
-            })
-            int cs = (int)csum;
-            RQH_REDUCE2(int, vq_addi, cs)
-            if (hl == 0 && live) {
-                o.sx[j][tok] = delta;
-                o.zx[j][tok] = izx;
-                o.R[j][tok] = cs - cx * C - C * izx;
-            }
+            const int cs = rq_quant_row<L>(q, lc, C, C, delta, zp, inv, wd, o.xq[j] + (size_t)tok * C, live, hi);
+            if (hl == 0 && live) rq_write_row(o.sx[j], o.zx[j], o.R[j], nullptr, tok, delta, zp, cs, C, wd.cx);
         }
     }
 }
 
 template <bool LN, int NOUT>
-static bool launch_smooth_multi(const half_t* x, const float* shift, const float* scale, float eps, const LnqFastOut& o,
+static bool launch_smooth_multi(const half_t* x, const float* shift, const float* scale, float eps, const LnqOut& o,
                                 half_t* xm, int n_tok, int C, int n_bits, int32_t* status, hipStream_t st) {
     constexpr int RPW = NOUT == 1 ? VQ_SM1_RPW : VQ_SMM_RPW, NWV = NOUT == 1 ? VQ_SM1_NWV : VQ_SMM_NWV;
     const size_t lds = (size_t)(2 * NOUT + (LN ? 2 : 0)) * C * sizeof(float);
@@ -1159,7 +736,7 @@ bool vq_rowquant_fast(const half_t* x, const half_t* add_rows, int add_div, cons
         return true;
     const bool half_wave = rq_block_width(C) && Kp == C && n_tok >= 2;
     if (hs && s_rcp && !ha && !zpf && half_wave) {
-        const LnqFastOut o = lnq_one(s, s_rcp, xq, sx, zx, R);
+        const LnqOut o = lnq_one(s, s_rcp, xq, sx, zx, R);
         if (vq_sm1_mode() && launch_smooth_multi<false, 1>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;
         if (launch_smooth_half<false, 2>(x, nullptr, nullptr, 0.f, o, 1, nullptr, n_tok, C, n_bits, status, st)) return true;
     }
@@ -1218,7 +795,7 @@ bool vq_lnq_pair_fast(const half_t* x, const float* shift, const float* scale, f
 
 template <int MAXCH>
 static void launch_lnq(int n_out, dim3 grid, hipStream_t st, const half_t* x, const float* shift, const float* scale,
-                       float eps, const LnqFastOut& o, half_t* xm, int n_tok, int C, int Kp, int n_bits,
+                       float eps, const LnqOut& o, half_t* xm, int n_tok, int C, int Kp, int n_bits,
                        int32_t* status) {
     auto go = [&](auto nout) {
         hipLaunchKernelGGL((ln_modulate_rowquant_fast_kernel<MAXCH, nout()>), grid, dim3(RQF_THREADS), 0, st, x, shift, scale, eps, o,
@@ -1282,7 +859,7 @@ bool vq_lnq_fast(const half_t* x, const float* shift, const float* scale, float 
         bool all = s && s_rcp && half_wave;
         for (int j = 0; all && j < n_out; ++j) all = s[j] && s_rcp[j];
         if (all) {
-            const LnqFastOut o = lnq_many(n_out, s, s_rcp, xq, sx, zx, R);
+            const LnqOut o = lnq_many(n_out, s, s_rcp, xq, sx, zx, R);
             if (n_out == 3 && launch_smooth_multi<true, 3>(x, shift, scale, eps, o, xm, n_tok, C, n_bits, status, st)) return true;
             if (n_out == 2 && launch_smooth_multi<true, 2>(x, shift, scale, eps, o, xm, n_tok, C, n_bits, status, st)) return true;
             if (n_out == 1 && vq_sm1_mode() && launch_smooth_multi<true, 1>(x, shift, scale, eps, o, xm, n_tok, C, n_bits, status, st)) return true;
@@ -1296,7 +873,7 @@ bool vq_lnq_fast(const half_t* x, const float* shift, const float* scale, float 
                                xq[0], sx[0], zx[0], R[0], n_tok, n_bits, status);
         });
     }
-    const LnqFastOut o = lnq_many(n_out, s, nullptr, xq, sx, zx, R);       // (IEEE division: no reciprocals)
+    const LnqOut o = lnq_many(n_out, s, nullptr, xq, sx, zx, R);       // (IEEE division: no reciprocals)
     dim3 grid((n_tok + RQF_WAVES - 1) / RQF_WAVES);
     vq_dispatch_maxch(Kp, [&](auto m) {
         if constexpr (m() <= 3)                               // (Kp <= 1536 here: no MAXCH = 9 form of this kernel exists)
@@ -1310,7 +887,7 @@ bool vq_rowquant_smooth_multi_fast(const half_t* x, int n_out, const float* cons
                                    int8_t* const* xq, float* const* sx, int32_t* const* zx, int32_t* const* R, int n_tok,
                                    int C, int Kp, int n_bits, int32_t* status, hipStream_t st) {
     if (Kp != C || !rq_block_width(C) || n_tok < 2) return false;
-    const LnqFastOut o = lnq_many(n_out, s, s_rcp, xq, sx, zx, R);
+    const LnqOut o = lnq_many(n_out, s, s_rcp, xq, sx, zx, R);
     if (n_out == 3 && launch_smooth_multi<false, 3>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;
     if (n_out == 2 && launch_smooth_multi<false, 2>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;
     if (n_out == 1 && vq_sm1_mode() && launch_smooth_multi<false, 1>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;

@@ -65,31 +65,6 @@ struct RqsArgs {
     int n_param, rows, n_tok, C, Kp, n_bits;
 };
 
-// lane -> column maps: NCH chunks of W consecutive channels per lane
-template <int NIT>
-struct RqsHalf {             // a half-wave owns a row of C = 128 * NIT channels (Kp == C)
-    static constexpr bool HALF = true;
-    static constexpr int NCH = NIT, W = 4, STEP = 128, ROWS = 2 * RQS_WAVES;
-};
-template <int MAXCH>
-struct RqsWave {             // a wave owns a row (SPLIT: half a row) of up to MAXCH * 512 padded channels
-    static constexpr bool HALF = false;
-    static constexpr int NCH = MAXCH, W = 8, STEP = 512, ROWS = RQS_WAVES;
-};
-
-template <bool HALF>
-__device__ __forceinline__ float rqs_sum_f(float v, bool hi) {
-    if constexpr (HALF) RQH_REDUCE2(float, vq_addf, v)
-    else v = wave_sum_f(v);
-    return v;
-}
-template <bool HALF>
-__device__ __forceinline__ int rqs_sum_i(int v, bool hi) {
-    if constexpr (HALF) RQH_REDUCE2(int, vq_addi, v)
-    else v = wave_sum_i(v);
-    return v;
-}
-
 // the grid of one (row, output): step, zero point, reciprocal and the tie guard of the product form (file comment)
 struct RqsGrid {
     float delta, zp, inv, thr;
@@ -128,27 +103,13 @@ __device__ __forceinline__ void rqs_quant(const float (&x)[N], const RqsGrid& g,
             if (!(__builtin_fabsf(t[i] - r[i]) <= g.thr)) r[i] = rintf(__fdiv_rn(x[i], g.delta));
     }
 #pragma unroll
-    for (int k = 0; k < N / 4; ++k) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float q = r[4 * k + e] + g.zp;
-            if constexpr (!SAT8) q = __builtin_amdgcn_fmed3f(q, 0.0f, qmax);
-            w = __builtin_amdgcn_cvt_pk_u8_f32(q, e, w);     // integer-valued (or infinite) input; saturates to [0, 255]
-        }
-        pk[k] = w;
-    }
-}
-
-template <int W>
-__device__ __forceinline__ void rqs_store_codes(int8_t* dst, const uint32_t (&pk)[W / 4]) {
-    if constexpr (W == 8) *reinterpret_cast<uint2*>(dst) = make_uint2(pk[0], pk[1]);
-    else *reinterpret_cast<uint32_t*>(dst) = pk[0];
+    for (int i = 0; i < N; ++i) r[i] += g.zp;
+    rq_pack_codes<N, SAT8>(r, qmax, pk);
 }
 
 // ---------------------------------------------------------------------------
-// L: RqsHalf<NIT> / RqsWave<MAXCH>.  ARM: plain / + add_rows[(r % n_tok) / add_div] / LayerNorm + modulate.
-// SPLIT (RqsWave only, Kp == C, C % 16 == 0): waves 2k / 2k + 1 take the two halves of a row and add their code sums
+// L: RqHalf<NIT> / RqWave<MAXCH>.  ARM: plain / + add_rows[(r % n_tok) / add_div] / LayerNorm + modulate.
+// SPLIT (RqWave only, Kp == C, C % 16 == 0): waves 2k / 2k + 1 take the two halves of a row and add their code sums
 // through LDS.  Dynamic LDS: [NOUT][s | 1/s][C] floats when any output is smoothed (staged once per workgroup).
 // At most 128 VGPRs (4 waves per SIMD asked of the compiler) wherever the row fits: every wave of a 16384-row launch
 // is resident at once; the LayerNorm arm of rows longer than 1536 channels holds 72 fp32 values per lane and is not bound.
@@ -157,7 +118,7 @@ template <class L, int ARM, int NOUT, bool SPLIT>
 __global__ __launch_bounds__(RQS_THREADS, (ARM == RQS_LN && L::NCH * L::W > 40) ? 1 : 4) void rowquant_static_kernel(RqsArgs a) {
     static_assert(!SPLIT || (!L::HALF && ARM != RQS_LN), "split rows: one-row-per-wave map, no row statistics");
     constexpr int NCH = L::NCH, W = L::W;
-    typedef _Float16 hvec __attribute__((ext_vector_type(W)));
+    typedef typename L::hvec hvec;
     extern __shared__ __attribute__((aligned(16))) float rqs_lds[];
     __shared__ int ps[SPLIT ? NOUT : 1][RQS_WAVES];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -186,17 +147,14 @@ __global__ __launch_bounds__(RQS_THREADS, (ARM == RQS_LN && L::NCH * L::W > 40) 
     const int seg = SPLIT ? C / 2 : C;                    // this wave's channels [col0, col0 + seg), padded to segp
     const int segp = SPLIT ? C / 2 : a.Kp;
     const int col0 = (SPLIT && (wv & 1)) ? C / 2 : 0;
-    const int lc = L::HALF ? (lane & 31) * 4 : lane * 8;  // + i * STEP: the lane's i-th chunk inside the segment
-    const float qmax = (float)((1 << a.n_bits) - 1);
-    const int cx = (a.n_bits == 8) ? 128 : 0;
-    const uint32_t flip = (a.n_bits == 8) ? 0x80808080u : 0u;
+    const int lc = L::lane_col(lane);                     // + i * STEP: the lane's i-th chunk inside the segment
+    const RqWidth wd = rq_width(a.n_bits);
+    const float qmax = wd.qmax;
     const int tok = row % a.n_tok;
     const half_t* xrow = a.x + (size_t)row * C + col0;
 
     hvec h[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-        if (L::HALF || lc + i * L::STEP < seg) h[i] = *reinterpret_cast<const hvec*>(xrow + lc + i * L::STEP);
+    rq_load_row<L>(xrow, lc, seg, h);
 
     RqsGrid g[NOUT];
 #pragma unroll
@@ -207,36 +165,8 @@ __global__ __launch_bounds__(RQS_THREADS, (ARM == RQS_LN && L::NCH * L::W > 40) 
     float mu = 0.f, rstd = 0.f;
     const float *shp = nullptr, *scp = nullptr;
     if constexpr (ARM == RQS_LN) {
-        float invC;                                       // (a constant in the half-wave kernel this mirrors)
-        if constexpr (L::HALF) invC = 1.0f / (float)(128 * NCH);
-        else invC = 1.0f / (float)C;
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i)
-            if (L::HALF || lc + i * L::STEP < C)
-#pragma unroll
-                for (int e = 0; e < W; ++e) {
-                    v[i][e] = (float)h[i][e];
-                    sum += v[i][e];
-                }
-        sum = rqs_sum_f<L::HALF>(sum, hi);
-        mu = sum * invC;
-        float sq = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i)
-            if (L::HALF || lc + i * L::STEP < C)
-#pragma unroll
-                for (int e = 0; e < W; ++e) {
-                    const float d = v[i][e] - mu;
-                    sq += d * d;
-                }
-        sq = rqs_sum_f<L::HALF>(sq, hi);
-        if constexpr (L::HALF) {
-            rstd = __fdiv_rn(1.0f, __fsqrt_rn(sq * invC + a.ln_eps));
-        } else {
-            const float var = sq * invC;
-            rstd = __fdiv_rn(1.0f, __fsqrt_rn(var + a.ln_eps));
-        }
+        rq_widen_row<L>(h, lc, C, v);
+        rq_ln_stats<L>(v, lc, C, a.ln_eps, hi, mu, rstd);
         const size_t bo = (size_t)(row / a.n_tok) * C;    // modulation vectors of the row's sample
         shp = a.shift + bo;
         scp = a.scale + bo;
@@ -255,28 +185,12 @@ __global__ __launch_bounds__(RQS_THREADS, (ARM == RQS_LN && L::NCH * L::W > 40) 
         if (L::HALF || c < seg) {
             float u[W];
             if constexpr (ARM == RQS_LN) {
-                float sc[W], sh[W];
-                if constexpr (W == 8) {
-                    *reinterpret_cast<float4v*>(sc) = *reinterpret_cast<const float4v*>(scp + c);
-                    *reinterpret_cast<float4v*>(sc + 4) = *reinterpret_cast<const float4v*>(scp + c + 4);
-                    *reinterpret_cast<float4v*>(sh) = *reinterpret_cast<const float4v*>(shp + c);
-                    *reinterpret_cast<float4v*>(sh + 4) = *reinterpret_cast<const float4v*>(shp + c + 4);
-                } else {
-                    *reinterpret_cast<float4v*>(sc) = *reinterpret_cast<const float4v*>(scp + c);
-                    *reinterpret_cast<float4v*>(sh) = *reinterpret_cast<const float4v*>(shp + c);
-                }
-                hvec hm;
-#pragma unroll
-                for (int e = 0; e < W; ++e) {
-                    const float y = (v[i][e] - mu) * rstd;
-                    const float m = y * (1.0f + sc[e]) + sh[e];
-                    hm[e] = (half_t)m;
-                    u[e] = (float)hm[e];                   // the grid quantizes the STORED fp16 activation
-                }
-                if (a.xm && live) *reinterpret_cast<hvec*>(a.xm + (size_t)row * C + c) = hm;
+                float sc1[W], sh[W];
+                rq_load_mod<W>(scp + c, shp + c, sc1, sh);
+                const hvec hm = rq_modulate<W>(v[i], mu, rstd, sc1, sh, a.xm && live, a.xm, (size_t)row * C + c);
+                rq_widen(hm, u);                           // the grid quantizes the STORED fp16 activation
             } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e) u[e] = (float)h[i][e];
+                rq_widen(h[i], u);
                 if constexpr (ARM == RQS_ADD) {
                     const hvec ad = *reinterpret_cast<const hvec*>(addp + c);
 #pragma unroll
@@ -289,13 +203,10 @@ __global__ __launch_bounds__(RQS_THREADS, (ARM == RQS_LN && L::NCH * L::W > 40) 
                 if (a.s[j]) {                              // kernel-uniform
                     const float* ls = rqs_lds + (2 * j) * C + col0 + c;
                     float sv[W];
-#pragma unroll
-                    for (int k = 0; k < W / 4; ++k) *reinterpret_cast<float4v*>(sv + 4 * k) = *reinterpret_cast<const float4v*>(ls + 4 * k);
+                    rq_load_f<W>(ls, sv);
                     if (a.r[j]) {
                         float rv[W];
-#pragma unroll
-                        for (int k = 0; k < W / 4; ++k)
-                            *reinterpret_cast<float4v*>(rv + 4 * k) = *reinterpret_cast<const float4v*>(ls + C + 4 * k);
+                        rq_load_f<W>(ls + C, rv);
 #pragma unroll
                         for (int e = 0; e < W; ++e) w[e] = rq_div_rcp(u[e], sv[e], rv[e]);
                     } else {
@@ -311,15 +222,15 @@ __global__ __launch_bounds__(RQS_THREADS, (ARM == RQS_LN && L::NCH * L::W > 40) 
 #pragma unroll
                 for (int k = 0; k < W / 4; ++k) {
                     csum[j] = __builtin_amdgcn_sad_u8(pk[k], 0u, csum[j]);
-                    pk[k] ^= flip;
+                    pk[k] ^= wd.flip;
                 }
-                if (live) rqs_store_codes<W>(a.xq[j] + (size_t)row * a.Kp + col0 + c, pk);
+                if (live) rq_store_codes<W>(a.xq[j] + (size_t)row * a.Kp + col0 + c, pk);
             }
         } else if (c < segp) {                             // pad columns [C, Kp)
             const uint32_t zero[W / 4] = {};
 #pragma unroll
             for (int j = 0; j < NOUT; ++j)
-                if (live) rqs_store_codes<W>(a.xq[j] + (size_t)row * a.Kp + col0 + c, zero);
+                if (live) rq_store_codes<W>(a.xq[j] + (size_t)row * a.Kp + col0 + c, zero);
         }
       }
     };
@@ -328,7 +239,7 @@ __global__ __launch_bounds__(RQS_THREADS, (ARM == RQS_LN && L::NCH * L::W > 40) 
     int rs[NOUT];
 #pragma unroll
     for (int j = 0; j < NOUT; ++j) {
-        rs[j] = rqs_sum_i<L::HALF>((int)csum[j], hi);
+        rs[j] = rq_sum_i<L::HALF>((int)csum[j], hi);
         if constexpr (SPLIT)
             if (lane == 0) ps[j][wv] = rs[j];
     }
@@ -337,12 +248,9 @@ __global__ __launch_bounds__(RQS_THREADS, (ARM == RQS_LN && L::NCH * L::W > 40) 
     if (writer) {
 #pragma unroll
         for (int j = 0; j < NOUT; ++j) {
-            const int izx = (int)g[j].zp - cx;
             int sum = rs[j];
             if constexpr (SPLIT) sum += ps[j][wv ^ 1];
-            a.sx[j][row] = g[j].delta;
-            a.zx[j][row] = izx;
-            a.R[j][row] = sum - cx * C - C * izx;
+            rq_write_row(a.sx[j], a.zx[j], a.R[j], nullptr, row, g[j].delta, g[j].zp, sum, C, wd.cx);
         }
     }
 }
@@ -355,7 +263,7 @@ static int rqs_launch(const RqsArgs& a, int n_out, hipStream_t st) {
     int lds = 0;
     for (int j = 0; j < n_out; ++j)
         if (a.s[j]) lds = 2 * n_out * a.C * (int)sizeof(float);
-    const int per = SPLIT ? RQS_WAVES / 2 : L::ROWS;
+    const int per = SPLIT ? RQS_WAVES / 2 : (L::HALF ? 2 : 1) * RQS_WAVES;   // rows per workgroup
     const dim3 grid((a.rows + per - 1) / per), block(RQS_THREADS);
     auto go = [&](auto nout) -> int {
         constexpr auto k = rowquant_static_kernel<L, ARM, nout(), SPLIT>;
@@ -378,12 +286,12 @@ static int rqs_dispatch(const RqsArgs& a, int n_out, int B, hipStream_t st) {
     const bool half_wave = block_w && (ARM != RQS_LN || B == 2);
     int rc = VQ_OK;
     if (half_wave) {
-        vq_dispatch_nit(a.C, [&](auto nit) { rc = rqs_launch<RqsHalf<nit()>, ARM, false>(a, n_out, st); });
+        vq_dispatch_nit(a.C, [&](auto nit) { rc = rqs_launch<RqHalf<nit()>, ARM, false>(a, n_out, st); });
         return rc;
     }
     if constexpr (ARM == RQS_PLAIN)
-        if (a.C == RQS_MAX_KP && a.Kp == a.C && a.rows >= 2) return rqs_launch<RqsWave<5>, ARM, true>(a, n_out, st);
-    vq_dispatch_maxch(a.Kp, [&](auto m) { rc = rqs_launch<RqsWave<m()>, ARM, false>(a, n_out, st); });
+        if (a.C == RQS_MAX_KP && a.Kp == a.C && a.rows >= 2) return rqs_launch<RqWave<5>, ARM, true>(a, n_out, st);
+    vq_dispatch_maxch(a.Kp, [&](auto m) { rc = rqs_launch<RqWave<m()>, ARM, false>(a, n_out, st); });
     return rc;
 }
 
