@@ -327,6 +327,27 @@ int vq_attn_temporal_long(const void* q, const void* k, const void* v, const flo
                           int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o, int B, int T,
                           int S, int H, int D, long ld_in, long ld_out, int Kp, float scale, void* stream);
 
+/* Temporal attention fused with the STATIC (calibrated, tensor-wise) quantizer of attn_temp.proj (stdit.py:112-118 ->
+ * QuantTemporalAttnLinear.forward, stdit_quant_layer.py:161-166 -> ActQuantizer.forward after init_done,
+ * base_quantizer.py:129-144): the static-grid forms of the kernels behind vq_attn_temporal_rowquant (T <= 16, same
+ * trimmed / generic choice) and vq_attn_temporal_long (17 <= T <= 64).  delta, zp: ONE fp32 value each in device
+ * memory, read by the kernel (no host synchronisation: graph-capturable); zp integer-valued.  n_bits 2..8.  Any B >= 1
+ * (a static grid is not shared over the batch) and no status word (no eps fill on a calibrated grid).
+ * Contract: xq [B*T*S, Kp] (codes - 128 at 8 bits, raw codes below; pad columns [H*D, Kp) zero), sx = delta,
+ * zx = (int)zp - cx and R = sum(xq) - H*D*zx are bit-identical to vq_rowquant(..., s, s_rcp, delta_in = delta,
+ * zp_in = zp, n_param = 1) of the kernel's own fp16 attention output.
+ * s / s_rcp: both null, or proj's smooth-quant channel scale [H*D] and its reciprocal from vq_smooth_reciprocal.
+ * o: nullable fp16 copy of the attention output, dense for T <= 16 (ld_out == H*D), rows of stride ld_out
+ * (% 8 == 0, >= H*D) for T > 16.
+ * VQ_EINVAL: a null required pointer (q, k, v, delta, zp, xq, sx, zx, R; s without s_rcp or the reverse), a non-positive
+ * extent, T outside 1..64.  VQ_ESHAPE: H > 16, H*D % 16 != 0, D outside {16, 32, 64, 72}, Kp % 128 != 0, Kp < H*D,
+ * ld_in % 8 != 0, the rules of o above, q / k / v / xq / s / s_rcp / o not 16-byte aligned, B > 65535, and for T > 16 a
+ * position whose rows span 2^31 bytes or more.  VQ_EUNSUP: n_bits outside 2..8.  All before any HIP call or dereference. */
+int vq_attn_temporal_rowquant_static(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
+                                     const float* delta, const float* zp, int8_t* xq, float* sx, int32_t* zx, int32_t* R,
+                                     void* o, int B, int T, int S, int H, int D, long ld_in, long ld_out, int Kp,
+                                     int n_bits, float scale, void* stream);
+
 /* ---- small fused elementwise helpers ---------------------------------------
  * mod[j, b, c] = table[j, c] + t0[b, j*C + c]  (stdit.py:100-102), fp32 out, chunk-major. */
 int vq_adaln_table(const void* table, const void* t0, float* mod, int B, int J, int C, void* stream);

@@ -22,7 +22,8 @@
 //
 // attn_temporal_quant_kernel / attn_temporal_quant2_kernel (T <= 16) and attn_temporal_long_kernel (T <= 64): temporal
 // attention with the consuming Linear's per-token quantizer fused in; one argument struct (TempQArgs), lane layout,
-// LDS exchange contract and row reductions in attn_rowquant.h.
+// LDS exchange contract and row reductions in attn_rowquant.h.  Each has a static-grid form (instantiated on the argument
+// struct TempQSArgs, vq_attn_temporal_rowquant_static): attn_temp.proj's calibrated tensor-wise quantizer at 2..8 bits.
 //
 // Host side: every launcher goes through vq_prepare_kernel (dynamic-LDS limit and CU count once per device, vq_common.h)
 // and every entry point picks the head dim with vq_dispatch_head_dim.  Nothing here reads the environment or depends on a
@@ -425,12 +426,22 @@ struct TempQArgs {
     int B, T, S, H, Kp;
     float c;
 };
+// the static-grid forms (ST) add the calibrated grid of the consuming Linear - one fp32 value each, read by the kernel -
+// and the code width; the dynamic forms keep their argument block as it was
+struct TempQSArgs : TempQArgs {
+    const float* delta;
+    const float* zp;
+    int n_bits;                                    // 2 .. 8
+};
 
 // HC: head count known at compile time (16 = STDiT-XL; 0 = take a.H): the chunk -> (tensor, row, piece) divisions of
 // the staging loops are by H * D / 8 and cost ~45 VALU instructions each with a run-time divisor
 typedef __fp16 h4t_t __attribute__((__vector_size__(4 * sizeof(__fp16))));   // operand type of the LDS transpose read
-template <int D, int HC>
-__global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(TempQArgs a) {
+// A = TempQSArgs: the static-grid form ST (attn_rowquant.h): a.delta / a.zp / a.n_bits instead of the row's own 8-bit
+// grid, any B
+template <int D, int HC, class A = TempQArgs>
+__global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
+    constexpr bool ST = std::is_same<A, TempQSArgs>::value;
     constexpr int KS = (D + 15) / 16;              // 16-dim k-steps of QK^T = 16-dim row tiles of O^T
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -501,6 +512,8 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(TempQArgs a) 
         }
     };
     const uint8_t* vs = smem + wave * D * 2;
+    [[maybe_unused]] TqStatic sq;
+    if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
 
     int pos = blockIdx.x;
     if (pos >= npos) return;
@@ -548,7 +561,7 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(TempQArgs a) 
 
         // ---- O^T[dim 16*dt + 4*g4 + r][query tq] = V^T P^T: P^T is the accumulator layout of S^T already
         float4v oacc[KS];
-        float vmin = INFINITY, vmax = -INFINITY;
+        [[maybe_unused]] float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
         for (int dt = 0; dt < KS; ++dt) {
             // V^T operand (dim tq, keys 4 g4 .. + 3) by ONE LDS transpose read of the row-major tile: lane i of a 16-lane
@@ -588,25 +601,30 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(TempQArgs a) 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) oacc[dt][r] = rq_div_rcp(oacc[dt][r], s4[r], r4[r]);
                 }
+                if constexpr (!ST) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    vmin = fminf(vmin, oacc[dt][r]);
-                    vmax = fmaxf(vmax, oacc[dt][r]);
+                    for (int r = 0; r < 4; ++r) {
+                        vmin = fminf(vmin, oacc[dt][r]);
+                        vmax = fmaxf(vmax, oacc[dt][r]);
+                    }
                 }
             }
         }
-        vmin = fminf(vmin, __shfl_xor(vmin, 16));
-        vmin = fminf(vmin, __shfl_xor(vmin, 32));
-        vmax = fmaxf(vmax, __shfl_xor(vmax, 16));
-        vmax = fmaxf(vmax, __shfl_xor(vmax, 32));
-        if (lane < 16) {
-            ex_min[wave * 16 + tq] = vmin;
-            ex_max[wave * 16 + tq] = vmax;
+        if constexpr (!ST) {
+            vmin = fminf(vmin, __shfl_xor(vmin, 16));
+            vmin = fminf(vmin, __shfl_xor(vmin, 32));
+            vmax = fmaxf(vmax, __shfl_xor(vmax, 16));
+            vmax = fmaxf(vmax, __shfl_xor(vmax, 32));
+            if (lane < 16) {
+                ex_min[wave * 16 + tq] = vmin;
+                ex_max[wave * 16 + tq] = vmax;
+            }
         }
         // (raw barriers in the loop: __syncthreads() also waits for vmcnt(0), i.e. for the rows just requested for the
         //  position after next - that serialised every iteration behind one HBM round trip)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();              // row statistics visible; every wave is done with the q | k | v tiles
+                                                   // (ST: nothing to publish, but store_qkv below reuses the V tile)
         if (has_next) {
             store_qkv(tx);                         // next position's V rows (visible after the barrier below) ...
 #pragma unroll
@@ -616,31 +634,41 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(TempQArgs a) 
             }
             if (npos_next + (int)gridDim.x < npos) load_qkv(npos_next + (int)gridDim.x, tx);   // ... and the position after it is requested
         }
-        vmin = INFINITY;
-        vmax = -INFINITY;
-        for (int w = 0; w < H; ++w) {
-            vmin = fminf(vmin, ex_min[w * 16 + tq]);
-            vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
-        }
-        float delta, zp;
-        bool small;
-        float inv;
-        vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
-        if (small && tid < 16 && tq < a.T && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
-        const int izx = (int)zp - 128;
+        [[maybe_unused]] float delta, zp, inv;
+        [[maybe_unused]] int izx;
         uint32_t csum = 0;
+        if constexpr (ST) {
+            RQ_BY_WIDTH(sq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
+                const int d0 = dt * 16 + 4 * g4;
+                if (d0 < D) {
+                    const float x4[4] = {oacc[dt][0], oacc[dt][1], oacc[dt][2], oacc[dt][3]};
+                    *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = tq_static_codes<SAT8_>(x4, sq, csum);
+                }
+            })
+        } else {
+            vmin = INFINITY;
+            vmax = -INFINITY;
+            for (int w = 0; w < H; ++w) {
+                vmin = fminf(vmin, ex_min[w * 16 + tq]);
+                vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
+            }
+            bool small;
+            vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
+            if (small && tid < 16 && tq < a.T && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
+            izx = (int)zp - 128;
 #pragma unroll
-        for (int dt = 0; dt < KS; ++dt) {
-            const int d0 = dt * 16 + 4 * g4;
-            if (d0 < D) {
-                uint32_t pk = 0;
-                const float x4[4] = {oacc[dt][0], oacc[dt][1], oacc[dt][2], oacc[dt][3]};
-                float c4[4];
-                rq_round_group<4>(x4, inv, delta, zp, c4);      // one tie test per four codes, packed fp32 math
+            for (int dt = 0; dt < KS; ++dt) {
+                const int d0 = dt * 16 + 4 * g4;
+                if (d0 < D) {
+                    uint32_t pk = 0;
+                    const float x4[4] = {oacc[dt][0], oacc[dt][1], oacc[dt][2], oacc[dt][3]};
+                    float c4[4];
+                    rq_round_group<4>(x4, inv, delta, zp, c4);      // one tie test per four codes, packed fp32 math
 #pragma unroll
-                for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
-                csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-                *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = pk ^ 0x80808080u;
+                    for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
+                    csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
+                    *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = pk ^ 0x80808080u;
+                }
             }
         }
         int cs = (int)csum;
@@ -664,9 +692,13 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(TempQArgs a) 
             int rs = 0;
             for (int w = 0; w < H; ++w) rs += ex_sum[w * 16 + tq];
             const long grow = ((long)b * a.T + tq) * a.S + s;
-            a.sx[grow] = delta;
-            a.zx[grow] = izx;
-            a.R[grow] = rs - 128 * C - C * izx;
+            if constexpr (ST) {
+                rq_write_row(a.sx, a.zx, a.R, nullptr, (size_t)grow, sq.g.delta, sq.g.zp, rs, C, sq.wd.cx);
+            } else {
+                a.sx[grow] = delta;
+                a.zx[grow] = izx;
+                a.R[grow] = rs - 128 * C - C * izx;
+            }
         }
     }
 }
@@ -687,8 +719,9 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(TempQArgs a) 
 // Codes / grids / row sums remain exact functions of the kernel's own fp16 output (bit-identical to vq_rowquant of it: same
 // vq_row_grid / rq_round_group arithmetic, tested).
 // ---------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(TempQArgs a) {
+template <int D, class A = TempQArgs>
+__global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
+    constexpr bool ST = std::is_same<A, TempQSArgs>::value;   // the static-grid form (attn_rowquant.h)
     constexpr int H = 16, C = H * D, NTHR = 64 * H;
     constexpr int KS = (D + 15) / 16, KS2 = (D + 31) / 32;
     constexpr int RS = C * 2 + 16, TILE = 16 * RS, RCH = C / 8, CROW = C + 16;
@@ -771,6 +804,9 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(TempQArgs a)
             if (tid + i * NTHR < 16 * RCH) *reinterpret_cast<int4v*>(smem + vlo[i]) = vals[i];
     };
 
+    [[maybe_unused]] TqStatic sq;
+    if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
+
     int pos = blockIdx.x;
     if (pos >= npos) return;
     load_v(pos);
@@ -809,7 +845,7 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(TempQArgs a)
 
         // ---- O^T = V^T P^T, rounded to fp16 as the stored tensor is
         float ov[KS][4];
-        float vmin = INFINITY, vmax = -INFINITY;
+        [[maybe_unused]] float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
         for (int dt = 0; dt < KS; ++dt) {
             const h4t_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
@@ -842,49 +878,63 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(TempQArgs a)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) ov[dt][r] = rq_div_rcp(ov[dt][r], s4[r], r4[r]);
                 }
+                if constexpr (!ST) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    vmin = fminf(vmin, ov[dt][r]);
-                    vmax = fmaxf(vmax, ov[dt][r]);
+                    for (int r = 0; r < 4; ++r) {
+                        vmin = fminf(vmin, ov[dt][r]);
+                        vmax = fmaxf(vmax, ov[dt][r]);
+                    }
                 }
             }
         }
-        vmin = tq_xor32(tq_xor16(vmin, false), false);
-        vmax = tq_xor32(tq_xor16(vmax, true), true);
-        if (lane < 16) {
-            ex_min[wave * 16 + tq] = vmin;
-            ex_max[wave * 16 + tq] = vmax;
+        if constexpr (!ST) {
+            vmin = tq_xor32(tq_xor16(vmin, false), false);
+            vmax = tq_xor32(tq_xor16(vmax, true), true);
+            if (lane < 16) {
+                ex_min[wave * 16 + tq] = vmin;
+                ex_max[wave * 16 + tq] = vmax;
+            }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (raw barrier: __syncthreads() would also wait for the loads in flight)
         __builtin_amdgcn_s_barrier();                        // row statistics visible; every wave is done with the V tile
+                                                             // (ST: nothing to publish, but store_v below reuses the tile)
         if (has_next) {
             store_v();                                       // the next position's V rows (visible after the barrier below)
             if (pos_n + G < npos) load_v(pos_n + G);
         }
-        vmin = INFINITY;
-        vmax = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < H; ++w) {
-            vmin = fminf(vmin, ex_min[w * 16 + tq]);
-            vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
-        }
-        float delta, zp, inv;
-        bool small;
-        vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
-        if (small && tid < 16 && tq < a.T && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
-        const int izx = (int)zp - 128;
+        [[maybe_unused]] float delta, zp, inv;
+        [[maybe_unused]] int izx;
         uint32_t csum = 0;
+        if constexpr (ST) {
+            RQ_BY_WIDTH(sq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
+                const int d0 = dt * 16 + 4 * g4;
+                if (d0 < D)
+                    *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = tq_static_codes<SAT8_>(ov[dt], sq, csum);
+            })
+        } else {
+            vmin = INFINITY;
+            vmax = -INFINITY;
 #pragma unroll
-        for (int dt = 0; dt < KS; ++dt) {
-            const int d0 = dt * 16 + 4 * g4;
-            if (d0 < D) {
-                uint32_t pk = 0;
-                float c4[4];
-                rq_round_group<4>(ov[dt], inv, delta, zp, c4);
+            for (int w = 0; w < H; ++w) {
+                vmin = fminf(vmin, ex_min[w * 16 + tq]);
+                vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
+            }
+            bool small;
+            vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
+            if (small && tid < 16 && tq < a.T && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
+            izx = (int)zp - 128;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
-                csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-                *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = pk ^ 0x80808080u;
+            for (int dt = 0; dt < KS; ++dt) {
+                const int d0 = dt * 16 + 4 * g4;
+                if (d0 < D) {
+                    uint32_t pk = 0;
+                    float c4[4];
+                    rq_round_group<4>(ov[dt], inv, delta, zp, c4);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
+                    csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
+                    *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = pk ^ 0x80808080u;
+                }
             }
         }
         const int cs = tq_isum4rows((int)csum);
@@ -906,9 +956,13 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(TempQArgs a)
 #pragma unroll
             for (int w = 0; w < H; ++w) rs += ex_sum[w * 16 + tq];
             const size_t grow = row0 + (size_t)tq * a.S;
-            a.sx[grow] = delta;
-            a.zx[grow] = izx;
-            a.R[grow] = rs - 128 * C - C * izx;
+            if constexpr (ST) {
+                rq_write_row(a.sx, a.zx, a.R, nullptr, grow, sq.g.delta, sq.g.zp, rs, C, sq.wd.cx);
+            } else {
+                a.sx[grow] = delta;
+                a.zx[grow] = izx;
+                a.R[grow] = rs - 128 * C - C * izx;
+            }
         }
     }
 }
@@ -935,8 +989,12 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(TempQArgs a)
 //     the kernel's own fp16 output), and the codes leave straight from registers: 4 bytes per lane, 16 contiguous bytes
 //     per row and 16-lane group.
 // ---------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(1024) void attn_temporal_long_kernel(TempQArgs a) {
+// A = TempQSArgs: the static-grid form ST (attn_rowquant.h; any B).  With no row statistics to publish a tile has ONE barrier, so the
+// code sums of successive tiles alternate between two [wave][16] areas (ex_sum and the idle ex_max): wave 0 may still
+// read tile n's sums while the others write tile n + 1's, and tile n + 2 writes behind the barrier of tile n + 1.
+template <int D, class A = TempQArgs>
+__global__ __launch_bounds__(1024) void attn_temporal_long_kernel(A a) {
+    constexpr bool ST = std::is_same<A, TempQSArgs>::value;
     constexpr int KS = (D + 15) / 16, KS2 = (D + 31) / 32, CHD = D / 8;
     constexpr int RSV = D * 2, VT = 64 * RSV;      // V tile of one head: row stride, bytes
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -951,7 +1009,10 @@ __global__ __launch_bounds__(1024) void attn_temporal_long_kernel(TempQArgs a) {
     const int npos = a.S * a.B;
     const int nt = (T + 15) >> 4;                  // 16-row tiles holding rows < T (keys and queries)
     const unsigned tstride = (unsigned)a.S * (unsigned)a.ld_in * 2u;          // bytes between the rows t, t + 1 of a position
-    const bool quant = a.xq != nullptr;
+    const bool quant = ST || a.xq != nullptr;
+    [[maybe_unused]] TqStatic sq;
+    [[maybe_unused]] int par = 0;                  // ST: which of the two code-sum areas this tile uses
+    if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
     const int npad = a.Kp / 16 - C / 16;           // 16-byte pad chunks [C, Kp) of a code row
     const unsigned vtro = (unsigned)((4 * g4 + (tq >> 2)) * RSV + 4 * (tq & 3) * 2);   // transpose-read lane offset
     const unsigned kqo = (unsigned)(wave * D + 8 * g4) * 2u;                           // + 64 bytes per k-step
@@ -1081,63 +1142,84 @@ __global__ __launch_bounds__(1024) void attn_temporal_long_kernel(TempQArgs a) {
                     for (int r = 0; r < 4; ++r) x4[r] = rq_div_rcp(x4[r], s4[r], r4[r]);
                 }
             };
-            float vmin = INFINITY, vmax = -INFINITY;
-#pragma unroll
-            for (int dt = 0; dt < KS; ++dt)
-                if (dt * 16 + 4 * g4 < D) {
-                    float x4[4];
-                    qin(dt, x4);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        vmin = fminf(vmin, x4[r]);
-                        vmax = fmaxf(vmax, x4[r]);
-                    }
-                }
-            vmin = tq_xor32(tq_xor16(vmin, false), false);
-            vmax = tq_xor32(tq_xor16(vmax, true), true);
-            if (lane < 16) {
-                ex_min[wave * 16 + tq] = vmin;
-                ex_max[wave * 16 + tq] = vmax;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (raw barrier: __syncthreads() would also wait for the loads in flight)
-            __builtin_amdgcn_s_barrier();                        // the tile's per-head row statistics are visible
-            vmin = INFINITY;
-            vmax = -INFINITY;
-            for (int w = 0; w < H; ++w) {
-                vmin = fminf(vmin, ex_min[w * 16 + tq]);
-                vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
-            }
-            float delta, zp, inv;
-            bool small;
-            vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
-            if (small && tid < 16 && qrow && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
-            const int izx = (int)zp - 128;
-            uint8_t* xrow = reinterpret_cast<uint8_t*>(a.xq) + grow * (size_t)a.Kp + wave * D;
+            [[maybe_unused]] float delta, zp, inv;
+            [[maybe_unused]] int izx;
+            int* exs = ex_sum;                     // this tile's code sums
             uint32_t csum = 0;
+            if constexpr (ST) {
+                exs = ex_sum - 256 * par;          // (ex_max's area: nothing else uses it here)
+                par ^= 1;
+                uint8_t* xrow = reinterpret_cast<uint8_t*>(a.xq) + grow * (size_t)a.Kp + wave * D;
+                RQ_BY_WIDTH(sq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
+                    const int d0 = dt * 16 + 4 * g4;
+                    if (d0 < D) {
+                        float x4[4];
+                        qin(dt, x4);
+                        const uint32_t pk = tq_static_codes<SAT8_>(x4, sq, csum);
+                        if (qrow) *reinterpret_cast<uint32_t*>(xrow + d0) = pk;
+                    }
+                })
+            } else {
+                float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
-            for (int dt = 0; dt < KS; ++dt) {
-                const int d0 = dt * 16 + 4 * g4;
-                if (d0 < D) {
-                    uint32_t pk = 0;
-                    float x4[4], c4[4];
-                    qin(dt, x4);
-                    rq_round_group<4>(x4, inv, delta, zp, c4);
+                for (int dt = 0; dt < KS; ++dt)
+                    if (dt * 16 + 4 * g4 < D) {
+                        float x4[4];
+                        qin(dt, x4);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
-                    csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-                    if (qrow) *reinterpret_cast<uint32_t*>(xrow + d0) = pk ^ 0x80808080u;
+                        for (int r = 0; r < 4; ++r) {
+                            vmin = fminf(vmin, x4[r]);
+                            vmax = fmaxf(vmax, x4[r]);
+                        }
+                    }
+                vmin = tq_xor32(tq_xor16(vmin, false), false);
+                vmax = tq_xor32(tq_xor16(vmax, true), true);
+                if (lane < 16) {
+                    ex_min[wave * 16 + tq] = vmin;
+                    ex_max[wave * 16 + tq] = vmax;
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (raw barrier: __syncthreads() would also wait for the loads in flight)
+                __builtin_amdgcn_s_barrier();                        // the tile's per-head row statistics are visible
+                vmin = INFINITY;
+                vmax = -INFINITY;
+                for (int w = 0; w < H; ++w) {
+                    vmin = fminf(vmin, ex_min[w * 16 + tq]);
+                    vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
+                }
+                bool small;
+                vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
+                if (small && tid < 16 && qrow && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
+                izx = (int)zp - 128;
+                uint8_t* xrow = reinterpret_cast<uint8_t*>(a.xq) + grow * (size_t)a.Kp + wave * D;
+#pragma unroll
+                for (int dt = 0; dt < KS; ++dt) {
+                    const int d0 = dt * 16 + 4 * g4;
+                    if (d0 < D) {
+                        uint32_t pk = 0;
+                        float x4[4], c4[4];
+                        qin(dt, x4);
+                        rq_round_group<4>(x4, inv, delta, zp, c4);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
+                        csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
+                        if (qrow) *reinterpret_cast<uint32_t*>(xrow + d0) = pk ^ 0x80808080u;
+                    }
                 }
             }
             const int cs = tq_isum4rows((int)csum);
-            if (lane < 16) ex_sum[wave * 16 + tq] = cs;
+            if (lane < 16) exs[wave * 16 + tq] = cs;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();        // code sums visible; every wave has read ex_min / ex_max of this tile
             if (tid < 16 && qrow) {
                 int rs = 0;
-                for (int w = 0; w < H; ++w) rs += ex_sum[w * 16 + tq];
-                a.sx[grow] = delta;
-                a.zx[grow] = izx;
-                a.R[grow] = rs - 128 * C - C * izx;
+                for (int w = 0; w < H; ++w) rs += exs[w * 16 + tq];
+                if constexpr (ST) {
+                    rq_write_row(a.sx, a.zx, a.R, nullptr, grow, sq.g.delta, sq.g.zp, rs, C, sq.wd.cx);
+                } else {
+                    a.sx[grow] = delta;
+                    a.zx[grow] = izx;
+                    a.R[grow] = rs - 128 * C - C * izx;
+                }
             }
             for (int c = tid; c < 16 * npad; c += nthr) {       // pad columns [C, Kp) zeroed like the row quantizers do
                 const int t = c / npad, ch = c - t * npad;
@@ -2647,14 +2729,14 @@ static bool temporal_quant_trimmed(const TempQArgs& a) {
     return a.H == 16 && a.Kp <= 2048 && (long)a.T * a.S * a.ld_in * 2 < (1l << 31) && (long)a.T * a.S * a.Kp < (1l << 31);
 }
 
-template <int D>
-static int launch_temporal_quant(const TempQArgs& a, hipStream_t st, bool trimmed) {
+template <int D, class A>
+static int launch_temporal_quant(const A& a, hipStream_t st, bool trimmed) {
     const int C = a.H * D;
     const int LDS = 16 * (C * 2 + 16) + 16 * (C + 16) + 3 * 1024;
     constexpr int LDS_MAX = 16 * (16 * 72 * 2 + 16) + 16 * (16 * 72 + 16) + 3 * 1024;
-    constexpr auto k2 = attn_temporal_quant2_kernel<D>;
-    constexpr auto k16 = attn_temporal_quant_kernel<D, 16>;
-    constexpr auto k0 = attn_temporal_quant_kernel<D, 0>;
+    constexpr auto k2 = attn_temporal_quant2_kernel<D, A>;
+    constexpr auto k16 = attn_temporal_quant_kernel<D, 16, A>;
+    constexpr auto k0 = attn_temporal_quant_kernel<D, 0, A>;
     int ncu = 0;
     if (const int rc = trimmed ? vq_prepare_kernel<k2>(LDS_MAX, &ncu)
                                : a.H == 16 ? vq_prepare_kernel<k16>(LDS_MAX, &ncu) : vq_prepare_kernel<k0>(LDS_MAX, &ncu))
@@ -2694,11 +2776,11 @@ extern "C" int vq_attn_temporal_rowquant(const void* q, const void* k, const voi
     return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_quant<d()>(a, st, temporal_quant_trimmed(a)); });
 }
 
-template <int D>
-static int launch_temporal_long(const TempQArgs& a, hipStream_t st) {
+template <int D, class A>
+static int launch_temporal_long(const A& a, hipStream_t st) {
     constexpr int LDS_MAX = 16 * 64 * D * 2 + 64 + 3 * 1024;
     const int LDS = a.H * 64 * D * 2 + 64 + 3 * 1024;
-    constexpr auto k = attn_temporal_long_kernel<D>;
+    constexpr auto k = attn_temporal_long_kernel<D, A>;
     int ncu = 0;
     if (const int rc = vq_prepare_kernel<k>(LDS_MAX, &ncu)) return rc;
     // persistent: 16 heads x 150 KB of LDS own a CU; small head counts fit two workgroups
@@ -2730,4 +2812,34 @@ extern "C" int vq_attn_temporal_long(const void* q, const void* k, const void* v
                 ld_out, B, T, S, H, Kp, scale * ATT_LOG2E};
     hipStream_t st = (hipStream_t)stream;
     return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_long<d()>(a, st); });
+}
+
+// Temporal attention + attn_temp.proj's STATIC (calibrated, tensor-wise) quantizer: the static-grid forms of the three
+// kernels above.  Every check comes before any HIP call or dereference.
+extern "C" int vq_attn_temporal_rowquant_static(const void* q, const void* k, const void* v, const float* s,
+                                                const float* s_rcp, const float* delta, const float* zp, int8_t* xq,
+                                                float* sx, int32_t* zx, int32_t* R, void* o, int B, int T, int S, int H,
+                                                int D, long ld_in, long ld_out, int Kp, int n_bits, float scale,
+                                                void* stream) {
+    if (!q || !k || !v || !delta || !zp || !xq || !sx || !zx || !R) return VQ_EINVAL;
+    if ((s != nullptr) != (s_rcp != nullptr)) return VQ_EINVAL;     // the division exists in reciprocal form only
+    if (B <= 0 || T <= 0 || S <= 0 || H <= 0 || D <= 0 || Kp <= 0 || T > 64) return VQ_EINVAL;
+    const long C = (long)H * D;
+    const bool is_long = T > 16;
+    if (D != 72 && D != 64 && D != 32 && D != 16) return VQ_ESHAPE;  // (vq_dispatch_head_dim)
+    if (H > 16 || B > 65535 || C % 16 != 0 || ld_in % 8 != 0 || Kp % 128 != 0 || Kp < C) return VQ_ESHAPE;
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)xq | (uintptr_t)s | (uintptr_t)s_rcp | (uintptr_t)o) % 16 != 0)
+        return VQ_ESHAPE;
+    // o: dense rows in the T <= 16 kernels, rows of stride ld_out in the long one
+    if (o && (is_long ? (ld_out % 8 != 0 || ld_out < C) : ld_out != C)) return VQ_ESHAPE;
+    // the long kernel: 32-bit byte offsets inside a position's rows
+    if (is_long && ((long)T * S * ld_in * 2 >= (1l << 31) || (long)T * S * Kp >= (1l << 31))) return VQ_ESHAPE;
+    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    TempQSArgs a{};
+    static_cast<TempQArgs&>(a) = TempQArgs{(const half_t*)q, (const half_t*)k, (const half_t*)v, xq, sx, zx, R, /*status*/ nullptr,
+                                           (half_t*)o, s, s_rcp, ld_in, is_long ? ld_out : C, B, T, S, H, Kp, scale * ATT_LOG2E};
+    a.delta = delta, a.zp = zp, a.n_bits = n_bits;
+    hipStream_t st = (hipStream_t)stream;
+    if (is_long) return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_long<d()>(a, st); });
+    return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_quant<d()>(a, st, temporal_quant_trimmed(a)); });
 }

@@ -12,8 +12,17 @@
 // each kernel: behind __forceinline__ helpers hipcc selects other instructions and allocates other registers for the
 // same arithmetic (the callee is simplified on its own before it is inlined), up to +12 VGPRs and +4 bytes of scratch -
 // profiles/refactor_attn_isa.md has the figures per helper.  A fourth kernel of this kind should start from there.
+//
+// The static-grid forms (the three kernels instantiated on TempQSArgs; vq_attn_temporal_rowquant_static) quantize every row
+// on ONE calibrated grid (delta, zp: one fp32 value each, read on the device) at a code width of 2..8 bits: no row
+// min / max, hence no ex_min / ex_max exchange, no vq_row_grid, no eps fill and no status word; only the row sum still
+// crosses the heads (ex_sum).  Their codes are rqs_grid / rqs_quant of rowquant_shared.h - rq_round_group's bound needs
+// the row's own grid - and bit-identical to vq_rowquant(delta_in, zp_in, n_param = 1) of the kernel's own fp16 output.
+// Everything the static arm adds sits in the helpers at the end of this file: the arm is an ``if constexpr`` of each
+// kernel, so the dynamic instantiations compile to what they were (profiles/static_quant/attn_resources.md).
 #pragma once
 #include "vq_common.h"
+#include "rowquant_shared.h"
 
 // ---- reductions over the four 16-lane rows of a wave (all 64 lanes receive the result) -------------------------------
 // (the swap builtins return a 2-vector: its elements are copied into scalars before any __builtin_bit_cast - written on the
@@ -53,3 +62,27 @@ __device__ __forceinline__ int tq_isum4rows(int x) {
     return (int)r[0] + (int)r[1];
 }
 
+// ---- the static-grid arm ----------------------------------------------------------------------------------------------
+struct TqStatic {
+    RqWidth wd;        // last level, int8 offset (128 at 8 bits only) and its packed form
+    RqsGrid g;         // the calibrated grid and the tie guard of its product form
+};
+// (kernel-uniform values computed by the VALU: handed to scalar registers, they are live for the whole position loop)
+__device__ __forceinline__ float tq_uniform(float x) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
+}
+__device__ __forceinline__ TqStatic tq_static(const float* delta, const float* zp, int n_bits) {
+    TqStatic q;
+    q.wd = rq_width(n_bits);
+    q.g = rqs_grid(delta, zp, 0, q.wd.qmax);
+    q.g.delta = tq_uniform(q.g.delta), q.g.zp = tq_uniform(q.g.zp), q.g.inv = tq_uniform(q.g.inv), q.g.thr = tq_uniform(q.g.thr);
+    return q;
+}
+// four values of one lane -> their dword of codes as stored (offset applied); csum += the raw codes
+template <bool SAT8>
+__device__ __forceinline__ uint32_t tq_static_codes(const float (&x4)[4], const TqStatic& q, uint32_t& csum) {
+    uint32_t pk[1];
+    rqs_quant<4, SAT8>(x4, q.g, q.wd.qmax, pk);
+    csum = __builtin_amdgcn_sad_u8(pk[0], 0u, csum);
+    return pk[0] ^ q.wd.flip;
+}

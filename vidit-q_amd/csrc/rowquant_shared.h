@@ -1,4 +1,5 @@
-// rowquant_shared.h - what the quantizer sources (rowquant.hip, rowquant_fast.hip, rowquant_static.hip) share: the
+// rowquant_shared.h - what the quantizer sources (rowquant.hip, rowquant_fast.hip, rowquant_static.hip; attention.hip for
+// the static grid of its fused quantizers) share: the
 // functions they call across files, the output struct, the width dispatch of the register-resident kernels, and the
 // per-row steps of those kernels - lane maps, reductions, row load, LayerNorm statistics, modulate, the quantize / store /
 // row-sum tail - each written once for both lane maps.
@@ -308,6 +309,66 @@ template <int W>
 __device__ __forceinline__ void rq_store_codes(int8_t* dst, const uint32_t (&pk)[W / 4]) {
     if constexpr (W == 8) *reinterpret_cast<uint2*>(dst) = make_uint2(pk[0], pk[1]);
     else *reinterpret_cast<uint32_t*>(dst) = pk[0];
+}
+
+// ---- device side: codes on a static (calibrated) grid ---------------------------------
+// (rowquant_static.hip and the static-grid forms of the fused temporal attention kernels, attention.hip)
+// round(x / delta) on a grid the row did not define.  rq_round_group's bound assumes |x / delta| <= 255; here a value
+// may lie anywhere (+-65504 against delta = 2^-k).  The product form is kept, with a window and a guard per (row,
+// output) - rqs_grid():
+//   inv = RN(1 / delta), t = RN(x inv), q = x / delta (exact), Q = RN(q) (what the oracle rounds).
+//   t = q (1 + e1)(1 + e2), |e| <= 2^-24 (inv is required to be a normal number, t is normal or rounds to 0 with Q),
+//   and |Q - q| <= |q| 2^-24, so |t - Q| <= 1.5 * 2^-23 (1 + 2^-22) |t| < 1.8e-7 |t|.
+//   Window W = qmax + |zp| + 2 (zp integer-valued: the precondition).  INSIDE, |t| <= W: |t - Q| < 1.8e-7 W < G with
+//   the guard G = max(1e-4, 2.4e-7 W); when |t - rint(t)| <= 0.5 - G, Q lies strictly between the same two ties as t
+//   and rint(Q) = rint(t); every other lane takes rint(__fdiv_rn(x, delta)), ties included.  (t - rint(t) is exact.)
+//   OUTSIDE, t > W: rint(t) >= W, so rint(t) + zp >= qmax + 2; and Q > (1 - 1.8e-7) W, so rint(Q) >= W - 1 as long as
+//   1.8e-7 W < 0.5, i.e. rint(Q) + zp >= qmax + 1: both clamp to qmax (t < -W: both to 0) whichever way each rounds -
+//   and a lane out there that fails the guard merely divides.  For W >= 2^21 (no calibrated grid: |zp| <= qmax) the
+//   guard 0.5 - G is negative and EVERY lane divides, so no W exists for which the outside argument is needed but
+//   fails.  inv outside [1e-30, 1e30] or NaN: guard -1, every lane divides.  +-inf products fail the guard (NaN
+//   distance) and divide.  Codes are therefore the oracle's for every input.
+
+// the grid of one (row, output): step, zero point, reciprocal and the tie guard of the product form (above)
+struct RqsGrid {
+    float delta, zp, inv, thr;
+};
+__device__ __forceinline__ RqsGrid rqs_grid(const float* __restrict__ delta, const float* __restrict__ zp, int p, float qmax) {
+    RqsGrid g;
+    g.delta = delta[p];
+    g.zp = zp[p];
+    g.inv = __fdiv_rn(1.0f, g.delta);
+    const float w = qmax + fabsf(g.zp) + 2.0f;
+    g.thr = 0.5f - fmaxf(1.0e-4f, w * 2.4e-7f);
+    if (!(g.inv >= 1.0e-30f && g.inv <= 1.0e30f)) g.thr = -1.0f;
+    return g;
+}
+
+// N values -> N / 4 dwords of raw codes clamp(rint(RN(x / delta)) + zp, 0, qmax); one tie test for the group
+template <int N, bool SAT8>
+__device__ __forceinline__ void rqs_quant(const float (&x)[N], const RqsGrid& g, float qmax, uint32_t (&pk)[N / 4]) {
+    static_assert(N % 4 == 0, "dwords of codes");
+    const float2v inv2 = {g.inv, g.inv};
+    float r[N], t[N];
+    float far = 0.f;
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) {
+        const float2v t2 = float2v{x[2 * j], x[2 * j + 1]} * inv2;
+        t[2 * j] = t2[0];
+        t[2 * j + 1] = t2[1];
+        r[2 * j] = __builtin_rintf(t2[0]);
+        r[2 * j + 1] = __builtin_rintf(t2[1]);
+        const float2v d = t2 - float2v{r[2 * j], r[2 * j + 1]};
+        far = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(d[0]), __builtin_fabsf(d[1])), far);
+    }
+    if (!(far <= g.thr)) {                               // (also taken by a NaN distance: an infinite product)
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+            if (!(__builtin_fabsf(t[i] - r[i]) <= g.thr)) r[i] = rintf(__fdiv_rn(x[i], g.delta));
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) r[i] += g.zp;
+    rq_pack_codes<N, SAT8>(r, qmax, pk);
 }
 
 // ---- device side: the dynamic tail ----------------------------------------------------

@@ -662,6 +662,59 @@ def attn_temporal_long(q, k, v, B, T, S, H, D, ld_in, o: Optional[torch.Tensor] 
     return QAct(xq, sx, zx, R, Cc, 8)
 
 
+ATTN_HEAD_DIMS = (16, 32, 64, 72)     # head dims the attention kernels are compiled for (csrc/vq_common.h)
+
+
+def attn_temporal_static_ok(T: int, H: int, D: int, Kp: int, n_bits: int) -> bool:
+    """Whether vq_attn_temporal_rowquant_static takes this launch: the entry point's refusals (include/viditq.h), mirrored
+    for callers that choose a route BEFORE they launch - a refused shape takes attention and the quantizer separately."""
+    if not (1 <= T <= 64 and 1 <= H <= 16 and D in ATTN_HEAD_DIMS and Kp > 0):
+        return False
+    Cc = H * D
+    return Cc % 16 == 0 and Kp % 128 == 0 and Kp >= Cc and 2 <= n_bits <= 8
+
+
+def attn_temporal_rowquant_static(q, k, v, B, T, S, H, D, ld_in, delta: torch.Tensor, zp: torch.Tensor, n_bits: int = 8,
+                                  scale: Optional[float] = None, o: Optional[torch.Tensor] = None,
+                                  s: Optional[torch.Tensor] = None) -> Optional[QAct]:
+    """Temporal attention (T <= 64, any B) + the consuming Linear's STATIC tensor-wise quantizer - ``delta`` / ``zp``: one
+    fp32 value each, read on the device - at ``n_bits`` (2..8) in one kernel.  Returns what
+    ``rowquant(o.view(B, T*S, H*D), n_bits, s=s, delta=delta, zp=zp)`` returns for the kernel's own fp16 output ``o``
+    (also written when given, [B*T*S, H*D]), bit for bit.  ``s``: the consuming Linear's smoothing vector; None is
+    returned (caller runs the two kernels) when its reciprocal form is not available."""
+    s_rcp = None
+    if s is not None:
+        s_rcp = smooth_rcp(s)
+        if s_rcp is None:
+            return None
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise VQError("%s must be a GPU fp16 tensor" % n)
+    delta = _req(delta.reshape(-1).contiguous(), torch.float32, "delta")
+    zp = _req(zp.reshape(-1).contiguous(), torch.float32, "zp")
+    if delta.numel() != 1 or zp.numel() != 1:
+        raise VQError("attn_temporal_rowquant_static: a tensor-wise grid (one delta, one zero point)")
+    Cc = H * D
+    Kp = pad128(Cc)
+    rows = B * T * S
+    dev = q.device
+    ld_out = Cc
+    if o is not None:
+        _req(o, torch.float16, "o")
+        if o.shape != (rows, Cc):
+            raise VQError("attn_temporal_rowquant_static: o must be [B*T*S, H*D]")
+        ld_out = o.stride(0)
+    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
+    sx = torch.empty(rows, dtype=torch.float32, device=dev)
+    zx = torch.empty(rows, dtype=torch.int32, device=dev)
+    R = torch.empty(rows, dtype=torch.int32, device=dev)
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    check(_L().vq_attn_temporal_rowquant_static(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(delta), _p(zp), _p(xq), _p(sx),
+                                                _p(zx), _p(R), _p(o), B, T, S, H, D, ld_in, ld_out, Kp, n_bits, scale,
+                                                _stream()), "vq_attn_temporal_rowquant_static")
+    return QAct(xq, sx, zx, R, Cc, n_bits)
+
+
 # --------------------------------------------------------------------------- misc
 def adaln_table(table: torch.Tensor, t0: torch.Tensor) -> torch.Tensor:
     """mod[J, B, C] fp32 = table[J, C] + t0[B, J*C]  (fp16 inputs); mod[j] is a contiguous [B, C]."""

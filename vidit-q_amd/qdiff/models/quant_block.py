@@ -100,6 +100,17 @@ class QuantAttention(nn.Module):
         return ops.attn_temporal_rowquant(qkv, qkv[:, C:], qkv[:, 2 * C:], B, T, S, self.num_heads, self.head_dim,
                                           qkv.stride(0), scale=self.scale, status=status, s=s)
 
+    def temporal_quantized_static(self, qkv: torch.Tensor, B: int, T: int, S: int, delta: torch.Tensor, zp: torch.Tensor,
+                                  n_bits: int, s=None):
+        """:meth:`temporal` + the STATIC tensor-wise quantizer (``delta``, ``zp``: one value each; ``n_bits`` 2..8) of the
+        next Linear (behind its smoothing vector ``s`` when it has one), one kernel, any B; None when that kernel does
+        not apply (then call :meth:`temporal` and the layer's own quantizer)."""
+        C = self.num_heads * self.head_dim
+        if not ops.attn_temporal_static_ok(T, self.num_heads, self.head_dim, ops.pad128(C), n_bits):
+            return None
+        return ops.attn_temporal_rowquant_static(qkv, qkv[:, C:], qkv[:, 2 * C:], B, T, S, self.num_heads, self.head_dim,
+                                                 qkv.stride(0), delta, zp, n_bits=n_bits, scale=self.scale, s=s)
+
     def cross(self, q: torch.Tensor, kv: torch.Tensor, kv_off: torch.Tensor, B: int, Nq: int,
               out: Optional[torch.Tensor] = None):
         """q [B*Nq, C]; kv [sum_L, 2*C] (k | v); sample b sees kv rows [kv_off[b], kv_off[b+1])."""
