@@ -852,11 +852,73 @@ def test_attn_cross_register_kernel_still_covered(ops, dev):
     from viditq_amd import _lib
     lib, D, H, Lq = _lib.load(), 72, 16, 200
     Cc, p = H * D, ctypes.c_void_p(1 << 20)
-    reg = int(re.search(r"#define VQ_ATTN_K_CROSS_REG (\d+)", open(os.path.join(ROOT, "include", "viditq.h")).read()).group(1))
+    reg = {v: k for k, v in _ATTN_K_NAMES.items()}["VQ_ATTN_K_CROSS_REG"]
     for B, lens in ((1, [120]), (1, [80]), (1, [17]), (1, [128]), (3, [17, 120, 1])):
         # the arguments _cross_case gives ops.attn_fwd for a varlen launch (pointers are not dereferenced by the hook)
         assert lib.vq_attn_fwd_route(p, p, p, p, B, Lq, max(lens), H, D, Lq * Cc, Cc, 0, 2 * Cc, Lq * Cc, Cc, p, D ** -0.5, None) == reg
         assert _cross_case(ops, dev, D, H, B, Lq, lens, True) < 1e-3, lens
+
+
+_ATTN_K_NAMES = {int(m.group(2)): m.group(1) for m in
+                 re.finditer(r"#define (VQ_ATTN_K_\w+) (\d+)", open(os.path.join(ROOT, "include", "viditq.h")).read())}
+
+
+def _attn_route(args, kv_off=None):
+    """(name of the VQ_ATTN_K_* id, id) that vq_attn_fwd_route gives for the launch arguments `args` of ops.attn_fwd, read
+    from include/viditq.h the way test_attn_cross_register_kernel_still_covered reads it."""
+    import ctypes
+    from viditq_amd import _lib
+    q, k, v, o = (ctypes.c_void_p(t.data_ptr()) for t in args[:4])
+    D = args[8]
+    off = None if kv_off is None else ctypes.c_void_p(kv_off.data_ptr())
+    rid = _lib.load().vq_attn_fwd_route(q, k, v, o, *args[4:], off, D ** -0.5, None)
+    return _ATTN_K_NAMES.get(rid, rid)
+
+
+@pytest.mark.parametrize("D", [16, 32, 64, 72])
+def test_attn_fwd_sixty_four_queries_per_wave_equal_thirty_two_row_for_row(ops, dev, D):
+    """attn_fwd64d_kernel and attn_fwd32d_kernel share the tile steps of attn_tile.h (the 64-query kernel keeps its softmax
+    block written out, the same statements) and take the rescale decision over the same aligned 32-query groups, so they
+    share the arithmetic of a query row: 2048 queries against 2077 keys (32 full key
+    tiles and a ragged one) in one launch (64 queries per wave) and as two launches of 1024 queries over the two halves of
+    the same Q and output rows (32 per wave) give the same bits."""
+    Lq, Lk, Cc = 2048, 2077, D
+    q = h16(Lq, Cc, scale=1.0, seed=D).to(dev)
+    kv = h16(Lk, 2 * Cc, scale=1.0, seed=D + 1).to(dev)
+    o64 = torch.full((Lq, Cc), float("nan"), dtype=torch.float16, device=dev)
+    o32 = torch.full((Lq, Cc), float("nan"), dtype=torch.float16, device=dev)
+    args = (q, kv, kv[:, Cc:], o64, 1, Lq, Lk, 1, D, Lq * Cc, Cc, Lk * 2 * Cc, 2 * Cc, Lq * Cc, Cc)
+    assert _attn_route(args) == "VQ_ATTN_K_FWD64D"
+    ops.attn_fwd(*args)
+    for half in range(2):
+        r0, Lh = half * (Lq // 2), Lq // 2
+        args = (q[r0:], kv, kv[:, Cc:], o32[r0:], 1, Lh, Lk, 1, D, Lh * Cc, Cc, Lk * 2 * Cc, 2 * Cc, Lh * Cc, Cc)
+        assert _attn_route(args) == "VQ_ATTN_K_FWD32D"
+        ops.attn_fwd(*args)
+    assert torch.isfinite(o64).all()
+    assert torch.equal(o64, o32)
+
+
+@pytest.mark.parametrize("D", [64, 72])
+def test_attn_cross_resident_images_same_rows_for_every_image_count(ops, dev, D):
+    """attn_cross32_kernel with 2, 3, 4 and 5 resident 64-key tile images (the Lk bound 128, 192, 256, 320 of one launch:
+    two sequences of 120 and 37 keys packed by kv_off, 257 queries - a ragged last query tile) walks the same half tiles
+    that hold keys with the same steps: the four outputs are the same bits."""
+    n, Lq, lens, H = 2, 257, [120, 37], 2
+    Cc = H * D
+    q = h16(n * Lq, Cc, scale=1.0, seed=D + 2).to(dev)
+    kv = h16(sum(lens), 2 * Cc, scale=1.0, seed=D + 3).to(dev)
+    off = torch.tensor([0, lens[0], sum(lens)], dtype=torch.int32, device=dev)
+    outs = []
+    for nt, bound in enumerate((128, 192, 256, 320), start=2):
+        o = torch.full((n * Lq, Cc), float("nan"), dtype=torch.float16, device=dev)
+        args = (q, kv, kv[:, Cc:], o, n, Lq, bound, H, D, Lq * Cc, Cc, 0, 2 * Cc, Lq * Cc, Cc)
+        assert _attn_route(args, off) == "VQ_ATTN_K_CROSS32_%d" % nt
+        ops.attn_fwd(*args, kv_off=off)
+        outs.append(o)
+    assert torch.isfinite(outs[0]).all()
+    for o in outs[1:]:
+        assert torch.equal(o, outs[0])
 
 
 @pytest.mark.parametrize("B,T,S,H,D", [(1, 16, 64, 16, 72), (2, 4, 9, 4, 16), (1, 16, 1024, 16, 72)])
@@ -1254,7 +1316,6 @@ def test_gemm_interior_epilogue_is_bit_identical_to_general_path(ops, dev, epi, 
         slow = ops.gemm_i8(qa, pw, bias=b, out=wide, **kw)[:, :N]
     assert torch.equal(fast, slow)
     assert torch.all(wide[:, N:] == 0)
-
 
 
 @pytest.mark.parametrize("M,N,K,act_in,act_out", [

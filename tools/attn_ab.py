@@ -1,7 +1,8 @@
 """Round 6: attention kernels timed from graph replays (GPU box only).  One process = one arm: VIDITQ_LIB selects another
 build of the same C ABI, --lab-kernel=<id> a retired spatial / image kernel of tools/lab/attn_lab.hip (ids in tools/lab/lab.py);
 run it alternately over the arms from a shell loop.  Prints one line per shape:
-spatial 16 x 1024 (STDiT), image 2 x 4096 (PixArt-Sigma, B = 2), cross 16384 x 120, temporal + quantizer 1024 x 16."""
+spatial 16 x 1024 (STDiT), image 2 x 4096 (PixArt-Sigma, B = 2), cross 16384 x 120, temporal + quantizer 1024 x 16; "short"
+(64 x 160 queries x 1024 keys, the four-wave attn_fwd8_kernel) only when named."""
 import os
 import sys
 
@@ -49,9 +50,55 @@ def timeit(fn, n=8, reps=10):
 
 tag = os.path.basename(os.path.dirname(_lib.LIB_PATH)) if LAB_KERNEL is None else "lab kernel %d" % LAB_KERNEL
 out = []
-# --dump=<file> / --cmp=<file>: the spatial / image outputs of a fixed input, saved by one library and compared bit for bit by another
+# --dump=<file> / --cmp=<file>: outputs of fixed inputs, saved by one library and compared bit for bit by another - the three
+# D = 72 self-attention shapes and every vq_attn_fwd entry of tests/attn_regimes._SHAPES (every route x head dim the suite
+# knows) under R2 rising with the case's own step and lead, so that both the taken and the deferred rescale run
 DUMP = next((w[7:] for w in WHICH if w.startswith("--dump=")), None)
 CMP = next((w[6:] for w in WHICH if w.startswith("--cmp=")), None)
+
+
+def regime_cases():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import attn_regimes as ar
+    seen = set()
+    for case in ar.cases():
+        if case["kernel"].startswith("VQ_ATTN_K_") and case["regime"][0] == "R2" and not case["regime"][3] and \
+                case["scale"] == case["D"] ** -0.5 and case["id"] not in seen:
+            seen.add(case["id"])
+            yield ar, case
+
+
+def run_regime_case(ar, case):
+    """The launch of tests/test_attention_softmax_gpu.py::_run_fwd; None when the K / V buffer cannot be allocated."""
+    sh, D, scale = case["shape"], case["D"], case["scale"]
+    n, Lq, lens, H = sh["n"], sh["Lq"], sh["lens"], sh["H"]
+    Cc, a = H * D, ar.fwd_layout(case)
+    q, k, v, _ = ar.build(case["regime"], n, Lq, lens, H, D, scale, case["seed"])
+    big = a["kv_rows"] * a["kv_tok"] * 2 >= 1 << 30            # only the 2 GiB buffer of the FWD8_NW8 entry may be skipped
+    try:
+        if a["offs"] is not None:
+            kvd = torch.cat([torch.cat([k[i, :L].reshape(L, Cc), v[i, :L].reshape(L, Cc)], 1) for i, L in enumerate(lens)]).to(dev)
+            off = torch.tensor(a["offs"], dtype=torch.int32, device=dev)
+        else:
+            kvd = torch.zeros((a["kv_rows"], a["kv_tok"]), dtype=torch.float16, device=dev)
+            kvd[:, :Cc] = k.reshape(n * lens[0], Cc).to(dev)
+            kvd[:, Cc:2 * Cc] = v.reshape(n * lens[0], Cc).to(dev)
+            off = None
+    except torch.cuda.OutOfMemoryError:
+        if not big:
+            raise
+        return None
+    o = torch.full((n * Lq, Cc), float("nan"), dtype=torch.float16, device=dev)
+    if LAB_KERNEL is None:                                     # the case runs the kernel its id names
+        largs = (a["n_seq"], Lq, a["Lk"], H, D, a["q_seq"], a["q_tok"], a["kv_seq"], a["kv_tok"], a["o_seq"], a["o_tok"])
+        route = _lib.load().vq_attn_fwd_route(o.data_ptr(), kvd.data_ptr(), kvd.data_ptr(), o.data_ptr(), *largs,
+                                              None if off is None else off.data_ptr(), scale, None)
+        assert route == ar.kernel_ids()[case["kernel"]], (case["id"], route)
+    self_attn(q.reshape(n * Lq, Cc).to(dev), kvd, kvd[:, Cc:], o, a["n_seq"], Lq, a["Lk"], H, D, a["q_seq"], a["q_tok"], a["kv_seq"],
+              a["kv_tok"], a["o_seq"], a["o_tok"], off, scale)
+    return o.cpu()
+
+
 if DUMP or CMP:
     res = {}
     for name, n_seq, L in (("spatial", 16, 1024), ("image", 2, 4096), ("ragged", 3, 1000)):
@@ -60,30 +107,42 @@ if DUMP or CMP:
         o = torch.zeros((M, 1152), dtype=torch.float16, device=dev)
         self_attn(q, q[:, 1152:], q[:, 2304:], o, n_seq, L, L, H, D, L * 3456, 3456, L * 3456, 3456, L * 1152, 1152)
         res[name] = o.cpu()
+    for ar, case in regime_cases():
+        out_ = run_regime_case(ar, case)
+        if out_ is None:
+            print("%-16s skipped %s: its K / V buffer could not be allocated" % (tag, case["id"]))
+        else:
+            res[case["id"]] = out_
     if DUMP:
         torch.save(res, DUMP)
-        print("%-16s dumped %s" % (tag, DUMP))
+        print("%-16s dumped %d cases to %s" % (tag, len(res), DUMP))
     else:
         ref = torch.load(CMP)
-        print("%-16s vs %s: %s" % (tag, CMP, ", ".join("%s %s (max |d| %.3g)" % (
-            k, "bit-identical" if torch.equal(res[k], ref[k]) else "DIFFERS", float((res[k].float() - ref[k].float()).abs().max())) for k in res)))
+        lines = ["%s %s (max |d| %.3g)" % (k, "bit-identical" if torch.equal(res[k], ref[k]) else "DIFFERS",
+                                           float((res[k].float() - ref[k].float()).abs().max())) if k in ref else "%s NOT IN DUMP" % k
+                 for k in res]
+        lines += ["%s ONLY IN DUMP" % k for k in ref if k not in res]
+        print("%-16s vs %s:\n  %s" % (tag, CMP, "\n  ".join(lines)))
+        print("%d cases, %d bit-identical" % (len(lines), sum(ln.endswith(")") and " bit-identical " in ln for ln in lines)))
+        sys.exit(0 if all(" bit-identical " in ln for ln in lines) else 1)
     sys.exit(0)
-for name, n_seq, L in (("spatial", 16, 1024), ("image", 2, 4096)):
-    if name not in WHICH:
+# "short" (only when named): 160 queries per sequence against 1024 keys - the four-wave attn_fwd8_kernel (VQ_ATTN_K_FWD8_NW4)
+for name, n_seq, L, Lq in (("spatial", 16, 1024, 1024), ("image", 2, 4096, 4096), ("short", 64, 1024, 160)):
+    if name not in WHICH or (name == "short" and "short" not in sys.argv[1:]):
         continue
     M = n_seq * L
     bufs = [torch.randn(M, 3 * 1152, generator=g).half().to(dev) for _ in range(3)]
-    o = torch.empty((M, 1152), dtype=torch.float16, device=dev)
+    o = torch.empty((n_seq * Lq, 1152), dtype=torch.float16, device=dev)
     ld = 3456
     i = [0]
 
     def f():
         i[0] = (i[0] + 1) % len(bufs)
-        q = bufs[i[0]]
-        self_attn(q, q[:, 1152:], q[:, 2304:], o, n_seq, L, L, H, D, L * ld, ld, L * ld, ld, L * 1152, 1152)
+        q = bufs[i[0]]       # (Lq < L: the first Lq rows of every sequence are its queries)
+        self_attn(q, q[:, 1152:], q[:, 2304:], o, n_seq, Lq, L, H, D, L * ld, ld, L * ld, ld, Lq * 1152, 1152)
     t = timeit(f)
-    fl = 4.0 * n_seq * L * L * H * D
-    out.append("%s %dx%d %.1f us (%.0f TF)" % (name, n_seq, L, t, fl / t / 1e6))
+    fl = 4.0 * n_seq * Lq * L * H * D
+    out.append("%s %dx%dx%d %.1f us (%.0f TF)" % (name, n_seq, Lq, L, t, fl / t / 1e6))
 if "cross" in WHICH:
     qs = [torch.randn(16384, 1152, generator=g).half().to(dev) for _ in range(3)]
     kv = torch.randn(120, 2304, generator=g).half().to(dev)

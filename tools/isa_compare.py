@@ -3,11 +3,11 @@
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 [-mllvm -amdgpu-mfma-vgpr-form] --offload-device-only -S x.hip -o x.s
 
-    tools/isa_compare.py before.s after.s [--rename OLD=NEW] [--markdown]
+    tools/isa_compare.py before.s after.s [--rename OLD=NEW]... [--markdown]
 
 Per kernel symbol: VGPRs, SGPRs, scratch bytes, static LDS bytes (the code object's metadata) and the number of
 instructions in its body.  Exit status 1 when the sets of symbols differ or any figure does.  --rename maps a substring of
-the old mangled names (an argument struct that was renamed) before the comparison."""
+the old mangled names (an argument struct that was renamed) before the comparison; it may be given more than once."""
 import re
 import sys
 
@@ -33,12 +33,12 @@ def main(argv):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("before")
     ap.add_argument("after")
-    ap.add_argument("--rename", metavar="OLD=NEW")
+    ap.add_argument("--rename", metavar="OLD=NEW", action="append", default=[])
     ap.add_argument("--markdown", action="store_true")
     ns = ap.parse_args(argv)
     before, after = kernels(ns.before), kernels(ns.after)
-    if ns.rename:
-        old, new = ns.rename.split("=", 1)
+    for ren in ns.rename:
+        old, new = ren.split("=", 1)
         before = {k.replace(old, new): v for k, v in before.items()}
     bad = sorted(set(before) ^ set(after))
     for k in bad:

@@ -1,8 +1,9 @@
 // attn_lab.hip - LAB ONLY: every attention arm that is not a product route, launched by an explicit kernel id (the form
 // vq_lab_gemm_i8 has for the GEMM).  This translation unit includes csrc/attention.hip - the product's kernels, argument
-// checks and launchers, unchanged - and adds the retired kernels (attn_phased.h, attn_stream.h), the wider
-// instantiations of attn_fwd32d / attn_fwd64d and the profiling ablations of attn_fwd8 / attn_fwd32d.  Every experiment
-// behind these ids is concluded: profiles/r04_experiments.md, r05_experiments.md, r06_attention_phases.md.
+// checks and launchers, unchanged - and adds the retired kernels (attn_phased.h, attn_stream.h) and the wider
+// instantiations of attn_fwd32d / attn_fwd64d.  Every experiment behind these ids is concluded: profiles/r05_experiments.md,
+// r06_attention_phases.md (the profiling ablations of attn_fwd8 / attn_fwd32d are gone with their template parameters; what
+// they measured is in profiles/r04_experiments.md and r06_attention_phases.md).
 // Part of libviditq_lab.so (tools/lab/build.py); the product library never sees this file.  (libviditq_lab.so therefore
 // also carries a copy of attention.hip's own entry points; nothing in tools/ calls those.)
 #include "attention.hip"
@@ -10,56 +11,12 @@
 #include "attn_phased.h"
 
 // Kernel ids of vq_lab_attn_fwd.  < 0: the product's own choice (the control arm, from the same build).
-#define VQ_LAB_ATTN_K_FWD32D_NW4 4      // attn_fwd32d_kernel<72, 0, 4, 64> (round 5; the id it had in include/viditq.h)
+#define VQ_LAB_ATTN_K_FWD32D_NW4 4      // attn_fwd32d_kernel<72, 4, 64> (round 5; the id it had in include/viditq.h)
 #define VQ_LAB_ATTN_K_64D_128 100       // attn_fwd64d_kernel<D, 8, 128>
 #define VQ_LAB_ATTN_K_64D_NW4 101       // attn_fwd64d_kernel<D, 4, 64>
 #define VQ_LAB_ATTN_K_64P 102           // attn_fwd64p_kernel, ring of 3 tile images (attn_phased.h)
 #define VQ_LAB_ATTN_K_64S 103           // attn_fwd64s_kernel (attn_stream.h)
 #define VQ_LAB_ATTN_K_64P_NB4 104       // attn_fwd64p_kernel, ring of 4
-#define VQ_LAB_ATTN_K_ABL32D 1000       // + ABLD of attn_fwd32d_kernel<72, ABLD>: 1, 4, 5, 8, 16, 24 (WRONG RESULTS by design)
-#define VQ_LAB_ATTN_K_ABL8 2000         // + ABL of attn_fwd8_kernel<72, 8, ABL>: 1, 2, 4, 6, 8, 15, 16, 32, 64, 96, 128 (same)
-
-template <auto K>
-static int lab_launch_512(int lds, dim3 grid, const AttnArgs& a, hipStream_t st) {
-    if (const int rc = vq_prepare_kernel<K>(lds)) return rc;
-    hipLaunchKernelGGL(K, grid, dim3(512), lds, st, a);
-    return vq_check_launch();
-}
-
-// attn_fwd32d_kernel<72, ABLD> on launch_attn32d<72>'s grid
-static int lab_abl32d(int abld, const AttnArgs& a, hipStream_t st) {
-    constexpr int LDS = 2 * Att8Cfg<72, 8>::KTILE + 2 * 64 * 192;
-    const dim3 grid(8 * ((a.n_seq * a.H + 7) / 8) * ((a.Lq + 255) / 256));
-    switch (abld) {
-        case 1: return lab_launch_512<attn_fwd32d_kernel<72, 1>>(LDS, grid, a, st);
-        case 4: return lab_launch_512<attn_fwd32d_kernel<72, 4>>(LDS, grid, a, st);
-        case 5: return lab_launch_512<attn_fwd32d_kernel<72, 5>>(LDS, grid, a, st);
-        case 8: return lab_launch_512<attn_fwd32d_kernel<72, 8>>(LDS, grid, a, st);
-        case 16: return lab_launch_512<attn_fwd32d_kernel<72, 16>>(LDS, grid, a, st);
-        case 24: return lab_launch_512<attn_fwd32d_kernel<72, 24>>(LDS, grid, a, st);
-        default: return VQ_EUNSUP;
-    }
-}
-
-// attn_fwd8_kernel<72, 8, ABL> on launch_attn8<72, 8>'s grid
-static int lab_abl8(int abl, const AttnArgs& a, hipStream_t st) {
-    constexpr int LDS = Att8Cfg<72, 8>::LDS;
-    const dim3 grid(8 * ((a.n_seq * a.H + 7) / 8) * ((a.Lq + 255) / 256));
-    switch (abl) {
-        case 1: return lab_launch_512<attn_fwd8_kernel<72, 8, 1>>(LDS, grid, a, st);
-        case 2: return lab_launch_512<attn_fwd8_kernel<72, 8, 2>>(LDS, grid, a, st);
-        case 4: return lab_launch_512<attn_fwd8_kernel<72, 8, 4>>(LDS, grid, a, st);
-        case 6: return lab_launch_512<attn_fwd8_kernel<72, 8, 6>>(LDS, grid, a, st);
-        case 8: return lab_launch_512<attn_fwd8_kernel<72, 8, 8>>(LDS, grid, a, st);
-        case 15: return lab_launch_512<attn_fwd8_kernel<72, 8, 15>>(LDS, grid, a, st);
-        case 16: return lab_launch_512<attn_fwd8_kernel<72, 8, 16>>(LDS, grid, a, st);
-        case 32: return lab_launch_512<attn_fwd8_kernel<72, 8, 32>>(LDS, grid, a, st);
-        case 64: return lab_launch_512<attn_fwd8_kernel<72, 8, 64>>(LDS, grid, a, st);
-        case 96: return lab_launch_512<attn_fwd8_kernel<72, 8, 96>>(LDS, grid, a, st);
-        case 128: return lab_launch_512<attn_fwd8_kernel<72, 8, 128>>(LDS, grid, a, st);
-        default: return VQ_EUNSUP;
-    }
-}
 
 // The lab kernels share the tile images of attn_fwd32d_kernel and with them its preconditions: one key length for all
 // sequences, more than two key tiles, K / V addressed with 32-bit byte offsets.  VQ_ESHAPE where a kernel cannot run the
@@ -68,15 +25,7 @@ template <int D>
 static int lab_launch_attn(int kernel, const AttnArgs& a, hipStream_t st) {
     if (kernel < 0) return launch_attn<D>(a, st);
     if (a.kv_off || a.Lk <= 128) return VQ_ESHAPE;
-    if (kernel >= VQ_LAB_ATTN_K_ABL8) {                // (attn_fwd8_kernel takes 64-bit K / V offsets)
-        if (D != 72 || a.Lq < 192) return D != 72 ? VQ_EUNSUP : VQ_ESHAPE;
-        return lab_abl8(kernel - VQ_LAB_ATTN_K_ABL8, a, st);
-    }
     if ((long)a.Lk * a.kv_tok_stride * 2 >= (1l << 31)) return VQ_ESHAPE;
-    if (kernel >= VQ_LAB_ATTN_K_ABL32D) {
-        if (D != 72 || a.Lq < 192) return D != 72 ? VQ_EUNSUP : VQ_ESHAPE;
-        return lab_abl32d(kernel - VQ_LAB_ATTN_K_ABL32D, a, st);
-    }
     if (kernel == VQ_LAB_ATTN_K_FWD32D_NW4) {
         if (a.Lq < 192) return VQ_ESHAPE;
         if constexpr (D == 72) return launch_attn32d<D, 4>(a, st);

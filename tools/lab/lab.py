@@ -1,4 +1,4 @@
-"""ctypes binding of tools/lab/libviditq_lab.so (retired GEMM and attention variants, ablations, probes) for the measurement
+"""ctypes binding of tools/lab/libviditq_lab.so (retired GEMM and attention variants, GEMM ablations, probes) for the measurement
 scripts in tools/.  ``gemm_i8`` has the signature of viditq_amd.ops.gemm_i8 with a mandatory ``variant``, ``attn_fwd`` that
 of viditq_amd.ops.attn_fwd behind a mandatory kernel id."""
 import ctypes as C
@@ -120,9 +120,8 @@ def gemm_sp(a, w, bias=None, out=None, epilogue=0, resid=None, gate=None, rows_p
     return out
 
 
-# kernel ids of vq_lab_attn_fwd (tools/lab/attn_lab.hip); ATTN_ABL32D / ATTN_ABL8 + the ablation mask (wrong results by design)
+# kernel ids of vq_lab_attn_fwd (tools/lab/attn_lab.hip)
 ATTN_PRODUCT, ATTN_FWD32D_NW4, ATTN_64D_128, ATTN_64D_NW4, ATTN_64P, ATTN_64S, ATTN_64P_NB4 = -1, 4, 100, 101, 102, 103, 104
-ATTN_ABL32D, ATTN_ABL8 = 1000, 2000
 
 
 def attn_fwd(kernel, q, k, v, o, n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride, o_seq_stride,

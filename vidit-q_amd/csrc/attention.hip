@@ -25,11 +25,17 @@
 // LDS exchange contract and row reductions in attn_rowquant.h.  Each has a static-grid form (instantiated on the argument
 // struct TempQSArgs, vq_attn_temporal_rowquant_static): attn_temp.proj's calibrated tensor-wise quantizer at 2..8 bits.
 //
+// The five flash-style kernels behind vq_attn_fwd are written on the shared steps of attn_tile.h (geometry, operand reads,
+// LDS-DMA delivery, softmax, epilogue): a kernel body here is its schedule.  Two blocks are written out where the helper cost
+// a measured register bound or timing band: attn_fwd8_kernel's lazy rescale, attn_fwd64d_kernel's softmax block.
+//
 // Host side: every launcher goes through vq_prepare_kernel (dynamic-LDS limit and CU count once per device, vq_common.h)
 // and every entry point picks the head dim with vq_dispatch_head_dim.  Nothing here reads the environment or depends on a
-// build flag; the retired kernels, profiling ablations and A/B arms are the lab's attn_lab.hip, which includes this file.
+// build flag, and no kernel has a profiling or ablation arm: the retired kernels and A/B arms are the lab's attn_lab.hip,
+// which includes this file.
 #include "vq_common.h"
 #include "attn_rowquant.h"
+#include "attn_tile.h"
 
 #define ATT_LOG2E 1.4426950408889634f
 
@@ -52,17 +58,7 @@ struct AttCfg {
     static_assert(DT * 32 > D, "needs a spare O^T row for the row sums");
 };
 
-struct AttnArgs {
-    const half_t* q;
-    const half_t* k;
-    const half_t* v;
-    half_t* o;
-    long q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride, o_seq_stride, o_tok_stride;
-    const int32_t* kv_off;
-    int n_seq, Lq, Lk, H;
-    float c;  // scale * log2(e)
-};
-
+// (AttnArgs, the argument block of every vq_attn_fwd kernel, is declared in attn_tile.h: the shared steps take it)
 template <int D>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     using C = AttCfg<D>;
@@ -71,39 +67,17 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     const int g = lane >> 5, l31 = lane & 31;
     const int qt = blockIdx.x, h = blockIdx.y, seq = blockIdx.z;
 
-    int kv_len = a.Lk;
     const half_t* kbase;
     const half_t* vbase;
-    if (a.kv_off) {
-        const int o0 = a.kv_off[seq];
-        kv_len = a.kv_off[seq + 1] - o0;
-        kbase = a.k + (long)o0 * a.kv_tok_stride + h * D;
-        vbase = a.v + (long)o0 * a.kv_tok_stride + h * D;
-    } else {
-        kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
-        vbase = a.v + (long)seq * a.kv_seq_stride + h * D;
-    }
+    const int kv_len = attn_kv_base<D>(a, seq, h, kbase, vbase);
     const int qi = qt * 128 + wave * 32 + l31;
     const bool q_ok = qi < a.Lq;
     const int qc = q_ok ? qi : a.Lq - 1;
-    const half_t* qrow = a.q + (long)seq * a.q_seq_stride + (long)qc * a.q_tok_stride + h * D;
 
-    // Q fragments (B operand): lane = query, 8 dims at ks*16 + 8g
-    half8 qf[C::KS];
-#pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) {
-        const int d0 = ks * 16 + 8 * g;
-        if (d0 < D) qf[ks] = *reinterpret_cast<const half8*>(qrow + d0);
-        else
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qf[ks][e] = (half_t)0.f;
-    }
-
+    half8 qf[C::KS];                                    // Q fragments (B operand): lane = query, 8 dims at ks*16 + 8g
+    attn_q_frags<D>(a.q + (long)seq * a.q_seq_stride + (long)qc * a.q_tok_stride + h * D, g, qf);
     float16v oacc[C::DT];
-#pragma unroll
-    for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
+    attn_zero(oacc);
     float m_run = -INFINITY;
 
     const int nkt = (kv_len + 63) / 64;
@@ -168,14 +142,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[sc][r] = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < C::KS; ++ks) {
-                const int d0 = ks * 16 + 8 * g;
-                half8 kf = *reinterpret_cast<const half8*>(kt_ + (sc * 32 + l31) * C::KROW + (d0 < D ? d0 : 0) * 2);
-                if (d0 >= D)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) kf[e] = (half_t)0.f;
-                s[sc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[sc], 0, 0, 0);
-            }
+            for (int ks = 0; ks < C::KS; ++ks)
+                s[sc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(attn_frag<D>(kt_ + (sc * 32 + l31) * C::KROW, ks, g), qf[ks], s[sc], 0, 0, 0);
         }
         // ---- online softmax (lane = query; its 64 keys sit in 32 registers here and 32 in lane^32) ----
         // VALU is the bound of this kernel (PMC: VALU busy 65 %, MFMA 18 %), so: masking only on a partial
@@ -183,19 +151,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
         // running max moved, and NO row-sum adds: column D of V is 1.0, so row D of O^T is sum_k P.
         if (kt * 64 + 64 > kv_len) {
 #pragma unroll
-            for (int sc = 0; sc < 2; ++sc)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kt * 64 + sc * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                    if (key >= kv_len) s[sc][r] = -INFINITY;
-                }
+            for (int sc = 0; sc < 2; ++sc) attn_mask(s[sc], kt * 64 + sc * 32, g, kv_len);
         }
-        float mloc = s[0][0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mloc = fmaxf(mloc, s[0][r]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[1][r]);
-        mloc = fmaxf(mloc, __shfl_xor(mloc, 32));
+        const float mloc = attn_rowmax_shfl(s);
         const float m_new = fmaxf(m_run, mloc);
         const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
         if (__any(m_new != m_run)) {
@@ -241,27 +199,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     }
 
     // ---- normalise and store: lane = query, accumulator quads = 4 consecutive dims ----
-    // row D of O^T = sum_k P: it lives in tile D/32, register (D%32 -> (r&3)+8(r>>2)+4g) of ONE half-wave
-    constexpr int LD_T = D / 32, LD_R = D % 32;
-    constexpr int LD_G = (LD_R >> 2) & 1, LD_REG = (LD_R & 3) + 4 * (LD_R >> 3);
-    float l_run = oacc[LD_T][LD_REG];
-    l_run = __shfl(l_run, l31 + 32 * LD_G);
-    const float inv = l_run > 0.f ? __fdiv_rn(1.0f, l_run) : 0.f;
-    if (q_ok) {
-        half_t* orow = a.o + (long)seq * a.o_seq_stride + (long)qi * a.o_tok_stride + h * D;
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int d = dt * 32 + 8 * rg + 4 * g;
-                if (d < D) {
-                    half4 ov;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ov[e] = (half_t)(oacc[dt][rg * 4 + e] * inv);
-                    *reinterpret_cast<half4*>(orow + d) = ov;
-                }
-            }
-    }
+    const float inv = attn_inv_row_sum<D>(oacc, l31);
+    if (q_ok) attn_store_rows_h4<D>(oacc, inv, a.o + (long)seq * a.o_seq_stride + (long)qi * a.o_tok_stride + h * D, g);
 }
 
 // ---------------------------------------------------------------------------
@@ -384,19 +323,7 @@ __global__ __launch_bounds__(256) void attn_temporal_kernel(TempArgs a) {
     }
     if (tq < a.T && s0 + sq < a.S) {
         const long grow = ((long)b * a.T + tq) * a.S + s0 + sq;
-        half_t* orow = a.o + grow * a.ld_out + (h0 + wave) * D;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int d = dt * 32 + 8 * rg + 4 * g;
-                if (d < D) {
-                    half4 ov;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ov[e] = (half_t)(oacc[dt][rg * 4 + e] * inv);
-                    *reinterpret_cast<half4*>(orow + d) = ov;
-                }
-            }
+        attn_store_rows_h4<D>(oacc, inv, a.o + grow * a.ld_out + (h0 + wave) * D, g);
     }
 }
 
@@ -436,7 +363,6 @@ struct TempQSArgs : TempQArgs {
 
 // HC: head count known at compile time (16 = STDiT-XL; 0 = take a.H): the chunk -> (tensor, row, piece) divisions of
 // the staging loops are by H * D / 8 and cost ~45 VALU instructions each with a run-time divisor
-typedef __fp16 h4t_t __attribute__((__vector_size__(4 * sizeof(__fp16))));   // operand type of the LDS transpose read
 // A = TempQSArgs: the static-grid form ST (attn_rowquant.h): a.delta / a.zp / a.n_bits instead of the row's own 8-bit
 // grid, any B
 template <int D, int HC, class A = TempQArgs>
@@ -568,8 +494,8 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
             // group points at [key 4 g4 + i / 4][dims 16 dt + 4 (i % 4) .. + 3] and receives column i of the 4 x 16 block
             // (four 2-byte reads and their packing before).  Dims >= D of the last tile read the neighbouring head / the
             // row padding: finite garbage in output rows nobody stores.
-            const h4t_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (__attribute__((address_space(3))) h4t_t*)(vs + (4 * g4 + (tq >> 2)) * RS + (dt * 16 + 4 * (tq & 3)) * 2));
+            const h4_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                (__attribute__((address_space(3))) h4_t*)(vs + (4 * g4 + (tq >> 2)) * RS + (dt * 16 + 4 * (tq & 3)) * 2));
             const half4 vf = {(half_t)vt[0], (half_t)vt[1], (half_t)vt[2], (half_t)vt[3]};
             oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf, float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
             // this lane: token tq, dims 16*dt + 4*g4 + r, rounded to fp16 like the stored tensor
@@ -848,8 +774,8 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
         [[maybe_unused]] float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
         for (int dt = 0; dt < KS; ++dt) {
-            const h4t_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (__attribute__((address_space(3))) h4t_t*)(vs + vtro + dt * 32));
+            const h4_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                (__attribute__((address_space(3))) h4_t*)(vs + vtro + dt * 32));
             const half4 vf = {(half_t)vt[0], (half_t)vt[1], (half_t)vt[2], (half_t)vt[3]};
             const float4v o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf, float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #pragma unroll
@@ -1111,8 +1037,8 @@ __global__ __launch_bounds__(1024) void attn_temporal_long_kernel(A a) {
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt)
                     if (kt < nt) {
-                        const h4t_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) h4t_t*)(vs + kt * 16 * RSV + vtro + dt * 32));
+                        const h4_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                            (__attribute__((address_space(3))) h4_t*)(vs + kt * 16 * RSV + vtro + dt * 32));
                         const half4 vf = {(half_t)vt[0], (half_t)vt[1], (half_t)vt[2], (half_t)vt[3]};
                         o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[kt], o4, 0, 0, 0);
                     }
@@ -1265,84 +1191,25 @@ struct Att8Cfg {
     static_assert(DT * 32 > D, "needs a spare O^T row for the row sums");
 };
 
-// ABL (profiling only, wrong results): 1 no exp, 2 no P.V MFMAs, 4 no QK MFMAs, 8 no staging after tile 0
-// NQ: independent 32-query blocks per wave.  NQ = 2 (with NW = 4: one wave per SIMD, the whole register file)
-// gives the in-order wave two independent MFMA -> softmax -> MFMA chains to interleave, and every K / V^T fragment
-// read from LDS feeds two MFMAs.
-template <int D, int NW, int ABL = 0, int NQ = 1>
-__global__ __launch_bounds__(64 * NW, NQ == 2 ? 1 : 8 / NW) void attn_fwd8_kernel(AttnArgs a) {
+template <int D, int NW>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd8_kernel(AttnArgs a) {
     using C = Att8Cfg<D, NW>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31;
-    // Workgroup -> (sequence, head, query tile).  Workgroups are dealt round-robin to the 8 XCDs; XCD x takes a
-    // CONTIGUOUS range of the (sequence, head) pairs and runs the query tiles of a pair back to back, so a
-    // pair's K/V panel is fetched into that XCD's L2 once for all its query tiles, and neighbouring heads
-    // (whose 2*D-byte row segments share cache lines) sit in the same L2.  With the plain (qt, h, seq) grid
-    // the 4 query tiles of a pair ran on 4 different XCDs: 341 MB read for 113 MB of q/k/v
-    // (profiles/r01_hbm_traffic.md), and re-staging K/V cost 50 of 188 us.
     int qt, h, seq;
-    {
-        const int nqt = (a.Lq + 32 * NW * NQ - 1) / (32 * NW * NQ);
-        const int G = a.n_seq * a.H;
-        const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-        const int q8 = G / 8, r8 = G % 8;
-        const int gbase = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-        const int gcount = xcd < r8 ? q8 + 1 : q8;
-        const int pl = idx / nqt;
-        if (pl >= gcount) return;                      // padded grid slot (whole workgroup: no barrier reached yet)
-        const int pair = gbase + pl;
-        qt = idx - pl * nqt;
-        seq = pair / a.H;
-        h = pair - seq * a.H;
-    }
-
-    long long* tsw = nullptr;
-    if constexpr ((ABL & 128) != 0) {
-        tsw = reinterpret_cast<long long*>(a.o + (size_t)a.n_seq * a.o_seq_stride) + (size_t)256 * NW * 16 * 8 + ((size_t)blockIdx.x * NW + wave) * 8;
-        if (lane == 0) {
-            tsw[0] = __builtin_readcyclecounter();
-            tsw[6] = wall_clock64();
-        }
-    }
-    int kv_len = a.Lk;
+    if (!attn_xcd_map(a, 32 * NW, qt, h, seq)) return;
     const half_t* kbase;
     const half_t* vbase;
-    if (a.kv_off) {
-        const int o0 = a.kv_off[seq];
-        kv_len = a.kv_off[seq + 1] - o0;
-        kbase = a.k + (long)o0 * a.kv_tok_stride + h * D;
-        vbase = a.v + (long)o0 * a.kv_tok_stride + h * D;
-    } else {
-        kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
-        vbase = a.v + (long)seq * a.kv_seq_stride + h * D;
-    }
-    int qi[NQ];
-    bool q_ok[NQ];
-    half8 qf[NQ][C::KS];
-    float16v oacc[NQ][C::DT];
-    float m_run[NQ];
-#pragma unroll
-    for (int nq = 0; nq < NQ; ++nq) {
-        qi[nq] = qt * (32 * NW * NQ) + (wave * NQ + nq) * 32 + l31;
-        q_ok[nq] = qi[nq] < a.Lq;
-        const int qc = q_ok[nq] ? qi[nq] : a.Lq - 1;
-        const half_t* qrow = a.q + (long)seq * a.q_seq_stride + (long)qc * a.q_tok_stride + h * D;
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) {
-            const int d0 = ks * 16 + 8 * g;
-            if (d0 < D) qf[nq][ks] = *reinterpret_cast<const half8*>(qrow + d0);
-            else
-#pragma unroll
-                for (int e = 0; e < 8; ++e) qf[nq][ks][e] = (half_t)0.f;
-        }
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[nq][dt][r] = 0.f;
-        m_run[nq] = -INFINITY;
-    }
+    const int kv_len = attn_kv_base<D>(a, seq, h, kbase, vbase);
+    const int qi = qt * (32 * NW) + wave * 32 + l31;
+    const bool q_ok = qi < a.Lq;
+    half8 qf[C::KS];
+    float16v oacc[C::DT];
+    float m_run = -INFINITY;
+    attn_q_frags<D>(a.q + (long)seq * a.q_seq_stride + (long)(q_ok ? qi : a.Lq - 1) * a.q_tok_stride + h * D, g, qf);
+    attn_zero(oacc);
 
     // V^T fragment addresses: lane = output dim d (row D = the ones row; rows above it are clamped, unused)
     int vaddr[C::DT][4];
@@ -1411,7 +1278,6 @@ __global__ __launch_bounds__(64 * NW, NQ == 2 ? 1 : 8 / NW) void attn_fwd8_kerne
                 const uint32_t lo0 = odd_lane ? (uint32_t)r0 : (uint32_t)vr[i][0], lo1 = odd_lane ? (uint32_t)r1 : (uint32_t)vr[i][1];
                 const uint32_t hi0 = odd_lane ? (uint32_t)vr[i][2] : (uint32_t)r0, hi1 = odd_lane ? (uint32_t)vr[i][3] : (uint32_t)r1;
                 uint8_t* vp = vt_ + vdst[i];
-                if (ABL & 32) continue;
                 *reinterpret_cast<uint32_t*>(vp) = __builtin_amdgcn_perm(hi0, lo0, 0x05040100u);
                 *reinterpret_cast<uint32_t*>(vp + C::VROWB) = __builtin_amdgcn_perm(hi0, lo0, 0x07060302u);
                 *reinterpret_cast<uint32_t*>(vp + 2 * C::VROWB) = __builtin_amdgcn_perm(hi1, lo1, 0x05040100u);
@@ -1429,213 +1295,92 @@ __global__ __launch_bounds__(64 * NW, NQ == 2 ? 1 : 8 / NW) void attn_fwd8_kerne
         store_tile(0, krA, vrA);
     }
     __syncthreads();
-    if (tsw && lane == 0) tsw[1] = __builtin_readcyclecounter();
     // one key tile; `cur` (LDS buffer) and the register sets are compile-time per call site: the loop below is
     // unrolled by two so that set A / set B never meet in a phi (the compiler otherwise copies them through
     // temporaries behind an s_waitcnt vmcnt(0) that exposes the whole global-load latency every tile)
     auto tile = [&](const int kt, const int cur, int4v (&krL)[C::KPT], int4v (&vrL)[C::KPT], int4v (&krS)[C::KPT],
                     int4v (&vrS)[C::KPT]) {
-        long long* ts = nullptr;
-        if constexpr ((ABL & 128) != 0) {
-            if (blockIdx.x < 256 && kt < 16)
-                ts = reinterpret_cast<long long*>(a.o + (size_t)a.n_seq * a.o_seq_stride) + (((size_t)blockIdx.x * NW + wave) * 16 + kt) * 8;
-            if (ts && lane == 0) ts[0] = __builtin_readcyclecounter();
-        }
-        if (!(ABL & 8) && !(ABL & 64) && kt + 2 < nkt) load_tile(kt + 2, krL, vrL);
+        if (kt + 2 < nkt) load_tile(kt + 2, krL, vrL);
         const uint8_t* kt_ = smem + cur * C::KTILE;
         const uint8_t* vt_ = smem + 2 * C::KTILE + cur * C::VTILE;
 
-        float16v s[NQ][2];
+        float16v s[2];
 #pragma unroll
         for (int sc = 0; sc < 2; ++sc) {
 #pragma unroll
-            for (int nq = 0; nq < NQ; ++nq)
+            for (int r = 0; r < 16; ++r) s[sc][r] = 0.f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) s[nq][sc][r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < C::KS; ++ks) {
-                const int d0 = ks * 16 + 8 * g;
-                half8 kf = *reinterpret_cast<const half8*>(kt_ + (sc * 32 + l31) * C::KROW + (d0 < D ? d0 : 0) * 2);
-                if (d0 >= D)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) kf[e] = (half_t)0.f;
-#pragma unroll
-                for (int nq = 0; nq < NQ; ++nq) {
-                    if (!(ABL & 4)) s[nq][sc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[nq][ks], s[nq][sc], 0, 0, 0);
-                    else s[nq][sc][ks] += (float)kf[0];
-                }
-            }
+            for (int ks = 0; ks < C::KS; ++ks)
+                s[sc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(attn_frag<D>(kt_ + (sc * 32 + l31) * C::KROW, ks, g), qf[ks], s[sc], 0, 0, 0);
         }
         // stage the NEXT tile while the QK^T MFMAs above are in flight: the other LDS buffer has had no reader
         // since the last barrier, and nothing below depends on these VALU / LDS-write instructions
         __builtin_amdgcn_sched_barrier(0);
-        if (ts && lane == 0) ts[1] = __builtin_readcyclecounter();
-        if (!(ABL & 8) && kt + 1 < nkt) store_tile(cur ^ 1, krS, vrS);
-        if (ts && lane == 0) ts[2] = __builtin_readcyclecounter();
+        if (kt + 1 < nkt) store_tile(cur ^ 1, krS, vrS);
         __builtin_amdgcn_sched_barrier(0);
         if (kt * 64 + 64 > kv_len) {
 #pragma unroll
-            for (int nq = 0; nq < NQ; ++nq)
-#pragma unroll
-                for (int sc = 0; sc < 2; ++sc)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = kt * 64 + sc * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                        if (key >= kv_len) s[nq][sc][r] = -INFINITY;
-                    }
+            for (int sc = 0; sc < 2; ++sc) attn_mask(s[sc], kt * 64 + sc * 32, g, kv_len);
         }
-        float mc[NQ];
+        // the lazy rescale of attn_tile.h's attn_lazy_rescale, kept inline in this one kernel: through the helper the D = 32
+        // forms need 130 VGPRs instead of 128 (three resident waves per SIMD instead of four)
+        const float mloc = attn_rowmax_shfl(s);
+        if (__any((mloc - m_run) * a.c > 8.0f)) {
+            const float m_new = fmaxf(m_run, mloc);
+            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+            const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * a.c);
 #pragma unroll
-        for (int nq = 0; nq < NQ; ++nq) {
-            float mloc = s[nq][0][0];
+            for (int dt = 0; dt < C::DT; ++dt)
 #pragma unroll
-            for (int r = 1; r < 16; ++r) mloc = fmaxf(mloc, s[nq][0][r]);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[nq][1][r]);
-            mloc = fmaxf(mloc, __shfl_xor(mloc, 32));
-            // deferred rescale: move the running max only when a tile max leads it by more than 2^8
-            if (__any((mloc - m_run[nq]) * a.c > 8.0f)) {
-                const float m_new = fmaxf(m_run[nq], mloc);
-                const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-                const float alpha = __builtin_amdgcn_exp2f((m_run[nq] - m_use) * a.c);
-#pragma unroll
-                for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) oacc[nq][dt][r] *= alpha;
-                m_run[nq] = m_new;
-            }
-            mc[nq] = ((m_run[nq] == -INFINITY) ? 0.f : m_run[nq]) * a.c;
+                for (int r = 0; r < 16; ++r) oacc[dt][r] *= alpha;
+            m_run = m_new;
         }
-        if (ts && lane == 0) ts[3] = __builtin_readcyclecounter();
-        // exp and P.V per 32-key sub-tile (and query block): the exponentials of the next piece run under the
-        // MFMAs of the previous one
+        const float mc = ((m_run == -INFINITY) ? 0.f : m_run) * a.c;
+        // exp and P.V per 32-key sub-tile: the exponentials of the next piece run under the MFMAs of the previous one
 #pragma unroll
         for (int sc = 0; sc < 2; ++sc) {
 #pragma unroll
-            for (int nq = 0; nq < NQ; ++nq)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    s[nq][sc][r] = (ABL & 1) ? fmaf(s[nq][sc][r], a.c, -mc[nq])
-                                             : __builtin_amdgcn_exp2f(fmaf(s[nq][sc][r], a.c, -mc[nq]));
+            for (int r = 0; r < 16; ++r) s[sc][r] = __builtin_amdgcn_exp2f(fmaf(s[sc][r], a.c, -mc));
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
                 const int kk = 2 * sc + k2, rq = 2 * k2;
-                half8 pf[NQ];
+                half8 pf;
 #pragma unroll
-                for (int nq = 0; nq < NQ; ++nq)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        pf[nq][e] = (half_t)s[nq][sc][4 * rq + e];
-                        pf[nq][4 + e] = (half_t)s[nq][sc][4 * rq + 4 + e];
-                    }
+                for (int e = 0; e < 4; ++e) {
+                    pf[e] = (half_t)s[sc][4 * rq + e];
+                    pf[4 + e] = (half_t)s[sc][4 * rq + 4 + e];
+                }
 #pragma unroll
                 for (int dt = 0; dt < C::DT; ++dt) {
                     const half8 vw = *reinterpret_cast<const half8*>(vt_ + vaddr[dt][kk]);
-#pragma unroll
-                    for (int nq = 0; nq < NQ; ++nq) {
-                        if (!(ABL & 2)) oacc[nq][dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vw, pf[nq], oacc[nq][dt], 0, 0, 0);
-                        else oacc[nq][dt][kk] += (float)vw[0] * (float)pf[nq][0];
-                    }
+                    oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vw, pf, oacc[dt], 0, 0, 0);
                 }
             }
         }
-        if (ts && lane == 0) ts[4] = __builtin_readcyclecounter();
-        if (!(ABL & 16)) __syncthreads();
-        if (ts && lane == 0) ts[5] = __builtin_readcyclecounter();
+        __syncthreads();
     };
     for (int kt = 0; kt < nkt; kt += 2) {
         tile(kt, 0, krA, vrA, krB, vrB);               // tile kt sits in buffer 0; loads kt+2 -> A, stages kt+1 <- B
         if (kt + 1 < nkt) tile(kt + 1, 1, krB, vrB, krA, vrA);
     }
 
-    if constexpr ((ABL & 128) != 0) {                  // stamps live BEHIND the output (the tool allocates the room)
-        if (lane == 0) tsw[2] = __builtin_readcyclecounter();
-    }
-    constexpr int LD_T = D / 32, LD_R = D % 32;
-    constexpr int LD_G = (LD_R >> 2) & 1, LD_REG = (LD_R & 3) + 4 * (LD_R >> 3);
-#pragma unroll
-    for (int nq = 0; nq < NQ; ++nq) {
-        float l_run = oacc[nq][LD_T][LD_REG];
-        l_run = __shfl(l_run, l31 + 32 * LD_G);
-        const float inv = l_run > 0.f ? __fdiv_rn(1.0f, l_run) : 0.f;
-        if (q_ok[nq]) {
-            half_t* orow = a.o + (long)seq * a.o_seq_stride + (long)qi[nq] * a.o_tok_stride + h * D;
-#pragma unroll
-            for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-                for (int rg = 0; rg < 4; ++rg) {
-                    const int d = dt * 32 + 8 * rg + 4 * g;
-                    if (d < D) {
-                        half4 ov;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) ov[e] = (half_t)(oacc[nq][dt][rg * 4 + e] * inv);
-                        *reinterpret_cast<half4*>(orow + d) = ov;
-                    }
-                }
-        }
-    }
-    if constexpr ((ABL & 128) != 0) {
-        if (lane == 0) {
-            tsw[3] = __builtin_readcyclecounter();
-            tsw[7] = wall_clock64();
-        }
-    }
+    const float inv = attn_inv_row_sum<D>(oacc, l31);
+    if (q_ok) attn_store_rows_h4<D>(oacc, inv, a.o + (long)seq * a.o_seq_stride + (long)qi * a.o_tok_stride + h * D, g);
 }
 
 // ---------------------------------------------------------------------------
-// attn_fwd32d_kernel: attn_fwd32h with the K / V tiles delivered by LDS-DMA (buffer_load_dwordx4 ... lds): no staging
-// registers, no ds_write pass, no vmcnt coupling between the staged tile and the fragment reads.  A wave-instruction
-// fills 64 consecutive 16-byte slots of the tile image; slot -> (row, piece) is the ordinary padded row-major layout
-// (K rows KROW bytes, V rows 192 bytes with the ones column behind the data), lanes whose slot is padding are masked
-// off, rows past the last key are out of the buffer's range and land as zeros.  The ~15 VGPRs this frees pay for
-// fragment reads that run two ahead of the MFMAs (pinned with sched_barrier).
+// attn_fwd32d_kernel: the K / V tiles delivered by LDS-DMA (buffer_load_dwordx4 ... lds, AttnKvDma of attn_tile.h): no
+// staging registers, no ds_write pass, no vmcnt coupling between the staged tile and the fragment reads.  The tile images
+// are the ordinary padded row-major layout (K rows KROW bytes, V rows 192 bytes with the ones column behind the data, read
+// as V^T with ds_read_b64_tr_b16).  The ~15 VGPRs this frees pay for fragment reads that run two ahead of the MFMAs
+// (pinned with sched_barrier).  32 queries per wave, four waves per SIMD.
 // ---------------------------------------------------------------------------
-typedef __fp16 h4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));   // operand type of the LDS transpose read
-
-// O^T leaves the 32 x 32 matrix core with 4 consecutive dims per lane and (dt, rg) group, the partner lane (g ^ 1) holding the
-// other half of each 8-dim group: one v_permlane32_swap per dword turns two groups into 8 consecutive dims per lane - 16-byte
-// stores, 32 contiguous bytes per row and instruction instead of 16 (the store tail of a row-per-lane epilogue is bound by
-// store INSTRUCTIONS, not bytes: cdna_hip_programming.md T21).  Every lane of the wave must call this (the swaps are
-// wave-wide); `row_ok` masks the stores only.  Round 4: cross attention; round 6: the self-attention kernels too.
-template <int D, int DT>
-__device__ __forceinline__ void attn_store_rows(const float16v (&oacc)[DT], float inv, half_t* orow, int g, bool row_ok) {
-    constexpr int NG = D / 8;                           // 8-dim groups: dt = grp / 4, rg = grp % 4
-#pragma unroll
-    for (int p2 = 0; p2 < NG / 2; ++p2) {
-        const int ga = 2 * p2, gb = 2 * p2 + 1;
-        uint32_t A[2], B[2];
-#pragma unroll
-        for (int w = 0; w < 2; ++w) {
-            typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-            const h2_t ha = {(half_t)(oacc[ga / 4][(ga % 4) * 4 + 2 * w] * inv), (half_t)(oacc[ga / 4][(ga % 4) * 4 + 2 * w + 1] * inv)};
-            const h2_t hb = {(half_t)(oacc[gb / 4][(gb % 4) * 4 + 2 * w] * inv), (half_t)(oacc[gb / 4][(gb % 4) * 4 + 2 * w + 1] * inv)};
-            A[w] = __builtin_bit_cast(uint32_t, ha);
-            B[w] = __builtin_bit_cast(uint32_t, hb);
-        }
-        // swap(A, B): first result = {low lanes: A of g = 0, high lanes: B of g = 0}, second = {A of g = 1, B of g = 1}
-        const auto s0 = __builtin_amdgcn_permlane32_swap(A[0], B[0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(A[1], B[1], false, false);
-        const int4v ov = {(int)s0[0], (int)s1[0], (int)s0[1], (int)s1[1]};
-        if (row_ok) *reinterpret_cast<int4v*>(orow + 16 * p2 + 8 * g) = ov;
-    }
-    if constexpr (NG % 2 == 1) {                        // the odd last group: 8-byte stores
-        constexpr int gl = NG - 1;
-        half4 ov;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ov[e] = (half_t)(oacc[gl / 4][(gl % 4) * 4 + e] * inv);
-        if (row_ok) *reinterpret_cast<half4*>(orow + 8 * gl + 4 * g) = ov;
-    }
-}
-
-template <int D, int ABLD = 0, int NW = 8, int KT = 64>
+template <int D, int NW = 8, int KT = 64>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(AttnArgs a) {
     static_assert(KT % 64 == 0, "key tile in 64-row DMA units");
-    constexpr int KTB = (KT / 64) * Att8Cfg<D, 8>::KTILE;      // K tile bytes
     using C = Att8Cfg<D, NW>;
-    constexpr int VRB = 192, VT = KT * VRB;                 // row-major V image (see attn_fwd_pp_kernel)
-    constexpr int KSL = C::KROW / 16, VSL = VRB / 16;       // 16-byte slots per row
-    constexpr int NKI = KSL * (KT / 64), NVI = VSL * (KT / 64);   // wave-instructions (64 slots) per K / V tile
-    constexpr int NI = NKI + NVI, IPW = (NI + NW - 1) / NW;
+    constexpr int KTB = (KT / 64) * C::KTILE;               // K tile bytes
+    constexpr int VRB = 192, VT = KT * VRB;                 // row-major V image
     constexpr int PF = 2;
     static_assert(D * 2 + 2 <= VRB && C::DT * 64 <= VRB, "dims + ones column inside a row; every 32-dim tile readable");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1643,20 +1388,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31;
     int qt, h, seq;
-    {
-        const int nqt = (a.Lq + 32 * NW - 1) / (32 * NW);
-        const int G = a.n_seq * a.H;
-        const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-        const int q8 = G / 8, r8 = G % 8;
-        const int gbase = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-        const int gcount = xcd < r8 ? q8 + 1 : q8;
-        const int pl = idx / nqt;
-        if (pl >= gcount) return;
-        const int pair = gbase + pl;
-        qt = idx - pl * nqt;
-        seq = pair / a.H;
-        h = pair - seq * a.H;
-    }
+    if (!attn_xcd_map(a, 32 * NW, qt, h, seq)) return;
     const int kv_len = a.Lk;
     const half_t* kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
     const half_t* vbase = a.v + (long)seq * a.kv_seq_stride + h * D;
@@ -1665,77 +1397,25 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A
     half8 qf[C::KS];
     float16v oacc[C::DT];
     float m_run = -INFINITY;
-    {
-        const half_t* qrow = a.q + (long)seq * a.q_seq_stride + (long)(q_ok ? qi : a.Lq - 1) * a.q_tok_stride + h * D;
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) {
-            const int d0 = ks * 16 + 8 * g;
-            if (d0 < D) qf[ks] = *reinterpret_cast<const half8*>(qrow + d0);
-            else
-#pragma unroll
-                for (int e = 0; e < 8; ++e) qf[ks][e] = (half_t)0.f;
-        }
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
-    }
+    attn_q_frags<D>(a.q + (long)seq * a.q_seq_stride + (long)(q_ok ? qi : a.Lq - 1) * a.q_tok_stride + h * D, g, qf);
+    attn_zero(oacc);
     const int nkt = (kv_len + KT - 1) / KT;
     const int strideB = (int)a.kv_tok_stride * 2;
     const unsigned nrec = kv_len > 0 ? (unsigned)(kv_len - 1) * (unsigned)strideB + D * 2 : 0u;
-    bool ok[IPW];
-    int voff[IPW];
-#pragma unroll
-    for (int i = 0; i < IPW; ++i) {
-        const int j = wave + NW * i;                       // wave-uniform instruction index: K tile first, then V
-        const bool isk = j < NKI;
-        const int slot = (isk ? j : j - NKI) * 64 + lane;
-        const int row = isk ? slot / KSL : slot / VSL;
-        const int piece = slot - row * (isk ? KSL : VSL);
-        ok[i] = j < NI && piece < C::CHD;
-        voff[i] = row * strideB + piece * 16;
-    }
-    auto issue = [&](int kt, int part = -1) __attribute__((always_inline)) {   // part 0: round i == 0, 1: the others, -1: all
-        const unsigned t0 = (unsigned)kt * (unsigned)KT * (unsigned)strideB;
-        const int buf = kt & 1;
-#pragma unroll
-        for (int i = 0; i < IPW; ++i) {
-            const int j = wave + NW * i;
-            if (j < NI && (part < 0 || (part == 0) == (i == 0))) {
-                const bool isk = j < NKI;
-                const uint8_t* b = reinterpret_cast<const uint8_t*>(isk ? kbase : vbase) + t0;
-                // issued through asm: the builtin makes the compiler order every later ds_read behind the DMA (vmcnt(0)
-                // before the first MFMAs of the tile); the only consumer-side wait needed is the one in wg_barrier().
-                // Hazards the recognizer would handle for its own instructions are spelled out: s_nop 4 covers the M0
-                // write -> LDS-DMA rule (1 wait state) and a VALU-written (v_readfirstlane) resource SGPR -> VMEM read (5)
-                const unsigned long ba = (unsigned long)b;
-                const int4v rs = {(int)__builtin_amdgcn_readfirstlane((unsigned)ba),
-                                  (int)__builtin_amdgcn_readfirstlane((unsigned)(ba >> 32) & 0xffffu),
-                                  (int)__builtin_amdgcn_readfirstlane(nrec - t0), 0x00020000};
-                const unsigned dst = __builtin_amdgcn_readfirstlane(
-                    (unsigned)(size_t)(__attribute__((address_space(3))) uint8_t*)smem +
-                    (isk ? buf * KTB + j * 1024 : 2 * KTB + buf * VT + (j - NKI) * 1024));
-                if (ok[i])
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(dst), "v"(voff[i]), "s"(rs)
-                                 : "memory", "m0");
-            }
-        }
+    AttnKvDma<D, NW, KT, C::KROW, VRB> dma;
+    dma.init(wave, lane, strideB);
+    const unsigned lds0 = attn_lds_addr(smem);
+    auto issue = [&](int kt, int part = -1) __attribute__((always_inline)) {   // tile kt -> image pair kt & 1
+        dma.issue(kbase, vbase, (unsigned)kt * (unsigned)KT * (unsigned)strideB, nrec, lds0 + (kt & 1) * KTB, lds0 + 2 * KTB + (kt & 1) * VT,
+                  wave, part);
     };
-    auto wg_barrier = [&]() __attribute__((always_inline)) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    for (int i = tid; i < 2 * KT * 3; i += 64 * NW) {   // pad columns of both V images: column D = 1.0, the rest 0
-        const int r = i / 3, ch = i % 3;                 // r runs over the rows of both images (contiguous)
-        *reinterpret_cast<int4v*>(smem + 2 * KTB + r * VRB + D * 2 + ch * 16) = int4v{ch == 0 ? 0x00003c00 : 0, 0, 0, 0};
-    }
+    attn_fill_pad<D, VRB>(smem + 2 * KTB, 2 * KT, tid, 64 * NW);   // both V images (contiguous)
     if (nkt > 0) issue(0);
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) asm volatile("" ::"v"(qf[ks]));   // the compiler's own wait for the Q loads goes HERE, not
                                                                           // (as vmcnt(0), stalling on the DMA) into the loop
-    wg_barrier();
-    const int vtr0 = (4 * g + ((lane & 15) >> 2)) * VRB + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+    attn_wg_barrier();
+    const int vtr0 = attn_vtr0<VRB>(lane, g);
 
     auto tile = [&](auto rag_tag, const int kt) __attribute__((always_inline)) {
         constexpr bool RAG = decltype(rag_tag)::value;
@@ -1745,27 +1425,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A
         for (int sc = 0; sc < KT / 32; ++sc) {
             float16v s;
             const float16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            union VF {
-                half8 v;
-                h4_t h[2];
-            };
-            VF vf[2 * C::DT];
-            auto rdv = [&](int idx) __attribute__((always_inline)) {      // V^T fragment idx = k2 * DT + dt of this half tile
-                const int kk = 2 * sc + idx / C::DT, dt = idx % C::DT;
-                const uint8_t* vp = vt_ + (16 * kk) * VRB + dt * 64;
-                vf[idx].h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4_t*)(vp));
-                vf[idx].h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4_t*)(vp + 8 * VRB));
-            };
+            AttnVF vf[2 * C::DT];
+            half8 kf[C::KS];
             // fragment reads run PF ahead of the MFMAs in ONE sequence (K fragments 0..KS-1, then the V^T fragments: the
             // first of those fly under the softmax); sched_barrier pins the order - left alone the scheduler sinks every
             // read next to its MFMA and exposes one LDS latency per MFMA
-            half8 kf[C::KS];
-            auto rdc = [&](int n) __attribute__((always_inline)) {
-                if (n < C::KS) {
-                    const int d0 = n * 16 + 8 * g;
-                    kf[n] = *reinterpret_cast<const half8*>(kt_ + sc * 32 * C::KROW + (d0 < D ? d0 : 0) * 2);
-                } else if (n - C::KS < 2 * C::DT) rdv(n - C::KS);
-            };
+            auto rdc = [&](int n) __attribute__((always_inline)) { attn_read_frag<D, VRB>(n, kt_ + sc * 32 * C::KROW, vt_ + sc * 32 * VRB, g, kf, vf); };
 #pragma unroll
             for (int n = 0; n < PF; ++n) rdc(n);
             __builtin_amdgcn_sched_barrier(0);
@@ -1780,78 +1445,20 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A
             // issue (~100 cycles per piece) sits in the waits for those chains' results
             // (in two instalments: A/B on one box 112.0-115.5 vs 115.3-118.0 us at 16 x 1024, 112 vs 122 us at 1 x 4096
             //  against all pieces behind the first chain; at the top of the tile, before any MFMA: 122.7 us)
-            if (sc < 2 && !(ABLD & 1) && kt + 1 < nkt) issue(kt + 1, sc);
-            if constexpr (RAG) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (kt * KT + sc * 32 + (r & 3) + 8 * (r >> 2) + 4 * g >= kv_len) s[r] = -INFINITY;
-            }
-            float mloc;
-            {
-                float mx;   // v_max3 chain in asm: fmaxf() would canonicalise every MFMA result first (one extra v_max each)
-                // The hazard recognizer does not look at asm operands: an asm VALU read of an accumulator the matrix core
-                // is still writing gets NO wait states and sees the previous contents (with one k-step, D = 16: the last
-                // tile's exponentials - a garbage running max, rows of zeros / NaN).  So the first read of the fresh
-                // accumulator is a compiler-visible VALU instruction (x + 0.0f is not foldable); the asm chain depends on it.
-                const float s0 = s[0] + 0.0f;
-                // ONE statement for the whole chain: between two dependent asm statements the compiler pads a wait state
-                // (an asm producer may write with dst_sel: DstSelForwardingHazard) - 8 s_nop per 32-key half otherwise
-                asm("v_max3_f32 %0, %1, %2, %3\n\tv_max3_f32 %0, %0, %4, %5\n\tv_max3_f32 %0, %0, %6, %7\n\t"
-                    "v_max3_f32 %0, %0, %8, %9\n\tv_max3_f32 %0, %0, %10, %11\n\tv_max3_f32 %0, %0, %12, %13\n\t"
-                    "v_max3_f32 %0, %0, %14, %15\n\tv_max_f32 %0, %0, %16"
-                    : "=&v"(mx)
-                    : "v"(s0), "v"(s[1]), "v"(s[2]), "v"(s[3]), "v"(s[4]), "v"(s[5]), "v"(s[6]), "v"(s[7]), "v"(s[8]), "v"(s[9]),
-                      "v"(s[10]), "v"(s[11]), "v"(s[12]), "v"(s[13]), "v"(s[14]), "v"(s[15]));
-                const unsigned mb = __builtin_bit_cast(unsigned, mx);
-                const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-                asm("v_max_f32 %0, %1, %2" : "=v"(mloc) : "v"(sw[0]), "v"(sw[1]));
-            }
-            if (__any((mloc - m_run) * a.c > 8.0f)) {
-                const float m_new = fmaxf(m_run, mloc);
-                const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * a.c);
-#pragma unroll
-                for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) oacc[dt][r] *= alpha;
-                m_run = m_new;
-            }
-            const float mc = ((m_run == -INFINITY) ? 0.f : m_run) * a.c;
+            if (sc < 2 && kt + 1 < nkt) issue(kt + 1, sc);
+            if constexpr (RAG) attn_mask(s, kt * KT + sc * 32, g, kv_len);
+            const float mc = attn_lazy_rescale(attn_rowmax_max3(s), m_run, oacc, a.c);
             half8 pf[2];
-            {
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    // two plain v_fma_f32, NOT one v_pk_fma_f32: beside the partner waves' MFMAs the packed form costs more than
-                    // the issue slot it saves (and a forwarding wait state in front of v_exp) - round 6, one box, alternating x 3:
-                    // 115.4 -> 111.0 us at 16 x 1024 x 1024, 187.3 -> 177.6 us at 2 x 4096 x 4096 (profiles/r06_experiments.md 1)
-                    const float t0 = __builtin_fmaf(s[r], a.c, -mc), t1 = __builtin_fmaf(s[r + 1], a.c, -mc);
-                    pf[r >> 3][r & 7] = (half_t)__builtin_amdgcn_exp2f(t0);
-                    pf[r >> 3][(r & 7) + 1] = (half_t)__builtin_amdgcn_exp2f(t1);
-                }
-            }
-            if constexpr ((ABLD & 16) != 0) {
-                // profiling only: the 8 cross-lane moves per 32-key half (16 per tile) that a second lane layout of P^T would
-                // need for 16 x 16 x 32 MFMAs over dims 64..79: DPP moves of the P registers, results wrong
-                int4v* pw = reinterpret_cast<int4v*>(pf);
-#pragma unroll
-                for (int w2 = 0; w2 < 2; ++w2)
-#pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2)
-                        pw[w2][e2] = __builtin_amdgcn_update_dpp(pw[w2][e2], pw[w2][e2], 0x141 /* row_half_mirror */, 0xf, 0xf, false);
-            }
+            attn_exp_pack(s, a.c, mc, pf);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int idx = 0; idx < 2 * C::DT; ++idx) {
                 rdc(C::KS + idx + PF);
-                const int dt = idx % C::DT;
-                // ABLD & 8 (profiling only, results wrong): one of the two MFMAs of the LAST 32-dim tile dropped per half -
-                // the 64 matrix-pipe cycles per 64-key tile that 16 x 16 x 32 MFMAs over dims 64..79 would save
-                if (!((ABLD & 8) != 0 && dt == C::DT - 1 && idx / C::DT == 1))
-                    oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[idx].v, pf[idx / C::DT], oacc[dt], 0, 0, 0);
+                oacc[idx % C::DT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[idx].v, pf[idx / C::DT], oacc[idx % C::DT], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (!(ABLD & 4)) wg_barrier();
+        attn_wg_barrier();
     };
     {
         const int nfull = kv_len / KT;
@@ -1859,33 +1466,16 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A
         for (; kt < nfull; ++kt) tile(std::false_type{}, kt);
         if (kt < nkt) tile(std::true_type{}, kt);
     }
-    constexpr int LD_T = D / 32, LD_R = D % 32;
-    constexpr int LD_G = (LD_R >> 2) & 1, LD_REG = (LD_R & 3) + 4 * (LD_R >> 3);
-    float l_run = oacc[LD_T][LD_REG];
-    l_run = __shfl(l_run, l31 + 32 * LD_G);
-    const float inv = l_run > 0.f ? __fdiv_rn(1.0f, l_run) : 0.f;
+    const float inv = attn_inv_row_sum<D>(oacc, l31);
     half_t* orow = a.o + (long)seq * a.o_seq_stride + (long)(q_ok ? qi : a.Lq - 1) * a.o_tok_stride + h * D;
-    if constexpr (D % 8 == 0 && D >= 16) attn_store_rows<D, C::DT>(oacc, inv, orow, g, q_ok);   // 16-byte stores (round 6: 9 -> 5 per lane at D = 72)
-    else if (q_ok) {
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int d = dt * 32 + 8 * rg + 4 * g;
-                if (d < D) {
-                    half4 ov;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ov[e] = (half_t)(oacc[dt][rg * 4 + e] * inv);
-                    *reinterpret_cast<half4*>(orow + d) = ov;
-                }
-            }
-    }
+    if constexpr (D % 8 == 0 && D >= 16) attn_store_rows<D>(oacc, inv, orow, g, q_ok);
+    else if (q_ok) attn_store_rows_h4<D>(oacc, inv, orow, g);
 }
 
 template <int D, int NW = 8, int KT = 64>
 static int launch_attn32d(const AttnArgs& a, hipStream_t st) {
     constexpr int LDS = 2 * (KT / 64) * Att8Cfg<D, 8>::KTILE + 2 * KT * 192;
-    constexpr auto k = attn_fwd32d_kernel<D, 0, NW, KT>;
+    constexpr auto k = attn_fwd32d_kernel<D, NW, KT>;
     const int nqt = (a.Lq + 32 * NW - 1) / (32 * NW), G = a.n_seq * a.H;
     if (const int rc = vq_prepare_kernel<k>(LDS)) return rc;
     hipLaunchKernelGGL(k, dim3(8 * ((G + 7) / 8) * nqt), dim3(64 * NW), LDS, st, a);
@@ -1903,12 +1493,9 @@ template <int D, int NW = 8, int KT = 64>
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
     static_assert(KT % 64 == 0, "key tile in 64-row DMA units");
     constexpr int NQ = 2;
-    constexpr int KTB = (KT / 64) * Att8Cfg<D, 8>::KTILE;
     using C = Att8Cfg<D, NW>;
+    constexpr int KTB = (KT / 64) * C::KTILE;
     constexpr int VRB = 192, VT = KT * VRB;
-    constexpr int KSL = C::KROW / 16, VSL = VRB / 16;
-    constexpr int NKI = KSL * (KT / 64), NVI = VSL * (KT / 64);
-    constexpr int NI = NKI + NVI, IPW = (NI + NW - 1) / NW;
     constexpr int PF = 2;
     static_assert(D * 2 + 2 <= VRB && C::DT * 64 <= VRB, "dims + ones column inside a row; every 32-dim tile readable");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1916,20 +1503,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31;
     int qt, h, seq;
-    {
-        const int nqt = (a.Lq + 32 * NQ * NW - 1) / (32 * NQ * NW);
-        const int G = a.n_seq * a.H;
-        const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-        const int q8 = G / 8, r8 = G % 8;
-        const int gbase = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-        const int gcount = xcd < r8 ? q8 + 1 : q8;
-        const int pl = idx / nqt;
-        if (pl >= gcount) return;
-        const int pair = gbase + pl;
-        qt = idx - pl * nqt;
-        seq = pair / a.H;
-        h = pair - seq * a.H;
-    }
+    if (!attn_xcd_map(a, 32 * NQ * NW, qt, h, seq)) return;
     const int kv_len = a.Lk;
     const half_t* kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
     const half_t* vbase = a.v + (long)seq * a.kv_seq_stride + h * D;
@@ -1943,73 +1517,27 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
         qi[nq] = qt * (32 * NQ * NW) + wave * (32 * NQ) + nq * 32 + l31;
         q_ok[nq] = qi[nq] < a.Lq;
         m_run[nq] = -INFINITY;
-        const half_t* qrow = a.q + (long)seq * a.q_seq_stride + (long)(q_ok[nq] ? qi[nq] : a.Lq - 1) * a.q_tok_stride + h * D;
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) {
-            const int d0 = ks * 16 + 8 * g;
-            if (d0 < D) qf[nq][ks] = *reinterpret_cast<const half8*>(qrow + d0);
-            else
-#pragma unroll
-                for (int e = 0; e < 8; ++e) qf[nq][ks][e] = (half_t)0.f;
-        }
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[nq][dt][r] = 0.f;
+        attn_q_frags<D>(a.q + (long)seq * a.q_seq_stride + (long)(q_ok[nq] ? qi[nq] : a.Lq - 1) * a.q_tok_stride + h * D, g, qf[nq]);
+        attn_zero(oacc[nq]);
     }
     const int nkt = (kv_len + KT - 1) / KT;
     const int strideB = (int)a.kv_tok_stride * 2;
     const unsigned nrec = kv_len > 0 ? (unsigned)(kv_len - 1) * (unsigned)strideB + D * 2 : 0u;
-    bool ok[IPW];
-    int voff[IPW];
-#pragma unroll
-    for (int i = 0; i < IPW; ++i) {
-        const int j = wave + NW * i;                       // wave-uniform instruction index: K tile first, then V
-        const bool isk = j < NKI;
-        const int slot = (isk ? j : j - NKI) * 64 + lane;
-        const int row = isk ? slot / KSL : slot / VSL;
-        const int piece = slot - row * (isk ? KSL : VSL);
-        ok[i] = j < NI && piece < C::CHD;
-        voff[i] = row * strideB + piece * 16;
-    }
-    auto issue = [&](int kt, int part = -1) __attribute__((always_inline)) {   // part 0: round i == 0, 1: the others, -1: all
-        const unsigned t0 = (unsigned)kt * (unsigned)KT * (unsigned)strideB;
-        const int buf = kt & 1;
-#pragma unroll
-        for (int i = 0; i < IPW; ++i) {
-            const int j = wave + NW * i;
-            if (j < NI && (part < 0 || (part == 0) == (i == 0))) {
-                const bool isk = j < NKI;
-                const uint8_t* b = reinterpret_cast<const uint8_t*>(isk ? kbase : vbase) + t0;
-                const unsigned long ba = (unsigned long)b;
-                const int4v rs = {(int)__builtin_amdgcn_readfirstlane((unsigned)ba),
-                                  (int)__builtin_amdgcn_readfirstlane((unsigned)(ba >> 32) & 0xffffu),
-                                  (int)__builtin_amdgcn_readfirstlane(nrec - t0), 0x00020000};
-                const unsigned dst = __builtin_amdgcn_readfirstlane(
-                    (unsigned)(size_t)(__attribute__((address_space(3))) uint8_t*)smem +
-                    (isk ? buf * KTB + j * 1024 : 2 * KTB + buf * VT + (j - NKI) * 1024));
-                if (ok[i])     // (asm, M0 and hazards: see attn_fwd32d_kernel)
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(dst), "v"(voff[i]), "s"(rs)
-                                 : "memory", "m0");
-            }
-        }
+    AttnKvDma<D, NW, KT, C::KROW, VRB> dma;
+    dma.init(wave, lane, strideB);
+    const unsigned lds0 = attn_lds_addr(smem);
+    auto issue = [&](int kt, int part = -1) __attribute__((always_inline)) {   // tile kt -> image pair kt & 1
+        dma.issue(kbase, vbase, (unsigned)kt * (unsigned)KT * (unsigned)strideB, nrec, lds0 + (kt & 1) * KTB, lds0 + 2 * KTB + (kt & 1) * VT,
+                  wave, part);
     };
-    auto wg_barrier = [&]() __attribute__((always_inline)) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    for (int i = tid; i < 2 * KT * 3; i += 64 * NW) {   // pad columns of both V images: column D = 1.0, the rest 0
-        const int r = i / 3, ch = i % 3;
-        *reinterpret_cast<int4v*>(smem + 2 * KTB + r * VRB + D * 2 + ch * 16) = int4v{ch == 0 ? 0x00003c00 : 0, 0, 0, 0};
-    }
+    attn_fill_pad<D, VRB>(smem + 2 * KTB, 2 * KT, tid, 64 * NW);   // both V images (contiguous)
     if (nkt > 0) issue(0);
 #pragma unroll
     for (int nq = 0; nq < NQ; ++nq)
 #pragma unroll
         for (int ks = 0; ks < C::KS; ++ks) asm volatile("" ::"v"(qf[nq][ks]));   // the compiler's wait for the Q loads goes HERE
-    wg_barrier();
-    const int vtr0 = (4 * g + ((lane & 15) >> 2)) * VRB + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+    attn_wg_barrier();
+    const int vtr0 = attn_vtr0<VRB>(lane, g);
 
     auto tile = [&](auto rag_tag, const int kt) __attribute__((always_inline)) {
         constexpr bool RAG = decltype(rag_tag)::value;
@@ -2019,24 +1547,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
         for (int sc = 0; sc < KT / 32; ++sc) {
             float16v s[NQ];
             const float16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            union VF {
-                half8 v;
-                h4_t h[2];
-            };
-            VF vf[2 * C::DT];
-            auto rdv = [&](int idx) __attribute__((always_inline)) {      // V^T fragment idx = k2 * DT + dt of this half tile
-                const int kk = 2 * sc + idx / C::DT, dt = idx % C::DT;
-                const uint8_t* vp = vt_ + (16 * kk) * VRB + dt * 64;
-                vf[idx].h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4_t*)(vp));
-                vf[idx].h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4_t*)(vp + 8 * VRB));
-            };
+            AttnVF vf[2 * C::DT];
             half8 kf[C::KS];
-            auto rdc = [&](int n) __attribute__((always_inline)) {
-                if (n < C::KS) {
-                    const int d0 = n * 16 + 8 * g;
-                    kf[n] = *reinterpret_cast<const half8*>(kt_ + sc * 32 * C::KROW + (d0 < D ? d0 : 0) * 2);
-                } else if (n - C::KS < 2 * C::DT) rdv(n - C::KS);
-            };
+            auto rdc = [&](int n) __attribute__((always_inline)) { attn_read_frag<D, VRB>(n, kt_ + sc * 32 * C::KROW, vt_ + sc * 32 * VRB, g, kf, vf); };
 #pragma unroll
             for (int n = 0; n < PF; ++n) rdc(n);
             __builtin_amdgcn_sched_barrier(0);
@@ -2053,6 +1566,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
             float mc[NQ];
             // decide(nq): row maxima of block nq, the lazy rescale of its O (a branch), the exponent offset.  Both blocks
             // decide FIRST, so that what remains - expo(nq): 16 fma + 16 v_exp + 8 cvt, straight-line - can sit between MFMAs
+            // (The mask, attn_rowmax_max3's chain, the lazy rescale and exp-and-pack of attn_tile.h, kept written out in this
+            //  one kernel: on the helpers it needs 211 VGPRs instead of 208 and 2 x 4096 x 4096 tokens took 174.7-176.6 us
+            //  against the parent's 171.2-171.9 us; this form is inside the parent's band - profiles/refactor_attention_isa.md)
             auto decide = [&](int nq) __attribute__((always_inline)) {
                 if constexpr (RAG) {
 #pragma unroll
@@ -2061,7 +1577,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
                 }
                 float mloc;
                 {
-                    float mx;   // (asm chain and the compiler-visible first read: see attn_fwd32d_kernel)
+                    float mx;   // (asm chain and the compiler-visible first read: see attn_rowmax_max3)
                     const float s0 = s[nq][0] + 0.0f;
                     asm("v_max3_f32 %0, %1, %2, %3\n\tv_max3_f32 %0, %0, %4, %5\n\tv_max3_f32 %0, %0, %6, %7\n\t"
                         "v_max3_f32 %0, %0, %8, %9\n\tv_max3_f32 %0, %0, %10, %11\n\tv_max3_f32 %0, %0, %12, %13\n\t"
@@ -2088,7 +1604,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
             };
             auto expo = [&](int nq) __attribute__((always_inline)) {
 #pragma unroll
-                for (int r = 0; r < 16; r += 2) {                     // plain v_fma_f32 (see attn_fwd32d_kernel)
+                for (int r = 0; r < 16; r += 2) {                     // plain v_fma_f32 (see attn_exp_pack)
                     const float t0 = __builtin_fmaf(s[nq][r], a.c, -mc[nq]), t1 = __builtin_fmaf(s[nq][r + 1], a.c, -mc[nq]);
                     pf[nq][r >> 3][r & 7] = (half_t)__builtin_amdgcn_exp2f(t0);
                     pf[nq][r >> 3][(r & 7) + 1] = (half_t)__builtin_amdgcn_exp2f(t1);
@@ -2111,7 +1627,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
                 oacc[1][idx % C::DT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[idx].v, pf[1][idx / C::DT], oacc[1][idx % C::DT], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-        wg_barrier();
+        attn_wg_barrier();
     };
     {
         const int nfull = kv_len / KT;
@@ -2119,16 +1635,10 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
         for (; kt < nfull; ++kt) tile(std::false_type{}, kt);
         if (kt < nkt) tile(std::true_type{}, kt);
     }
-    constexpr int LD_T = D / 32, LD_R = D % 32;
-    constexpr int LD_G = (LD_R >> 2) & 1, LD_REG = (LD_R & 3) + 4 * (LD_R >> 3);
 #pragma unroll
     for (int nq = 0; nq < NQ; ++nq) {
-        float l_run = oacc[nq][LD_T][LD_REG];
-        l_run = __shfl(l_run, l31 + 32 * LD_G);
-        const float inv = l_run > 0.f ? __fdiv_rn(1.0f, l_run) : 0.f;
         half_t* orow = a.o + (long)seq * a.o_seq_stride + (long)(q_ok[nq] ? qi[nq] : a.Lq - 1) * a.o_tok_stride + h * D;
-        static_assert(D % 8 == 0 && D >= 16, "16-byte store epilogue");
-        attn_store_rows<D, C::DT>(oacc[nq], inv, orow, g, q_ok[nq]);
+        attn_store_rows<D>(oacc[nq], attn_inv_row_sum<D>(oacc[nq], l31), orow, g, q_ok[nq]);
     }
 }
 
@@ -2162,8 +1672,6 @@ template <int D, int NW = 8, int NT = 2>
 __global__ __launch_bounds__(64 * NW, NT == 2 ? 32 / NW : 16 / NW) void attn_cross32_kernel(AttnArgs a, int nslice) {
     using C = Att8Cfg<D, NW>;
     constexpr int KT = 64, KTB = C::KTILE, VRB = 192, VT = KT * VRB;
-    constexpr int KSL = C::KROW / 16, VSL = VRB / 16;       // 16-byte slots per row
-    constexpr int NKI = KSL, NVI = VSL, NI = NKI + NVI, IPW = (NI + NW - 1) / NW;   // wave-instructions per 64-key tile
     static_assert(D * 2 + 2 <= VRB && C::DT * 64 <= VRB, "dims + ones column inside a row; every 32-dim tile readable");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -2176,53 +1684,22 @@ __global__ __launch_bounds__(64 * NW, NT == 2 ? 32 / NW : 16 / NW) void attn_cro
     const int slice = (idx / G) * 8 + xcd, pair = idx % G;
     if (slice >= nslice) return;
     const int seq = pair / a.H, h = pair - seq * a.H;
-    int kv_len = a.Lk;
     const half_t* kbase;
     const half_t* vbase;
-    if (a.kv_off) {
-        const int o0 = a.kv_off[seq];
-        kv_len = a.kv_off[seq + 1] - o0;
-        kbase = a.k + (long)o0 * a.kv_tok_stride + h * D;
-        vbase = a.v + (long)o0 * a.kv_tok_stride + h * D;
-    } else {
-        kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
-        vbase = a.v + (long)seq * a.kv_seq_stride + h * D;
-    }
-    kv_len = kv_len < NT * KT ? kv_len : NT * KT;          // host guarantees <= NT * 64
-    const int nkt = (kv_len + KT - 1) / KT;
+    const int kv_len = attn_kv_base<D>(a, seq, h, kbase, vbase, NT * KT);   // host guarantees <= NT * 64
     const int strideB = (int)a.kv_tok_stride * 2;
     const unsigned nrec = kv_len > 0 ? (unsigned)(kv_len - 1) * (unsigned)strideB + D * 2 : 0u;
-    // ---- prologue: both tile images by LDS-DMA (rows past the last key are outside num_records: zeros)
+    // ---- prologue: every tile image by LDS-DMA (rows past the last key are outside num_records: zeros)
+    {
+        AttnKvDma<D, NW, KT, C::KROW, VRB> dma;
+        dma.init(wave, lane, strideB);
+        const unsigned lds0 = attn_lds_addr(smem);
 #pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-        const unsigned t0 = (unsigned)kt * (unsigned)KT * (unsigned)strideB;
-#pragma unroll
-        for (int i = 0; i < IPW; ++i) {
-            const int j = wave + NW * i;                   // wave-uniform instruction index: K tile first, then V
-            if (j < NI) {
-                const bool isk = j < NKI;
-                const int slot = (isk ? j : j - NKI) * 64 + lane;
-                const int row = isk ? slot / KSL : slot / VSL;
-                const int piece = slot - row * (isk ? KSL : VSL);
-                const int voff = row * strideB + piece * 16;
-                const uint8_t* b = reinterpret_cast<const uint8_t*>(isk ? kbase : vbase) + t0;
-                const unsigned long ba = (unsigned long)b;
-                const int4v rs = {(int)__builtin_amdgcn_readfirstlane((unsigned)ba),
-                                  (int)__builtin_amdgcn_readfirstlane((unsigned)(ba >> 32) & 0xffffu),
-                                  (int)__builtin_amdgcn_readfirstlane(nrec > t0 ? nrec - t0 : 0u), 0x00020000};
-                const unsigned dst = __builtin_amdgcn_readfirstlane(
-                    (unsigned)(size_t)(__attribute__((address_space(3))) uint8_t*)smem +
-                    (isk ? kt * KTB + j * 1024 : NT * KTB + kt * VT + (j - NKI) * 1024));
-                if (piece < C::CHD)
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(dst), "v"(voff), "s"(rs)
-                                 : "memory", "m0");
-            }
-        }
+        for (int kt = 0; kt < NT; ++kt)
+            dma.template issue<true>(kbase, vbase, (unsigned)kt * (unsigned)KT * (unsigned)strideB, nrec, lds0 + kt * KTB,
+                                     lds0 + NT * KTB + kt * VT, wave);
     }
-    for (int i = tid; i < NT * KT * 3; i += 64 * NW) {   // pad columns of every V image: column D = 1.0, the rest 0
-        const int r = i / 3, ch = i % 3;
-        *reinterpret_cast<int4v*>(smem + NT * KTB + r * VRB + D * 2 + ch * 16) = int4v{ch == 0 ? 0x00003c00 : 0, 0, 0, 0};
-    }
+    attn_fill_pad<D, VRB>(smem + NT * KTB, NT * KT, tid, 64 * NW);   // every V image (contiguous)
     const int nqt = (a.Lq + 32 * NW - 1) / (32 * NW);
     const half_t* qseq = a.q + (long)seq * a.q_seq_stride + h * D;
     half_t* oseq = a.o + (long)seq * a.o_seq_stride + h * D;
@@ -2232,48 +1709,29 @@ __global__ __launch_bounds__(64 * NW, NT == 2 ? 32 / NW : 16 / NW) void attn_cro
     // operand fragments are then ds_read_b128 of that image (conflict-free: odd number of slots per row).
     constexpr int QSL = C::KROW / 16, QW = 32 * C::KROW, NQI = (32 * QSL + 63) / 64;
     uint8_t* qreg = smem + NT * KTB + NT * VT + wave * QW;
-    const unsigned qdst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) uint8_t*)qreg);
-    int qvoff[NQI];
-    bool qok[NQI];
+    const unsigned qdst = __builtin_amdgcn_readfirstlane(attn_lds_addr(qreg));
+    AttnDmaSlot qsl[NQI];
 #pragma unroll
-    for (int i = 0; i < NQI; ++i) {
-        const int slot = i * 64 + lane, row = slot / QSL, piece = slot - row * QSL;
-        qok[i] = row < 32 && piece < C::CHD;
-        qvoff[i] = row * (int)a.q_tok_stride * 2 + piece * 16;
-    }
+    for (int i = 0; i < NQI; ++i) qsl[i] = attn_dma_slot<QSL, C::CHD, 32>(i, lane, (int)a.q_tok_stride * 2);
     auto issue_q = [&](int qt) __attribute__((always_inline)) {
         int q0 = qt * (32 * NW) + wave * 32;
         const int last = a.Lq - 1;
         const int nrows = q0 > last ? 0 : (last - q0 + 1 < 32 ? last - q0 + 1 : 32);
         q0 = q0 > last ? last : q0;
-        const unsigned long ba = (unsigned long)(qseq + (long)q0 * a.q_tok_stride);
         // rows past the last query are outside num_records: they land as zeros
         const unsigned nr = nrows > 0 ? (unsigned)(nrows - 1) * (unsigned)a.q_tok_stride * 2u + D * 2 : 0u;
-        const int4v rs = {(int)__builtin_amdgcn_readfirstlane((unsigned)ba),
-                          (int)__builtin_amdgcn_readfirstlane((unsigned)(ba >> 32) & 0xffffu),
-                          (int)__builtin_amdgcn_readfirstlane(nr), 0x00020000};
 #pragma unroll
-        for (int i = 0; i < NQI; ++i) {
-            const unsigned dst = qdst + i * 1024;
-            if (qok[i])
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(dst), "v"(qvoff[i]), "s"(rs)
-                             : "memory", "m0");
-        }
+        for (int i = 0; i < NQI; ++i) attn_dma_instr(qseq + (long)q0 * a.q_tok_stride, nr, qdst + i * 1024, qsl[i]);
     };
     int qt = slice;
     if (qt < nqt) issue_q(qt);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // the K / V images (and the first Q tile) have landed
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    attn_wg_barrier();                                     // the K / V images (and the first Q tile) have landed
     const uint8_t* q_l = qreg + l31 * C::KROW;
     int stores_behind = 0;                                 // store instructions issued after the Q DMA in flight (wave-uniform)
-    constexpr int NST = (D / 8 + 1) / 2;                   // store instructions per tile (see the epilogue)
-    const int vtr0 = (4 * g + ((lane & 15) >> 2)) * VRB + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
-    constexpr int LD_T = D / 32, LD_R = D % 32;
-    constexpr int LD_G = (LD_R >> 2) & 1, LD_REG = (LD_R & 3) + 4 * (LD_R >> 3);
+    constexpr int NST = (D / 8 + 1) / 2;                   // store instructions per tile (see attn_store_rows)
     const int nhalf = (kv_len + 31) / 32;                  // 32-key half tiles that hold keys (wave-uniform, 1 .. 2 NT)
     const uint8_t* k_l = smem + l31 * C::KROW;
-    const uint8_t* v_l = smem + NT * KTB + vtr0;
+    const uint8_t* v_l = smem + NT * KTB + attn_vtr0<VRB>(lane, g);
 
     for (; qt < nqt; qt += nslice) {
         const int qnext = qt + nslice;
@@ -2282,20 +1740,11 @@ __global__ __launch_bounds__(64 * NW, NT == 2 ? 32 / NW : 16 / NW) void attn_cro
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         half8 qf[C::KS];
 #pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) {
-            const int d0 = ks * 16 + 8 * g;
-            qf[ks] = *reinterpret_cast<const half8*>(q_l + (d0 < D ? d0 : 0) * 2);
-            if (d0 >= D)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) qf[ks][e] = (half_t)0.f;
-        }
+        for (int ks = 0; ks < C::KS; ++ks) qf[ks] = attn_frag<D>(q_l, ks, g);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // fragments are in registers: the image is free
         if (qnext < nqt) issue_q(qnext);                              // next tile: in flight under this tile's work
         float16v oacc[C::DT];
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
+        attn_zero(oacc);
         float m_run = -INFINITY;
 #pragma nounroll
         for (int hf = 0; hf < nhalf; ++hf) {               // the image rows of half hf: K rows hf * 32.., V rows the same
@@ -2304,82 +1753,23 @@ __global__ __launch_bounds__(64 * NW, NT == 2 ? 32 / NW : 16 / NW) void attn_cro
             {
                 half8 kf[C::KS];
 #pragma unroll
-                for (int ks = 0; ks < C::KS; ++ks) {
-                    const int d0 = ks * 16 + 8 * g;
-                    kf[ks] = *reinterpret_cast<const half8*>(k_l + hf * 32 * C::KROW + (d0 < D ? d0 : 0) * 2);
-                }
+                for (int ks = 0; ks < C::KS; ++ks) kf[ks] = attn_frag<D, false>(k_l + hf * 32 * C::KROW, ks, g);
 #pragma unroll
                 for (int ks = 0; ks < C::KS; ++ks)
                     s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[ks], ks == 0 ? zero16 : s, 0, 0, 0);
             }
-            union VF {
-                half8 v;
-                h4_t h[2];
-            };
-            VF vf[2 * C::DT];                              // V^T fragments: requested here, they fly under the softmax
+            AttnVF vf[2 * C::DT];                          // V^T fragments: requested here, they fly under the softmax
 #pragma unroll
-            for (int idx2 = 0; idx2 < 2 * C::DT; ++idx2) {
-                const int kk = 2 * hf + idx2 / C::DT, dt = idx2 % C::DT;   // 16-key step kk of the (contiguous) V images
-                const uint8_t* vp = v_l + (16 * kk) * VRB + dt * 64;
-                vf[idx2].h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4_t*)(vp));
-                vf[idx2].h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4_t*)(vp + 8 * VRB));
-            }
-            if ((hf + 1) * 32 > kv_len) {                  // wave-uniform: the ragged last half
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (hf * 32 + (r & 3) + 8 * (r >> 2) + 4 * g >= kv_len) s[r] = -INFINITY;
-            }
-            float mloc;
-            {
-                float mx = fmaxf(fmaxf(s[0], s[1]), s[2]);
-#pragma unroll
-                for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s[r]), s[r + 1]);
-                mx = fmaxf(mx, s[15]);
-                const unsigned mb = __builtin_bit_cast(unsigned, mx);
-                const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-                // (the two halves are copied out of the vector FIRST: hipcc of ROCm 7.2 reads element 0 for BOTH operands of
-                //  __builtin_bit_cast(float, sw[i]) written on the vector elements directly - rounds 4-5 shipped this kernel with
-                //  mloc = the maximum over only half of the keys of a 32-key tile: still an exact softmax, the reference point
-                //  just was not the row maximum, so P could exceed the 2^8 the lazy rescale assumes; found in round 6)
-                const unsigned sw0 = sw[0], sw1 = sw[1];
-                mloc = fmaxf(__builtin_bit_cast(float, sw0), __builtin_bit_cast(float, sw1));
-            }
-            if (__any((mloc - m_run) * a.c > 8.0f)) {
-                const float m_new = fmaxf(m_run, mloc);
-                const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * a.c);
-#pragma unroll
-                for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) oacc[dt][r] *= alpha;
-                m_run = m_new;
-            }
-            const float mc = ((m_run == -INFINITY) ? 0.f : m_run) * a.c;
+            for (int idx2 = 0; idx2 < 2 * C::DT; ++idx2) attn_vt_frag<C::DT, VRB>(v_l + hf * 32 * VRB, idx2, vf[idx2]);
+            if ((hf + 1) * 32 > kv_len) attn_mask(s, hf * 32, g, kv_len);   // wave-uniform: the ragged last half
+            const float mc = attn_lazy_rescale(attn_rowmax_swap(s), m_run, oacc, a.c);
             half8 pf[2];
-            {
+            attn_exp_pack(s, a.c, mc, pf);
 #pragma unroll
-                for (int r = 0; r < 16; r += 2) {                    // plain v_fma_f32 as in attn_fwd32d_kernel: 30.0-31.2 vs 31.2-32.4 us (profiles/r06_experiments.md 8)
-#if defined(VQ_CROSS_PKFMA) && VQ_CROSS_PKFMA
-                    const float2v cc2 = {a.c, a.c}, mm2 = {-mc, -mc};
-                    float2v t = {s[r], s[r + 1]};
-                    t = __builtin_elementwise_fma(t, cc2, mm2);      // v_pk_fma_f32 (rounds 4-5; lab builds)
-                    const float t0 = t[0], t1 = t[1];
-#else
-                    const float t0 = __builtin_fmaf(s[r], a.c, -mc), t1 = __builtin_fmaf(s[r + 1], a.c, -mc);
-#endif
-                    pf[r >> 3][r & 7] = (half_t)__builtin_amdgcn_exp2f(t0);
-                    pf[r >> 3][(r & 7) + 1] = (half_t)__builtin_amdgcn_exp2f(t1);
-                }
-            }
-#pragma unroll
-            for (int idx2 = 0; idx2 < 2 * C::DT; ++idx2) {
-                const int dt = idx2 % C::DT;
-                oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[idx2].v, pf[idx2 / C::DT], oacc[dt], 0, 0, 0);
-            }
+            for (int idx2 = 0; idx2 < 2 * C::DT; ++idx2)
+                oacc[idx2 % C::DT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[idx2].v, pf[idx2 / C::DT], oacc[idx2 % C::DT], 0, 0, 0);
         }
-        float l_run = oacc[LD_T][LD_REG];
-        l_run = __shfl(l_run, l31 + 32 * LD_G);
-        const float inv = l_run > 0.f ? __fdiv_rn(1.0f, l_run) : 0.f;
+        const float inv = attn_inv_row_sum<D>(oacc, l31);
         const int qi = qt * (32 * NW) + wave * 32 + l31;
         const bool wave_live = qt * (32 * NW) + wave * 32 < a.Lq;      // wave-uniform
         if (wave_live) {
@@ -2431,19 +1821,9 @@ __global__ __launch_bounds__(512) void attn_cross_reg_kernel(AttnArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane & 15, g4 = lane >> 4;
     const int h = blockIdx.y * 8 + wave, seq = blockIdx.z;
-    int kv_len = a.Lk;
     const half_t* kbase;
     const half_t* vbase;
-    if (a.kv_off) {
-        const int o0 = a.kv_off[seq];
-        kv_len = a.kv_off[seq + 1] - o0;
-        kbase = a.k + (long)o0 * a.kv_tok_stride + h * D;
-        vbase = a.v + (long)o0 * a.kv_tok_stride + h * D;
-    } else {
-        kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
-        vbase = a.v + (long)seq * a.kv_seq_stride + h * D;
-    }
-    kv_len = kv_len < 16 * NKT ? kv_len : 16 * NKT;   // host guarantees <= 128
+    const int kv_len = attn_kv_base<D>(a, seq, h, kbase, vbase, 16 * NKT);   // host guarantees <= 128
     const half8 z8 = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
     const half4 z4 = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
 
@@ -2599,12 +1979,12 @@ static int launch_cross_reg(const AttnArgs& a, hipStream_t st) {
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
-template <int D, int NW, int NQ = 1>
+template <int D, int NW>
 static int launch_attn8(const AttnArgs& a, hipStream_t st) {
     using C = Att8Cfg<D, NW>;
-    constexpr auto k = attn_fwd8_kernel<D, NW, 0, NQ>;
+    constexpr auto k = attn_fwd8_kernel<D, NW>;
     if (const int rc = vq_prepare_kernel<k>(C::LDS)) return rc;
-    const int nqt = (a.Lq + 32 * NW * NQ - 1) / (32 * NW * NQ), G = a.n_seq * a.H;
+    const int nqt = (a.Lq + 32 * NW - 1) / (32 * NW), G = a.n_seq * a.H;
     dim3 grid(8 * ((G + 7) / 8) * nqt);
     hipLaunchKernelGGL(k, grid, dim3(64 * NW), C::LDS, st, a);
     return vq_check_launch();
