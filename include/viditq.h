@@ -348,6 +348,35 @@ int vq_attn_temporal_rowquant_static(const void* q, const void* k, const void* v
                                      void* o, int B, int T, int S, int H, int D, long ld_in, long ld_out, int Kp,
                                      int n_bits, float scale, void* stream);
 
+/* Spatial / cross / image attention (vq_attn_fwd) fused with the STATIC (calibrated, tensor-wise) quantizer of the Linear
+ * that consumes its output - attn.proj and cross_attn.proj of STDiTBlock (opensora/models/layers/blocks.py:151-195,292-310;
+ * stdit.py:104-109,121), PixArt's self-attention proj (PixArt_blocks.py:151-155) -> ActQuantizer.forward after init_done
+ * (base_quantizer.py:129-144) behind the smooth-quant division of quant_layer.py:136-140.  The arguments are those of
+ * vq_attn_fwd plus the quantizer's; the kernel is the static-grid form of the one vq_attn_fwd_route names for the same
+ * arguments: attn_fwd_kernel, attn_fwd32d_kernel, attn_fwd64d_kernel, attn_cross32_kernel (VQ_ATTN_K_FWD, FWD32D, FWD64D,
+ * CROSS32_2..5).  The quantizer is one more epilogue step of that kernel: attention arithmetic and fp16 rounding are its own.
+ * delta, zp: ONE fp32 value each in device memory, read by the kernel (no host synchronisation: graph-capturable); zp
+ * integer-valued.  n_bits 2..8.  No status word (no eps fill on a calibrated grid).  Quantized rows are dense:
+ * row = sequence * Lq + query.  R is zeroed by this call on `stream` before the launch (a small kernel; every head adds
+ * its part of a row's term with an integer atomic): callers do not pre-zero, and R is bit-reproducible.
+ * Contract: o, when set, is bit-identical to vq_attn_fwd with the same arguments; xq [n_seq*Lq, Kp] (codes - 128 at 8
+ * bits, raw codes below; pad columns [H*D, Kp) zero), sx = delta, zx = (int)zp - cx and R = sum(xq) - H*D*zx are
+ * bit-identical to vq_rowquant(..., s, s_rcp, delta_in = delta, zp_in = zp, n_param = 1) of that output.
+ * s / s_rcp: both null, or the consuming Linear's smooth-quant channel scale [H*D] and its reciprocal from
+ * vq_smooth_reciprocal (the division exists in reciprocal form only here).  o: nullable.
+ * VQ_EINVAL: a null required pointer (q, k, v, delta, zp, xq, sx, zx, R); s without s_rcp or the reverse; a non-positive
+ * extent (n_seq, Lq, H, D, Kp; Lk without kv_off).  VQ_ESHAPE: the rules of vq_attn_fwd (strides % 8, q / k / v / o 16-byte
+ * aligned, n_seq, H <= 65535); Kp % 128 != 0, Kp < H*D, D % 4 != 0; xq / s / s_rcp not 16-byte aligned; n_seq*Lq beyond
+ * int32.  VQ_EUNSUP: n_bits outside 2..8; D outside {16, 32, 64, 72}; a route without a static-grid form
+ * (VQ_ATTN_K_FWD8_NW4, VQ_ATTN_K_FWD8_NW8, VQ_ATTN_K_CROSS_REG): the caller keeps vq_attn_fwd + vq_rowquant.  All before
+ * any HIP call or dereference. */
+int vq_attn_fwd_rowquant_static(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
+                                const float* delta, const float* zp, int8_t* xq, float* sx, int32_t* zx, int32_t* R,
+                                void* o, int n_seq, int Lq, int Lk, int H, int D,
+                                long q_seq_stride, long q_tok_stride, long kv_seq_stride, long kv_tok_stride,
+                                long o_seq_stride, long o_tok_stride, const int32_t* kv_off,
+                                int Kp, int n_bits, float scale, void* stream);
+
 /* ---- small fused elementwise helpers ---------------------------------------
  * mod[j, b, c] = table[j, c] + t0[b, j*C + c]  (stdit.py:100-102), fp32 out, chunk-major. */
 int vq_adaln_table(const void* table, const void* t0, float* mod, int B, int J, int C, void* stream);

@@ -49,6 +49,7 @@ SIGNATURES = {
                                        _vp]),
     "vq_attn_temporal_long": (_i, [_vp] * 11 + [_i] * 5 + [_l, _l, _i, _f, _vp]),
     "vq_attn_temporal_rowquant_static": (_i, [_vp] * 12 + [_i] * 5 + [_l, _l, _i, _i, _f, _vp]),
+    "vq_attn_fwd_rowquant_static": (_i, [_vp] * 12 + [_i] * 5 + [_l] * 6 + [_vp, _i, _i, _f, _vp]),
     "vq_adaln_table": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "vq_linear_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _vp]),
     "vq_cfg_ddim_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),

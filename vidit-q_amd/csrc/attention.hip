@@ -59,13 +59,18 @@ struct AttCfg {
 };
 
 // (AttnArgs, the argument block of every vq_attn_fwd kernel, is declared in attn_tile.h: the shared steps take it)
-template <int D>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
+// A = AttnQSArgs: the static-grid form ST (attn_tile.h: attn_quant_rows) - the consuming Linear's calibrated quantizer as one
+// more epilogue step, `o` optional.  The same holds for attn_fwd32d_kernel, attn_fwd64d_kernel and attn_cross32_kernel.
+template <int D, class A = AttnArgs>
+__global__ __launch_bounds__(256) void attn_fwd_kernel(A a) {
+    constexpr bool ST = std::is_same<A, AttnQSArgs>::value;
     using C = AttCfg<D>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 5, l31 = lane & 31;
     const int qt = blockIdx.x, h = blockIdx.y, seq = blockIdx.z;
+    [[maybe_unused]] TqStatic sq;
+    if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
 
     const half_t* kbase;
     const half_t* vbase;
@@ -200,7 +205,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 
     // ---- normalise and store: lane = query, accumulator quads = 4 consecutive dims ----
     const float inv = attn_inv_row_sum<D>(oacc, l31);
-    if (q_ok) attn_store_rows_h4<D>(oacc, inv, a.o + (long)seq * a.o_seq_stride + (long)qi * a.o_tok_stride + h * D, g);
+    if constexpr (ST) {
+        if (a.o && q_ok) attn_store_rows_h4<D>(oacc, inv, a.o + (long)seq * a.o_seq_stride + (long)qi * a.o_tok_stride + h * D, g);
+        attn_quant_rows<D>(oacc, inv, a, sq, seq * a.Lq + qc, h, g, q_ok);
+    } else {
+        if (q_ok) attn_store_rows_h4<D>(oacc, inv, a.o + (long)seq * a.o_seq_stride + (long)qi * a.o_tok_stride + h * D, g);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1375,8 +1385,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd8_kernel(AttnArgs a) 
 // as V^T with ds_read_b64_tr_b16).  The ~15 VGPRs this frees pay for fragment reads that run two ahead of the MFMAs
 // (pinned with sched_barrier).  32 queries per wave, four waves per SIMD.
 // ---------------------------------------------------------------------------
-template <int D, int NW = 8, int KT = 64>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(AttnArgs a) {
+template <int D, int NW = 8, int KT = 64, class A = AttnArgs>
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A a) {
+    constexpr bool ST = std::is_same<A, AttnQSArgs>::value;
     static_assert(KT % 64 == 0, "key tile in 64-row DMA units");
     using C = Att8Cfg<D, NW>;
     constexpr int KTB = (KT / 64) * C::KTILE;               // K tile bytes
@@ -1389,6 +1400,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A
     const int g = lane >> 5, l31 = lane & 31;
     int qt, h, seq;
     if (!attn_xcd_map(a, 32 * NW, qt, h, seq)) return;
+    [[maybe_unused]] TqStatic sq;
+    if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
     const int kv_len = a.Lk;
     const half_t* kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
     const half_t* vbase = a.v + (long)seq * a.kv_seq_stride + h * D;
@@ -1468,14 +1481,19 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A
     }
     const float inv = attn_inv_row_sum<D>(oacc, l31);
     half_t* orow = a.o + (long)seq * a.o_seq_stride + (long)(q_ok ? qi : a.Lq - 1) * a.o_tok_stride + h * D;
-    if constexpr (D % 8 == 0 && D >= 16) attn_store_rows<D>(oacc, inv, orow, g, q_ok);
-    else if (q_ok) attn_store_rows_h4<D>(oacc, inv, orow, g);
+    if constexpr (ST) {
+        if (a.o) attn_store_rows<D>(oacc, inv, orow, g, q_ok);        // kernel-uniform
+        attn_quant_rows<D>(oacc, inv, a, sq, seq * a.Lq + (q_ok ? qi : a.Lq - 1), h, g, q_ok);
+    } else {
+        if constexpr (D % 8 == 0 && D >= 16) attn_store_rows<D>(oacc, inv, orow, g, q_ok);
+        else if (q_ok) attn_store_rows_h4<D>(oacc, inv, orow, g);
+    }
 }
 
-template <int D, int NW = 8, int KT = 64>
-static int launch_attn32d(const AttnArgs& a, hipStream_t st) {
+template <int D, int NW = 8, int KT = 64, class A>
+static int launch_attn32d(const A& a, hipStream_t st) {
     constexpr int LDS = 2 * (KT / 64) * Att8Cfg<D, 8>::KTILE + 2 * KT * 192;
-    constexpr auto k = attn_fwd32d_kernel<D, NW, KT>;
+    constexpr auto k = attn_fwd32d_kernel<D, NW, KT, A>;
     const int nqt = (a.Lq + 32 * NW - 1) / (32 * NW), G = a.n_seq * a.H;
     if (const int rc = vq_prepare_kernel<k>(LDS)) return rc;
     hipLaunchKernelGGL(k, dim3(8 * ((G + 7) / 8) * nqt), dim3(64 * NW), LDS, st, a);
@@ -1489,8 +1507,9 @@ static int launch_attn32d(const AttnArgs& a, hipStream_t st) {
 // v_exp) is issued between block A's P.V MFMAs.  Same tile images, fragment layouts, lazy rescale and ones-column row sums;
 // per query row the arithmetic is that of attn_fwd32d_kernel (bit-identical outputs, tested).
 // ---------------------------------------------------------------------------
-template <int D, int NW = 8, int KT = 64>
-__global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
+template <int D, int NW = 8, int KT = 64, class A = AttnArgs>
+__global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(A a) {
+    constexpr bool ST = std::is_same<A, AttnQSArgs>::value;
     static_assert(KT % 64 == 0, "key tile in 64-row DMA units");
     constexpr int NQ = 2;
     using C = Att8Cfg<D, NW>;
@@ -1504,6 +1523,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
     const int g = lane >> 5, l31 = lane & 31;
     int qt, h, seq;
     if (!attn_xcd_map(a, 32 * NQ * NW, qt, h, seq)) return;
+    [[maybe_unused]] TqStatic sq;
+    if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
     const int kv_len = a.Lk;
     const half_t* kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
     const half_t* vbase = a.v + (long)seq * a.kv_seq_stride + h * D;
@@ -1638,14 +1659,20 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(AttnArgs a) {
 #pragma unroll
     for (int nq = 0; nq < NQ; ++nq) {
         half_t* orow = a.o + (long)seq * a.o_seq_stride + (long)(q_ok[nq] ? qi[nq] : a.Lq - 1) * a.o_tok_stride + h * D;
-        attn_store_rows<D>(oacc[nq], attn_inv_row_sum<D>(oacc[nq], l31), orow, g, q_ok[nq]);
+        if constexpr (ST) {
+            const float inv = attn_inv_row_sum<D>(oacc[nq], l31);
+            if (a.o) attn_store_rows<D>(oacc[nq], inv, orow, g, q_ok[nq]);   // kernel-uniform
+            attn_quant_rows<D>(oacc[nq], inv, a, sq, seq * a.Lq + (q_ok[nq] ? qi[nq] : a.Lq - 1), h, g, q_ok[nq]);
+        } else {
+            attn_store_rows<D>(oacc[nq], attn_inv_row_sum<D>(oacc[nq], l31), orow, g, q_ok[nq]);
+        }
     }
 }
 
-template <int D, int NW = 8, int KT = 64>
-static int launch_attn64d(const AttnArgs& a, hipStream_t st) {
+template <int D, int NW = 8, int KT = 64, class A>
+static int launch_attn64d(const A& a, hipStream_t st) {
     constexpr int LDS = 2 * (KT / 64) * Att8Cfg<D, 8>::KTILE + 2 * KT * 192;
-    constexpr auto k = attn_fwd64d_kernel<D, NW, KT>;
+    constexpr auto k = attn_fwd64d_kernel<D, NW, KT, A>;
     const int nqt = (a.Lq + 64 * NW - 1) / (64 * NW), G = a.n_seq * a.H;
     if (const int rc = vq_prepare_kernel<k>(LDS)) return rc;
     hipLaunchKernelGGL(k, dim3(8 * ((G + 7) / 8) * nqt), dim3(64 * NW), LDS, st, a);
@@ -1668,8 +1695,9 @@ static int launch_attn64d(const AttnArgs& a, hipStream_t st) {
 // NT (round 6): 64-key tile images resident in LDS - 2 for the <= 128 prompt tokens of STDiT / PixArt-alpha (two workgroups per
 // CU), 3 ... 5 for PixArt-Sigma's prompts of up to 300 tokens (one workgroup per CU; the generic kernel those launches took
 // restaged K / V per 128 queries: 25.4 us per launch, 5 % of that step).
-template <int D, int NW = 8, int NT = 2>
-__global__ __launch_bounds__(64 * NW, NT == 2 ? 32 / NW : 16 / NW) void attn_cross32_kernel(AttnArgs a, int nslice) {
+template <int D, int NW = 8, int NT = 2, class A = AttnArgs>
+__global__ __launch_bounds__(64 * NW, NT == 2 ? 32 / NW : 16 / NW) void attn_cross32_kernel(A a, int nslice) {
+    constexpr bool ST = std::is_same<A, AttnQSArgs>::value;
     using C = Att8Cfg<D, NW>;
     constexpr int KT = 64, KTB = C::KTILE, VRB = 192, VT = KT * VRB;
     static_assert(D * 2 + 2 <= VRB && C::DT * 64 <= VRB, "dims + ones column inside a row; every 32-dim tile readable");
@@ -1774,20 +1802,29 @@ __global__ __launch_bounds__(64 * NW, NT == 2 ? 32 / NW : 16 / NW) void attn_cro
         const bool wave_live = qt * (32 * NW) + wave * 32 < a.Lq;      // wave-uniform
         if (wave_live) {
             half_t* orow = oseq + (long)(qi < a.Lq ? qi : a.Lq - 1) * a.o_tok_stride;
-            attn_store_rows<D, C::DT>(oacc, inv, orow, g, qi < a.Lq);   // 16-byte stores (NST of them per lane, + one 8-byte store for an odd group)
-            stores_behind = NST;
+            if constexpr (ST) {
+                // (the stores and loads behind the Q DMA in flight are not a fixed number here: the next tile waits for all)
+                // (the grid is read per tile - one scalar load and a division - not held in registers across the walk)
+                if (a.o) attn_store_rows<D, C::DT>(oacc, inv, orow, g, qi < a.Lq);   // kernel-uniform
+                const TqStatic sq = tq_static(a.delta, a.zp, a.n_bits);
+                attn_quant_rows<D, C::DT>(oacc, inv, a, sq, seq * a.Lq + (qi < a.Lq ? qi : a.Lq - 1), h, g, qi < a.Lq);
+                stores_behind = 0;
+            } else {
+                attn_store_rows<D, C::DT>(oacc, inv, orow, g, qi < a.Lq);   // 16-byte stores (NST of them per lane, + one 8-byte store for an odd group)
+                stores_behind = NST;
+            }
         } else {
             stores_behind = 0;
         }
     }
 }
 
-template <int D, int NT = 2>
-static int launch_cross32(const AttnArgs& a, hipStream_t st) {
+template <int D, int NT = 2, class A>
+static int launch_cross32(const A& a, hipStream_t st) {
     constexpr int NW = 8;
     constexpr int LDS = NT * Att8Cfg<D, 8>::KTILE + NT * 64 * 192 + NW * 32 * Att8Cfg<D, 8>::KROW;
     static_assert(LDS <= 163840, "LDS budget of one CU");
-    constexpr auto k = attn_cross32_kernel<D, NW, NT>;
+    constexpr auto k = attn_cross32_kernel<D, NW, NT, A>;
     int ncu = 0;
     if (const int rc = vq_prepare_kernel<k>(LDS, &ncu)) return rc;
     // NT == 2: two 8-wave workgroups per CU (four waves per SIMD; 1 / 3 / 4 measured slower, round 6); more tile images: one (LDS).
@@ -2019,21 +2056,40 @@ static int attn_route(const AttnArgs& a) {
     return VQ_ATTN_K_FWD;
 }
 
-template <int D>
-static int launch_attn(const AttnArgs& a, hipStream_t st) {
-    switch (attn_route<D>(a)) {
+// R[0, n) = 0 in front of a static-grid launch.  A kernel, not hipMemsetAsync: captured into a graph by the runtime of
+// ROCm 7.2 the memset took effect in no replay (R kept growing from replay to replay; measured, GPU test
+// test_switched_on_forward_replays_from_a_graph replays twice), a kernel node does.
+__global__ void attn_zero_rows_kernel(int32_t* R, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) R[i] = 0;
+}
+
+// A = AttnQSArgs (vq_attn_fwd_rowquant_static): the static-grid form of the route's kernel; the routes without one
+// (attn_fwd8_kernel, attn_cross_reg_kernel) return VQ_EUNSUP before any HIP call, the others zero R first on the same
+// stream (every head adds its part of a row's term - attn_quant_rows).
+template <int D, class A>
+static int launch_attn(const A& a, hipStream_t st) {
+    constexpr bool ST = std::is_same<A, AttnQSArgs>::value;
+    const int route = attn_route<D>(a);
+    if constexpr (ST) {
+        if (route == VQ_ATTN_K_CROSS_REG || route == VQ_ATTN_K_FWD8_NW8 || route == VQ_ATTN_K_FWD8_NW4) return VQ_EUNSUP;
+        const int rows = a.n_seq * a.Lq;
+        hipLaunchKernelGGL(attn_zero_rows_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, a.R, rows);
+        if (const int rc = vq_check_launch()) return rc;
+    }
+    switch (route) {
         case VQ_ATTN_K_CROSS32_2: return launch_cross32<D>(a, st);
         case VQ_ATTN_K_CROSS32_3: if constexpr (D >= 64) return launch_cross32<D, 3>(a, st); break;
         case VQ_ATTN_K_CROSS32_4: if constexpr (D >= 64) return launch_cross32<D, 4>(a, st); break;
         case VQ_ATTN_K_CROSS32_5: if constexpr (D >= 64) return launch_cross32<D, 5>(a, st); break;
-        case VQ_ATTN_K_CROSS_REG: return launch_cross_reg(a, st);
+        case VQ_ATTN_K_CROSS_REG: if constexpr (!ST) return launch_cross_reg(a, st); break;
         case VQ_ATTN_K_FWD64D: return launch_attn64d<D>(a, st);
         case VQ_ATTN_K_FWD32D: return launch_attn32d<D>(a, st);
-        case VQ_ATTN_K_FWD8_NW8: return launch_attn8<D, 8>(a, st);
-        case VQ_ATTN_K_FWD8_NW4: return launch_attn8<D, 4>(a, st);
+        case VQ_ATTN_K_FWD8_NW8: if constexpr (!ST) return launch_attn8<D, 8>(a, st); break;
+        case VQ_ATTN_K_FWD8_NW4: if constexpr (!ST) return launch_attn8<D, 4>(a, st); break;
         case VQ_ATTN_K_FWD: {
             using C = AttCfg<D>;
-            constexpr auto k = attn_fwd_kernel<D>;
+            constexpr auto k = attn_fwd_kernel<D, A>;
             if (const int rc = vq_prepare_kernel<k>(C::LDS)) return rc;
             dim3 grid((a.Lq + 127) / 128, a.H, a.n_seq);
             hipLaunchKernelGGL(k, grid, dim3(256), C::LDS, st, a);
@@ -2045,10 +2101,12 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
 }
 
 // Argument checks of vq_attn_fwd / vq_attn_fwd_route (no dereference, no HIP call): VQ_OK with *a filled, or the error code.
+// o_optional: vq_attn_fwd_rowquant_static, whose fp16 output is a copy for callers that need both.
 static int attn_fwd_args(const void* q, const void* k, const void* v, void* o, int n_seq, int Lq, int Lk, int H,
                          long q_seq_stride, long q_tok_stride, long kv_seq_stride, long kv_tok_stride,
-                         long o_seq_stride, long o_tok_stride, const int32_t* kv_off, float scale, AttnArgs* a) {
-    if (!q || !k || !v || !o) return VQ_EINVAL;
+                         long o_seq_stride, long o_tok_stride, const int32_t* kv_off, float scale, AttnArgs* a,
+                         bool o_optional = false) {
+    if (!q || !k || !v || (!o && !o_optional)) return VQ_EINVAL;
     if (n_seq <= 0 || Lq <= 0 || H <= 0 || (Lk <= 0 && !kv_off)) return VQ_EINVAL;
     if ((q_tok_stride | kv_tok_stride | o_tok_stride | q_seq_stride | kv_seq_stride | o_seq_stride) % 8 != 0)
         return VQ_ESHAPE;  // 16-byte alignment of every row
@@ -2067,6 +2125,33 @@ extern "C" int vq_attn_fwd(const void* q, const void* k, const void* v, void* o,
     const int rc = attn_fwd_args(q, k, v, o, n_seq, Lq, Lk, H, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride,
                                  o_seq_stride, o_tok_stride, kv_off, scale, &a);
     if (rc != VQ_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return vq_dispatch_head_dim(D, [&](auto d) { return launch_attn<d()>(a, st); });
+}
+
+// Spatial / cross attention + the consuming Linear's STATIC (calibrated, tensor-wise) quantizer: the static-grid forms of
+// attn_fwd_kernel, attn_fwd32d_kernel, attn_fwd64d_kernel and attn_cross32_kernel, chosen by the same attn_route.  Every
+// check comes before any HIP call or dereference.
+extern "C" int vq_attn_fwd_rowquant_static(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
+                                           const float* delta, const float* zp, int8_t* xq, float* sx, int32_t* zx,
+                                           int32_t* R, void* o, int n_seq, int Lq, int Lk, int H, int D, long q_seq_stride,
+                                           long q_tok_stride, long kv_seq_stride, long kv_tok_stride, long o_seq_stride,
+                                           long o_tok_stride, const int32_t* kv_off, int Kp, int n_bits, float scale,
+                                           void* stream) {
+    if (!delta || !zp || !xq || !sx || !zx || !R) return VQ_EINVAL;
+    if ((s != nullptr) != (s_rcp != nullptr)) return VQ_EINVAL;     // the division exists in reciprocal form only
+    if (D <= 0 || Kp <= 0) return VQ_EINVAL;
+    AttnQSArgs a{};
+    const int rc = attn_fwd_args(q, k, v, o, n_seq, Lq, Lk, H, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride,
+                                 o_seq_stride, o_tok_stride, kv_off, scale, &a, /*o_optional*/ true);
+    if (rc != VQ_OK) return rc;
+    if (Kp % 128 != 0 || Kp < (long)H * D || D % 4 != 0) return VQ_ESHAPE;
+    // float4 reads of s / s_rcp, 8-byte code stores (16 bytes asked, as everywhere else)
+    if (((uintptr_t)xq | (uintptr_t)s | (uintptr_t)s_rcp) % 16 != 0) return VQ_ESHAPE;
+    if ((long)n_seq * Lq > 0x7fffffffL) return VQ_ESHAPE;            // rows are indexed with 32 bits
+    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    if (D != 72 && D != 64 && D != 32 && D != 16) return VQ_EUNSUP;  // (vq_dispatch_head_dim)
+    a.s = s, a.s_rcp = s_rcp, a.delta = delta, a.zp = zp, a.xq = xq, a.sx = sx, a.zx = zx, a.R = R, a.Kp = Kp, a.n_bits = n_bits;
     hipStream_t st = (hipStream_t)stream;
     return vq_dispatch_head_dim(D, [&](auto d) { return launch_attn<d()>(a, st); });
 }

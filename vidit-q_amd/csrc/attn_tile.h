@@ -8,6 +8,7 @@
 // compiler-quirk notes that belong to it.
 #pragma once
 #include "vq_common.h"
+#include "attn_rowquant.h"
 
 // The argument block of every vq_attn_fwd kernel (filled by attn_fwd_args of attention.hip); it lives here because the
 // geometry steps below take it.
@@ -20,6 +21,21 @@ struct AttnArgs {
     const int32_t* kv_off;
     int n_seq, Lq, Lk, H;
     float c;  // scale * log2(e)
+};
+
+// The static-grid forms (the kernels instantiated on AttnQSArgs; vq_attn_fwd_rowquant_static) add the consuming Linear's
+// calibrated tensor-wise quantizer - its grid one fp32 value each, read by the kernel - the code width and the quantizer's
+// outputs; `o` is optional there.  The plain forms keep their argument block as it was.
+struct AttnQSArgs : AttnArgs {
+    const float* s;                                // nullable [H*D]: smooth-quant channel scale of the consuming Linear
+    const float* s_rcp;                            //                 and its reciprocal (vq_smooth_reciprocal)
+    const float* delta;
+    const float* zp;
+    int8_t* xq;                                    // [n_seq*Lq, Kp] codes, dense rows (row = seq * Lq + query)
+    float* sx;
+    int32_t* zx;
+    int32_t* R;                                    // zero when the kernel starts: every head ADDS its part of a row's term
+    int Kp, n_bits;                                // n_bits 2 .. 8
 };
 
 typedef __fp16 h4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));   // operand type of the LDS transpose read
@@ -350,5 +366,78 @@ __device__ __forceinline__ void attn_store_rows(const float16v (&oacc)[DT], floa
 #pragma unroll
         for (int e = 0; e < 4; ++e) ov[e] = (half_t)(oacc[gl / 4][(gl % 4) * 4 + e] * inv);
         if (row_ok) *reinterpret_cast<half4*>(orow + 8 * gl + 4 * g) = ov;
+    }
+}
+
+// ---- epilogue of the static-grid forms: the consuming Linear's quantizer on the row the steps above store ----------------
+// Codes of the lane's 8-dim groups (dims 8 grp + 4 g .. + 3 of query l31, as attn_store_rows numbers them) on the grid `sq`,
+// from the value those steps store - float(half(oacc * inv)) - divided by the smoothing vector `s` (of this head; null: none)
+// in reciprocal form.  One dword of codes per group; one v_permlane32_swap turns the dwords of two groups into 8
+// consecutive codes per lane (8-byte stores; the odd last group: 4-byte stores).  Every lane of the wave must call this
+// (the swaps are wave-wide); `row_ok` masks the stores only.  Returns the sum of the lane's raw codes (v_sad_u8).
+// (the swap builtin returns a 2-vector: its elements are copied into scalars before they are used - attn_rowquant.h)
+template <int D, int DT, bool SAT8>
+__device__ __forceinline__ uint32_t attn_quant_codes(const float16v (&oacc)[DT], float inv, const float* s, const float* s_rcp,
+                                                     const TqStatic& sq, int8_t* xrow, int g, bool row_ok) {
+    static_assert(D % 8 == 0 && D >= 16, "8-dim groups, 8-byte code stores");
+    constexpr int NG = D / 8;                           // 8-dim groups: dt = grp / 4, rg = grp % 4
+    uint32_t csum = 0;
+    auto codes = [&](int grp) __attribute__((always_inline)) {
+        float x4[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x4[e] = (float)(half_t)(oacc[grp / 4][(grp % 4) * 4 + e] * inv);
+        if (s) {                                        // kernel-uniform
+            const float4v s4 = *reinterpret_cast<const float4v*>(s + 8 * grp + 4 * g);
+            const float4v r4 = *reinterpret_cast<const float4v*>(s_rcp + 8 * grp + 4 * g);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x4[e] = rq_div_rcp(x4[e], s4[e], r4[e]);
+        }
+        return tq_static_codes<SAT8>(x4, sq, csum);
+    };
+#pragma unroll
+    for (int p2 = 0; p2 < NG / 2; ++p2) {
+        const uint32_t A = codes(2 * p2), B = codes(2 * p2 + 1);
+        // swap(A, B): first result = {low lanes: A of g = 0, high lanes: B of g = 0}, second = {A of g = 1, B of g = 1}
+        const auto sw = __builtin_amdgcn_permlane32_swap(A, B, false, false);
+        const uint32_t c0 = sw[0], c1 = sw[1];
+        if (row_ok) *reinterpret_cast<uint2*>(xrow + 16 * p2 + 8 * g) = make_uint2(c0, c1);
+    }
+    if constexpr (NG % 2 == 1) {
+        const uint32_t pk = codes(NG - 1);
+        if (row_ok) *reinterpret_cast<uint32_t*>(xrow + 8 * (NG - 1) + 4 * g) = pk;
+    }
+    return csum;
+}
+// Quantizer outputs of query row `row` (= seq * Lq + query; lane l31 of both half-waves) for head h.  Codes: above.  The
+// row term R = sum(raw codes) - C * (int)zp crosses the heads, which sit in different workgroups: every head adds
+// sum(raw codes of its D dims) - D * (int)zp to R[row] - zeroed by the entry point on the same stream - with ONE relaxed
+// agent-scope integer atomic per row, issued by the g = 0 lanes: 32 consecutive rows = one 128-byte segment per
+// wave-instruction.  Integer adds commute, so R is bit-reproducible.  sx / zx: the head-0 workgroups; the pad columns
+// [H * D, Kp): the last head's.  Rows with !row_ok (clamped duplicates of row Lq - 1) write and add nothing.
+template <int D, int DT>
+__device__ __forceinline__ void attn_quant_rows(const float16v (&oacc)[DT], float inv, const AttnQSArgs& a, const TqStatic& sq,
+                                                int row, int h, int g, bool row_ok) {
+    // (the addresses below are derived HERE: inside attn_cross32_kernel's walk the compiler otherwise computes every one of
+    //  them once in front of the loop and keeps them - ~30 VGPRs of lane pointers, spilled - for its whole length)
+    asm volatile("" : "+v"(g));
+    int8_t* xrow = a.xq + (long)row * a.Kp + h * D;
+    const float* s = a.s ? a.s + h * D : nullptr;
+    const float* s_rcp = a.s ? a.s_rcp + h * D : nullptr;
+    uint32_t csum;
+    if (sq.wd.qmax == 255.0f) csum = attn_quant_codes<D, DT, true>(oacc, inv, s, s_rcp, sq, xrow, g, row_ok);   // kernel-uniform
+    else csum = attn_quant_codes<D, DT, false>(oacc, inv, s, s_rcp, sq, xrow, g, row_ok);
+    const auto sw = __builtin_amdgcn_permlane32_swap(csum, csum, false, false);     // the two halves of the row's dims
+    const int c0 = (int)sw[0], c1 = (int)sw[1];
+    const int izp = (int)sq.g.zp;
+    if (row_ok && g == 0) {
+        __hip_atomic_fetch_add(a.R + row, c0 + c1 - D * izp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (h == 0) {
+            a.sx[row] = sq.g.delta;
+            a.zx[row] = izp - sq.wd.cx;
+        }
+    }
+    if (h == a.H - 1 && row_ok) {                       // pad columns zeroed like the row quantizers do
+        int8_t* prow = a.xq + (long)row * a.Kp + a.H * D;
+        for (int c = 8 * g; c < a.Kp - a.H * D; c += 16) *reinterpret_cast<uint2*>(prow + c) = make_uint2(0u, 0u);
     }
 }

@@ -715,6 +715,73 @@ def attn_temporal_rowquant_static(q, k, v, B, T, S, H, D, ld_in, delta: torch.Te
     return QAct(xq, sx, zx, R, Cc, n_bits)
 
 
+# routes of vq_attn_fwd_route (VQ_ATTN_K_* of include/viditq.h) whose kernel has a static-grid form
+ATTN_FWD_STATIC_ROUTES = (0, 3, 5, 6, 7, 8, 9)     # FWD, FWD32D, FWD64D, CROSS32_2 .. CROSS32_5
+
+
+def attn_fwd_static_ok(n_seq: int, Lq: int, Lk: int, H: int, D: int, q_tok_stride: int, kv_tok_stride: int, Kp: int,
+                       n_bits: int, kv_off: bool = False, q_seq_stride: Optional[int] = None,
+                       kv_seq_stride: Optional[int] = None) -> bool:
+    """Whether vq_attn_fwd_rowquant_static takes this launch: the entry point's refusals (include/viditq.h), mirrored for
+    callers that choose a route BEFORE they launch - a refused shape takes attention and the quantizer separately.  The
+    route is asked of vq_attn_fwd_route (dummy pointers: it makes no HIP call and dereferences nothing)."""
+    if n_seq <= 0 or Lq <= 0 or H <= 0 or D <= 0 or Kp <= 0 or (Lk <= 0 and not kv_off):
+        return False
+    if D not in ATTN_HEAD_DIMS or not 2 <= n_bits <= 8:
+        return False
+    if Kp % 128 != 0 or Kp < H * D or n_seq * Lq > 0x7fffffff:
+        return False
+    q_seq = Lq * q_tok_stride if q_seq_stride is None else q_seq_stride
+    kv_seq = (0 if kv_off else Lk * kv_tok_stride) if kv_seq_stride is None else kv_seq_stride
+    one = 256                                           # non-null, 16-byte aligned
+    route = _L().vq_attn_fwd_route(one, one, one, one, n_seq, Lq, Lk, H, D, q_seq, q_tok_stride, kv_seq, kv_tok_stride,
+                                   Lq * H * D, H * D, one if kv_off else None, 1.0, None)
+    return route in ATTN_FWD_STATIC_ROUTES
+
+
+def attn_fwd_rowquant_static(q, k, v, n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride,
+                             delta: torch.Tensor, zp: torch.Tensor, n_bits: int = 8,
+                             kv_off: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                             o: Optional[torch.Tensor] = None, o_seq_stride: int = 0, o_tok_stride: int = 0,
+                             s: Optional[torch.Tensor] = None, Kp: Optional[int] = None) -> Optional[QAct]:
+    """:func:`attn_fwd` + the consuming Linear's STATIC tensor-wise quantizer - ``delta`` / ``zp``: one fp32 value each,
+    read on the device - at ``n_bits`` (2..8) in one kernel.  Returns what ``rowquant(o.view(1, n_seq*Lq, H*D), n_bits,
+    s=s, delta=delta, zp=zp)`` returns for the fp16 output ``o`` of :func:`attn_fwd` (also written when given, with its
+    strides; bit-identical to attn_fwd's), bit for bit.  ``s``: the consuming Linear's smoothing vector; None is returned
+    (caller runs the two kernels) when its reciprocal form is not available.  A launch the entry point refuses raises:
+    ask :func:`attn_fwd_static_ok` first."""
+    s_rcp = None
+    if s is not None:
+        s_rcp = smooth_rcp(s)
+        if s_rcp is None:
+            return None
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise VQError("%s must be a GPU fp16 tensor" % n)
+    if kv_off is not None:
+        _req(kv_off, torch.int32, "kv_off")
+    delta = _req(delta.reshape(-1).contiguous(), torch.float32, "delta")
+    zp = _req(zp.reshape(-1).contiguous(), torch.float32, "zp")
+    if delta.numel() != 1 or zp.numel() != 1:
+        raise VQError("attn_fwd_rowquant_static: a tensor-wise grid (one delta, one zero point)")
+    if o is not None and (not o.is_cuda or o.dtype != torch.float16):
+        raise VQError("o must be a GPU fp16 tensor")
+    Cc = H * D
+    Kp = pad128(Cc) if Kp is None else Kp
+    rows = n_seq * Lq
+    dev = q.device
+    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
+    sx = torch.empty(rows, dtype=torch.float32, device=dev)
+    zx = torch.empty(rows, dtype=torch.int32, device=dev)
+    R = torch.empty(rows, dtype=torch.int32, device=dev)
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    check(_L().vq_attn_fwd_rowquant_static(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(delta), _p(zp), _p(xq), _p(sx), _p(zx),
+                                           _p(R), _p(o), n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_stride, kv_seq_stride,
+                                           kv_tok_stride, o_seq_stride, o_tok_stride, _p(kv_off), Kp, n_bits, scale,
+                                           _stream()), "vq_attn_fwd_rowquant_static")
+    return QAct(xq, sx, zx, R, Cc, n_bits)
+
+
 # --------------------------------------------------------------------------- misc
 def adaln_table(table: torch.Tensor, t0: torch.Tensor) -> torch.Tensor:
     """mod[J, B, C] fp32 = table[J, C] + t0[B, J*C]  (fp16 inputs); mod[j] is a contiguous [B, C]."""

@@ -62,6 +62,18 @@ class QuantAttention(nn.Module):
                      L * ld, ld, L * ld, ld, L * out.stride(0), out.stride(0), scale=self.scale)
         return out
 
+    def spatial_quantized_static(self, qkv: torch.Tensor, n_seq: int, L: int, delta: torch.Tensor, zp: torch.Tensor,
+                                 n_bits: int, s=None):
+        """:meth:`spatial` + the STATIC tensor-wise quantizer (``delta``, ``zp``: one value each; ``n_bits`` 2..8) of the
+        next Linear (behind its smoothing vector ``s`` when it has one), one kernel; None when that kernel does not apply
+        (then call :meth:`spatial` and the layer's own quantizer)."""
+        C = self.num_heads * self.head_dim
+        ld = qkv.stride(0)
+        if not ops.attn_fwd_static_ok(n_seq, L, L, self.num_heads, self.head_dim, ld, ld, ops.pad128(C), n_bits):
+            return None
+        return ops.attn_fwd_rowquant_static(qkv, qkv[:, C:], qkv[:, 2 * C:], n_seq, L, L, self.num_heads, self.head_dim,
+                                            L * ld, ld, L * ld, ld, delta, zp, n_bits=n_bits, scale=self.scale, s=s)
+
     def temporal(self, qkv: torch.Tensor, B: int, T: int, S: int, out: Optional[torch.Tensor] = None):
         """rows ordered (b, t, s); attention over t for every (b, s, head)."""
         C = self.num_heads * self.head_dim
@@ -123,3 +135,16 @@ class QuantAttention(nn.Module):
         ops.attn_fwd(q, kv, kv[:, C:], out, B, Nq, bound, self.num_heads, self.head_dim, Nq * q.stride(0),
                      q.stride(0), 0, kv.stride(0), Nq * out.stride(0), out.stride(0), kv_off=kv_off, scale=self.scale)
         return out
+
+    def cross_quantized_static(self, q: torch.Tensor, kv: torch.Tensor, kv_off: torch.Tensor, B: int, Nq: int,
+                               delta: torch.Tensor, zp: torch.Tensor, n_bits: int, s=None):
+        """:meth:`cross` + the STATIC tensor-wise quantizer of the next Linear, one kernel; None when that kernel does not
+        apply (then call :meth:`cross` and the layer's own quantizer)."""
+        C = self.num_heads * self.head_dim
+        bound = int(getattr(kv_off, "max_len", 0)) or kv.shape[0]
+        if not ops.attn_fwd_static_ok(B, Nq, bound, self.num_heads, self.head_dim, q.stride(0), kv.stride(0), ops.pad128(C),
+                                      n_bits, kv_off=True):
+            return None
+        return ops.attn_fwd_rowquant_static(q, kv, kv[:, C:], B, Nq, bound, self.num_heads, self.head_dim, Nq * q.stride(0),
+                                            q.stride(0), 0, kv.stride(0), delta, zp, n_bits=n_bits, kv_off=kv_off,
+                                            scale=self.scale, s=s)

@@ -225,20 +225,28 @@ class PixArtMSBlock(nn.Module):
         r, s = sv(a1.qkv)
         qa = STDiTBlock._ln_quant(x3, shift_msa, scale_msa, (a1.qkv,), [s], st)[0]   # dynamic or calibrated static grid
         qkv = ops.gemm_i8(qa, a1.qkv.packed_weight(r, s), bias=a1.qkv.bias_f32())
-        att_o = a1.attend(qkv, B, N, HW)                   # (plain: the HIP kernel straight on the q | k | v buffer)
+        from ..t2v.stdit import fwd_attn_quantized_static, prompt_kv_exact_fill
         r, s = sv(a1.proj)
-        qa = a1.proj.quantize_input(att_o.view(B, N, C), s)
+        att_o, qa = None, None
+        if a1.plain:                                       # attention + proj's static tensor-wise quantizer, when switched on
+            qa = fwd_attn_quantized_static(a1.proj, s, lambda d, z, nb, sm: a1.core.spatial_quantized_static(
+                qkv, B, N, d, z, nb, s=sm))
+        if qa is None:
+            att_o = a1.attend(qkv, B, N, HW)               # (plain: the HIP kernel straight on the q | k | v buffer)
+            qa = a1.proj.quantize_input(att_o.view(B, N, C), s)
         ops.gemm_i8(qa, a1.proj.packed_weight(r, s), bias=a1.proj.bias_f32(), out=x2, epilogue=ops.EPI_GATE_RESID,
                     resid=x2, gate=gate_msa, rows_per_gate=N)
         r, s = sv(ca.q_linear)
         q = ops.gemm_i8(ca.q_linear.quantize_input(x3, s), ca.q_linear.packed_weight(r, s), bias=ca.q_linear.bias_f32())
         r, s = sv(ca.kv_linear)
-        from ..t2v.stdit import prompt_kv_exact_fill
         kv = prompt_kv_exact_fill(ca.kv_linear, y2.view(1, -1, C), r, s, ca.kv_linear.packed_weight(r, s))
-        att_o = ca.core.cross(q, kv, kv_off, B, N, out=att_o)
         r, s = sv(ca.proj)
-        ops.gemm_i8(ca.proj.quantize_input(att_o.view(B, N, C), s), ca.proj.packed_weight(r, s),
-                    bias=ca.proj.bias_f32(), out=x2, epilogue=ops.EPI_RESID, resid=x2)
+        qa = fwd_attn_quantized_static(ca.proj, s, lambda d, z, nb, sm: ca.core.cross_quantized_static(
+            q, kv, kv_off, B, N, d, z, nb, s=sm))
+        if qa is None:
+            att_o = ca.core.cross(q, kv, kv_off, B, N, out=att_o)
+            qa = ca.proj.quantize_input(att_o.view(B, N, C), s)
+        ops.gemm_i8(qa, ca.proj.packed_weight(r, s), bias=ca.proj.bias_f32(), out=x2, epilogue=ops.EPI_RESID, resid=x2)
         r, s = sv(fc1)
         qa = STDiTBlock._ln_quant(x3, shift_mlp, scale_mlp, (fc1,), [s], st)[0]
         from ..t2v.stdit import _GELU_QUANT

@@ -362,6 +362,32 @@ def _static_attn_quant(proj, T, H, D) -> bool:
     return ops.attn_temporal_static_ok(T, H, D, ops.pad128(H * D), aq.n_bits)
 
 
+# spatial / cross attention + proj's static tensor-wise quantizer in one kernel (ops.attn_fwd_rowquant_static) instead of
+# attention + one quantizer pass.  The fused kernel's fp16 output IS attn_fwd's, so a static plan's output does not move;
+# off by default until the timing table decides: two tests pin today's launches of a static block.
+# VQ_STATIC_FWD_ATTN_QUANT=1 turns it on; independent of VQ_STATIC_ATTN_QUANT.
+_STATIC_FWD_ATTN_QUANT = __import__("os").environ.get("VQ_STATIC_FWD_ATTN_QUANT", "0") != "0"
+
+
+def _static_fwd_attn_quant(proj) -> bool:
+    """Whether the spatial / cross attention in front of ``proj`` may also run proj's quantizer: the switch, a calibrated
+    tensor-wise grid and the one-pass static route.  (Whether the entry point takes the launch is asked by
+    QuantAttention.spatial_quantized_static / cross_quantized_static, which return None when it does not.)"""
+    aq = proj.act_quantizer
+    if not (_STATIC_FWD_ATTN_QUANT and _STATIC_FUSED) or isinstance(aq, DynamicActQuantizer):
+        return False
+    return aq.delta.numel() == 1 and aq.zero_point.numel() == 1
+
+
+def fwd_attn_quantized_static(proj, sv, fused_call):
+    """proj's input codes from ``fused_call(delta, zp, n_bits, s)`` - attention with proj's static quantizer fused in -
+    or None when the route is off or refuses (the caller then runs attention and proj's quantizer separately)."""
+    if not _static_fwd_attn_quant(proj):
+        return None
+    aq = proj.act_quantizer
+    return fused_call(aq.delta.float(), aq.zero_point.float(), aq.n_bits, sv)
+
+
 
 def _static_one_pass(layers, C, add_rows=False, ln=False) -> bool:
     """Whether ONE ops.rowquant_static launch serves the calibrated quantizers of ``layers`` (which share an input):
@@ -570,8 +596,12 @@ class STDiTBlock(nn.Module):
         svs = [svec(l) for l in (a1.q, a1.k, a1.v)]
         qas = self._ln_quant(x3, shift_msa, scale_msa, (a1.q, a1.k, a1.v), svs, st)
         qkv = qkv_proj(a1, qas)
-        att_o = a1.core.spatial(qkv, B * T, S)
-        qa = a1.proj.quantize_input(att_o.view(B, N, C), svec(a1.proj))
+        att_o = None
+        qa = fwd_attn_quantized_static(a1.proj, svec(a1.proj), lambda d, z, nb, s: a1.core.spatial_quantized_static(
+            qkv, B * T, S, d, z, nb, s=s))
+        if qa is None:
+            att_o = a1.core.spatial(qkv, B * T, S)
+            qa = a1.proj.quantize_input(att_o.view(B, N, C), svec(a1.proj))
         ops.gemm_i8(qa, a1.proj.packed_weight(r, svec(a1.proj)), bias=a1.proj.bias_f32(), out=x2,
                     epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate_msa, rows_per_gate=N)
 
@@ -608,8 +638,11 @@ class STDiTBlock(nn.Module):
         qa = ca.q_linear.quantize_input(x3, svec(ca.q_linear))
         q = ops.gemm_i8(qa, ca.q_linear.packed_weight(r, svec(ca.q_linear)), bias=ca.q_linear.bias_f32())
         kv = kv_ready if kv_ready is not None else self.prompt_kv(y2)   # batched over the blocks by STDiT.forward
-        att_o = ca.core.cross(q, kv, y_lens, B, N, out=att_o)
-        qa = ca.proj.quantize_input(att_o.view(B, N, C), svec(ca.proj))
+        qa = fwd_attn_quantized_static(ca.proj, svec(ca.proj), lambda d, z, nb, s: ca.core.cross_quantized_static(
+            q, kv, y_lens, B, N, d, z, nb, s=s))
+        if qa is None:
+            att_o = ca.core.cross(q, kv, y_lens, B, N, out=att_o)
+            qa = ca.proj.quantize_input(att_o.view(B, N, C), svec(ca.proj))
         ops.gemm_i8(qa, ca.proj.packed_weight(r, svec(ca.proj)), bias=ca.proj.bias_f32(), out=x2,
                     epilogue=ops.EPI_RESID, resid=x2)
 
