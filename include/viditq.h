@@ -176,6 +176,32 @@ int vq_fakequant_act(const void* x, void* out, uint8_t* codes, float* delta_out,
 int vq_epsfill_fixup(const int32_t* flag, const void* x, const float* s, const void* wdq, const void* bias,
                      void* out, int n_batch, int L, int C, int N, int n_bits, void* stream);
 
+/* ---- running smooth-quant act-scale statistic, device-resident ---------------
+ * Replaces QuantLayer's momentum statistic where a script leaves it running at inference (quant_txt2img.py:297-300):
+ * the update of qdiff/models/quant_layer.py:118-126 and :147-154,
+ *   cur = input.abs().amax(dim=-2).mean(dim=0);  act_scale = cur if act_scale.abs().mean() == 0
+ *                                                else act_scale * momentum + cur * (1 - momentum),
+ * followed by the zero patch of the channel-wise scale (:128-133: entries that are exactly zero become 1e-5) - with the
+ * two host-visible tests of the reference evaluated on the device: no synchronisation, capturable in a graph.
+ * x          [B, n_tok, C] fp16, rows contiguous, finite values
+ * act_scale  [C] fp32 device state, updated in place (one time range's slice of act_quantizer.act_scale)
+ * cur_out    nullable [C] fp32: this call's cur
+ * scratch    [B*C] uint32 owned by the caller; zeroed by this call on `stream` (a small kernel) - callers do not pre-zero
+ * Contract:
+ *   m[b][c] = max over tok of |x[b, tok, c]| as fp16, taken as the integer maximum of `bits & 0x7fff` (independent of the
+ *     order of rows and workgroups: the integer atomic between workgroups is bit-reproducible);
+ *   cur[c] = (float(m[0][c]) + float(m[1][c]) + ... in order b = 0 .. B-1) / B;
+ *   every entry of act_scale zero: act_scale = cur; otherwise
+ *   act_scale[c] = RN(RN(act_scale[c] * momentum) + RN(cur[c] * one_minus_momentum)) - three fp32 roundings, no fma; the
+ *     host passes one_minus_momentum = (float)(1.0 - momentum) evaluated in double, as torch does for a Python scalar;
+ *   then entries of act_scale that are exactly zero become 1.0e-5f.
+ * Bit-exact against the reference lines on the CPU (for B > 2 up to the reference's own summation order).
+ * Errors, all before any HIP call or dereference, null pointers first: VQ_EINVAL for a null x, act_scale or scratch, a
+ * non-positive extent, B > 65535, B*C beyond int32, a momentum outside [0, 1]; VQ_ESHAPE for C % 8 or x off 16 bytes. */
+int vq_act_scale_momentum(const void* x, float* act_scale, float* cur_out, uint32_t* scratch,
+                          float momentum, float one_minus_momentum,
+                          int B, int n_tok, int C, void* stream);
+
 /* ---- weight packer ---------------------------------------------------------
  * Replaces WeightQuantizer.forward on W*s (base_quantizer.py:129-144 via
  * quant_layer.py:174-185): codes = clamp(round(W*s/delta)+zp, 0, 2^b-1) on the

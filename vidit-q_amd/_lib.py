@@ -32,6 +32,7 @@ SIGNATURES = {
     "vq_rowquant_smooth_multi": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "vq_rowquant_static": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                 _i, _i, _i, _i, _i, _vp]),
+    "vq_act_scale_momentum": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp]),
     "vq_smooth_div_check": (_i, [_vp, _vp, _vp, _vp, _l, _vp]),
     "vq_fakequant_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vq_epsfill_fixup": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -117,6 +117,33 @@ def smooth_rcp(s: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return out
 
 
+def act_scale_momentum(x: torch.Tensor, act_scale: torch.Tensor, momentum: float, scratch: Optional[torch.Tensor] = None,
+                       cur_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One update of a running smooth-quant statistic on the device: ``act_scale`` [C] fp32 (a contiguous view of one time
+    range of ``act_quantizer.act_scale``) moves IN PLACE by the per-channel abs-max of x [B, n_tok, C] fp16 averaged over B,
+    first call or momentum form decided on the device, zeros patched to 1e-5 (include/viditq.h: vq_act_scale_momentum).
+    ``scratch`` [B*C] int32 work space (allocated when not given; its content on entry does not matter)."""
+    _req(x, torch.float16, "x")
+    assert x.dim() == 3
+    B, n_tok, Cc = x.shape
+    _req(act_scale, torch.float32, "act_scale")
+    if act_scale.numel() != Cc:
+        raise VQError("act_scale must hold one entry per channel of x")
+    if scratch is None:
+        scratch = torch.empty(B * Cc, dtype=torch.int32, device=x.device)
+    _req(scratch, torch.int32, "scratch")
+    if scratch.numel() < B * Cc:
+        raise VQError("scratch must hold B*C words")
+    if cur_out is not None:
+        _req(cur_out, torch.float32, "cur_out")
+        assert cur_out.numel() == Cc
+    m = float(momentum)
+    # 1 - momentum in double, rounded once to fp32: what torch makes of the Python scalar in `cur * (1 - momentum)`
+    check(_L().vq_act_scale_momentum(_p(x), _p(act_scale), _p(cur_out), _p(scratch), m, 1.0 - m, B, n_tok, Cc, _stream()),
+          "vq_act_scale_momentum")
+    return act_scale
+
+
 def smooth_div_check(a: torch.Tensor, b: torch.Tensor):
     """(reciprocal-form quotient, IEEE quotient) of a / b elementwise - test hook."""
     _req(a, torch.float32, "a")

@@ -302,6 +302,85 @@ class QuantLayer(nn.Module):
             return None
         return ops.gelu_rowquant(h3, n_bits=self.act_quantizer.n_bits, s=s, status=self.status)
 
+    # ------------------------------------------------------------------ running statistic, device-resident
+    def running_stat_device_ok(self) -> bool:
+        """Whether :meth:`running_stat_step` serves this layer: a momentum act-scale statistic left RUNNING at inference
+        (quant_txt2img.py:297-300) on a layer of the integer route with a dynamic per-token activation quantizer, whose fp16
+        master weight is still here (W*s is re-packed from it in every call) and whose statistic, once it exists, is fp32
+        device memory.  Reads host-side fields only."""
+        if not getattr(self, "smooth_quant_running_stat", False):
+            return False
+        if "momentum" not in str(getattr(self, "channel_wise_scale_type", "")) or not hasattr(self, "timerange_num"):
+            return False
+        if not self.int_route_ok() or not isinstance(self.act_quantizer, DynamicActQuantizer):
+            return False
+        W = self.weight
+        if W.numel() == 0 or W.dtype != torch.float16 or not W.is_cuda or not W.is_contiguous():
+            return False                                   # released by shard.release_fp_weights, or not the fp16 hot path
+        a = getattr(self.act_quantizer, "act_scale", None)
+        return a is None or (a.is_cuda and a.dtype == torch.float32 and a.is_contiguous() and a.dim() == 3
+                             and a.shape[0] == self.timerange_num and a.shape[-1] == W.shape[1])
+
+    def _running_buffers(self, r: int, B: int, dev) -> dict:
+        """The fixed device buffers of :meth:`running_stat_step` for (time range, weight bit width): allocated on first
+        sight, kept while the weight grid and the weight itself stay what they were (captured graphs hold the addresses)."""
+        wq = self.weight_quantizer
+        key = ("run", r, wq.n_bits)
+        ent = self._packed.get(key)
+        if ent is not None and ent["delta"] is wq.delta and ent["wver"] == self.weight._version and ent["B"] >= B:
+            return ent
+        N, K = self.weight.shape
+        if ent is not None:
+            PACK_EPOCH[0] += 1                             # the replaced buffers may be referenced by captured HIP graphs
+        ent = {"delta": wq.delta, "wver": self.weight._version, "B": B,
+               "d": wq.delta.reshape(-1).float().contiguous(), "z": wq.zero_point.reshape(-1).float().contiguous(),
+               "scratch": torch.empty(B * K, dtype=torch.int32, device=dev),
+               "out": [torch.empty(shape, dtype=dt, device=dev) for shape, dt in ops.packed_shapes(N, K, wq.n_bits)],
+               "s": None, "tmp": None, "wpow": None, "alpha": None}
+        self._packed[key] = ent
+        return ent
+
+    def running_stat_step(self, x3: torch.Tensor):
+        """One forward's worth of a running statistic WITHOUT the host: what :meth:`forward` does on the integer route for a
+        layer with ``smooth_quant_running_stat`` - update ``act_scale[r]`` from the input (quant_layer.py:118-126, :147-154),
+        patch its zeros (:128-133), re-derive s, re-pack W*s, quantize x / s - as kernels and element-wise torch ops on the
+        current stream: no host read of device data, no allocation of state after the first call for a (time range, weight
+        bit width), the packed weight in the SAME buffers every call (PACK_EPOCH does not move).  x3 [B, n, K] fp16
+        contiguous.  Returns ``(QAct, PackedWeight)`` for ``ops.gemm_i8``.  With ``smooth_quant`` off the statistic alone
+        moves (the ``elif`` branch of :meth:`forward`): quantizer and packer run without s.
+        Ask :meth:`running_stat_device_ok` first."""
+        aq, wq = self.act_quantizer, self.weight_quantizer
+        B, _, K = x3.shape
+        r, alpha = self._range_and_alpha()
+        # the predicate is the caller's question (fused_running_ok asks it on every forward); here it is checked once, when
+        # the buffers of a (range, bit width) are about to be created
+        if ("run", r, wq.n_bits) not in self._packed and not self.running_stat_device_ok():
+            raise RuntimeError("%s: running_stat_step on a layer it does not serve (running_stat_device_ok() is False)"
+                               % getattr(self, "module_name", type(self).__name__))
+        if aq.act_scale is None:                           # (a None test is not a synchronisation)
+            aq.act_scale = torch.zeros([self.timerange_num, 1, K], device=x3.device, dtype=torch.float32)
+        ent = self._running_buffers(r, B, x3.device)
+        a_r = aq.act_scale[r]                              # [1, K] view of the state
+        ops.act_scale_momentum(x3, a_r.view(-1), self.smooth_quant_momentum, scratch=ent["scratch"])
+        # the statistic moved behind torch's back (no version bump): the layerwise route must not find an older vector
+        self._packed.pop(("s", r), None)
+        s = None
+        if self.smooth_quant:
+            if ent["s"] is None or ent["alpha"] != alpha:
+                # (max_rows|W|)^(1-alpha) of channel_wise_scale, once per (range, alpha, weight version: _running_buffers)
+                ent["wpow"] = self._master_weight().abs().amax(dim=0).float().pow(1 - alpha)
+                ent["tmp"] = torch.empty_like(a_r)
+                ent["s"] = torch.empty_like(a_r) if ent["s"] is None else ent["s"]
+                ent["alpha"] = alpha
+            # the torch expression of channel_wise_scale, into fixed buffers: bit-identical to what the layerwise route
+            # derives from the same statistic (no HIP powf)
+            torch.pow(a_r, alpha, out=ent["tmp"])
+            torch.div(ent["tmp"], ent["wpow"], out=ent["s"])
+            s = ent["s"].view(-1)
+        pw = ops.pack_weight(self._master_weight(), ent["d"], ent["z"], wq.n_bits, s=s, out=ent["out"])
+        qa = ops.rowquant(x3, n_bits=aq.n_bits, s=s, fast_div=False, status=self.status)
+        return qa, pw
+
     # ------------------------------------------------------------------ exact global eps-fill (prompt K/V)
     def dequantized_weight_f16(self, r: int = 0, s: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The fake-quantized weight the reference multiplies with, as fp16 [N, K] (quant_layer.py:202-203 casts the

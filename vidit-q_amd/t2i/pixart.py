@@ -27,7 +27,8 @@ from ..qdiff.models.quant_block import QuantAttention
 from ..qdiff.models.quant_layer import QuantLayer
 from ..qdiff.quantizer.dynamic_quantizer import DynamicActQuantizer
 from ..t2v.stdit import (CaptionEmbedder, Mlp, fp_edge_linear, MultiHeadCrossAttention, STDiTBlock, T2IFinalLayer, TimestepEmbedder,
-                         approx_gelu, get_1d_sincos_pos_embed_from_grid, seq_offsets, t2i_modulate)
+                         approx_gelu, fused_running_rules, get_1d_sincos_pos_embed_from_grid, seq_offsets, t2i_modulate,
+                         takes_fused)
 
 
 def get_2d_sincos_pos_embed(embed_dim, grid_size, pe_interpolation=1.0, base_size=16):
@@ -184,6 +185,8 @@ class PixArtMSBlock(nn.Module):
                 self.cross_attn.proj, self.mlp.fc1, self.mlp.fc2]
 
     def fused_ok(self) -> bool:
+        # (twin: fused_running_ok / t2v/stdit.py fused_running_rules restate these rules for the opt-in route of a running
+        # statistic on mlp.fc2 - a rule added here belongs there too)
         for m in self.hot_layers():
             if not (isinstance(m, QuantLayer) and m.int_route_ok()):
                 return False
@@ -195,6 +198,11 @@ class PixArtMSBlock(nn.Module):
                 # job (host-visible statistics) - such a block takes the reference data flow, layer by layer
                 return False
         return True
+
+    def fused_running_ok(self) -> bool:
+        """:meth:`fused_ok` with a running smooth-quant statistic tolerated on ``mlp.fc2`` (served on the device by
+        QuantLayer.running_stat_step); consulted only under VQ_RUNNING_SMOOTH_DEVICE (t2v/stdit.py)."""
+        return fused_running_rules(self)
 
     def forward(self, x, y, t, mask=None, HW=None, **kwargs):
         """PixArtMS.py:71-79 (reference data flow)."""
@@ -250,13 +258,19 @@ class PixArtMSBlock(nn.Module):
         r, s = sv(fc1)
         qa = STDiTBlock._ln_quant(x3, shift_mlp, scale_mlp, (fc1,), [s], st)[0]
         from ..t2v.stdit import _GELU_QUANT
-        r2, s2 = sv(fc2)
-        # GELU inside fc2's quantizer pass (see t2v/stdit.py), also for the uncond | cond pair of the t2i loop
-        one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, s2)
-        h = ops.gemm_i8(qa, fc1.packed_weight(r, s), bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
-        r, s = r2, s2
-        qa = fc2.quantize_gelu_input(h.view(B, N, -1), s) if one_pass else fc2.quantize_input(h.view(B, N, -1), s)
-        ops.gemm_i8(qa, fc2.packed_weight(r, s), bias=fc2.bias_f32(), out=x2,
+        if getattr(fc2, "smooth_quant_running_stat", False):
+            # a running statistic needs the activation itself before s exists: GELU in fc1's epilogue, then fc2's device step
+            h = ops.gemm_i8(qa, fc1.packed_weight(r, s), bias=fc1.bias_f32(), epilogue=ops.EPI_GELU)
+            qa, pw2 = fc2.running_stat_step(h.view(B, N, -1))
+        else:
+            r2, s2 = sv(fc2)
+            # GELU inside fc2's quantizer pass (see t2v/stdit.py), also for the uncond | cond pair of the t2i loop
+            one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, s2)
+            h = ops.gemm_i8(qa, fc1.packed_weight(r, s), bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
+            r, s = r2, s2
+            qa = fc2.quantize_gelu_input(h.view(B, N, -1), s) if one_pass else fc2.quantize_input(h.view(B, N, -1), s)
+            pw2 = fc2.packed_weight(r, s)
+        ops.gemm_i8(qa, pw2, bias=fc2.bias_f32(), out=x2,
                     epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate_mlp, rows_per_gate=N)
         return x2
 
@@ -352,13 +366,14 @@ class _PixArtBase(nn.Module):
 
     def _run_blocks(self, x, y, t0, y_lens):
         """Every block whose Linears are all on the integer route runs fused (residual stream updated in place);
-        any other block (FP / calibration states, a running smooth-quant statistic) runs the reference data flow."""
+        any other block (FP / calibration states, a running smooth-quant statistic - unless VQ_RUNNING_SMOOTH_DEVICE serves it
+        on the device, t2v/stdit.py) runs the reference data flow."""
         bs, N, C = x.shape
         x = x.contiguous()
         can_fuse = x.is_cuda and x.dtype == torch.float16
         y2 = off = t0c = None
         for block in self.blocks:
-            if can_fuse and block.fused_ok():
+            if can_fuse and takes_fused(block):
                 if y2 is None:
                     y2 = y.reshape(-1, C).contiguous()
                     off = seq_offsets(y_lens, x.device)

@@ -379,6 +379,33 @@ def _static_fwd_attn_quant(proj) -> bool:
     return aq.delta.numel() == 1 and aq.zero_point.numel() == 1
 
 
+# a running smooth-quant statistic on mlp.fc2 (the released t2i script leaves it on for blocks.27.mlp.fc2 at inference,
+# quant_txt2img.py:297-300) served on the fused route by QuantLayer.running_stat_step: statistic, s, W*s and the quantizer
+# on the device, no host read.  Off by default: a test pins today's layer-by-layer route of such a block, and the timing
+# table decides the flip.  VQ_RUNNING_SMOOTH_DEVICE=1 turns it on.
+_RUNNING_SMOOTH_DEVICE = __import__("os").environ.get("VQ_RUNNING_SMOOTH_DEVICE", "0") != "0"
+
+
+def fused_running_rules(block) -> bool:
+    """``fused_ok()``'s per-layer rules for ``block`` (STDiTBlock or a PixArt block), with a running statistic tolerated on
+    ``mlp.fc2`` only and only where QuantLayer.running_stat_device_ok() holds.  A twin of the loops in both ``fused_ok()``
+    bodies, which stay as they are (tests pin them): a rule added there belongs here too."""
+    for m in block.hot_layers():
+        if not (isinstance(m, QuantLayer) and m.int_route_ok()):
+            return False
+        aq = m.act_quantizer
+        if not isinstance(aq, DynamicActQuantizer) and aq.per_group:
+            return False
+        if getattr(m, "smooth_quant_running_stat", False) and not (m is block.mlp.fc2 and m.running_stat_device_ok()):
+            return False
+    return True
+
+
+def takes_fused(block) -> bool:
+    """The route of ``block``: ``fused_ok()``, or - switched on - ``fused_running_ok()`` (never consulted otherwise)."""
+    return block.fused_ok() or (_RUNNING_SMOOTH_DEVICE and block.fused_running_ok())
+
+
 def fwd_attn_quantized_static(proj, sv, fused_call):
     """proj's input codes from ``fused_call(delta, zp, n_bits, s)`` - attention with proj's static quantizer fused in -
     or None when the route is off or refuses (the caller then runs attention and proj's quantizer separately)."""
@@ -452,6 +479,8 @@ class STDiTBlock(nn.Module):
                 self.mlp.fc1, self.mlp.fc2]
 
     def fused_ok(self) -> bool:
+        # (twin: fused_running_ok / t2v/stdit.py fused_running_rules restate these rules for the opt-in route of a running
+        # statistic on mlp.fc2 - a rule added here belongs there too)
         for m in self.hot_layers():
             if not (isinstance(m, QuantLayer) and m.int_route_ok()):
                 return False
@@ -463,6 +492,17 @@ class STDiTBlock(nn.Module):
         for att in (self.attn, self.attn_temp):
             # q, k and v are quantized from ONE pass over their common input: that needs one activation bit-width
             # and one kind of quantizer (a mixed-precision YAML may set them apart: then the layerwise route runs)
+            aqs = [l.act_quantizer for l in (att.q, att.k, att.v)]
+            if len({(a.n_bits, isinstance(a, DynamicActQuantizer)) for a in aqs}) != 1:
+                return False
+        return True
+
+    def fused_running_ok(self) -> bool:
+        """:meth:`fused_ok` with a running smooth-quant statistic tolerated on ``mlp.fc2`` (served on the device by
+        QuantLayer.running_stat_step); consulted only under VQ_RUNNING_SMOOTH_DEVICE."""
+        if not fused_running_rules(self):
+            return False
+        for att in (self.attn, self.attn_temp):
             aqs = [l.act_quantizer for l in (att.q, att.k, att.v)]
             if len({(a.n_bits, isinstance(a, DynamicActQuantizer)) for a in aqs}) != 1:
                 return False
@@ -489,7 +529,7 @@ class STDiTBlock(nn.Module):
         return [l.quantize_input(xm, s) for l, s in zip(layers, svs)]
 
     def forward(self, x, y, t, mask=None, tpe=None):
-        if x.is_cuda and x.dtype == torch.float16 and self.fused_ok():
+        if x.is_cuda and x.dtype == torch.float16 and takes_fused(self):
             B, N, C = x.shape
             x2 = x.reshape(B * N, C).clone()
             lens = mask if mask is not None else [y.reshape(-1, C).shape[0] // B] * B
@@ -649,11 +689,17 @@ class STDiTBlock(nn.Module):
         # ---- MLP: x += gate_mlp * fc2(gelu(fc1(LN-mod(x))))                   (stdit.py:124-128)
         fc1, fc2 = self.mlp.fc1, self.mlp.fc2
         qa = self._ln_quant(x3, shift_mlp, scale_mlp, (fc1,), [svec(fc1)], st)[0]
-        one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, svec(fc2))
-        h = ops.gemm_i8(qa, fc1.packed_weight(r, svec(fc1)), bias=fc1.bias_f32(),
-                        epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
-        qa = fc2.quantize_gelu_input(h.view(B, N, -1), svec(fc2)) if one_pass else fc2.quantize_input(h.view(B, N, -1), svec(fc2))
-        ops.gemm_i8(qa, fc2.packed_weight(r, svec(fc2)), bias=fc2.bias_f32(), out=x2,
+        if getattr(fc2, "smooth_quant_running_stat", False):
+            # a running statistic needs the activation itself before s exists: GELU in fc1's epilogue, then fc2's device step
+            h = ops.gemm_i8(qa, fc1.packed_weight(r, svec(fc1)), bias=fc1.bias_f32(), epilogue=ops.EPI_GELU)
+            qa, pw2 = fc2.running_stat_step(h.view(B, N, -1))
+        else:
+            one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, svec(fc2))
+            h = ops.gemm_i8(qa, fc1.packed_weight(r, svec(fc1)), bias=fc1.bias_f32(),
+                            epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
+            qa = fc2.quantize_gelu_input(h.view(B, N, -1), svec(fc2)) if one_pass else fc2.quantize_input(h.view(B, N, -1), svec(fc2))
+            pw2 = fc2.packed_weight(r, svec(fc2))
+        ops.gemm_i8(qa, pw2, bias=fc2.bias_f32(), out=x2,
                     epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate_mlp, rows_per_gate=N)
         return x2
 
@@ -857,7 +903,7 @@ class STDiT(nn.Module):
             t0 = self.t_block(t)
         y, y_lens, off = self._prompt_tokens(y, mask, C)
 
-        fused = x.is_cuda and x.dtype == torch.float16 and all(b.fused_ok() for b in self.blocks)
+        fused = x.is_cuda and x.dtype == torch.float16 and all(takes_fused(b) for b in self.blocks)
         if fused:
             x2 = x.reshape(B * self.num_patches, C)
             y2 = y.reshape(-1, C).contiguous()
