@@ -967,6 +967,50 @@ def test_attn_temporal_rowquant_equals_two_kernels(ops, dev, T, S, H, D):
         assert torch.equal(getattr(got3, f), getattr(ref3, f)), f
 
 
+@pytest.mark.parametrize("D", [16, 72])
+def test_attn_temporal_rowquant_sixteen_heads_wide_code_rows(ops, dev, D):
+    """H = 16 with code rows padded past 2048 columns (Kp = 2176): the route on which sixteen heads run
+    attn_temporal_quant_kernel instead of the instruction-trimmed kernel, reachable through the C ABI only (ops pads to
+    128).  Dynamic and static grid: codes in [0, C), scales, zero points and row terms bit-identical to vq_rowquant of the
+    fp16 copy the kernel emits, columns [C, Kp) zero, and that copy within one fp16 ulp of the stand-alone attention
+    kernel.  (Not compared with the trimmed kernel: the two invert the softmax row sum differently by design.)"""
+    from viditq_amd import _lib
+    T, S, H, Kp = 16, 5, 16, 2176
+    Cc, rows = H * D, T * S
+    qkv = h16(rows, 3 * Cc, seed=D).to(dev)
+    q, k, v = qkv, qkv[:, Cc:], qkv[:, 2 * Cc:]
+    o_ref = torch.empty((rows, Cc), dtype=torch.float16, device=dev)
+    ops.attn_temporal(q, k, v, o_ref, 1, T, S, H, D, 3 * Cc, Cc)
+
+    def outputs():
+        return (torch.full((rows, Kp), 77, dtype=torch.int8, device=dev), torch.empty(rows, dtype=torch.float32, device=dev),
+                torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
+                torch.zeros((rows, Cc), dtype=torch.float16, device=dev))
+
+    def check(xq, sx, zx, R, o, ref):
+        assert torch.equal(xq[:, :Cc], ref.xq[:, :Cc]) and not bool(xq[:, Cc:].any())
+        assert torch.equal(sx, ref.sx) and torch.equal(zx, ref.zx) and torch.equal(R, ref.R)
+        assert bool(((o.float() - o_ref.float()).abs() <= 2.0 ** -10 * o_ref.float().abs().clamp(min=2.0 ** -14)).all())   # one fp16 ulp
+
+    xq, sx, zx, R, o = outputs()
+    st1, st0 = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().vq_attn_temporal_rowquant(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), None, None, xq.data_ptr(), sx.data_ptr(), zx.data_ptr(), R.data_ptr(),
+        st1.data_ptr(), o.data_ptr(), 1, T, S, H, D, 3 * Cc, Kp, D ** -0.5, None), "vq_attn_temporal_rowquant")
+    check(xq, sx, zx, R, o, ops.rowquant(o.view(1, rows, Cc), status=st0))
+    assert int(st0.item()) == int(st1.item())
+    for n_bits in (8, 6):
+        qmax = 2 ** n_bits - 1
+        delta = torch.tensor([2.0 / qmax], device=dev)
+        zp = torch.tensor([float(round(qmax / 2))], device=dev)
+        xq, sx, zx, R, o = outputs()
+        _lib.check(_lib.load().vq_attn_temporal_rowquant_static(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), None, None, delta.data_ptr(), zp.data_ptr(), xq.data_ptr(), sx.data_ptr(),
+            zx.data_ptr(), R.data_ptr(), o.data_ptr(), 1, T, S, H, D, 3 * Cc, Cc, Kp, n_bits, D ** -0.5, None),
+            "vq_attn_temporal_rowquant_static")
+        check(xq, sx, zx, R, o, ops.rowquant(o.view(1, rows, Cc), n_bits=n_bits, delta=delta, zp=zp))
+
+
 # ----------------------------------------------------------------------------- small fused helpers
 def test_adaln_table_and_cfg_ddim(ops, dev):
     B, J, C = 2, 6, 64

@@ -21,9 +21,12 @@
 // block-diagonal mask.
 //
 // attn_temporal_quant_kernel / attn_temporal_quant2_kernel (T <= 16) and attn_temporal_long_kernel (T <= 64): temporal
-// attention with the consuming Linear's per-token quantizer fused in; one argument struct (TempQArgs), lane layout,
-// LDS exchange contract and row reductions in attn_rowquant.h.  Each has a static-grid form (instantiated on the argument
-// struct TempQSArgs, vq_attn_temporal_rowquant_static): attn_temp.proj's calibrated tensor-wise quantizer at 2..8 bits.
+// attention with the consuming Linear's per-token quantizer fused in; one argument struct (TempQArgs), and the lane layout,
+// LDS exchange contract and every step of a position that does not depend on a kernel's load schedule or LDS map - softmax,
+// V^T operand, fp16 copy, x / s, row statistics, grid, encode, code-sum exchange, record, LDS barrier - once in
+// attn_rowquant.h: a kernel body here is its load schedule, LDS map, barrier placement, O^T accumulation and the way its codes
+// leave.  Each has a static-grid form (instantiated on the argument struct TempQSArgs, vq_attn_temporal_rowquant_static):
+// attn_temp.proj's calibrated tensor-wise quantizer at 2..8 bits, on the same steps through the one grid type TqGrid.
 //
 // The five flash-style kernels behind vq_attn_fwd are written on the shared steps of attn_tile.h (geometry, operand reads,
 // LDS-DMA delivery, softmax, epilogue): a kernel body here is its schedule.  Two blocks are written out where the helper cost
@@ -69,7 +72,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(A a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 5, l31 = lane & 31;
     const int qt = blockIdx.x, h = blockIdx.y, seq = blockIdx.z;
-    [[maybe_unused]] TqStatic sq;
+    [[maybe_unused]] TqGrid sq;
     if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
 
     const half_t* kbase;
@@ -371,11 +374,11 @@ struct TempQSArgs : TempQArgs {
     int n_bits;                                    // 2 .. 8
 };
 
-// HC: head count known at compile time (16 = STDiT-XL; 0 = take a.H): the chunk -> (tensor, row, piece) divisions of
-// the staging loops are by H * D / 8 and cost ~45 VALU instructions each with a run-time divisor
+// The head count is a.H (the chunk -> (tensor, row, piece) divisions of the staging loops are by H * D / 8 and cost ~45
+// VALU instructions each with a run-time divisor: the H = 16 kernel is attn_temporal_quant2_kernel below).
 // A = TempQSArgs: the static-grid form ST (attn_rowquant.h): a.delta / a.zp / a.n_bits instead of the row's own 8-bit
 // grid, any B
-template <int D, int HC, class A = TempQArgs>
+template <int D, class A = TempQArgs>
 __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
     constexpr bool ST = std::is_same<A, TempQSArgs>::value;
     constexpr int KS = (D + 15) / 16;              // 16-dim k-steps of QK^T = 16-dim row tiles of O^T
@@ -383,7 +386,7 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // = head
     const int tq = lane & 15, g4 = lane >> 4;      // MFMA 16x16x16: lane = (row or column tq, k / row group g4)
-    const int H = HC ? HC : a.H, C = H * D, nthr = 64 * H;
+    const int H = a.H, C = H * D, nthr = 64 * H;
     const int RS = C * 2 + 16;                     // LDS row stride (odd number of 16-byte slots)
     const int TILE = 16 * RS;
     const int RCH = C / 8;                         // 16-byte chunks per tensor row
@@ -448,8 +451,8 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
         }
     };
     const uint8_t* vs = smem + wave * D * 2;
-    [[maybe_unused]] TqStatic sq;
-    if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
+    TqGrid gq;                                     // ST: the calibrated grid; else every row's own, behind its statistics
+    if constexpr (ST) gq = tq_static(a.delta, a.zp, a.n_bits);
 
     int pos = blockIdx.x;
     if (pos >= npos) return;
@@ -471,95 +474,41 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
         asm volatile("" : "+v"(tx));
 
         // ---- S^T[key 4*g4 + r][query tq] = K Q^T, 16 x 16 per head: lane holds 8 dims of key row tq and of query row tq
-        float4v sc = {0.f, 0.f, 0.f, 0.f};
+        float4v sc[1] = {{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-        for (int ks = 0; ks < KS2; ++ks) sc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kfc[ks], qfc[ks], sc, 0, 0, 0);
-        float mloc = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (4 * g4 + r >= a.T) sc[r] = -INFINITY;
-            mloc = fmaxf(mloc, sc[r]);
-        }
-        mloc = fmaxf(mloc, __shfl_xor(mloc, 16));
-        mloc = fmaxf(mloc, __shfl_xor(mloc, 32));
-        const float m_use = (mloc == -INFINITY) ? 0.f : mloc;
-        float psum = 0.f;
-        half4 pf;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float p = __builtin_amdgcn_exp2f((sc[r] - m_use) * a.c);
-            psum += p;
-            pf[r] = (half_t)p;
-        }
-        psum += __shfl_xor(psum, 16);
-        psum += __shfl_xor(psum, 32);
-        const float inv_p = psum > 0.f ? __fdiv_rn(1.0f, psum) : 0.f;
+        for (int ks = 0; ks < KS2; ++ks) sc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kfc[ks], qfc[ks], sc[0], 0, 0, 0);
+        half4 pf[1];
+        const float psum = tq_softmax16<1>(sc, g4, a.T, a.c, pf);
+        const float inv_p = psum > 0.f ? __fdiv_rn(1.0f, psum) : 0.f;    // (IEEE here, v_rcp_f32 in the other two: attn_rowquant.h)
 
-        // ---- O^T[dim 16*dt + 4*g4 + r][query tq] = V^T P^T: P^T is the accumulator layout of S^T already
-        float4v oacc[KS];
-        [[maybe_unused]] float vmin = INFINITY, vmax = -INFINITY;
+        // ---- O^T[dim 16*dt + 4*g4 + r][query tq] = V^T P^T: P^T is the accumulator layout of S^T already.
+        // this lane: token tq, dims 16*dt + 4*g4 + r, rounded to fp16 like the stored tensor
+        // (float4v, and x4 copies at the encode: in this shape hipcc selects v_fma_mixlo_f16 - ONE rounding of o4 * inv_p to
+        //  fp16 - for the same 2 / 6 / 8 of the lane's values at D = 32 / 64 / 72 of the dynamic form as in the written-out
+        //  kernel, and the two-rounding v_mul + v_cvt_pk_f16_f32 for all others; as float[KS][4] every value rounds twice and
+        //  ~1e-5 of the fp16 outputs move by an ulp: profiles/refactor_temporal_steps.md)
+        float4v ov[KS];
 #pragma unroll
         for (int dt = 0; dt < KS; ++dt) {
-            // V^T operand (dim tq, keys 4 g4 .. + 3) by ONE LDS transpose read of the row-major tile: lane i of a 16-lane
-            // group points at [key 4 g4 + i / 4][dims 16 dt + 4 (i % 4) .. + 3] and receives column i of the 4 x 16 block
-            // (four 2-byte reads and their packing before).  Dims >= D of the last tile read the neighbouring head / the
-            // row padding: finite garbage in output rows nobody stores.
-            const h4_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (__attribute__((address_space(3))) h4_t*)(vs + (4 * g4 + (tq >> 2)) * RS + (dt * 16 + 4 * (tq & 3)) * 2));
-            const half4 vf = {(half_t)vt[0], (half_t)vt[1], (half_t)vt[2], (half_t)vt[3]};
-            oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf, float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-            // this lane: token tq, dims 16*dt + 4*g4 + r, rounded to fp16 like the stored tensor
+            const half4 vf = tq_vt_frag(vs + (4 * g4 + (tq >> 2)) * RS + (dt * 16 + 4 * (tq & 3)) * 2);
+            const float4v o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[0], float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) oacc[dt][r] = (float)(half_t)(oacc[dt][r] * inv_p);
+            for (int r = 0; r < 4; ++r) ov[dt][r] = (float)(half_t)(o4[r] * inv_p);
         }
-        if (a.o && tq < a.T) {                     // optional fp16 copy (tests, callers that need both)
-            half_t* orow = a.o + (((long)b * a.T + tq) * a.S + s) * C + wave * D;
-#pragma unroll
-            for (int dt = 0; dt < KS; ++dt) {
-                const int d0 = dt * 16 + 4 * g4;
-                if (d0 < D) {
-                    half4 ov;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) ov[r] = (half_t)oacc[dt][r];
-                    *reinterpret_cast<half4*>(orow + d0) = ov;
-                }
-            }
-        }
-        // the quantizer's input: the fp16 output, divided by the consuming Linear's smoothing vector when it has one
-        // (x / s, quant_layer.py:140; reciprocal form, bit-identical to the IEEE quotient - vq_common.h)
+        if (a.o && tq < a.T)                       // optional fp16 copy (tests, callers that need both)
+            tq_store_o<D>(a.o + (((long)b * a.T + tq) * a.S + s) * C + wave * D, ov, g4);
+        // the quantizer's input, and this head's part of the row statistics
+        [[maybe_unused]] float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
         for (int dt = 0; dt < KS; ++dt) {
             const int d0 = dt * 16 + 4 * g4;
             if (d0 < D) {
-                if (a.s) {                         // kernel-uniform
-                    const float4v s4 = *reinterpret_cast<const float4v*>(a.s + wave * D + d0);
-                    const float4v r4 = *reinterpret_cast<const float4v*>(a.s_rcp + wave * D + d0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) oacc[dt][r] = rq_div_rcp(oacc[dt][r], s4[r], r4[r]);
-                }
-                if constexpr (!ST) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        vmin = fminf(vmin, oacc[dt][r]);
-                        vmax = fmaxf(vmax, oacc[dt][r]);
-                    }
-                }
+                tq_div_s(ov[dt], a.s, a.s_rcp, wave * D + d0);
+                if constexpr (!ST) tq_minmax4(ov[dt], vmin, vmax);
             }
         }
-        if constexpr (!ST) {
-            vmin = fminf(vmin, __shfl_xor(vmin, 16));
-            vmin = fminf(vmin, __shfl_xor(vmin, 32));
-            vmax = fmaxf(vmax, __shfl_xor(vmax, 16));
-            vmax = fmaxf(vmax, __shfl_xor(vmax, 32));
-            if (lane < 16) {
-                ex_min[wave * 16 + tq] = vmin;
-                ex_max[wave * 16 + tq] = vmax;
-            }
-        }
-        // (raw barriers in the loop: __syncthreads() also waits for vmcnt(0), i.e. for the rows just requested for the
-        //  position after next - that serialised every iteration behind one HBM round trip)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();              // row statistics visible; every wave is done with the q | k | v tiles
+        if constexpr (!ST) tq_publish_minmax(vmin, vmax, ex_min, ex_max, wave, lane);
+        tq_lds_barrier();                          // row statistics visible; every wave is done with the q | k | v tiles
                                                    // (ST: nothing to publish, but store_qkv below reuses the V tile)
         if (has_next) {
             store_qkv(tx);                         // next position's V rows (visible after the barrier below) ...
@@ -570,49 +519,17 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
             }
             if (npos_next + (int)gridDim.x < npos) load_qkv(npos_next + (int)gridDim.x, tx);   // ... and the position after it is requested
         }
-        [[maybe_unused]] float delta, zp, inv;
-        [[maybe_unused]] int izx;
+        if constexpr (!ST) gq = tq_row_grid(ex_min, ex_max, H, tq, tid < 16 && tq < a.T, a.status);
         uint32_t csum = 0;
-        if constexpr (ST) {
-            RQ_BY_WIDTH(sq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
-                const int d0 = dt * 16 + 4 * g4;
-                if (d0 < D) {
-                    const float x4[4] = {oacc[dt][0], oacc[dt][1], oacc[dt][2], oacc[dt][3]};
-                    *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = tq_static_codes<SAT8_>(x4, sq, csum);
-                }
-            })
-        } else {
-            vmin = INFINITY;
-            vmax = -INFINITY;
-            for (int w = 0; w < H; ++w) {
-                vmin = fminf(vmin, ex_min[w * 16 + tq]);
-                vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
+        RQ_BY_WIDTH(gq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
+            const int d0 = dt * 16 + 4 * g4;
+            if (d0 < D) {
+                const float x4[4] = {ov[dt][0], ov[dt][1], ov[dt][2], ov[dt][3]};
+                *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = tq_codes<ST, SAT8_>(x4, gq, csum);
             }
-            bool small;
-            vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
-            if (small && tid < 16 && tq < a.T && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
-            izx = (int)zp - 128;
-#pragma unroll
-            for (int dt = 0; dt < KS; ++dt) {
-                const int d0 = dt * 16 + 4 * g4;
-                if (d0 < D) {
-                    uint32_t pk = 0;
-                    const float x4[4] = {oacc[dt][0], oacc[dt][1], oacc[dt][2], oacc[dt][3]};
-                    float c4[4];
-                    rq_round_group<4>(x4, inv, delta, zp, c4);      // one tie test per four codes, packed fp32 math
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
-                    csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-                    *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = pk ^ 0x80808080u;
-                }
-            }
-        }
-        int cs = (int)csum;
-        cs += __shfl_xor(cs, 16);
-        cs += __shfl_xor(cs, 32);
-        if (lane < 16) ex_sum[wave * 16 + tq] = cs;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        })
+        tq_publish_sum(csum, ex_sum, wave, lane);
+        tq_lds_barrier();
         // ---- codes out as whole 16-byte chunks (pad columns [C, Kp) zeroed like the row quantizers do); the next
         //      iteration touches codes / ex_sum only after its own first barrier, which every thread reaches after this
         const int kch = a.Kp / 16, cch = C / 16;
@@ -624,18 +541,9 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
                 *reinterpret_cast<int4v*>(a.xq + grow * a.Kp + ch * 16) = val;
             }
         }
-        if (tid < 16 && tq < a.T) {
-            int rs = 0;
-            for (int w = 0; w < H; ++w) rs += ex_sum[w * 16 + tq];
-            const long grow = ((long)b * a.T + tq) * a.S + s;
-            if constexpr (ST) {
-                rq_write_row(a.sx, a.zx, a.R, nullptr, (size_t)grow, sq.g.delta, sq.g.zp, rs, C, sq.wd.cx);
-            } else {
-                a.sx[grow] = delta;
-                a.zx[grow] = izx;
-                a.R[grow] = rs - 128 * C - C * izx;
-            }
-        }
+        if (tid < 16 && tq < a.T)
+            rq_write_row(a.sx, a.zx, a.R, nullptr, (size_t)(((long)b * a.T + tq) * a.S + s), gq.g.delta, gq.g.zp,
+                         tq_collect_sum(ex_sum, H, tq), C, gq.wd.cx);
     }
 }
 
@@ -648,12 +556,13 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
 //     above recomputed five 64-bit addresses per position with v_mad_u64_u32 / v_mul_lo_u32 chains to save registers);
 //   * the K / Q operand registers are requested again right behind the QK^T MFMAs that consume them - one set, no copy of
 //     a "next" set into a "current" one (24 registers and 24 moves per position less: the spill of the kernel above is gone);
-//   * the cross-row reductions over the four 16-lane rows of a wave are v_permlane16_swap / v_permlane32_swap + one VALU
-//     instruction each instead of ds_bpermute round trips (ten dependent LDS latencies per position);
 //   * 1 / sum(p) is v_rcp_f32 (1 ulp; the fp16 rounding that follows is 2^13 times coarser) instead of an IEEE division;
+//   (the cross-row reductions over the four 16-lane rows of a wave as v_permlane16_swap / v_permlane32_swap + one VALU
+//    instruction each instead of ds_bpermute round trips - ten dependent LDS latencies per position - came with this kernel
+//    too; they are the shared steps' reductions now, so the kernel above has them as well)
 //   * the chunk -> (row, column) decomposition of the code stores is per-lane state, not a division per chunk.
-// Codes / grids / row sums remain exact functions of the kernel's own fp16 output (bit-identical to vq_rowquant of it: same
-// vq_row_grid / rq_round_group arithmetic, tested).
+// Codes / grids / row sums remain exact functions of the kernel's own fp16 output (bit-identical to vq_rowquant of it: the
+// shared steps of attn_rowquant.h, tested).
 // ---------------------------------------------------------------------------
 template <int D, class A = TempQArgs>
 __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
@@ -740,8 +649,8 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
             if (tid + i * NTHR < 16 * RCH) *reinterpret_cast<int4v*>(smem + vlo[i]) = vals[i];
     };
 
-    [[maybe_unused]] TqStatic sq;
-    if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
+    TqGrid gq;                                             // ST: the calibrated grid; else every row's own, behind its statistics
+    if constexpr (ST) gq = tq_static(a.delta, a.zp, a.n_bits);
 
     int pos = blockIdx.x;
     if (pos >= npos) return;
@@ -756,127 +665,50 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
         const size_t row0 = base_of(pos);
 
         // ---- S^T = K Q^T (16 x 16 per head), then the operand registers are requested again for the next position
-        float4v sc = {0.f, 0.f, 0.f, 0.f};
+        float4v sc[1] = {{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-        for (int ks = 0; ks < KS2; ++ks) sc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[ks], qf[ks], sc, 0, 0, 0);
+        for (int ks = 0; ks < KS2; ++ks) sc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[ks], qf[ks], sc[0], 0, 0, 0);
         if (has_next) load_kq(pos_n);
-        float mloc = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (4 * g4 + r >= a.T) sc[r] = -INFINITY;
-            mloc = fmaxf(mloc, sc[r]);
-        }
-        mloc = tq_xor32(tq_xor16(mloc, true), true);
-        const float m_use = (mloc == -INFINITY) ? 0.f : mloc;
-        float psum = 0.f;
-        half4 pf;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float p = __builtin_amdgcn_exp2f((sc[r] - m_use) * a.c);
-            psum += p;
-            pf[r] = (half_t)p;
-        }
-        psum = tq_sum4rows(psum);
+        half4 pf[1];
+        const float psum = tq_softmax16<1>(sc, g4, a.T, a.c, pf);
         const float inv_p = psum > 0.f ? __builtin_amdgcn_rcpf(psum) : 0.f;
 
         // ---- O^T = V^T P^T, rounded to fp16 as the stored tensor is
         float ov[KS][4];
-        [[maybe_unused]] float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
         for (int dt = 0; dt < KS; ++dt) {
-            const h4_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (__attribute__((address_space(3))) h4_t*)(vs + vtro + dt * 32));
-            const half4 vf = {(half_t)vt[0], (half_t)vt[1], (half_t)vt[2], (half_t)vt[3]};
-            const float4v o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf, float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            const half4 vf = tq_vt_frag(vs + vtro + dt * 32);
+            const float4v o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[0], float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #pragma unroll
             for (int r = 0; r < 4; ++r) ov[dt][r] = (float)(half_t)(o4[r] * inv_p);
         }
-        if (a.o && tq < a.T) {                             // optional fp16 copy (tests, callers that need both)
-            half_t* orow = a.o + (row0 + (size_t)tq * a.S) * C + wave * D;
-#pragma unroll
-            for (int dt = 0; dt < KS; ++dt) {
-                const int d0 = dt * 16 + 4 * g4;
-                if (d0 < D) {
-                    half4 o4;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o4[r] = (half_t)ov[dt][r];
-                    *reinterpret_cast<half4*>(orow + d0) = o4;
-                }
-            }
-        }
+        if (a.o && tq < a.T)                               // optional fp16 copy (tests, callers that need both)
+            tq_store_o<D>(a.o + (row0 + (size_t)tq * a.S) * C + wave * D, ov, g4);
+        // the quantizer's input, and this head's part of the row statistics
+        [[maybe_unused]] float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
         for (int dt = 0; dt < KS; ++dt) {
             const int d0 = dt * 16 + 4 * g4;
             if (d0 < D) {
-                if (a.s) {                                 // kernel-uniform: x / s of the consuming Linear's smoothing vector
-                    const float4v s4 = *reinterpret_cast<const float4v*>(a.s + wave * D + d0);
-                    const float4v r4 = *reinterpret_cast<const float4v*>(a.s_rcp + wave * D + d0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) ov[dt][r] = rq_div_rcp(ov[dt][r], s4[r], r4[r]);
-                }
-                if constexpr (!ST) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        vmin = fminf(vmin, ov[dt][r]);
-                        vmax = fmaxf(vmax, ov[dt][r]);
-                    }
-                }
+                tq_div_s(ov[dt], a.s, a.s_rcp, wave * D + d0);
+                if constexpr (!ST) tq_minmax4(ov[dt], vmin, vmax);
             }
         }
-        if constexpr (!ST) {
-            vmin = tq_xor32(tq_xor16(vmin, false), false);
-            vmax = tq_xor32(tq_xor16(vmax, true), true);
-            if (lane < 16) {
-                ex_min[wave * 16 + tq] = vmin;
-                ex_max[wave * 16 + tq] = vmax;
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (raw barrier: __syncthreads() would also wait for the loads in flight)
-        __builtin_amdgcn_s_barrier();                        // row statistics visible; every wave is done with the V tile
+        if constexpr (!ST) tq_publish_minmax(vmin, vmax, ex_min, ex_max, wave, lane);
+        tq_lds_barrier();                                    // row statistics visible; every wave is done with the V tile
                                                              // (ST: nothing to publish, but store_v below reuses the tile)
         if (has_next) {
             store_v();                                       // the next position's V rows (visible after the barrier below)
             if (pos_n + G < npos) load_v(pos_n + G);
         }
-        [[maybe_unused]] float delta, zp, inv;
-        [[maybe_unused]] int izx;
+        if constexpr (!ST) gq = tq_row_grid(ex_min, ex_max, H, tq, tid < 16 && tq < a.T, a.status);
         uint32_t csum = 0;
-        if constexpr (ST) {
-            RQ_BY_WIDTH(sq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
-                const int d0 = dt * 16 + 4 * g4;
-                if (d0 < D)
-                    *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = tq_static_codes<SAT8_>(ov[dt], sq, csum);
-            })
-        } else {
-            vmin = INFINITY;
-            vmax = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < H; ++w) {
-                vmin = fminf(vmin, ex_min[w * 16 + tq]);
-                vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
-            }
-            bool small;
-            vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
-            if (small && tid < 16 && tq < a.T && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
-            izx = (int)zp - 128;
-#pragma unroll
-            for (int dt = 0; dt < KS; ++dt) {
-                const int d0 = dt * 16 + 4 * g4;
-                if (d0 < D) {
-                    uint32_t pk = 0;
-                    float c4[4];
-                    rq_round_group<4>(ov[dt], inv, delta, zp, c4);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
-                    csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-                    *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = pk ^ 0x80808080u;
-                }
-            }
-        }
-        const int cs = tq_isum4rows((int)csum);
-        if (lane < 16) ex_sum[wave * 16 + tq] = cs;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        RQ_BY_WIDTH(gq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
+            const int d0 = dt * 16 + 4 * g4;
+            if (d0 < D) *reinterpret_cast<uint32_t*>(codes + tq * CROW + wave * D + d0) = tq_codes<ST, SAT8_>(ov[dt], gq, csum);
+        })
+        tq_publish_sum(csum, ex_sum, wave, lane);
+        tq_lds_barrier();
         // ---- codes out as whole 16-byte chunks (pad columns [C, Kp) zeroed like the row quantizers do)
         {
             uint8_t* xb = reinterpret_cast<uint8_t*>(a.xq) + row0 * (size_t)a.Kp;
@@ -887,19 +719,9 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
                     *reinterpret_cast<int4v*>(xb + cgo[j]) = val;
                 }
         }
-        if (tid < 16 && tq < a.T) {
-            int rs = 0;
-#pragma unroll
-            for (int w = 0; w < H; ++w) rs += ex_sum[w * 16 + tq];
-            const size_t grow = row0 + (size_t)tq * a.S;
-            if constexpr (ST) {
-                rq_write_row(a.sx, a.zx, a.R, nullptr, grow, sq.g.delta, sq.g.zp, rs, C, sq.wd.cx);
-            } else {
-                a.sx[grow] = delta;
-                a.zx[grow] = izx;
-                a.R[grow] = rs - 128 * C - C * izx;
-            }
-        }
+        if (tid < 16 && tq < a.T)
+            rq_write_row(a.sx, a.zx, a.R, nullptr, row0 + (size_t)tq * a.S, gq.g.delta, gq.g.zp, tq_collect_sum(ex_sum, H, tq), C,
+                         gq.wd.cx);
     }
 }
 
@@ -946,9 +768,9 @@ __global__ __launch_bounds__(1024) void attn_temporal_long_kernel(A a) {
     const int nt = (T + 15) >> 4;                  // 16-row tiles holding rows < T (keys and queries)
     const unsigned tstride = (unsigned)a.S * (unsigned)a.ld_in * 2u;          // bytes between the rows t, t + 1 of a position
     const bool quant = ST || a.xq != nullptr;
-    [[maybe_unused]] TqStatic sq;
+    TqGrid gq;                                     // ST: the calibrated grid; else every row's own, behind its statistics
     [[maybe_unused]] int par = 0;                  // ST: which of the two code-sum areas this tile uses
-    if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
+    if constexpr (ST) gq = tq_static(a.delta, a.zp, a.n_bits);
     const int npad = a.Kp / 16 - C / 16;           // 16-byte pad chunks [C, Kp) of a code row
     const unsigned vtro = (unsigned)((4 * g4 + (tq >> 2)) * RSV + 4 * (tq & 3) * 2);   // transpose-read lane offset
     const unsigned kqo = (unsigned)(wave * D + 8 * g4) * 2u;                           // + 64 bytes per k-step
@@ -1024,6 +846,10 @@ __global__ __launch_bounds__(1024) void attn_temporal_long_kernel(A a) {
                     mloc = fmaxf(mloc, sc[kt][r]);
                 }
             }
+            // (the softmax is written out in this kernel - tq_softmax16<4> of attn_rowquant.h is the same arithmetic: with the
+            //  mask and maximum of all four tiles behind the conditional MFMA blocks instead of between them, the static form
+            //  at D = 72 has 2393 instructions against 2345 and its T = 64, S = 1024 time left the band of the written-out
+            //  kernel: median 199.7 us against 196.4 .. 199.6 - profiles/refactor_temporal_steps.md)
             mloc = tq_xor32(tq_xor16(mloc, true), true);
             const float m_use = (mloc == -INFINITY) ? 0.f : mloc;
             float psum = 0.f;
@@ -1046,55 +872,24 @@ __global__ __launch_bounds__(1024) void attn_temporal_long_kernel(A a) {
                 float4v o4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt)
-                    if (kt < nt) {
-                        const h4_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) h4_t*)(vs + kt * 16 * RSV + vtro + dt * 32));
-                        const half4 vf = {(half_t)vt[0], (half_t)vt[1], (half_t)vt[2], (half_t)vt[3]};
-                        o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[kt], o4, 0, 0, 0);
-                    }
+                    if (kt < nt) o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(tq_vt_frag(vs + kt * 16 * RSV + vtro + dt * 32), pf[kt], o4, 0, 0, 0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ov[dt][r] = (half_t)(o4[r] * inv_p);
             }
             const size_t grow = row0 + (size_t)tr * a.S;
-            if (a.o && qrow) {
-                half_t* orow = a.o + grow * a.ld_out + wave * D;
-#pragma unroll
-                for (int dt = 0; dt < KS; ++dt) {
-                    const int d0 = dt * 16 + 4 * g4;
-                    if (d0 < D) *reinterpret_cast<half4*>(orow + d0) = ov[dt];
-                }
-            }
+            if (a.o && qrow) tq_store_o<D>(a.o + grow * a.ld_out + wave * D, ov, g4);
             if (!quant) continue;                  // kernel-uniform
 
             // ---- quantizer of the consuming Linear on the fp16 output (x / s first when it has a smoothing vector)
             auto qin = [&](int dt, float (&x4)[4]) {
-                const int d0 = dt * 16 + 4 * g4;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) x4[r] = (float)ov[dt][r];
-                if (a.s) {                         // kernel-uniform
-                    const float4v s4 = *reinterpret_cast<const float4v*>(a.s + wave * D + d0);
-                    const float4v r4 = *reinterpret_cast<const float4v*>(a.s_rcp + wave * D + d0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) x4[r] = rq_div_rcp(x4[r], s4[r], r4[r]);
-                }
+                tq_div_s(x4, a.s, a.s_rcp, wave * D + dt * 16 + 4 * g4);
             };
-            [[maybe_unused]] float delta, zp, inv;
-            [[maybe_unused]] int izx;
             int* exs = ex_sum;                     // this tile's code sums
-            uint32_t csum = 0;
             if constexpr (ST) {
                 exs = ex_sum - 256 * par;          // (ex_max's area: nothing else uses it here)
                 par ^= 1;
-                uint8_t* xrow = reinterpret_cast<uint8_t*>(a.xq) + grow * (size_t)a.Kp + wave * D;
-                RQ_BY_WIDTH(sq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
-                    const int d0 = dt * 16 + 4 * g4;
-                    if (d0 < D) {
-                        float x4[4];
-                        qin(dt, x4);
-                        const uint32_t pk = tq_static_codes<SAT8_>(x4, sq, csum);
-                        if (qrow) *reinterpret_cast<uint32_t*>(xrow + d0) = pk;
-                    }
-                })
             } else {
                 float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
@@ -1102,61 +897,28 @@ __global__ __launch_bounds__(1024) void attn_temporal_long_kernel(A a) {
                     if (dt * 16 + 4 * g4 < D) {
                         float x4[4];
                         qin(dt, x4);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            vmin = fminf(vmin, x4[r]);
-                            vmax = fmaxf(vmax, x4[r]);
-                        }
+                        tq_minmax4(x4, vmin, vmax);
                     }
-                vmin = tq_xor32(tq_xor16(vmin, false), false);
-                vmax = tq_xor32(tq_xor16(vmax, true), true);
-                if (lane < 16) {
-                    ex_min[wave * 16 + tq] = vmin;
-                    ex_max[wave * 16 + tq] = vmax;
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (raw barrier: __syncthreads() would also wait for the loads in flight)
-                __builtin_amdgcn_s_barrier();                        // the tile's per-head row statistics are visible
-                vmin = INFINITY;
-                vmax = -INFINITY;
-                for (int w = 0; w < H; ++w) {
-                    vmin = fminf(vmin, ex_min[w * 16 + tq]);
-                    vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
-                }
-                bool small;
-                vq_row_grid(vmin, vmax, 255.0f, delta, zp, small, inv);
-                if (small && tid < 16 && qrow && a.status) atomicOr(a.status, VQ_ST_EPSFILL);
-                izx = (int)zp - 128;
-                uint8_t* xrow = reinterpret_cast<uint8_t*>(a.xq) + grow * (size_t)a.Kp + wave * D;
-#pragma unroll
-                for (int dt = 0; dt < KS; ++dt) {
-                    const int d0 = dt * 16 + 4 * g4;
-                    if (d0 < D) {
-                        uint32_t pk = 0;
-                        float x4[4], c4[4];
-                        qin(dt, x4);
-                        rq_round_group<4>(x4, inv, delta, zp, c4);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) pk = __builtin_amdgcn_cvt_pk_u8_f32(c4[r], r, pk);
-                        csum = __builtin_amdgcn_sad_u8(pk, 0u, csum);
-                        if (qrow) *reinterpret_cast<uint32_t*>(xrow + d0) = pk ^ 0x80808080u;
-                    }
-                }
+                tq_publish_minmax(vmin, vmax, ex_min, ex_max, wave, lane);
+                tq_lds_barrier();                  // the tile's per-head row statistics are visible
+                gq = tq_row_grid(ex_min, ex_max, H, tq, tid < 16 && qrow, a.status);
             }
-            const int cs = tq_isum4rows((int)csum);
-            if (lane < 16) exs[wave * 16 + tq] = cs;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();        // code sums visible; every wave has read ex_min / ex_max of this tile
-            if (tid < 16 && qrow) {
-                int rs = 0;
-                for (int w = 0; w < H; ++w) rs += exs[w * 16 + tq];
-                if constexpr (ST) {
-                    rq_write_row(a.sx, a.zx, a.R, nullptr, grow, sq.g.delta, sq.g.zp, rs, C, sq.wd.cx);
-                } else {
-                    a.sx[grow] = delta;
-                    a.zx[grow] = izx;
-                    a.R[grow] = rs - 128 * C - C * izx;
+            // codes leave straight from the registers
+            uint8_t* xrow = reinterpret_cast<uint8_t*>(a.xq) + grow * (size_t)a.Kp + wave * D;
+            uint32_t csum = 0;
+            RQ_BY_WIDTH(gq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
+                const int d0 = dt * 16 + 4 * g4;
+                if (d0 < D) {
+                    float x4[4];
+                    qin(dt, x4);
+                    const uint32_t pk = tq_codes<ST, SAT8_>(x4, gq, csum);
+                    if (qrow) *reinterpret_cast<uint32_t*>(xrow + d0) = pk;
                 }
-            }
+            })
+            tq_publish_sum(csum, exs, wave, lane);
+            tq_lds_barrier();                      // code sums visible; every wave has read ex_min / ex_max of this tile
+            if (tid < 16 && qrow)
+                rq_write_row(a.sx, a.zx, a.R, nullptr, grow, gq.g.delta, gq.g.zp, tq_collect_sum(exs, H, tq), C, gq.wd.cx);
             for (int c = tid; c < 16 * npad; c += nthr) {       // pad columns [C, Kp) zeroed like the row quantizers do
                 const int t = c / npad, ch = c - t * npad;
                 if (16 * qt + t < T) {
@@ -1400,7 +1162,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_fwd32d_kernel(A
     const int g = lane >> 5, l31 = lane & 31;
     int qt, h, seq;
     if (!attn_xcd_map(a, 32 * NW, qt, h, seq)) return;
-    [[maybe_unused]] TqStatic sq;
+    [[maybe_unused]] TqGrid sq;
     if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
     const int kv_len = a.Lk;
     const half_t* kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
@@ -1523,7 +1285,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd64d_kernel(A a) {
     const int g = lane >> 5, l31 = lane & 31;
     int qt, h, seq;
     if (!attn_xcd_map(a, 32 * NQ * NW, qt, h, seq)) return;
-    [[maybe_unused]] TqStatic sq;
+    [[maybe_unused]] TqGrid sq;
     if constexpr (ST) sq = tq_static(a.delta, a.zp, a.n_bits);
     const int kv_len = a.Lk;
     const half_t* kbase = a.k + (long)seq * a.kv_seq_stride + h * D;
@@ -1806,7 +1568,7 @@ __global__ __launch_bounds__(64 * NW, NT == 2 ? 32 / NW : 16 / NW) void attn_cro
                 // (the stores and loads behind the Q DMA in flight are not a fixed number here: the next tile waits for all)
                 // (the grid is read per tile - one scalar load and a division - not held in registers across the walk)
                 if (a.o) attn_store_rows<D, C::DT>(oacc, inv, orow, g, qi < a.Lq);   // kernel-uniform
-                const TqStatic sq = tq_static(a.delta, a.zp, a.n_bits);
+                const TqGrid sq = tq_static(a.delta, a.zp, a.n_bits);
                 attn_quant_rows<D, C::DT>(oacc, inv, a, sq, seq * a.Lq + (qi < a.Lq ? qi : a.Lq - 1), h, g, qi < a.Lq);
                 stores_behind = 0;
             } else {
@@ -2200,17 +1962,14 @@ static int launch_temporal_quant(const A& a, hipStream_t st, bool trimmed) {
     const int LDS = 16 * (C * 2 + 16) + 16 * (C + 16) + 3 * 1024;
     constexpr int LDS_MAX = 16 * (16 * 72 * 2 + 16) + 16 * (16 * 72 + 16) + 3 * 1024;
     constexpr auto k2 = attn_temporal_quant2_kernel<D, A>;
-    constexpr auto k16 = attn_temporal_quant_kernel<D, 16, A>;
-    constexpr auto k0 = attn_temporal_quant_kernel<D, 0, A>;
+    constexpr auto k1 = attn_temporal_quant_kernel<D, A>;
     int ncu = 0;
-    if (const int rc = trimmed ? vq_prepare_kernel<k2>(LDS_MAX, &ncu)
-                               : a.H == 16 ? vq_prepare_kernel<k16>(LDS_MAX, &ncu) : vq_prepare_kernel<k0>(LDS_MAX, &ncu))
-        return rc;
+    if (const int rc = trimmed ? vq_prepare_kernel<k2>(LDS_MAX, &ncu) : vq_prepare_kernel<k1>(LDS_MAX, &ncu)) return rc;
     // persistent: a 1024-thread workgroup at up to 128 VGPRs owns its CU; small problems get one position each
     const int npos = a.S * a.B;
     const int per_cu = a.H > 8 ? 1 : (LDS > 80 * 1024 ? 1 : (LDS > 52 * 1024 ? 2 : 3));
     const int grid = npos < ncu * per_cu ? npos : ncu * per_cu;
-    hipLaunchKernelGGL(trimmed ? k2 : a.H == 16 ? k16 : k0, dim3(grid), dim3(64 * a.H), LDS, st, a);
+    hipLaunchKernelGGL(trimmed ? k2 : k1, dim3(grid), dim3(64 * a.H), LDS, st, a);
     return vq_check_launch();
 }
 

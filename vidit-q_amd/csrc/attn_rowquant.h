@@ -5,24 +5,34 @@
 // g4 = lane >> 4).  S^T = K Q^T leaves lane (tq, g4) with keys 16 kt + 4 g4 .. + 3 of query tq; O^T = V^T P^T leaves it
 // with dims 16 dt + 4 g4 .. + 3 of token tq.  A token's quantizer needs its whole row (all heads): every wave reduces its
 // head's part over its four 16-lane rows, the parts meet in LDS (ex_min / ex_max / ex_sum: [wave][16] each, between two
-// s_waitcnt lgkmcnt(0) + s_barrier pairs), and every wave derives the same grid from them.  The contract: codes, scale,
-// zero point and row sum are bit-identical to vq_rowquant of the kernel's own fp16 output (vq_row_grid / rq_round_group).
+// tq_lds_barrier()s), and every wave derives the same grid from them.  The contract: codes, scale, zero point and row
+// sum are bit-identical to vq_rowquant of the kernel's own fp16 output.
 //
-// Only the row reductions live here.  The softmax / x / s / min-max / encode / record steps are still written out in
-// each kernel: behind __forceinline__ helpers hipcc selects other instructions and allocates other registers for the
-// same arithmetic (the callee is simplified on its own before it is inlined), up to +12 VGPRs and +4 bytes of scratch -
-// profiles/refactor_attn_isa.md has the figures per helper.  A fourth kernel of this kind should start from there.
+// Every step of a position that does not depend on a kernel's load schedule or LDS map is written ONCE here and used by
+// all three kernels in both of their forms (one exception, measured: the long kernel keeps its softmax written out, see
+// there): the masked 16-key softmax (tq_softmax16), the V^T operand (tq_vt_frag), the
+// optional fp16 copy (tq_store_o), x / s (tq_div_s), the row statistics of the dynamic grid (tq_minmax4 /
+// tq_publish_minmax / tq_row_grid), the encode (tq_codes), the code-sum exchange (tq_publish_sum / tq_collect_sum), the
+// record (rq_write_row of rowquant_shared.h) and the LDS barrier.  The kernels keep their load schedules, LDS maps, the
+// place of their barriers, the O^T accumulation and the way codes leave.
+// NOT shared: the reciprocal of the softmax row sum.  tq_softmax16 returns the sum and the caller inverts it - IEEE
+// __fdiv_rn in the first-generation kernel, v_rcp_f32 (1 ulp) in the other two - because the fp16 output of each kernel
+// is pinned bit for bit and the two differ in that ulp.
+// (hipcc simplifies a forced-inline callee on its own before it inlines it, so these kernels do not compile to the
+//  instruction streams of their written-out forms: profiles/refactor_attn_isa.md has what moved at the first attempt,
+//  profiles/refactor_temporal_steps.md the resources and the timing on the MI355X that this form was accepted on.)
 //
-// The static-grid forms (the three kernels instantiated on TempQSArgs; vq_attn_temporal_rowquant_static) quantize every row
-// on ONE calibrated grid (delta, zp: one fp32 value each, read on the device) at a code width of 2..8 bits: no row
+// One grid type, TqGrid, serves both forms.  The dynamic form (TempQArgs) derives it per row from the row's min / max
+// (vq_row_grid, 8 bits) and encodes with rq_quant; the static form (TempQSArgs; vq_attn_temporal_rowquant_static) reads
+// ONE calibrated grid (delta, zp: one fp32 value each, read on the device) at a code width of 2..8 bits: no row
 // min / max, hence no ex_min / ex_max exchange, no vq_row_grid, no eps fill and no status word; only the row sum still
-// crosses the heads (ex_sum).  Their codes are rqs_grid / rqs_quant of rowquant_shared.h - rq_round_group's bound needs
-// the row's own grid - and bit-identical to vq_rowquant(delta_in, zp_in, n_param = 1) of the kernel's own fp16 output.
-// Everything the static arm adds sits in the helpers at the end of this file: the arm is an ``if constexpr`` of each
-// kernel, so the dynamic instantiations compile to what they were (profiles/static_quant/attn_resources.md).
+// crosses the heads.  Its codes are rqs_grid / rqs_quant of rowquant_shared.h - rq_round_group's bound needs the row's
+// own grid - and bit-identical to vq_rowquant(delta_in, zp_in, n_param = 1) of the kernel's own fp16 output.
 #pragma once
 #include "vq_common.h"
 #include "rowquant_shared.h"
+
+typedef __fp16 h4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));   // operand type of the LDS transpose read
 
 // ---- reductions over the four 16-lane rows of a wave (all 64 lanes receive the result) -------------------------------
 // (the swap builtins return a 2-vector: its elements are copied into scalars before any __builtin_bit_cast - written on the
@@ -62,27 +72,162 @@ __device__ __forceinline__ int tq_isum4rows(int x) {
     return (int)r[0] + (int)r[1];
 }
 
-// ---- the static-grid arm ----------------------------------------------------------------------------------------------
-struct TqStatic {
+// ---- the LDS barrier of the position loops ----------------------------------------------------------------------------
+// (raw: __syncthreads() also waits for vmcnt(0), i.e. for the global loads in flight for the next positions - that
+//  serialised every iteration behind one HBM round trip)
+__device__ __forceinline__ void tq_lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+}
+
+// ---- softmax of one query over NKT tiles of 16 keys ---------------------------------------------------------------------
+// sc[kt][r]: the score of key 16 kt + 4 g4 + r (keys >= T are masked here); pf: exp2((s - m) c) as the fp16 B operand
+// of O^T = V^T P^T.  Returns the sum of the fp32 exponentials over all keys of the query (every lane of the query's
+// column has it); a fully masked query (no row tq < T feeds it) gets m = 0, p = 0 and the sum 0.
+template <int NKT>
+__device__ __forceinline__ float tq_softmax16(float4v (&sc)[NKT], int g4, int T, float c, half4 (&pf)[NKT]) {
+    float mloc = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (16 * kt + 4 * g4 + r >= T) sc[kt][r] = -INFINITY;
+            mloc = fmaxf(mloc, sc[kt][r]);
+        }
+    mloc = tq_xor32(tq_xor16(mloc, true), true);
+    const float m_use = (mloc == -INFINITY) ? 0.f : mloc;
+    float psum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float p = __builtin_amdgcn_exp2f((sc[kt][r] - m_use) * c);
+            psum += p;
+            pf[kt][r] = (half_t)p;
+        }
+    return tq_sum4rows(psum);
+}
+
+// ---- the V^T operand of O^T = V^T P^T ------------------------------------------------------------------------------------
+// (dim tq, keys 4 g4 .. + 3) by ONE LDS transpose read of a row-major tile: lane i of a 16-lane group points at
+// [key 4 g4 + i / 4][dims 16 dt + 4 (i % 4) .. + 3] - p, the caller's LDS map - and receives column i of the 4 x 16 block
+// (four 2-byte reads and their packing before).  Dims >= D of the last tile read whatever lies behind the head's
+// columns: finite values in output rows nobody stores.
+__device__ __forceinline__ half4 tq_vt_frag(const uint8_t* p) {
+    const h4_t vt = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4_t*)p);
+    return half4{(half_t)vt[0], (half_t)vt[1], (half_t)vt[2], (half_t)vt[3]};
+}
+
+// ---- the optional fp16 copy of a 16-query tile: this lane's dims 16 dt + 4 g4 .. + 3 of its token's head ---------------
+// (ov: the fp16-rounded output, held as fp32 or as half4)
+template <int D, class V>
+__device__ __forceinline__ void tq_store_o(half_t* orow, const V (&ov)[(D + 15) / 16], int g4) {
+#pragma unroll
+    for (int dt = 0; dt < (D + 15) / 16; ++dt) {
+        const int d0 = dt * 16 + 4 * g4;
+        if (d0 < D) {
+            half4 o4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o4[r] = (half_t)ov[dt][r];
+            *reinterpret_cast<half4*>(orow + d0) = o4;
+        }
+    }
+}
+
+// ---- the quantizer's input: x / s of the consuming Linear's smoothing vector when it has one ----------------------------
+// (quant_layer.py:140; reciprocal form, bit-identical to the IEEE quotient - vq_common.h.)  ch: the channel of x4[0].
+template <class V>                                 // V: float[4] or float4v
+__device__ __forceinline__ void tq_div_s(V& x4, const float* s, const float* s_rcp, int ch) {
+    if (s) {                                       // kernel-uniform
+        const float4v s4 = *reinterpret_cast<const float4v*>(s + ch);
+        const float4v r4 = *reinterpret_cast<const float4v*>(s_rcp + ch);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x4[r] = rq_div_rcp(x4[r], s4[r], r4[r]);
+    }
+}
+
+// ---- one grid for both forms ---------------------------------------------------------------------------------------------
+struct TqGrid {
     RqWidth wd;        // last level, int8 offset (128 at 8 bits only) and its packed form
-    RqsGrid g;         // the calibrated grid and the tie guard of its product form
+    RqsGrid g;         // step, zero point, reciprocal; thr: the tie guard of the static product form (unused by the dynamic one)
 };
 // (kernel-uniform values computed by the VALU: handed to scalar registers, they are live for the whole position loop)
 __device__ __forceinline__ float tq_uniform(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
 }
-__device__ __forceinline__ TqStatic tq_static(const float* delta, const float* zp, int n_bits) {
-    TqStatic q;
+// the static form's grid: once per kernel
+__device__ __forceinline__ TqGrid tq_static(const float* delta, const float* zp, int n_bits) {
+    TqGrid q;
     q.wd = rq_width(n_bits);
     q.g = rqs_grid(delta, zp, 0, q.wd.qmax);
     q.g.delta = tq_uniform(q.g.delta), q.g.zp = tq_uniform(q.g.zp), q.g.inv = tq_uniform(q.g.inv), q.g.thr = tq_uniform(q.g.thr);
     return q;
 }
-// four values of one lane -> their dword of codes as stored (offset applied); csum += the raw codes
+
+// ---- row statistics of the dynamic form ----------------------------------------------------------------------------------
+template <class V>
+__device__ __forceinline__ void tq_minmax4(const V& x4, float& vmin, float& vmax) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        vmin = fminf(vmin, x4[r]);
+        vmax = fmaxf(vmax, x4[r]);
+    }
+}
+// this head's min / max of token tq: reduced over the wave's four rows, published for the other heads
+__device__ __forceinline__ void tq_publish_minmax(float vmin, float vmax, float* ex_min, float* ex_max, int wave, int lane) {
+    vmin = tq_xor32(tq_xor16(vmin, false), false);
+    vmax = tq_xor32(tq_xor16(vmax, true), true);
+    if (lane < 16) {
+        ex_min[wave * 16 + lane] = vmin;
+        ex_max[wave * 16 + lane] = vmax;
+    }
+}
+// (behind the barrier) token tq's min / max over the H heads -> its 8-bit grid, as vq_rowquant derives it; ``flag``: this
+// lane reports the row's eps fill (one lane per stored row)
+__device__ __forceinline__ TqGrid tq_row_grid(const float* ex_min, const float* ex_max, int H, int tq, bool flag, int32_t* status) {
+    float vmin = INFINITY, vmax = -INFINITY;
+    for (int w = 0; w < H; ++w) {
+        vmin = fminf(vmin, ex_min[w * 16 + tq]);
+        vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
+    }
+    TqGrid q;
+    q.wd = rq_width(8);
+    q.g.thr = 0.f;
+    bool small;
+    vq_row_grid(vmin, vmax, q.wd.qmax, q.g.delta, q.g.zp, small, q.g.inv);
+    if (small && flag && status) atomicOr(status, VQ_ST_EPSFILL);
+    return q;
+}
+
+// ---- encode: four values of one lane -> their dword of codes as stored (offset applied); csum += the raw codes ----------
+// (SAT8: inside RQ_BY_WIDTH(q.wd.qmax, ...), once around the caller's loop; the dynamic form's width is a constant, so
+//  its other arm folds away)
 template <bool SAT8>
-__device__ __forceinline__ uint32_t tq_static_codes(const float (&x4)[4], const TqStatic& q, uint32_t& csum) {
+__device__ __forceinline__ uint32_t tq_static_codes(const float (&x4)[4], const TqGrid& q, uint32_t& csum) {
     uint32_t pk[1];
     rqs_quant<4, SAT8>(x4, q.g, q.wd.qmax, pk);
     csum = __builtin_amdgcn_sad_u8(pk[0], 0u, csum);
     return pk[0] ^ q.wd.flip;
+}
+template <bool ST, bool SAT8>
+__device__ __forceinline__ uint32_t tq_codes(const float (&x4)[4], const TqGrid& q, uint32_t& csum) {
+    if constexpr (ST) {
+        return tq_static_codes<SAT8>(x4, q, csum);
+    } else {
+        uint32_t pk[1];
+        rq_quant<4, SAT8>(x4, q.g.inv, q.g.delta, q.g.zp, q.wd.qmax, pk);   // one tie test per four codes, packed fp32 math
+        csum = __builtin_amdgcn_sad_u8(pk[0], 0u, csum);
+        return pk[0] ^ q.wd.flip;
+    }
+}
+
+// ---- code-sum exchange: this head's part of token tq's row sum into exs[wave][16]; (behind the barrier) the row's sum ----
+__device__ __forceinline__ void tq_publish_sum(uint32_t csum, int* exs, int wave, int lane) {
+    const int cs = tq_isum4rows((int)csum);
+    if (lane < 16) exs[wave * 16 + lane] = cs;
+}
+__device__ __forceinline__ int tq_collect_sum(const int* exs, int H, int tq) {
+    int rs = 0;
+    for (int w = 0; w < H; ++w) rs += exs[w * 16 + tq];
+    return rs;
 }

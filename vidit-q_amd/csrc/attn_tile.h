@@ -38,8 +38,6 @@ struct AttnQSArgs : AttnArgs {
     int Kp, n_bits;                                // n_bits 2 .. 8
 };
 
-typedef __fp16 h4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));   // operand type of the LDS transpose read
-
 // ---- geometry ----------------------------------------------------------------------------------------------------------
 // Workgroup -> (sequence, head, query tile of `wg_rows` queries).  Workgroups are dealt round-robin to the 8 XCDs; XCD x
 // takes a CONTIGUOUS range of the (sequence, head) pairs and runs the query tiles of a pair back to back, so a pair's
@@ -378,7 +376,7 @@ __device__ __forceinline__ void attn_store_rows(const float16v (&oacc)[DT], floa
 // (the swap builtin returns a 2-vector: its elements are copied into scalars before they are used - attn_rowquant.h)
 template <int D, int DT, bool SAT8>
 __device__ __forceinline__ uint32_t attn_quant_codes(const float16v (&oacc)[DT], float inv, const float* s, const float* s_rcp,
-                                                     const TqStatic& sq, int8_t* xrow, int g, bool row_ok) {
+                                                     const TqGrid& sq, int8_t* xrow, int g, bool row_ok) {
     static_assert(D % 8 == 0 && D >= 16, "8-dim groups, 8-byte code stores");
     constexpr int NG = D / 8;                           // 8-dim groups: dt = grp / 4, rg = grp % 4
     uint32_t csum = 0;
@@ -415,7 +413,7 @@ __device__ __forceinline__ uint32_t attn_quant_codes(const float16v (&oacc)[DT],
 // wave-instruction.  Integer adds commute, so R is bit-reproducible.  sx / zx: the head-0 workgroups; the pad columns
 // [H * D, Kp): the last head's.  Rows with !row_ok (clamped duplicates of row Lq - 1) write and add nothing.
 template <int D, int DT>
-__device__ __forceinline__ void attn_quant_rows(const float16v (&oacc)[DT], float inv, const AttnQSArgs& a, const TqStatic& sq,
+__device__ __forceinline__ void attn_quant_rows(const float16v (&oacc)[DT], float inv, const AttnQSArgs& a, const TqGrid& sq,
                                                 int row, int h, int g, bool row_ok) {
     // (the addresses below are derived HERE: inside attn_cross32_kernel's walk the compiler otherwise computes every one of
     //  them once in front of the loop and keeps them - ~30 VGPRs of lane pointers, spilled - for its whole length)
