@@ -38,6 +38,17 @@ def _req(t: torch.Tensor, dtype, name: str):
     return t
 
 
+def _req_rows(t: torch.Tensor, dtype, name: str):
+    """As _req, for an operand whose rows may be strided: only the last dimension has to be dense."""
+    if not t.is_cuda:
+        raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % name)
+    if t.dtype != dtype:
+        raise VQError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    if t.stride(-1) != 1:
+        raise VQError("%s must be contiguous in its last dimension" % name)
+    return t
+
+
 def pad128(k: int) -> int:
     return (k + 127) // 128 * 128
 
@@ -828,9 +839,10 @@ ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 def linear_f16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act_in: int = ACT_NONE,
                act_out: int = ACT_NONE) -> torch.Tensor:
     """act_out(act_in(x) @ w.T + bias) for the FP edge Linears (embedders, t_block, final layer, patch embedding as a
-    matmul): x [..., K] fp16 (last dim contiguous), w [N, K] fp16, bias [N] fp16; fp32 accumulation, fp16 result."""
-    _req(x, torch.float16, "x")
-    _req(w, torch.float16, "w")
+    matmul): x [..., K] fp16, w [N, K] fp16, bias [N] fp16; fp32 accumulation, fp16 result.  Rows of x and w may be
+    further apart than K (a column slice of a wider matrix): the kernel takes both pitches."""
+    _req_rows(x, torch.float16, "x")
+    _req_rows(w, torch.float16, "w")
     K = x.shape[-1]
     N = w.shape[0]
     assert w.dim() == 2 and w.shape[1] == K and w.stride(1) == 1
