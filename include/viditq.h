@@ -275,6 +275,36 @@ int vq_gemm_i8_grouped(int ngroups, const int8_t* const* xq, const float* const*
                        const int32_t* const* zw, const int32_t* const* cs, const float* const* bias, void* out,
                        int ldo, int M, int N, int K, int Kp, int w_bits, void* stream);
 
+/* mlp.fc1 with GELU(tanh) AND the STATIC (calibrated, tensor-wise) activation quantizer of mlp.fc2 in the GEMM's epilogue:
+ * replaces F.linear(x_hat, W_hat, bias) (qdiff/models/quant_layer.py:211) + nn.GELU(approximate="tanh")
+ * (t2v/opensora/models/layers/blocks.py:27; modules.py:57) + ActQuantizer.forward after init_done
+ * (qdiff/quantizer/base_quantizer.py:129-144) behind the smooth-quant division of the consuming Linear
+ * (quant_layer.py:136-140).  The fp16 activation [M, N] is never written: every output element is rounded to fp16 as
+ * vq_gemm_i8(VQ_EPI_GELU) would store it and quantized where it sits.
+ * xq .. bias, M, N, K, Kp, w_bits, variant: as vq_gemm_i8 (8-bit weight storage only: 4 < w_bits <= 8).
+ * s / s_rcp: both null, or the consuming Linear's smooth-quant channel scale per OUTPUT column [N] and its reciprocal from
+ *   vq_smooth_reciprocal (the division exists in reciprocal form only here; s_rcp without s is ignored).
+ * delta, zp: ONE fp32 value each in device memory, read by the kernel (no host synchronisation: graph-capturable); zp
+ *   integer-valued, delta > 0.  n_bits 2..8.  No status word (no eps fill on a calibrated grid).
+ * Contract: xq_out [M, Kp_out] (codes - 128 at 8 bits, raw codes below; pad columns [N, Kp_out) zero), sx_out[r] = delta,
+ *   zx_out[r] = (int)zp - cx and R_out[r] = sum(raw codes) - N * (int)zp are bit-identical to
+ *   vq_rowquant(..., s, s_rcp, delta_in = delta, zp_in = zp, n_param = 1) of the fp16 matrix vq_gemm_i8(..., VQ_EPI_GELU,
+ *   variant) writes, for every variant.  R_out is zeroed by this call on `stream` before the launch (a small kernel; every
+ *   wave adds its columns' part of a row's term with one relaxed integer atomic per row): callers do not pre-zero, and
+ *   R_out is bit-reproducible.
+ * variant: VQ_GEMM_DEFAULT, 11, 16 or 19 with the meaning (and 19's conditions: M % 256 == 0, N % 288 == 0) of vq_gemm_i8.
+ * Errors, all before any HIP call or dereference, null pointers first: VQ_EINVAL for a null required pointer (all but
+ *   bias, s, s_rcp) or a non-positive extent; VQ_ESHAPE for what vq_gemm_i8 refuses (Kp % 128, Kp < K, K > 16384, an
+ *   operand image of 2^32 bytes or more), N % 8, Kp_out % 128, Kp_out < N, xq_out / s / s_rcp off 16 bytes, variant 19's
+ *   conditions; VQ_EUNSUP for w_bits <= 4 or > 8, n_bits outside 2..8, s without s_rcp, an unknown variant. */
+int vq_gemm_i8_rowquant_static(const int8_t* xq, const float* sx, const int32_t* zx, const int32_t* R,
+                               const void* wq, const float* sw, const int32_t* zw, const int32_t* cs,
+                               const float* bias, const float* s, const float* s_rcp,
+                               const float* delta, const float* zp,
+                               int8_t* xq_out, float* sx_out, int32_t* zx_out, int32_t* R_out,
+                               int M, int N, int K, int Kp, int Kp_out, int w_bits, int n_bits,
+                               int variant, void* stream);
+
 /* ---- fp16 attention (fp32 online softmax) -----------------------------------
  * Replaces flash_attn_func / the softmax branch of Attention.forward
  * (opensora/models/layers/blocks.py:169-187), xformers block-diagonal

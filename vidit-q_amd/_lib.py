@@ -42,6 +42,7 @@ SIGNATURES = {
     "vq_gemm_i8_grouped": (_i, [_i] + [_vp] * 10 + [_i] * 6 + [_vp]),
     "vq_gemm_i8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp,
                         _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vq_gemm_i8_rowquant_static": (_i, [_vp] * 17 + [_i] * 8 + [_vp]),
     "vq_gemm_i8_stamped": (_i, [_vp] * 10 + [_i] * 5 + [_vp, _l, _vp]),
     "vq_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _l, _l, _l, _l, _vp, _f, _vp]),
     "vq_attn_fwd_route": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _l, _l, _l, _l, _vp, _f, _vp]),

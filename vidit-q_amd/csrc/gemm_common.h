@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "vq_common.h"
+#include "attn_rowquant.h"   // tq_isum4rows; rowquant_shared.h: rqs_grid / rqs_quant, the one copy of the static rounding rule
 
 template <int BK>
 __device__ __forceinline__ int swz(int row) {
@@ -527,5 +528,190 @@ __device__ __forceinline__ void ring_epilogue(const GemmArgs& a, uint8_t* smem,
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ts[6] = __builtin_readcyclecounter();
         ts[8] = wall_clock64();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Quantizing epilogue (vq_gemm_i8_rowquant_static): GELU(tanh), rounded to fp16 as VQ_EPI_GELU stores it, then the
+// STATIC tensor-wise quantizer of the Linear that consumes the output - never the fp16 matrix itself.  (delta, zp) is known
+// before the launch, so every accumulator element is quantized where it sits; only the integer row sum crosses waves
+// and workgroups (one relaxed agent-scope atomic per row and wave: integer adds commute, R is bit-reproducible).
+// Internal epilogue id of the kernel templates; vq_gemm_i8 does not accept it.
+// ---------------------------------------------------------------------------------------------------------------
+#define VQ_EPI_GELU_QUANT 8
+struct GemmQArgs : GemmArgs {
+    const float* qs;       // smoothing vector of the consuming Linear per output column [N], or null
+    const float* qs_rcp;   // RN(1 / qs) (set whenever qs is)
+    const float* qdelta;   // one fp32 each, read on the device
+    const float* qzp;
+    int8_t* qxq;           // [M, Kp_out] codes - cx, pad columns [N, Kp_out) zero
+    float* qsx;
+    int32_t* qzx;
+    int32_t* qR;           // zeroed in front of the launch
+    int Kp_out, n_bits;
+};
+
+// The smoothing vector of a tile's BN columns travels like the channel parameters: one column per thread, loaded with them,
+// parked in the 8 * BN bytes in front of the parameter block.  The codes' slabs (below) end far in front of it.
+struct SmoothParams {
+    float s, r;
+};
+template <int BN>
+__device__ __forceinline__ SmoothParams ring_load_smooth(const GemmQArgs& a, int n0, int tid) {
+    SmoothParams p{1.0f, 1.0f};
+    if (a.qs && tid < BN && n0 + tid < a.N) {
+        p.s = a.qs[n0 + tid];
+        p.r = a.qs_rcp[n0 + tid];
+    }
+    return p;
+}
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+__device__ __forceinline__ void ring_park_smooth(const GemmQArgs& a, const SmoothParams& p, uint8_t* smem, int tid) {
+    constexpr int QS_OFF = WAVES_M * WAVES_N * (BM / WAVES_M) * ((BN / WAVES_N) * 2 + 16) - 8 * BN;
+    static_assert(BN <= 64 * WAVES_M * WAVES_N, "one column per thread");
+    if (a.qs && tid < BN) {
+        reinterpret_cast<float*>(smem + QS_OFF)[tid] = p.s;
+        reinterpret_cast<float*>(smem + QS_OFF)[BN + tid] = p.r;
+    }
+}
+
+// Called like ring_epilogue (after the barrier that publishes the parameter blocks, which lie where the fp16 epilogues keep
+// them).  A lane holds four consecutive columns of one row per (i, j): rqs_quant<4> -> one dword of codes, written to the
+// wave's LDS slab, which is LINEAR (row pitch WTN bytes, no pad: 2-way write conflicts as the fp16 slabs have, conflict-free
+// 16-byte reads); the store pass moves it as 16-byte chunks of 16 codes, WTN / 16 per row.  INTERIOR: every tile of the
+// launch lies inside the matrix (the launcher checks) - no bounds in the kernel.  Otherwise columns >= N and rows >= M
+// neither store nor count (N % 8 == 0: a lane's four columns and a chunk's halves are inside or outside together).
+// sx / zx: the workgroups of the first column tile; pad columns: those of the last.
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool INTERIOR>
+__device__ __forceinline__ void ring_epilogue_quant(const GemmQArgs& a, uint8_t* smem,
+                                                    int4v (&acc)[BN / WAVES_N / 16][BM / WAVES_M / 16], int m0, int n0,
+                                                    int tid) {
+    constexpr int NW = WAVES_M * WAVES_N, NT = 64 * NW;
+    constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
+    constexpr int TM = WTM / 16, TN = WTN / 16;
+    constexpr int PAR_OFF = NW * WTM * (WTN * 2 + 16), QS_OFF = PAR_OFF - 8 * BN;
+    constexpr int SLAB = WTM * WTN;
+    constexpr int CPR = WTN / 16, NCH = WTM * CPR, NITER = (NCH + 63) / 64;
+    static_assert(WTN % 16 == 0 && NW * SLAB <= QS_OFF, "whole chunks; slabs in front of the smoothing vector");
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    const int frow = lane & 15, fc = lane >> 4;
+    const float* l_sw = reinterpret_cast<const float*>(smem + PAR_OFF);
+    const int* l_nzw = reinterpret_cast<const int*>(smem + PAR_OFF) + BN;
+    const int* l_cs = reinterpret_cast<const int*>(smem + PAR_OFF) + 2 * BN;
+    const float* l_b = reinterpret_cast<const float*>(smem + PAR_OFF) + 3 * BN;
+    const float* l_sx = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN);
+    const int* l_nzx = reinterpret_cast<const int*>(smem + PAR_OFF + 16 * BN) + BM;
+    const int* l_R = reinterpret_cast<const int*>(smem + PAR_OFF + 16 * BN) + 2 * BM;
+    const float* l_qs = reinterpret_cast<const float*>(smem + QS_OFF);
+    uint8_t* slab = smem + wave * SLAB;
+    const int mrow0 = m0 + wm * WTM, ncol0 = n0 + wn * WTN;
+
+    const RqWidth wd = rq_width(a.n_bits);
+    RqsGrid g = rqs_grid(a.qdelta, a.qzp, 0, wd.qmax);
+    g.delta = tq_uniform(g.delta), g.zp = tq_uniform(g.zp), g.inv = tq_uniform(g.inv), g.thr = tq_uniform(g.thr);
+    const bool smooth = a.qs != nullptr;              // kernel-uniform
+
+    float sxm[TM];
+    int nzx[TM], Rm[TM];                              // (the bit patterns of V = sx * (-zx) and U = sx * R: ring_dequant<true>)
+    uint32_t csum[TM];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int rl = wm * WTM + i * 16 + frow;
+        sxm[i] = l_sx[rl];
+        nzx[i] = l_nzx[rl];
+        Rm[i] = l_R[rl];
+        csum[i] = 0;
+    }
+    // one kernel-uniform branch on the code width and one on the smoothing vector around the whole phase
+    auto phase = [&](auto sat8, auto sm) {
+        constexpr bool SAT8_ = decltype(sat8)::value, SM_ = decltype(sm)::value;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int nl = wn * WTN + j * 16 + 4 * fc;
+            const float4v fsw_ = *reinterpret_cast<const float4v*>(l_sw + nl);
+            const int4v nzw = *reinterpret_cast<const int4v*>(l_nzw + nl);
+            const int4v ics = *reinterpret_cast<const int4v*>(l_cs + nl);
+            const float4v fb = *reinterpret_cast<const float4v*>(l_b + nl);
+            float4v s4 = {1.f, 1.f, 1.f, 1.f}, r4 = {1.f, 1.f, 1.f, 1.f};
+            if constexpr (SM_) {
+                s4 = *reinterpret_cast<const float4v*>(l_qs + nl);
+                r4 = *reinterpret_cast<const float4v*>(l_qs + BN + nl);
+            }
+            const bool col_ok = INTERIOR || n0 + nl < a.N;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                float x4[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float y = ring_dequant<true>(acc[j][i][e], sxm[i], nzx[i], Rm[i], fsw_[e], nzw[e], ics[e], fb[e]);
+                    y = gelu_tanh_f(y);
+                    x4[e] = (float)(half_t)y;         // the value VQ_EPI_GELU stores: the quantizer's input
+                    if constexpr (SM_) x4[e] = rq_div_rcp(x4[e], s4[e], r4[e]);
+                }
+                uint32_t pk[1];
+                rqs_quant<4, SAT8_>(x4, g, wd.qmax, pk);
+                const uint32_t cs1 = __builtin_amdgcn_sad_u8(pk[0], 0u, csum[i]);
+                csum[i] = col_ok ? cs1 : csum[i];
+                asm volatile("" : "+v"(csum[i]));     // summed HERE: left to the scheduler, the codes were held (spilled) to the end of the phase
+                *reinterpret_cast<uint32_t*>(slab + (i * 16 + frow) * WTN + j * 16 + 4 * fc) = pk[0] ^ wd.flip;
+            }
+        }
+    };
+    if (wd.qmax == 255.0f) {
+        if (smooth) phase(std::true_type{}, std::true_type{});
+        else phase(std::true_type{}, std::false_type{});
+    } else {
+        if (smooth) phase(std::false_type{}, std::true_type{});
+        else phase(std::false_type{}, std::false_type{});
+    }
+    // store pass: this wave's slab as row-major 16-byte chunks (same wave wrote it: LDS operations are in order); the last
+    // pass is masked where the slab is no whole number of passes (32-row wave tiles: 288 chunks)
+    {
+        uint8_t* obase = reinterpret_cast<uint8_t*>(a.qxq) + ((size_t)mrow0 * a.Kp_out + ncol0);   // wave-uniform
+#pragma unroll
+        for (int it = 0; it < NITER; ++it) {
+            const int c = lane + it * 64;
+            if (NCH % 64 != 0 && it == NITER - 1 && c >= NCH) continue;
+            const int row = c / CPR, cc = c - row * CPR;
+            const int4v v = *reinterpret_cast<const int4v*>(slab + c * 16);
+            uint8_t* dst = obase + (uint32_t)(row * a.Kp_out + cc * 16);
+            if constexpr (INTERIOR) {
+                *reinterpret_cast<int4v*>(dst) = v;
+            } else {
+                const int n = ncol0 + cc * 16;
+                if (mrow0 + row < a.M) {
+                    if (n + 16 <= a.N) *reinterpret_cast<int4v*>(dst) = v;
+                    else if (n + 8 <= a.N) *reinterpret_cast<int2v*>(dst) = int2v{v[0], v[1]};
+                }
+            }
+        }
+    }
+    // row terms: this wave's columns of R = sum(raw codes) - N * (int)zp, reduced over the four column groups of a row
+    {
+        const int izp = (int)g.zp;
+        const int ncw = INTERIOR ? WTN : (a.N - ncol0 < WTN ? a.N - ncol0 : WTN);   // this wave's columns inside the matrix
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int rs = tq_isum4rows((int)csum[i]);
+            const int m = mrow0 + i * 16 + frow;
+            if (fc == 0 && (INTERIOR || m < a.M) && ncw > 0) {
+                __hip_atomic_fetch_add(a.qR + m, rs - ncw * izp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (ncol0 == 0) {
+                    a.qsx[m] = g.delta;
+                    a.qzx[m] = izp - wd.cx;
+                }
+            }
+        }
+    }
+    // pad columns [N, Kp_out) of the tile's rows, zeroed like the row quantizers do (8-byte steps: N % 8 == 0)
+    if (n0 + BN >= a.N) {
+        const int padc = (a.Kp_out - a.N) >> 3;
+        for (int idx = tid; idx < BM * padc; idx += NT) {
+            const int row = idx / padc, c = idx - row * padc;
+            if (INTERIOR || m0 + row < a.M)
+                *reinterpret_cast<int2v*>(a.qxq + ((size_t)(m0 + row) * a.Kp_out + a.N + c * 8)) = int2v{0, 0};
+        }
     }
 }

@@ -135,3 +135,51 @@ extern "C" int vq_gemm_i8_grouped(int ngroups, const int8_t* const* xq, const fl
     if (w_bits <= 4) return launch_gemm_auto<true>(a, st, VQ_GEMM_DEFAULT);
     return launch_gemm_auto<false>(a, st, VQ_GEMM_DEFAULT);
 }
+
+// R[0, n) = 0 in front of a quantizing launch (every wave adds its columns' part of a row's term).  A kernel, not
+// hipMemsetAsync: a memset node captured into a graph took effect in no replay (attention.hip, attn_zero_rows_kernel).
+__global__ void gemm_zero_rows_kernel(int32_t* R, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) R[i] = 0;
+}
+
+// mlp.fc1 + GELU(tanh) + fc2's STATIC tensor-wise activation quantizer: the GEMM of vq_gemm_i8(VQ_EPI_GELU) with the
+// quantizing epilogue (gemm_common.h, ring_epilogue_quant) in the four forms launch_gemm_auto picks, 8-bit weights.
+// Replaces F.linear (quant_layer.py:211) + nn.GELU(approximate="tanh") (blocks.py:27) + ActQuantizer.forward after init_done
+// (base_quantizer.py:129-144) behind the smooth-quant division (quant_layer.py:140).  Every check comes before any HIP call
+// or dereference.
+extern "C" int vq_gemm_i8_rowquant_static(const int8_t* xq, const float* sx, const int32_t* zx, const int32_t* R,
+                                          const void* wq, const float* sw, const int32_t* zw, const int32_t* cs,
+                                          const float* bias, const float* s, const float* s_rcp, const float* delta,
+                                          const float* zp, int8_t* xq_out, float* sx_out, int32_t* zx_out, int32_t* R_out,
+                                          int M, int N, int K, int Kp, int Kp_out, int w_bits, int n_bits, int variant,
+                                          void* stream) {
+    if (!xq || !sx || !zx || !R || !wq || !sw || !zw || !cs || !delta || !zp || !xq_out || !sx_out || !zx_out || !R_out)
+        return VQ_EINVAL;
+    if (M <= 0 || N <= 0 || K <= 0 || Kp <= 0 || Kp_out <= 0) return VQ_EINVAL;
+    // what vq_gemm_i8 refuses (N % 8 covers its N % 4) ...
+    if (Kp % 128 != 0 || Kp < K || K > 16384) return VQ_ESHAPE;
+    if ((long)M * Kp >= (1L << 32) || (long)N * Kp >= (1L << 32)) return VQ_ESHAPE;
+    // ... and the quantizer's: whole 8-byte runs of codes, rows the int8 GEMM reads, 16-byte chunk stores and float4 reads
+    if (N % 8 != 0 || Kp_out % 128 != 0 || Kp_out < N) return VQ_ESHAPE;
+    if ((((uintptr_t)xq_out | (uintptr_t)s | (uintptr_t)s_rcp) & 15u) != 0) return VQ_ESHAPE;
+    const bool half = variant == 16 || (variant == VQ_GEMM_DEFAULT && vq_half_tiles(M, N, 1));
+    const int bm = half ? 128 : 256;
+    const bool interior = M % bm == 0 && N % 288 == 0;
+    if (variant == 19 && (!interior || half)) return VQ_ESHAPE;
+    if (w_bits <= 4 || w_bits > 8) return VQ_EUNSUP;           // nibble weights: no quantizing form
+    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    if (s && !s_rcp) return VQ_EUNSUP;                         // the division exists in reciprocal form only
+    if (variant != VQ_GEMM_DEFAULT && variant != 11 && variant != 16 && variant != 19) return VQ_EUNSUP;
+    GemmQArgs a{};
+    static_cast<GemmArgs&>(a) = GemmArgs{xq, sx, zx, R, (const uint8_t*)wq, sw, zw, cs, bias, nullptr, nullptr, nullptr,
+                                         N, 1, M, N, K, Kp, VQ_EPI_GELU, 0};
+    a.qs = s, a.qs_rcp = s ? s_rcp : nullptr, a.qdelta = delta, a.qzp = zp;
+    a.qxq = xq_out, a.qsx = sx_out, a.qzx = zx_out, a.qR = R_out, a.Kp_out = Kp_out, a.n_bits = n_bits;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(gemm_zero_rows_kernel, dim3((M + 255) / 256), dim3(256), 0, st, R_out, M);
+    if (const int rc = vq_check_launch()) return rc;
+    if (variant == 19 || (variant == VQ_GEMM_DEFAULT && interior))
+        return half ? launch_gemm_wide_quant<128, 288, 4, 2, 1>(a, st) : launch_gemm_wide_quant<256, 288, 4, 2, 1>(a, st);
+    return half ? launch_gemm_wide_quant<128, 288, 4, 2, 0>(a, st) : launch_gemm_wide_quant<256, 288, 4, 2, 0>(a, st);
+}

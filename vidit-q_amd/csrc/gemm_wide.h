@@ -41,8 +41,11 @@ struct WideCfg {
     static_assert(LDS <= 163840, "LDS budget of one CU");
 };
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool W4, bool STAMP = false, int INT = 0>
-__device__ __forceinline__ void gemm_i8_wide_tile(const GemmArgs a0, const int vb, const int tid_) {
+// Args: GemmArgs, or GemmQArgs with EPI = VQ_EPI_GELU_QUANT (the quantizing epilogue, ring_epilogue_quant)
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool W4, bool STAMP = false, int INT = 0, class Args = GemmArgs>
+__device__ __forceinline__ void gemm_i8_wide_tile(const Args a0, const int vb, const int tid_) {
+    constexpr bool QUANT = EPI == VQ_EPI_GELU_QUANT;
+    static_assert(QUANT == std::is_same<Args, GemmQArgs>::value && !(QUANT && (W4 || STAMP)), "the quantizing epilogue: 8-bit weights");
     using Cfg = WideCfg<BM, BN, WAVES_M, WAVES_N, W4>;
     constexpr int NW = Cfg::NW;
     constexpr bool ASYM = INT != 0;                   // one issuing wave per SIMD
@@ -195,7 +198,7 @@ __device__ __forceinline__ void gemm_i8_wide_tile(const GemmArgs a0, const int v
     };
     const int nkt = a0.Kp / 128;
 
-    GemmArgs a = a0;
+    Args a = a0;
     TileSrc src;
     select(a, vb, src);
     if constexpr (INT == 0) {
@@ -303,18 +306,49 @@ __device__ __forceinline__ void gemm_i8_wide_tile(const GemmArgs a0, const int v
     constexpr bool PAR_IN_RING = NW * WTM * (WTN * 2 + 16) < 2 * STAGE;
     const auto colp = ring_load_col_params<BN, 64 * NW>(a, src.n0, tid, gate_row);
     const RowParams rowp = ring_load_row_params<BM>(a, src.m0, tid);
-    if constexpr (PAR_IN_RING) __syncthreads();
+    if constexpr (QUANT) {
+        // the consuming Linear's smoothing vector, parked in front of the parameter block: past the ring, or behind the
+        // barrier that frees it
+        static_assert(PAR_IN_RING || NW * WTM * (WTN * 2 + 16) - 8 * BN >= 2 * STAGE, "smoothing vector outside the live ring");
+        const SmoothParams smp = ring_load_smooth<BN>(a, src.n0, tid);
+        if constexpr (PAR_IN_RING) __syncthreads();
+        ring_park_smooth<BM, BN, WAVES_M, WAVES_N>(a, smp, smem, tid);
+    } else {
+        if constexpr (PAR_IN_RING) __syncthreads();
+    }
     ring_park_col_params<BM, BN, WAVES_M, WAVES_N, 16, true>(colp, smem, tid);
     ring_park_row_params<BM, BN, WAVES_M, WAVES_N, 16, true>(rowp, smem, tid);
     __syncthreads();
-    // (INT != 0: the launcher has checked what the interior epilogue needs for every tile - launch_gemm_wide_e)
-    ring_epilogue<BM, BN, WAVES_M, WAVES_N, EPI, 16, true, 0, INT != 0 && !STAMP>(a, smem, acc, src.m0, src.n0, ts, tid,
-                                                                                 gate_row != nullptr);
+    if constexpr (QUANT) {
+        ring_epilogue_quant<BM, BN, WAVES_M, WAVES_N, INT != 0>(a, smem, acc, src.m0, src.n0, tid);
+    } else {
+        // (INT != 0: the launcher has checked what the interior epilogue needs for every tile - launch_gemm_wide_e)
+        ring_epilogue<BM, BN, WAVES_M, WAVES_N, EPI, 16, true, 0, INT != 0 && !STAMP>(a, smem, acc, src.m0, src.n0, ts, tid,
+                                                                                     gate_row != nullptr);
+    }
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool W4, bool STAMP = false, int INT = 0>
 __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_i8_wide_kernel(GemmArgs a) {
     gemm_i8_wide_tile<BM, BN, WAVES_M, WAVES_N, EPI, W4, STAMP, INT>(a, blockIdx.x, threadIdx.x);
+}
+
+// the same tile with the quantizing epilogue (vq_gemm_i8_rowquant_static): 8-bit weights, general and interior form
+template <int BM, int BN, int WAVES_M, int WAVES_N, int INT>
+__global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_i8_wide_quant_kernel(GemmQArgs a) {
+    gemm_i8_wide_tile<BM, BN, WAVES_M, WAVES_N, VQ_EPI_GELU_QUANT, false, false, INT>(a, blockIdx.x, threadIdx.x);
+}
+
+template <int BM, int BN, int WAVES_M, int WAVES_N, int INT>
+static int launch_gemm_wide_quant(const GemmQArgs& a, hipStream_t st) {
+    using Cfg = WideCfg<BM, BN, WAVES_M, WAVES_N, false>;
+    constexpr size_t LDS = Cfg::LDS;
+    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
+    if (INT != 0 && (a.M % BM != 0 || a.N % BN != 0)) return VQ_ESHAPE;     // interior tiles only
+    constexpr auto k = gemm_i8_wide_quant_kernel<BM, BN, WAVES_M, WAVES_N, INT>;
+    if (const int rc = vq_prepare_kernel<k>((int)LDS)) return rc;
+    hipLaunchKernelGGL(k, dim3(tiles), dim3(64 * WAVES_M * WAVES_N), LDS, st, a);
+    return vq_check_launch();
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool W4, int INT = 0>

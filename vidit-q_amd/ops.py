@@ -498,6 +498,72 @@ def gemm_i8(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor] = None, out: 
     return out
 
 
+def gemm_rowquant_static_ok(M: int, N: int, K: int, w_bits: int, n_bits: int, variant: int = -1) -> bool:
+    """Whether vq_gemm_i8_rowquant_static takes this launch (Kp and Kp_out the 128-padded K and N, aligned buffers): the
+    entry point's refusals (include/viditq.h), mirrored for callers that choose a route BEFORE they launch - a refused
+    shape takes the GEMM's GELU epilogue and the quantizer pass, it does not raise."""
+    if M <= 0 or N <= 0 or K <= 0:
+        return False
+    Kp = pad128(K)
+    if K > 16384 or M * Kp >= 1 << 32 or N * Kp >= 1 << 32 or N % 8:
+        return False
+    if not (4 < w_bits <= 8 and 2 <= n_bits <= 8) or variant not in (-1, 11, 16, 19):
+        return False
+    return variant != 19 or (M % 256 == 0 and N % 288 == 0)
+
+
+def gemm_i8_rowquant_static(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor], delta: torch.Tensor, zp: torch.Tensor,
+                            n_bits: int, s: Optional[torch.Tensor] = None, variant: int = -1) -> Optional[QAct]:
+    """fc1 + GELU(tanh) + the consuming Linear's STATIC tensor-wise quantizer - ``delta`` / ``zp``: one fp32 value each,
+    read on the device - at ``n_bits`` (2..8) in ONE GEMM launch that never writes the fp16 activation.  Returns what
+    ``rowquant(gemm_i8(a, w, bias, epilogue=EPI_GELU, variant=variant).view(1, M, N), n_bits, s=s, delta=delta, zp=zp)``
+    returns, bit for bit.  ``s``: the consuming Linear's smoothing vector [N]; None is returned (the caller keeps the two
+    launches) when its reciprocal form is not available.  A launch the entry point refuses raises: ask
+    :func:`gemm_rowquant_static_ok` first."""
+    for t, n in ((a.xq, "a.xq"), (w.wq, "w.wq")):
+        if not t.is_cuda:
+            raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % n)
+    s_rcp = None
+    if s is not None:
+        _req(s, torch.float32, "s")
+        if s.numel() != w.N:
+            raise VQError("s must hold one entry per output column")
+        s_rcp = smooth_rcp(s)
+        if s_rcp is None:
+            return None
+    if a.K != w.K or a.Kp != w.Kp:
+        raise VQError("K mismatch: activation %d/%d weight %d/%d" % (a.K, a.Kp, w.K, w.Kp))
+    delta = _req(delta.reshape(-1).contiguous(), torch.float32, "delta")
+    zp = _req(zp.reshape(-1).contiguous(), torch.float32, "zp")
+    if delta.numel() != 1 or zp.numel() != 1:
+        raise VQError("gemm_i8_rowquant_static: a tensor-wise grid (one delta, one zero point)")
+    if bias is not None:
+        _req(bias, torch.float32, "bias")
+    M, N = a.rows, w.N
+    Kp_out = pad128(N)
+    dev = a.xq.device
+    xq = torch.empty((M, Kp_out), dtype=torch.int8, device=dev)
+    sx = torch.empty(M, dtype=torch.float32, device=dev)
+    zx = torch.empty(M, dtype=torch.int32, device=dev)
+    R = torch.empty(M, dtype=torch.int32, device=dev)
+    if variant < 0:
+        variant = DEFAULT_GEMM_VARIANT
+    timing = GEMM_TIMING
+    if timing is not None:
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(_L().vq_gemm_i8_rowquant_static(_p(a.xq), _p(a.sx), _p(a.zx), _p(a.R), _p(w.wq), _p(w.sw), _p(w.zw), _p(w.cs),
+                                          _p(bias), _p(s), _p(s_rcp), _p(delta), _p(zp), _p(xq), _p(sx), _p(zx), _p(R),
+                                          M, N, a.K, a.Kp, Kp_out, w.n_bits, n_bits, variant, _stream()),
+          "vq_gemm_i8_rowquant_static")
+    if timing is not None:
+        e1.record()
+        # fused byte model: both operands, the codes (pad columns included) and the three row terms; no fp16 matrix
+        timing.append((e0, e1, 2.0 * M * N * a.K, M * a.K + N * a.K + M * Kp_out + 12 * M))
+    return QAct(xq, sx, zx, R, N, n_bits)
+
+
 def gemm_i8_stamped(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor] = None):
     """Diagnostics: ONE launch of the default 8-bit GEMM (256 x 288 tile, plain epilogue) with per-wave stamps.
     -> (out [M, N] fp16, stamps [tiles, 8, 10] int64: 0-6 shader cycles per phase boundary, 7 / 8 the chip's 100 MHz wall

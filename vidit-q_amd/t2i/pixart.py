@@ -264,11 +264,15 @@ class PixArtMSBlock(nn.Module):
             qa, pw2 = fc2.running_stat_step(h.view(B, N, -1))
         else:
             r2, s2 = sv(fc2)
-            # GELU inside fc2's quantizer pass (see t2v/stdit.py), also for the uncond | cond pair of the t2i loop
-            one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, s2)
-            h = ops.gemm_i8(qa, fc1.packed_weight(r, s), bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
-            r, s = r2, s2
-            qa = fc2.quantize_gelu_input(h.view(B, N, -1), s) if one_pass else fc2.quantize_input(h.view(B, N, -1), s)
+            from ..t2v.stdit import mlp_quantized_static
+            pw1 = fc1.packed_weight(r, s)
+            qa2 = mlp_quantized_static(fc1, fc2, qa, pw1, s2)      # fc2's static quantizer in fc1's epilogue, when switched on
+            if qa2 is None:
+                # GELU inside fc2's quantizer pass (see t2v/stdit.py), also for the uncond | cond pair of the t2i loop
+                one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, s2)
+                h = ops.gemm_i8(qa, pw1, bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
+                qa2 = fc2.quantize_gelu_input(h.view(B, N, -1), s2) if one_pass else fc2.quantize_input(h.view(B, N, -1), s2)
+            r, s, qa = r2, s2, qa2
             pw2 = fc2.packed_weight(r, s)
         ops.gemm_i8(qa, pw2, bias=fc2.bias_f32(), out=x2,
                     epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate_mlp, rows_per_gate=N)

@@ -379,6 +379,35 @@ def _static_fwd_attn_quant(proj) -> bool:
     return aq.delta.numel() == 1 and aq.zero_point.numel() == 1
 
 
+# mlp.fc1's GEMM with GELU and fc2's static tensor-wise quantizer in its epilogue (ops.gemm_i8_rowquant_static) instead of
+# the GELU epilogue + one quantizer pass over the [M, 4608] fp16 activation, which is then never written.  The codes are
+# those of the two launches bit for bit, so a static plan's output does not move; off by default until the timing table
+#  decides: tests pin today's launches of a static block.  VQ_STATIC_GEMM_QUANT=1 turns it on;
+# independent of the two attention switches.
+_STATIC_GEMM_QUANT = __import__("os").environ.get("VQ_STATIC_GEMM_QUANT", "0") != "0"
+
+
+def _static_gemm_quant(pw1, fc2, M: int) -> bool:
+    """Whether fc1's GEMM (``pw1``: its packed weight, ``M`` rows) also runs fc2's quantizer: the switch, the one-pass
+    static route, a calibrated tensor-wise grid on fc2, no running statistic there, and nothing the entry point would
+    refuse."""
+    aq = fc2.act_quantizer
+    if not (_STATIC_GEMM_QUANT and _STATIC_FUSED) or isinstance(aq, DynamicActQuantizer):
+        return False
+    if aq.delta.numel() != 1 or aq.zero_point.numel() != 1 or getattr(fc2, "smooth_quant_running_stat", False):
+        return False
+    return ops.gemm_rowquant_static_ok(M, pw1.N, pw1.K, pw1.n_bits, aq.n_bits)
+
+
+def mlp_quantized_static(fc1, fc2, qa, pw1, s2):
+    """fc2's input codes from fc1's GEMM (``qa``: fc1's input codes, ``pw1``: its packed weight, ``s2``: fc2's smoothing
+    vector), or None when the route is off or refuses (the caller then runs the GEMM and fc2's quantizer separately)."""
+    if not _static_gemm_quant(pw1, fc2, qa.rows):
+        return None
+    aq = fc2.act_quantizer
+    return ops.gemm_i8_rowquant_static(qa, pw1, fc1.bias_f32(), aq.delta.float(), aq.zero_point.float(), aq.n_bits, s=s2)
+
+
 # a running smooth-quant statistic on mlp.fc2 (the released t2i script leaves it on for blocks.27.mlp.fc2 at inference,
 # quant_txt2img.py:297-300) served on the fused route by QuantLayer.running_stat_step: statistic, s, W*s and the quantizer
 # on the device, no host read.  Off by default: a test pins today's layer-by-layer route of such a block, and the timing
@@ -694,10 +723,13 @@ class STDiTBlock(nn.Module):
             h = ops.gemm_i8(qa, fc1.packed_weight(r, svec(fc1)), bias=fc1.bias_f32(), epilogue=ops.EPI_GELU)
             qa, pw2 = fc2.running_stat_step(h.view(B, N, -1))
         else:
-            one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, svec(fc2))
-            h = ops.gemm_i8(qa, fc1.packed_weight(r, svec(fc1)), bias=fc1.bias_f32(),
-                            epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
-            qa = fc2.quantize_gelu_input(h.view(B, N, -1), svec(fc2)) if one_pass else fc2.quantize_input(h.view(B, N, -1), svec(fc2))
+            pw1 = fc1.packed_weight(r, svec(fc1))
+            qa2 = mlp_quantized_static(fc1, fc2, qa, pw1, svec(fc2))     # fc2's static quantizer in fc1's epilogue, when switched on
+            if qa2 is None:
+                one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, svec(fc2))
+                h = ops.gemm_i8(qa, pw1, bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
+                qa2 = fc2.quantize_gelu_input(h.view(B, N, -1), svec(fc2)) if one_pass else fc2.quantize_input(h.view(B, N, -1), svec(fc2))
+            qa = qa2
             pw2 = fc2.packed_weight(r, svec(fc2))
         ops.gemm_i8(qa, pw2, bias=fc2.bias_f32(), out=x2,
                     epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate_mlp, rows_per_gate=N)
