@@ -365,10 +365,31 @@ int vq_attn_temporal(const void* q, const void* k, const void* v, void* o,
  * vq_smooth_reciprocal (the division x / s of quant_layer.py:140 exists in reciprocal form only in this kernel).
  * o: nullable, dense [B*T*S, H*D] fp16 copy of the attention output for callers that need both.
  * H <= 16, T <= 16, H*D % 16 == 0, Kp % 128 == 0.  q, k, v, xq and, when set, s, s_rcp and o are 16-byte
- * aligned (VQ_ESHAPE otherwise). */
+ * aligned (VQ_ESHAPE otherwise).  With B > 1 its grids are per row; grids shared by the samples of a joint forward are
+ * vq_attn_temporal_rowquant_shared. */
 int vq_attn_temporal_rowquant(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
                               int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o, int B, int T,
                               int S, int H, int D, long ld_in, int Kp, float scale, void* stream);
+
+/* Temporal attention fused with the per-token dynamic quantizer of attn_temp.proj for a JOINT cond | uncond forward, at
+ * 2..8 bits (stdit.py:112-118 -> QuantTemporalAttnLinear.forward, stdit_quant_layer.py:161-166 -> DynamicActQuantizer,
+ * dynamic_quantizer.py:16-45; the joint forward over cat([x, x]) of iddpm/__init__.py:141-163): a token's grid is shared by
+ * the rows of all B samples (base_quantizer.py:177-189: [B, n, C] -> [n, B*C]).  B is 1 or 2, T <= 16: the shared-grid
+ * forms of the two kernels behind vq_attn_temporal_rowquant, one workgroup per spatial position of every sample.
+ * Rows are r = (b*T + t)*S + s.  Contract: xq [B*T*S, Kp] (codes - 128 at 8 bits, raw codes below; pad columns
+ * [H*D, Kp) zero), sx, zx (one grid per token, replicated per row), R (per row) and the VQ_ST_EPSFILL bit of status are
+ * bit-identical to vq_rowquant(x = o viewed [B, T*S, H*D], s, s_rcp, n_bits) of the kernel's own fp16 output o, and o of
+ * sample b is what vq_attn_temporal_rowquant writes for that sample alone.
+ * s / s_rcp: both null, or proj's smooth-quant channel scale [H*D] and its reciprocal from vq_smooth_reciprocal.
+ * o: nullable, dense [B*T*S, H*D] fp16 copy of the attention output.  status: nullable.
+ * VQ_EINVAL: a null q / k / v / xq / sx / zx / R, s without s_rcp or the reverse, a non-positive B, T, S, H, D or Kp.
+ * VQ_ESHAPE: T > 16, H > 16, ld_in % 8 != 0, H*D % 16 != 0, Kp % 128 != 0, Kp < H*D, 16 * (H*D / 8) > 192 * H (the V
+ * staging registers), q / k / v / xq / s / s_rcp / o not 16-byte aligned, D outside {16, 32, 64, 72}, B > 2.
+ * VQ_EUNSUP: n_bits outside 2..8.  In this order, all before any HIP call or dereference. */
+int vq_attn_temporal_rowquant_shared(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
+                                     int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o,
+                                     int B, int T, int S, int H, int D, long ld_in, int Kp, int n_bits,
+                                     float scale, void* stream);
 
 /* Temporal attention for up to 64 frames (OpenSORA 64x512x512; STDiTBlock's temporal branch, stdit.py:112-118), with
  * the per-token 8-bit dynamic quantizer of attn_temp.proj (QuantTemporalAttnLinear.forward, stdit_quant_layer.py:161-166)

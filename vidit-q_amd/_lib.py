@@ -49,6 +49,7 @@ SIGNATURES = {
     "vq_attn_temporal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _f, _vp]),
     "vq_attn_temporal_rowquant": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _i, _f,
                                        _vp]),
+    "vq_attn_temporal_rowquant_shared": (_i, [_vp] * 11 + [_i] * 5 + [_l, _i, _i, _f, _vp]),
     "vq_attn_temporal_long": (_i, [_vp] * 11 + [_i] * 5 + [_l, _l, _i, _f, _vp]),
     "vq_attn_temporal_rowquant_static": (_i, [_vp] * 12 + [_i] * 5 + [_l, _l, _i, _i, _f, _vp]),
     "vq_attn_fwd_rowquant_static": (_i, [_vp] * 12 + [_i] * 5 + [_l] * 6 + [_vp, _i, _i, _f, _vp]),

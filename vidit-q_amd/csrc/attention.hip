@@ -374,13 +374,30 @@ struct TempQSArgs : TempQArgs {
     int n_bits;                                    // 2 .. 8
 };
 
+// the shared-grid form (SH; vq_attn_temporal_rowquant_shared): the dynamic form for B <= 2 samples whose tokens share ONE grid
+// per (t, s) at a code width of 2..8 bits - a joint cond | uncond forward (iddpm/__init__.py:141-163, base_quantizer.py:177-189)
+struct TempQPArgs : TempQArgs {
+    int n_bits;                                    // 2 .. 8
+};
+// The walk of a persistent workgroup over its positions.  Dynamic / static forms: position = (b, s), pos = b * S + s, one
+// after the other in steps of the grid.  SH: a workgroup owns the spatial position s of ALL samples, pos = s * B + b with b
+// fastest (B is 1 or 2), and moves on by the grid only behind the last sample.
+template <bool SH>
+__device__ __forceinline__ int tq_next_pos(int pos, int G, int B) {
+    if constexpr (SH) return (pos & (B - 1)) == B - 1 ? pos + (G - 1) * B + 1 : pos + 1;
+    else return pos + G;
+}
+
 // The head count is a.H (the chunk -> (tensor, row, piece) divisions of the staging loops are by H * D / 8 and cost ~45
 // VALU instructions each with a run-time divisor: the H = 16 kernel is attn_temporal_quant2_kernel below).
 // A = TempQSArgs: the static-grid form ST (attn_rowquant.h): a.delta / a.zp / a.n_bits instead of the row's own 8-bit
-// grid, any B
+// grid, any B.  A = TempQPArgs: the shared-grid form SH (attn_rowquant.h): one grid per token over both samples at a.n_bits;
+// LDS: a code area and a sum area per sample, and the parked fp16 output of every sample behind them
 template <int D, class A = TempQArgs>
 __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
     constexpr bool ST = std::is_same<A, TempQSArgs>::value;
+    constexpr bool SH = std::is_same<A, TempQPArgs>::value;
+    constexpr int NCB = SH ? 2 : 1;                // code / sum areas (one per sample of a shared grid)
     constexpr int KS = (D + 15) / 16;              // 16-dim k-steps of QK^T = 16-dim row tiles of O^T
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -391,11 +408,18 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
     const int TILE = 16 * RS;
     const int RCH = C / 8;                         // 16-byte chunks per tensor row
     const int CROW = C + 16;                       // code row stride in LDS (rows land 4 banks apart)
-    uint8_t* codes = smem + TILE;                 // [V tile | codes | row statistics]
-    float* ex_min = reinterpret_cast<float*>(codes + 16 * CROW);
+    // [V tile | codes | row statistics]; SH: [V tile | row statistics | codes | parked output] - with two code areas in
+    // front of them the statistics would lie beyond the 64 KB that a DS instruction's offset reaches, and every one of the
+    // 2 * H addresses of tq_row_grid's reads became a register of its own
+    uint8_t* codes = smem + TILE + (SH ? 4 * 1024 : 0);
+    float* ex_min = reinterpret_cast<float*>(SH ? smem + TILE : codes + 16 * CROW);
     float* ex_max = ex_min + 256;
     int* ex_sum = reinterpret_cast<int*>(ex_max + 256);
-    const int npos = a.S * a.B;
+    [[maybe_unused]] uint8_t* park = codes + NCB * 16 * CROW;
+    const int npos = a.S * a.B, G = (int)gridDim.x;
+    // pos -> (s, b)
+    auto pos_s = [&](int pos) { if constexpr (SH) return pos >> (a.B - 1); else return pos % a.S; };
+    auto pos_b = [&](int pos) { if constexpr (SH) return pos & (a.B - 1); else return pos / a.S; };
 
     // One workgroup walks positions p, p + G, ...: while position p is computed, the rows of the next one are in flight
     // into registers (a one-position-per-workgroup version ran load -> compute -> store in lockstep on every CU:
@@ -411,7 +435,7 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
     // (tx: an opaque per-position copy of the thread id, so that the chunk -> address arithmetic is recomputed per
     //  position instead of being hoisted out of the loop and kept in registers)
     auto load_qkv = [&](int pos, int tx) {
-        const int s = pos % a.S, b = pos / a.S;
+        const int s = pos_s(pos), b = pos_b(pos);
 #pragma unroll
         for (int i = 0; i < NITMAX; ++i) {
             const int c = tx + i * nthr;
@@ -454,7 +478,7 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
     TqGrid gq;                                     // ST: the calibrated grid; else every row's own, behind its statistics
     if constexpr (ST) gq = tq_static(a.delta, a.zp, a.n_bits);
 
-    int pos = blockIdx.x;
+    int pos = SH ? blockIdx.x * a.B : blockIdx.x;
     if (pos >= npos) return;
     load_qkv(pos, tid);
     store_qkv(tid);
@@ -465,11 +489,13 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
         qfc[ks] = qfn[ks];
     }
     __syncthreads();
-    if (pos + (int)gridDim.x < npos) load_qkv(pos + (int)gridDim.x, tid);
-    for (; pos < npos; pos += gridDim.x) {
-        const int s = pos % a.S, b = pos / a.S;
-        const int npos_next = pos + (int)gridDim.x;
+    if (tq_next_pos<SH>(pos, G, a.B) < npos) load_qkv(tq_next_pos<SH>(pos, G, a.B), tid);
+    [[maybe_unused]] float shmin = INFINITY, shmax = -INFINITY;   // SH: a token's extremes, carried from one sample to the next
+    for (int npos_next; pos < npos; pos = npos_next) {
+        const int s = pos_s(pos), b = pos_b(pos);
+        npos_next = tq_next_pos<SH>(pos, G, a.B);
         const bool has_next = npos_next < npos;    // workgroup-uniform; its rows are already in flight
+        [[maybe_unused]] const bool last = !SH || b == a.B - 1;   // SH: the position's statistics are complete
         int tx = tid;
         asm volatile("" : "+v"(tx));
 
@@ -481,6 +507,72 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
         const float psum = tq_softmax16<1>(sc, g4, a.T, a.c, pf);
         const float inv_p = psum > 0.f ? __fdiv_rn(1.0f, psum) : 0.f;    // (IEEE here, v_rcp_f32 in the other two: attn_rowquant.h)
 
+        if constexpr (SH) {
+            // the shared-grid form: a dim tile at a time - round (as the dynamic form of this kernel does: tq_round_o), store,
+            // park, and this head's part of the token's extremes over the samples so far
+            half_t* orow = a.o + (((long)b * a.T + tq) * a.S + s) * C + wave * D;
+#pragma unroll
+            for (int dt = 0; dt < KS; ++dt) {
+                const half4 vf = tq_vt_frag(vs + (4 * g4 + (tq >> 2)) * RS + (dt * 16 + 4 * (tq & 3)) * 2);
+                const float4v o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[0], float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                const half4 oh = tq_round_o<true>(o4, inv_p, dt);
+                const int d0 = dt * 16 + 4 * g4;
+                if (d0 < D) {
+                    if (a.o && tq < a.T) *reinterpret_cast<half4*>(orow + d0) = oh;
+                    tq_park(park + b * KS * nthr * 8, nthr, tid, dt, oh);
+                    float x4[4] = {(float)oh[0], (float)oh[1], (float)oh[2], (float)oh[3]};
+                    tq_div_s(x4, a.s, a.s_rcp, wave * D + d0);
+                    tq_minmax4(x4, shmin, shmax);
+                }
+            }
+            if (last) {
+                tq_publish_minmax(shmin, shmax, ex_min, ex_max, wave, lane);
+                shmin = INFINITY, shmax = -INFINITY;
+            }
+            tq_lds_barrier();                      // row statistics visible; every wave is done with the q | k | v tiles
+            if (has_next) {                        // (as below)
+                store_qkv(tx);
+#pragma unroll
+                for (int ks = 0; ks < KS2; ++ks) {
+                    kfc[ks] = kfn[ks];
+                    qfc[ks] = qfn[ks];
+                }
+                if (tq_next_pos<SH>(npos_next, G, a.B) < npos) load_qkv(tq_next_pos<SH>(npos_next, G, a.B), tx);
+            }
+            if (last) {                            // one grid for the token's rows of all samples, each from where it was parked
+                gq = tq_row_grid(ex_min, ex_max, H, tq, tid < 16 && tq < a.T, a.status, a.n_bits);
+                for (int bb = 0; bb < a.B; ++bb) {
+                    uint32_t csum = 0;
+                    RQ_BY_WIDTH(gq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
+                        const int d0 = dt * 16 + 4 * g4;
+                        if (d0 < D) {
+                            float x4[4];
+                            tq_unpark(park + bb * KS * nthr * 8, nthr, tid, dt, x4);
+                            tq_div_s(x4, a.s, a.s_rcp, wave * D + d0);
+                            *reinterpret_cast<uint32_t*>(codes + (bb * 16 + tq) * CROW + wave * D + d0) = tq_codes<false, SAT8_>(x4, gq, csum);
+                        }
+                    })
+                    tq_publish_sum(csum, ex_sum + bb * 256, wave, lane);
+                }
+            }
+            tq_lds_barrier();                      // (not last: only the next sample's V rows become visible)
+            if (!last) continue;
+            const int kch = a.Kp / 16, cch = C / 16;
+            for (int bb = 0; bb < a.B; ++bb) {
+                for (int c = tid; c < 16 * kch; c += nthr) {
+                    const int t = c / kch, ch = c - t * kch;
+                    if (t < a.T) {
+                        const long grow = ((long)bb * a.T + t) * a.S + s;
+                        const int4v val = ch < cch ? *reinterpret_cast<const int4v*>(codes + (bb * 16 + t) * CROW + ch * 16) : int4v{0, 0, 0, 0};
+                        *reinterpret_cast<int4v*>(a.xq + grow * a.Kp + ch * 16) = val;
+                    }
+                }
+                if (tid < 16 && tq < a.T)
+                    rq_write_row(a.sx, a.zx, a.R, nullptr, (size_t)(((long)bb * a.T + tq) * a.S + s), gq.g.delta, gq.g.zp,
+                                 tq_collect_sum(ex_sum + bb * 256, H, tq), C, gq.wd.cx);
+            }
+            continue;
+        }
         // ---- O^T[dim 16*dt + 4*g4 + r][query tq] = V^T P^T: P^T is the accumulator layout of S^T already.
         // this lane: token tq, dims 16*dt + 4*g4 + r, rounded to fp16 like the stored tensor
         // (float4v, and x4 copies at the encode: in this shape hipcc selects v_fma_mixlo_f16 - ONE rounding of o4 * inv_p to
@@ -517,7 +609,7 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
                 kfc[ks] = kfn[ks];
                 qfc[ks] = qfn[ks];
             }
-            if (npos_next + (int)gridDim.x < npos) load_qkv(npos_next + (int)gridDim.x, tx);   // ... and the position after it is requested
+            if (tq_next_pos<SH>(npos_next, G, a.B) < npos) load_qkv(tq_next_pos<SH>(npos_next, G, a.B), tx);   // ... and the position after it is requested
         }
         if constexpr (!ST) gq = tq_row_grid(ex_min, ex_max, H, tq, tid < 16 && tq < a.T, a.status);
         uint32_t csum = 0;
@@ -567,6 +659,8 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant_kernel(A a) {
 template <int D, class A = TempQArgs>
 __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
     constexpr bool ST = std::is_same<A, TempQSArgs>::value;   // the static-grid form (attn_rowquant.h)
+    constexpr bool SH = std::is_same<A, TempQPArgs>::value;   // the shared-grid form: as in the kernel above
+    constexpr int NCB = SH ? 2 : 1;
     constexpr int H = 16, C = H * D, NTHR = 64 * H;
     constexpr int KS = (D + 15) / 16, KS2 = (D + 31) / 32;
     constexpr int RS = C * 2 + 16, TILE = 16 * RS, RCH = C / 8, CROW = C + 16;
@@ -575,10 +669,11 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // = head
     const int tq = lane & 15, g4 = lane >> 4;
-    uint8_t* codes = smem + TILE;
-    float* ex_min = reinterpret_cast<float*>(codes + 16 * CROW);
+    uint8_t* codes = smem + TILE + (SH ? 4 * 1024 : 0);   // (the LDS maps of the kernel above)
+    float* ex_min = reinterpret_cast<float*>(SH ? smem + TILE : codes + 16 * CROW);
     float* ex_max = ex_min + 256;
     int* ex_sum = reinterpret_cast<int*>(ex_max + 256);
+    [[maybe_unused]] uint8_t* park = codes + NCB * 16 * CROW;
     const int npos = a.S * a.B, G = (int)gridDim.x;
     const unsigned tstride = (unsigned)a.S * (unsigned)a.ld_in * 2u;          // bytes between the rows t, t + 1 of a position
 
@@ -613,9 +708,10 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
 
     int4v vals[NIT];
     half8 kf[KS2], qf[KS2];
+    auto row_of = [&](int b, int s) -> size_t { return ((size_t)b * a.T * a.S + s); };
     auto base_of = [&](int pos) -> size_t {                // first row (t = 0) of the position, in ELEMENTS of ld_in rows
-        const int s = pos % a.S, b = pos / a.S;
-        return ((size_t)b * a.T * a.S + s);
+        if constexpr (SH) return row_of(pos & (a.B - 1), pos >> (a.B - 1));
+        else return row_of(pos / a.S, pos % a.S);
     };
     auto load_v = [&](int pos) {
         const uint8_t* vb = reinterpret_cast<const uint8_t*>(a.v) + base_of(pos) * (size_t)a.ld_in * 2;
@@ -652,17 +748,20 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
     TqGrid gq;                                             // ST: the calibrated grid; else every row's own, behind its statistics
     if constexpr (ST) gq = tq_static(a.delta, a.zp, a.n_bits);
 
-    int pos = blockIdx.x;
+    int pos = SH ? blockIdx.x * a.B : blockIdx.x;
     if (pos >= npos) return;
     load_v(pos);
     load_kq(pos);
     store_v();
     __syncthreads();
-    if (pos + G < npos) load_v(pos + G);
-    for (; pos < npos; pos += G) {
-        const int pos_n = pos + G;
+    if (tq_next_pos<SH>(pos, G, a.B) < npos) load_v(tq_next_pos<SH>(pos, G, a.B));
+    [[maybe_unused]] float shmin = INFINITY, shmax = -INFINITY;   // SH: a token's extremes, carried from one sample to the next
+    for (int pos_n; pos < npos; pos = pos_n) {
+        pos_n = tq_next_pos<SH>(pos, G, a.B);
         const bool has_next = pos_n < npos;                // workgroup-uniform
         const size_t row0 = base_of(pos);
+        [[maybe_unused]] const int b = SH ? pos & (a.B - 1) : 0;
+        [[maybe_unused]] const bool last = !SH || b == a.B - 1;   // SH: the position's statistics are complete
 
         // ---- S^T = K Q^T (16 x 16 per head), then the operand registers are requested again for the next position
         float4v sc[1] = {{0.f, 0.f, 0.f, 0.f}};
@@ -673,6 +772,66 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
         const float psum = tq_softmax16<1>(sc, g4, a.T, a.c, pf);
         const float inv_p = psum > 0.f ? __builtin_amdgcn_rcpf(psum) : 0.f;
 
+        if constexpr (SH) {
+            // the shared-grid form: a dim tile at a time - round, store, park, and this head's part of the token's extremes
+            // over the samples so far (the 20 output registers of the dynamic form are not held across the barrier)
+            half_t* orow = a.o + (row0 + (size_t)tq * a.S) * C + wave * D;
+#pragma unroll
+            for (int dt = 0; dt < KS; ++dt) {
+                const half4 vf = tq_vt_frag(vs + vtro + dt * 32);
+                const float4v o4 = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[0], float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                const half4 oh = tq_round_o<false>(o4, inv_p, dt);
+                const int d0 = dt * 16 + 4 * g4;
+                if (d0 < D) {
+                    if (a.o && tq < a.T) *reinterpret_cast<half4*>(orow + d0) = oh;
+                    tq_park(park + b * KS * NTHR * 8, NTHR, tid, dt, oh);
+                    float x4[4] = {(float)oh[0], (float)oh[1], (float)oh[2], (float)oh[3]};
+                    tq_div_s(x4, a.s, a.s_rcp, wave * D + d0);
+                    tq_minmax4(x4, shmin, shmax);
+                }
+            }
+            if (last) {
+                tq_publish_minmax(shmin, shmax, ex_min, ex_max, wave, lane);
+                shmin = INFINITY, shmax = -INFINITY;
+            }
+            tq_lds_barrier();                                // row statistics visible; every wave is done with the V tile
+            if (has_next) {
+                store_v();                                   // the next sample's or position's V rows (visible after the barrier below)
+                if (tq_next_pos<SH>(pos_n, G, a.B) < npos) load_v(tq_next_pos<SH>(pos_n, G, a.B));
+            }
+            if (last) {                                      // one grid for the token's rows of all samples, each from where it was parked
+                gq = tq_row_grid(ex_min, ex_max, H, tq, tid < 16 && tq < a.T, a.status, a.n_bits);
+                for (int bb = 0; bb < a.B; ++bb) {
+                    uint32_t csum = 0;
+                    RQ_BY_WIDTH(gq.wd.qmax, _Pragma("unroll") for (int dt = 0; dt < KS; ++dt) {
+                        const int d0 = dt * 16 + 4 * g4;
+                        if (d0 < D) {
+                            float x4[4];
+                            tq_unpark(park + bb * KS * NTHR * 8, NTHR, tid, dt, x4);
+                            tq_div_s(x4, a.s, a.s_rcp, wave * D + d0);
+                            *reinterpret_cast<uint32_t*>(codes + (bb * 16 + tq) * CROW + wave * D + d0) = tq_codes<false, SAT8_>(x4, gq, csum);
+                        }
+                    })
+                    tq_publish_sum(csum, ex_sum + bb * 256, wave, lane);
+                }
+            }
+            tq_lds_barrier();                                // (not last: only the next sample's V rows become visible)
+            if (!last) continue;
+            for (int bb = 0; bb < a.B; ++bb) {
+                const size_t rowb = row_of(bb, pos >> (a.B - 1));
+                uint8_t* xb = reinterpret_cast<uint8_t*>(a.xq) + rowb * (size_t)a.Kp;
+#pragma unroll
+                for (int j = 0; j < NCI; ++j)
+                    if (cok[j]) {
+                        const int4v val = cpad[j] ? int4v{0, 0, 0, 0} : *reinterpret_cast<const int4v*>(codes + bb * 16 * CROW + clo[j]);
+                        *reinterpret_cast<int4v*>(xb + cgo[j]) = val;
+                    }
+                if (tid < 16 && tq < a.T)
+                    rq_write_row(a.sx, a.zx, a.R, nullptr, rowb + (size_t)tq * a.S, gq.g.delta, gq.g.zp,
+                                 tq_collect_sum(ex_sum + bb * 256, H, tq), C, gq.wd.cx);
+            }
+            continue;
+        }
         // ---- O^T = V^T P^T, rounded to fp16 as the stored tensor is
         float ov[KS][4];
 #pragma unroll
@@ -699,7 +858,7 @@ __global__ __launch_bounds__(1024) void attn_temporal_quant2_kernel(A a) {
                                                              // (ST: nothing to publish, but store_v below reuses the tile)
         if (has_next) {
             store_v();                                       // the next position's V rows (visible after the barrier below)
-            if (pos_n + G < npos) load_v(pos_n + G);
+            if (tq_next_pos<SH>(pos_n, G, a.B) < npos) load_v(tq_next_pos<SH>(pos_n, G, a.B));
         }
         if constexpr (!ST) gq = tq_row_grid(ex_min, ex_max, H, tq, tid < 16 && tq < a.T, a.status);
         uint32_t csum = 0;
@@ -1998,6 +2157,46 @@ extern "C" int vq_attn_temporal_rowquant(const void* q, const void* k, const voi
     if (const int rc = temporal_quant_args(q, k, v, s, s_rcp, xq, sx, zx, R, status, o, B, T, S, H, D, ld_in, Kp, scale, &a)) return rc;
     hipStream_t st = (hipStream_t)stream;
     return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_quant<d()>(a, st, temporal_quant_trimmed(a)); });
+}
+
+// The shared-grid forms of the two T <= 16 kernels: one workgroup per spatial position (of both samples).  LDS: the V tile,
+// a code area per sample, the row statistics with a sum area per sample, and the parked fp16 output of each sample
+// (8 bytes per thread and 16-dim tile): 160 512 of 163 840 B at H = 16, D = 72 - one workgroup per CU, as the dynamic form there.
+template <int D>
+static int launch_temporal_shared(const TempQPArgs& a, hipStream_t st, bool trimmed) {
+    constexpr int KS = (D + 15) / 16;
+    const int C = a.H * D;
+    const int LDS = 16 * (C * 2 + 16) + 2 * 16 * (C + 16) + 4 * 1024 + 2 * KS * 64 * a.H * 8;
+    constexpr int LDS_MAX = 16 * (16 * D * 2 + 16) + 2 * 16 * (16 * D + 16) + 4 * 1024 + 2 * KS * 64 * 16 * 8;
+    constexpr auto k2 = attn_temporal_quant2_kernel<D, TempQPArgs>;
+    constexpr auto k1 = attn_temporal_quant_kernel<D, TempQPArgs>;
+    int ncu = 0;
+    if (const int rc = trimmed ? vq_prepare_kernel<k2>(LDS_MAX, &ncu) : vq_prepare_kernel<k1>(LDS_MAX, &ncu)) return rc;
+    // persistent: a 1024-thread workgroup owns its CU; smaller ones share its 160 KB of LDS, three at the most
+    const int fit = 160 * 1024 / LDS;
+    const int per_cu = a.H > 8 || fit < 2 ? 1 : (fit > 3 ? 3 : fit);
+    const int grid = a.S < ncu * per_cu ? a.S : ncu * per_cu;
+    hipLaunchKernelGGL(trimmed ? k2 : k1, dim3(grid), dim3(64 * a.H), LDS, st, a);
+    return vq_check_launch();
+}
+
+// Temporal attention + attn_temp.proj's dynamic per-token quantizer for a joint forward: B <= 2 samples share a token's grid,
+// n_bits 2..8.  Every check comes before any HIP call or dereference: null pointers and extents, then shapes, then the width.
+extern "C" int vq_attn_temporal_rowquant_shared(const void* q, const void* k, const void* v, const float* s, const float* s_rcp,
+                                                int8_t* xq, float* sx, int32_t* zx, int32_t* R, int32_t* status, void* o,
+                                                int B, int T, int S, int H, int D, long ld_in, int Kp, int n_bits,
+                                                float scale, void* stream) {
+    if (!q || !k || !v || !xq || !sx || !zx || !R) return VQ_EINVAL;
+    if ((s != nullptr) != (s_rcp != nullptr)) return VQ_EINVAL;     // the division exists in reciprocal form only here
+    if (B <= 0 || T <= 0 || S <= 0 || H <= 0 || D <= 0 || Kp <= 0) return VQ_EINVAL;
+    TempQPArgs a{};
+    if (const int rc = temporal_quant_args(q, k, v, s, s_rcp, xq, sx, zx, R, status, o, B, T, S, H, D, ld_in, Kp, scale, &a)) return rc;
+    if (D != 72 && D != 64 && D != 32 && D != 16) return VQ_ESHAPE;  // (vq_dispatch_head_dim)
+    if (B > 2) return VQ_ESHAPE;                                     // one workgroup holds a position of every sample
+    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    a.n_bits = n_bits;
+    hipStream_t st = (hipStream_t)stream;
+    return vq_dispatch_head_dim(D, [&](auto d) { return launch_temporal_shared<d()>(a, st, temporal_quant_trimmed(a)); });
 }
 
 template <int D, class A>

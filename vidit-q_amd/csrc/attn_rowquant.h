@@ -22,12 +22,18 @@
 //  instruction streams of their written-out forms: profiles/refactor_attn_isa.md has what moved at the first attempt,
 //  profiles/refactor_temporal_steps.md the resources and the timing on the MI355X that this form was accepted on.)
 //
-// One grid type, TqGrid, serves both forms.  The dynamic form (TempQArgs) derives it per row from the row's min / max
+// One grid type, TqGrid, serves all forms.  The dynamic form (TempQArgs) derives it per row from the row's min / max
 // (vq_row_grid, 8 bits) and encodes with rq_quant; the static form (TempQSArgs; vq_attn_temporal_rowquant_static) reads
 // ONE calibrated grid (delta, zp: one fp32 value each, read on the device) at a code width of 2..8 bits: no row
 // min / max, hence no ex_min / ex_max exchange, no vq_row_grid, no eps fill and no status word; only the row sum still
 // crosses the heads.  Its codes are rqs_grid / rqs_quant of rowquant_shared.h - rq_round_group's bound needs the row's
 // own grid - and bit-identical to vq_rowquant(delta_in, zp_in, n_param = 1) of the kernel's own fp16 output.
+// The shared-grid form (TempQPArgs; vq_attn_temporal_rowquant_shared; the two T <= 16 kernels) is the dynamic form for a joint
+// cond | uncond forward (B <= 2) at 2..8 bits: a token's grid comes from its min / max over all heads AND both samples
+// (base_quantizer.py:177-189), so one workgroup owns a spatial position of every sample.  It runs the attention steps per
+// sample, carries the lane's min / max from one sample to the next, keeps every sample's fp16 output in LDS (tq_park /
+// tq_unpark: each lane reads back what it wrote, no barrier) and encodes the samples' rows on the one grid; the division
+// by s is redone at the encode (deterministic, so the statistics and the codes see the same values).
 #pragma once
 #include "vq_common.h"
 #include "rowquant_shared.h"
@@ -134,6 +140,51 @@ __device__ __forceinline__ void tq_store_o(half_t* orow, const V (&ov)[(D + 15) 
     }
 }
 
+// ---- the shared-grid form: a dim tile's O^T * (1 / sum p) rounded to fp16, and its parking place ----------------------------
+// The fp16 output of the shared-grid form is pinned, bit for bit, to the dynamic form of the same kernel, and that form's
+// rounding is hipcc's choice (profiles/refactor_temporal_steps.md, "A rounding the compiler chooses"): v_mul_f32 +
+// v_cvt_pk_f16_f32 (the product rounded to fp32, then to fp16) everywhere in attn_temporal_quant2_kernel; in
+// attn_temporal_quant_kernel the ONE rounding of v_fma_mixlo_f16 for the first two values of every dim tile but the first,
+// two roundings for the rest.  MIXED spells that selection out, each rounding behind an asm so that it stays what is written
+// (the instantiation alone, with the park as one more consumer, was compiled to two roundings everywhere); the other
+// kernel's expression is the dynamic form's own, and its assembly is checked to hold no v_fma_mix* (profiles/temporal_shared).
+// (the asm reads an MFMA result, and the wait states between the two are the compiler's to insert for instructions it knows:
+//  an asm block is not one of them, so it brings its own - 12, where hipcc puts 8 at the most (s_nop 7) between such an MFMA
+//  and the first VALU read of its result in these kernels)
+template <bool MIXED>
+__device__ __forceinline__ half4 tq_round_o(const float4v& o4, float inv_p, int dt) {
+    half4 h;
+    if constexpr (MIXED) {
+        if (dt >= 1) {
+            uint32_t lo0, lo1;
+            asm("s_nop 7\n\ts_nop 3\n\tv_fma_mixlo_f16 %0, %2, %3, 0\n\tv_fma_mixlo_f16 %1, %2, %4, 0"
+                : "=&v"(lo0), "=&v"(lo1)
+                : "v"(inv_p), "v"(o4[0]), "v"(o4[1]));
+            h[0] = __builtin_bit_cast(half_t, (uint16_t)lo0);
+            h[1] = __builtin_bit_cast(half_t, (uint16_t)lo1);
+        }
+#pragma unroll
+        for (int r = dt >= 1 ? 2 : 0; r < 4; ++r) {
+            float p = o4[r] * inv_p;
+            asm("" : "+v"(p));
+            h[r] = (half_t)p;
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) h[r] = (half_t)(o4[r] * inv_p);
+    }
+    return h;
+}
+// this lane's four fp16 outputs of dim tile dt, [dt][thread] 8 bytes each: each lane reads back what it wrote, no barrier
+__device__ __forceinline__ void tq_park(uint8_t* park, int nthr, int tid, int dt, const half4& h) {
+    *reinterpret_cast<half4*>(park + ((size_t)dt * nthr + tid) * 8) = h;
+}
+__device__ __forceinline__ void tq_unpark(const uint8_t* park, int nthr, int tid, int dt, float (&x4)[4]) {
+    const half4 h = *reinterpret_cast<const half4*>(park + ((size_t)dt * nthr + tid) * 8);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) x4[r] = (float)h[r];
+}
+
 // ---- the quantizer's input: x / s of the consuming Linear's smoothing vector when it has one ----------------------------
 // (quant_layer.py:140; reciprocal form, bit-identical to the IEEE quotient - vq_common.h.)  ch: the channel of x4[0].
 template <class V>                                 // V: float[4] or float4v
@@ -182,16 +233,17 @@ __device__ __forceinline__ void tq_publish_minmax(float vmin, float vmax, float*
         ex_max[wave * 16 + lane] = vmax;
     }
 }
-// (behind the barrier) token tq's min / max over the H heads -> its 8-bit grid, as vq_rowquant derives it; ``flag``: this
-// lane reports the row's eps fill (one lane per stored row)
-__device__ __forceinline__ TqGrid tq_row_grid(const float* ex_min, const float* ex_max, int H, int tq, bool flag, int32_t* status) {
+// (behind the barrier) token tq's min / max over the H heads -> its grid at n_bits (8 in the dynamic form), as vq_rowquant
+// derives it; ``flag``: this lane reports the row's eps fill (one lane per stored row)
+__device__ __forceinline__ TqGrid tq_row_grid(const float* ex_min, const float* ex_max, int H, int tq, bool flag, int32_t* status,
+                                              int n_bits = 8) {
     float vmin = INFINITY, vmax = -INFINITY;
     for (int w = 0; w < H; ++w) {
         vmin = fminf(vmin, ex_min[w * 16 + tq]);
         vmax = fmaxf(vmax, ex_max[w * 16 + tq]);
     }
     TqGrid q;
-    q.wd = rq_width(8);
+    q.wd = rq_width(n_bits);
     q.g.thr = 0.f;
     bool small;
     vq_row_grid(vmin, vmax, q.wd.qmax, q.g.delta, q.g.zp, small, q.g.inv);

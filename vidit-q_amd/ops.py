@@ -723,6 +723,55 @@ def attn_temporal_rowquant(q, k, v, B, T, S, H, D, ld_in, scale: Optional[float]
     return QAct(xq, sx, zx, R, Cc, 8)
 
 
+def attn_temporal_shared_ok(B: int, T: int, H: int, D: int, Kp: int, n_bits: int) -> bool:
+    """Whether vq_attn_temporal_rowquant_shared takes this launch: every refusal of the entry point (include/viditq.h) that
+    these six arguments decide, mirrored for callers that choose a route BEFORE they launch - a refused shape takes
+    attention and the quantizer separately.  (S, ld_in and the pointers stay with the entry point.)"""
+    if min(B, T, H, D, Kp) <= 0:                                   # VQ_EINVAL
+        return False
+    Cc = H * D
+    if B > 2 or T > 16 or H > 16 or D not in (16, 32, 64, 72) or Cc % 16 != 0 or Kp % 128 != 0 or Kp < Cc:   # VQ_ESHAPE
+        return False
+    if 16 * (Cc // 8) > 3 * 64 * H or D % 4 != 0:                  # VQ_ESHAPE: the V staging registers of the kernel
+        return False
+    return 2 <= n_bits <= 8                                        # VQ_EUNSUP
+
+
+def attn_temporal_rowquant_shared(q, k, v, B, T, S, H, D, ld_in, n_bits: int = 8, scale: Optional[float] = None,
+                                  status: Optional[torch.Tensor] = None, o: Optional[torch.Tensor] = None,
+                                  s: Optional[torch.Tensor] = None) -> Optional[QAct]:
+    """Temporal attention (T <= 16) + the consuming Linear's per-token dynamic quantizer at ``n_bits`` (2..8) for a joint
+    forward of B <= 2 samples, whose rows of a token share one grid, in one kernel.  Returns what
+    ``rowquant(o.view(B, T*S, H*D), n_bits=n_bits, s=s)`` returns for the kernel's own fp16 output ``o`` (also written when
+    given, [B*T*S, H*D]), bit for bit.  ``s``: the consuming Linear's smoothing vector; None is returned (caller runs the
+    two kernels) when its reciprocal form is not available."""
+    s_rcp = None
+    if s is not None:
+        s_rcp = smooth_rcp(s)
+        if s_rcp is None:
+            return None
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise VQError("%s must be a GPU fp16 tensor" % n)
+    Cc = H * D
+    Kp = pad128(Cc)
+    rows = B * T * S
+    dev = q.device
+    if o is not None:
+        _req(o, torch.float16, "o")
+        if o.shape != (rows, Cc):
+            raise VQError("attn_temporal_rowquant_shared: o must be [B*T*S, H*D]")
+    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
+    sx = torch.empty(rows, dtype=torch.float32, device=dev)
+    zx = torch.empty(rows, dtype=torch.int32, device=dev)
+    R = torch.empty(rows, dtype=torch.int32, device=dev)
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    check(_L().vq_attn_temporal_rowquant_shared(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(xq), _p(sx), _p(zx), _p(R),
+                                                _p(status), _p(o), B, T, S, H, D, ld_in, Kp, n_bits, scale, _stream()),
+          "vq_attn_temporal_rowquant_shared")
+    return QAct(xq, sx, zx, R, Cc, n_bits)
+
+
 def attn_temporal_long(q, k, v, B, T, S, H, D, ld_in, o: Optional[torch.Tensor] = None, quant: bool = False,
                        scale: Optional[float] = None, status: Optional[torch.Tensor] = None,
                        s: Optional[torch.Tensor] = None):

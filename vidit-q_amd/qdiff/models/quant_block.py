@@ -112,6 +112,16 @@ class QuantAttention(nn.Module):
         return ops.attn_temporal_rowquant(qkv, qkv[:, C:], qkv[:, 2 * C:], B, T, S, self.num_heads, self.head_dim,
                                           qkv.stride(0), scale=self.scale, status=status, s=s)
 
+    def temporal_quantized_shared(self, qkv: torch.Tensor, B: int, T: int, S: int, n_bits: int, status=None, s=None):
+        """:meth:`temporal` + the dynamic per-token quantizer of the next Linear at ``n_bits`` (2..8) for a joint forward
+        (B <= 2, T <= 16: the samples' rows of a token share one grid), one kernel; None when that kernel does not apply
+        (then call :meth:`temporal` and the layer's own quantizer)."""
+        C = self.num_heads * self.head_dim
+        if not ops.attn_temporal_shared_ok(B, T, self.num_heads, self.head_dim, ops.pad128(C), n_bits):
+            return None
+        return ops.attn_temporal_rowquant_shared(qkv, qkv[:, C:], qkv[:, 2 * C:], B, T, S, self.num_heads, self.head_dim,
+                                                 qkv.stride(0), n_bits=n_bits, scale=self.scale, status=status, s=s)
+
     def temporal_quantized_static(self, qkv: torch.Tensor, B: int, T: int, S: int, delta: torch.Tensor, zp: torch.Tensor,
                                   n_bits: int, s=None):
         """:meth:`temporal` + the STATIC tensor-wise quantizer (``delta``, ``zp``: one value each; ``n_bits`` 2..8) of the

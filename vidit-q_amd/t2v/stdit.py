@@ -344,6 +344,12 @@ _GELU_QUANT = __import__('os').environ.get('VQ_GELU_QUANT', '1') != '0'
 # pass per Linear behind a LayerNorm launch.  Bit-identical; False restores that route (tests compare the two).
 _STATIC_FUSED = True
 
+# temporal attention + attn_temp.proj's DYNAMIC per-token quantizer in one kernel for what the B == 1, 8-bit route above does
+# not take: a joint cond | uncond forward (B = 2, cfg_split: False) and code widths of 2..7 bits, T <= 16
+# (ops.attn_temporal_rowquant_shared).  Off by default for the reason VQ_STATIC_ATTN_QUANT is: the fused kernels round a few
+# fp16 attention outputs an ulp away from attn_temporal_kernel's, so a joint or sub-8-bit plan's
+# output moves inside its parity bound; VQ_ATTN_QUANT_JOINT=1 turns it on (DESIGN section 8 has the criterion for the default).
+_ATTN_QUANT_JOINT = __import__("os").environ.get("VQ_ATTN_QUANT_JOINT", "0") != "0"
 # temporal attention + attn_temp.proj's static tensor-wise quantizer in one kernel (ops.attn_temporal_rowquant_static)
 # instead of attention + one quantizer pass.  Off by default: the fused kernel's fp16 output differs from
 # attn_temporal_kernel's by one ulp in a few elements, so a static plan's output moves inside its
@@ -690,9 +696,14 @@ class STDiTBlock(nn.Module):
             qas = [l.quantize_input(x3, s, add_rows=tpe2, add_div=S) for l, s in zip((a2.q, a2.k, a2.v), svs)]
         qkv = qkv_proj(a2, qas)
         qa = None
-        if _ATTN_QUANT and isinstance(a2.proj.act_quantizer, DynamicActQuantizer) and a2.proj.act_quantizer.n_bits == 8:
+        if _ATTN_QUANT and isinstance(a2.proj.act_quantizer, DynamicActQuantizer) and a2.proj.act_quantizer.n_bits == 8 \
+                and (B == 1 or not _ATTN_QUANT_JOINT):
             # attention + proj's quantizer (behind proj's smoothing vector, if any) in one kernel
             qa = a2.core.temporal_quantized(qkv, B, T, S, status=a2.proj.status, s=svec(a2.proj))
+        elif _ATTN_QUANT and _ATTN_QUANT_JOINT and isinstance(a2.proj.act_quantizer, DynamicActQuantizer):
+            # the same for a joint forward (B = 2) and for code widths below 8 bits: one grid per token over the samples
+            qa = a2.core.temporal_quantized_shared(qkv, B, T, S, a2.proj.act_quantizer.n_bits, status=a2.proj.status,
+                                                   s=svec(a2.proj))
         elif _static_attn_quant(a2.proj, T, a2.core.num_heads, a2.core.head_dim):
             aq = a2.proj.act_quantizer
             qa = a2.core.temporal_quantized_static(qkv, B, T, S, aq.delta.float(), aq.zero_point.float(), aq.n_bits,
