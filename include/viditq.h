@@ -120,6 +120,26 @@ int vq_rowquant_smooth_multi(const void* x, int n_out, const float* const* s, co
                              int8_t* const* xq, float* const* sx, int32_t* const* zx, int32_t* const* R,
                              int n_tok, int C, int Kp, int n_bits, int32_t* status, void* stream);
 
+/* The same for a JOINT forward over cat([x, x]) (cfg_split: False; iddpm/__init__.py:141-163): x [2, n_tok, C] fp16 and
+ * n_out (1..3) smoothed per-token dynamic quantizers from ONE pass over the rows, the grid of a token shared by its rows
+ * of both samples (base_quantizer.py:177-189, line 185), outputs indexed by row = sample * n_tok + token with the shared
+ * step replicated, as vq_rowquant(B = 2) writes them.  Input arm, one of:
+ *   plain (shift = scale = NULL): output j is vq_rowquant(x, s[j], s_rcp[j], B = 2), bit for bit - the q / k / v
+ *   quantizers of temporal attention (stdit.py:112-118; quant_layer.py:136-160; dynamic_quantizer.py:16-45);
+ *   LayerNorm(ln_eps, no affine) + (1 + scale[b]) * y + shift[b] (shift / scale fp32 [2, C], both set; stdit.py:100-103,
+ *   124; layers/blocks.py:51): output j is vq_ln_modulate_rowquant(n_out = 1, s[j], B = 2), bit for bit.
+ * s, s_rcp, xq, sx, zx, R are HOST arrays of n_out device pointers, reciprocals (vq_smooth_reciprocal) mandatory.
+ * There is no xm_out and there are no added rows.
+ * Errors, each before any device call or dereference of a device pointer, checked in this order: VQ_EINVAL for a null
+ * required pointer or array entry below n_out, exactly one of shift / scale, n_out outside 1..3, a non-positive B, n_tok
+ * or C; VQ_ESHAPE for C % 8, Kp % 128 or Kp < C and VQ_EUNSUP for n_bits outside 2..8; VQ_ESHAPE for x, shift, scale, s[j],
+ * s_rcp[j] or xq[j] off 16 bytes; VQ_EUNSUP for B != 2, a width other than 768, 1024, 1152 or 1280, or Kp != C - the
+ * caller then runs one launch per output. */
+int vq_rowquant_smooth_multi_shared(const void* x, const float* shift, const float* scale, float ln_eps, int n_out,
+                                    const float* const* s, const float* const* s_rcp, int8_t* const* xq, float* const* sx,
+                                    int32_t* const* zx, int32_t* const* R, int B, int n_tok, int C, int Kp, int n_bits,
+                                    int32_t* status, void* stream);
+
 /* One pass over x [B, n_tok, C] fp16 -> n_out (1..3) quantized copies on STATIC calibrated grids: ActQuantizer.forward
  * after init_done (qdiff/quantizer/base_quantizer.py:129-144) for Linears that share an input (q / k / v), with what
  * precedes them in a block in the same pass.  Input arm, one of:

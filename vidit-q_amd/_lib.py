@@ -30,6 +30,7 @@ SIGNATURES = {
                                      _i, _i, _i, _i, _i, _vp, _vp]),
     "vq_smooth_reciprocal": (_i, [_vp, _vp, _i, _vp, _vp]),
     "vq_rowquant_smooth_multi": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "vq_rowquant_smooth_multi_shared": (_i, [_vp, _vp, _vp, _f, _i] + [_vp] * 6 + [_i] * 5 + [_vp, _vp]),
     "vq_rowquant_static": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                 _i, _i, _i, _i, _i, _vp]),
     "vq_act_scale_momentum": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp]),
@@ -74,6 +75,14 @@ def load(path: str = LIB_PATH):
         raise VQError(
             "libviditq_hip.so not found at %s - build it with `python -c \"import __graft_entry__ as g; g.build()\"` "
             "(hipcc --offload-arch=gfx950); there is no CPU/eager fallback for the product path" % path)
+    # torch first: a torch wheel that bundles its own libamdhip64 asks for it by the unversioned name, which a runtime
+    # already loaded under its soname does not satisfy - bound before torch, this library would sit on a SECOND HIP runtime
+    # in the process, whose initialisation fails (every launch then returns hipErrorNoDevice).  Loaded after torch, the
+    # library's versioned dependency resolves to the runtime torch brought, and device pointers and streams are shared.
+    try:
+        import torch  # noqa: F401
+    except ImportError:
+        pass                                                # the bare C ABI, without the tensor-level wrappers
     lib = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the ABI and the header drift apart

@@ -575,3 +575,24 @@ extern "C" int vq_rowquant_smooth_multi(const void* x, int n_out, const float* c
         return VQ_EUNSUP;
     return vq_check_launch();
 }
+
+static bool rq_off16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+
+extern "C" int vq_rowquant_smooth_multi_shared(const void* x, const float* shift, const float* scale, float ln_eps, int n_out,
+                                               const float* const* s, const float* const* s_rcp, int8_t* const* xq,
+                                               float* const* sx, int32_t* const* zx, int32_t* const* R, int B, int n_tok, int C,
+                                               int Kp, int n_bits, int32_t* status, void* stream) {
+    if (!x || !s || !s_rcp || !xq || !sx || !zx || !R || (shift == nullptr) != (scale == nullptr)) return VQ_EINVAL;
+    if (n_out < 1 || n_out > 3 || B <= 0 || n_tok <= 0 || C <= 0) return VQ_EINVAL;
+    for (int j = 0; j < n_out; ++j)
+        if (!s[j] || !s_rcp[j] || !xq[j] || !sx[j] || !zx[j] || !R[j]) return VQ_EINVAL;
+    if (const int e = rq_check_shape(C, Kp, n_bits)) return e;
+    if (rq_off16(x) || rq_off16(shift) || rq_off16(scale)) return VQ_ESHAPE;   // 16-byte loads and 4 / 8-byte stores
+    for (int j = 0; j < n_out; ++j)
+        if (rq_off16(s[j]) || rq_off16(s_rcp[j]) || rq_off16(xq[j])) return VQ_ESHAPE;
+    if (B != 2 || !rq_block_width(C) || Kp != C) return VQ_EUNSUP;               // one launch per output instead
+    if (!vq_rowquant_smooth_multi_pair_fast((const half_t*)x, shift, scale, ln_eps, n_out, s, s_rcp, xq, sx, zx, R, n_tok, C, Kp,
+                                            n_bits, status, (hipStream_t)stream))
+        return VQ_EUNSUP;
+    return vq_check_launch();
+}

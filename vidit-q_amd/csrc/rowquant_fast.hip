@@ -621,20 +621,27 @@ static bool launch_smooth_half(const half_t* x, const float* shift, const float*
 // waves per SIMD asked of the compiler, row pairs per wave, waves per workgroup: one output / two or three
 constexpr int VQ_SM1_MINW = 6, VQ_SM1_RPW = 1, VQ_SM1_NWV = 8;
 constexpr int VQ_SMM_MINW = 4, VQ_SMM_RPW = 1, VQ_SMM_NWV = 8;
-template <int NIT, bool LN, int NOUT, int RPW, int NWV>
+// PAIR (vq_rowquant_smooth_multi_shared): x [2, n_tok, C], the wave's two rows are the two samples of ONE token (see
+// rowquant_half_kernel), whose grid the reference shares over the batch (base_quantizer.py:185): per output the min / max
+// of the two half-waves are combined, everything else - the LayerNorm statistics, the codes, the row sums - stays per
+// row, and both samples' modulation vectors ([2, C]) are staged, the upper half reading sample 1's.  A workgroup owns
+// NWV * RPW tokens.  Same per-lane expressions in the same order as smooth_rowquant_half_kernel<.., PAIR>: output j is
+// that kernel's launch with vector j, bit for bit (tested).  No xm_out in this form.
+template <int NIT, bool LN, int NOUT, int RPW, int NWV, bool PAIR = false>
 __global__ __launch_bounds__(64 * NWV, NOUT == 1 ? VQ_SM1_MINW : VQ_SMM_MINW) void smooth_rowquant_multi_kernel(
     const half_t* __restrict__ x, const float* __restrict__ shift, const float* __restrict__ scale, float ln_eps,
     LnqOut o, half_t* __restrict__ xm_out, int n_tok, int n_bits, int32_t* status) {
     using L = RqHalf<NIT>;
     constexpr int C = 128 * NIT;
-    extern __shared__ __attribute__((aligned(16))) float smq_lds[];   // [NOUT][s | r][C], then (LN) [1 + scale | shift][C]
+    constexpr int NMOD = PAIR ? 2 : 1;                     // samples whose [1 + scale | shift] are staged
+    extern __shared__ __attribute__((aligned(16))) float smq_lds[];   // [NOUT][s | r][C], then (LN) [NMOD][1 + scale | shift][C]
     const int lane = threadIdx.x & 63, hl = lane & 31, lc = L::lane_col(lane);
     const bool hi = lane >= 32;
     const RqWidth wd = rq_width(n_bits);
     const int pair0 = (blockIdx.x * NWV + (threadIdx.x >> 6)) * RPW;
     bool live;
     half4 hn[NIT];                                         // the first rows are requested before the staging loads
-    rq_load_row<L>(x + (size_t)rqh_row<false>(pair0, hi, n_tok, live) * C, lc, C, hn);
+    rq_load_row<L>(x + (size_t)rqh_row<PAIR>(pair0, hi, n_tok, live) * C, lc, C, hn);
     for (int i = threadIdx.x; i < C / 4; i += 64 * NWV) {
 #pragma unroll
         for (int j = 0; j < NOUT; ++j) {
@@ -642,21 +649,25 @@ __global__ __launch_bounds__(64 * NWV, NOUT == 1 ? VQ_SM1_MINW : VQ_SMM_MINW) vo
             reinterpret_cast<float4v*>(smq_lds + (2 * j + 1) * C)[i] = reinterpret_cast<const float4v*>(o.r[j])[i];
         }
         if constexpr (LN) {
-            float sc1[4], sh[4];
-            rq_load_mod<4>(scale + 4 * i, shift + 4 * i, sc1, sh);
-            reinterpret_cast<float4v*>(smq_lds + (2 * NOUT) * C)[i] = *reinterpret_cast<const float4v*>(sc1);
-            reinterpret_cast<float4v*>(smq_lds + (2 * NOUT + 1) * C)[i] = *reinterpret_cast<const float4v*>(sh);
+#pragma unroll
+            for (int b = 0; b < NMOD; ++b) {
+                float sc1[4], sh[4];
+                rq_load_mod<4>(scale + b * C + 4 * i, shift + b * C + 4 * i, sc1, sh);
+                reinterpret_cast<float4v*>(smq_lds + (2 * NOUT + 2 * b) * C)[i] = *reinterpret_cast<const float4v*>(sc1);
+                reinterpret_cast<float4v*>(smq_lds + (2 * NOUT + 2 * b + 1) * C)[i] = *reinterpret_cast<const float4v*>(sh);
+            }
         }
     }
     __syncthreads();
+    const float* lmod = smq_lds + (2 * NOUT + ((PAIR && hi) ? 2 : 0)) * C;   // modulation vectors of this half's sample
     for (int it = 0; it < RPW; ++it) {
-        if ((pair0 + it) * 2 >= n_tok) break;              // wave-uniform
-        const int tok = rqh_row<false>(pair0 + it, hi, n_tok, live);
+        if ((PAIR ? pair0 + it : (pair0 + it) * 2) >= n_tok) break;   // wave-uniform
+        const int tok = rqh_row<PAIR>(pair0 + it, hi, n_tok, live);
         float w[NIT][4];
         rq_widen_row<L>(hn, lc, C, w);
         if (it + 1 < RPW) {                                // next pair's rows fly under this pair's arithmetic
             bool unused;
-            rq_load_row<L>(x + (size_t)rqh_row<false>(pair0 + it + 1, hi, n_tok, unused) * C, lc, C, hn);
+            rq_load_row<L>(x + (size_t)rqh_row<PAIR>(pair0 + it + 1, hi, n_tok, unused) * C, lc, C, hn);
         }
         if constexpr (LN) {
             float mu, rstd;
@@ -664,9 +675,9 @@ __global__ __launch_bounds__(64 * NWV, NOUT == 1 ? VQ_SM1_MINW : VQ_SMM_MINW) vo
 #pragma unroll
             for (int i = 0; i < NIT; ++i) {
                 float sc1[4], sh[4];
-                rq_load_f<4>(smq_lds + (2 * NOUT) * C + lc + i * 128, sc1);
-                rq_load_f<4>(smq_lds + (2 * NOUT + 1) * C + lc + i * 128, sh);
-                rq_modulate<4>(w[i], mu, rstd, sc1, sh, xm_out && live, xm_out, (size_t)tok * C + lc + i * 128);
+                rq_load_f<4>(lmod + lc + i * 128, sc1);
+                rq_load_f<4>(lmod + C + lc + i * 128, sh);
+                rq_modulate<4>(w[i], mu, rstd, sc1, sh, !PAIR && xm_out && live, xm_out, (size_t)tok * C + lc + i * 128);
             }
         }
 #pragma unroll
@@ -680,26 +691,27 @@ __global__ __launch_bounds__(64 * NWV, NOUT == 1 ? VQ_SM1_MINW : VQ_SMM_MINW) vo
                 rq_load_f<4>(smq_lds + (2 * j + 1) * C + lc + i * 128, r4);
                 rq_smooth_chunk<4>(w[i], s4, r4, q[i], vmin, vmax);
             }
-            rqh_minmax<false>(vmin, vmax, hi);
+            rqh_minmax<PAIR>(vmin, vmax, hi);
             float delta, zp, inv;
             bool small;
             vq_row_grid(vmin, vmax, wd.qmax, delta, zp, small, inv);
-            if (small && hl == 0 && live && status) atomicOr(status, VQ_ST_EPSFILL);
+            if (small && (PAIR ? lane == 0 : hl == 0) && live && status) atomicOr(status, VQ_ST_EPSFILL);   // once per grid
             const int cs = rq_quant_row<L>(q, lc, C, C, delta, zp, inv, wd, o.xq[j] + (size_t)tok * C, live, hi);
             if (hl == 0 && live) rq_write_row(o.sx[j], o.zx[j], o.R[j], nullptr, tok, delta, zp, cs, C, wd.cx);
         }
     }
 }
 
-template <bool LN, int NOUT>
+template <bool LN, int NOUT, bool PAIR = false>
 static bool launch_smooth_multi(const half_t* x, const float* shift, const float* scale, float eps, const LnqOut& o,
                                 half_t* xm, int n_tok, int C, int n_bits, int32_t* status, hipStream_t st) {
     constexpr int RPW = NOUT == 1 ? VQ_SM1_RPW : VQ_SMM_RPW, NWV = NOUT == 1 ? VQ_SM1_NWV : VQ_SMM_NWV;
-    const size_t lds = (size_t)(2 * NOUT + (LN ? 2 : 0)) * C * sizeof(float);
-    dim3 grid((n_tok + 2 * NWV * RPW - 1) / (2 * NWV * RPW));
-    return vq_dispatch_nit(C, [&](auto nit) {              // <= 8 x 5 KB of LDS: inside the 64 KB every kernel may use
-        hipLaunchKernelGGL((smooth_rowquant_multi_kernel<nit(), LN, NOUT, RPW, NWV>), grid, dim3(64 * NWV), lds, st, x, shift,
-                           scale, eps, o, xm, n_tok, n_bits, status);
+    constexpr int PER = (PAIR ? 1 : 2) * NWV * RPW;        // rows (PAIR: tokens) per workgroup
+    const size_t lds = (size_t)(2 * NOUT + (LN ? (PAIR ? 4 : 2) : 0)) * C * sizeof(float);
+    dim3 grid((n_tok + PER - 1) / PER);
+    return vq_dispatch_nit(C, [&](auto nit) {              // <= 10 x 5 KB of LDS: inside the 64 KB every kernel may use
+        hipLaunchKernelGGL((smooth_rowquant_multi_kernel<nit(), LN, NOUT, RPW, NWV, PAIR>), grid, dim3(64 * NWV), lds, st, x,
+                           shift, scale, eps, o, xm, n_tok, n_bits, status);
     });
 }
 
@@ -892,4 +904,21 @@ bool vq_rowquant_smooth_multi_fast(const half_t* x, int n_out, const float* cons
     if (n_out == 2 && launch_smooth_multi<false, 2>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;
     if (n_out == 1 && vq_sm1_mode() && launch_smooth_multi<false, 1>(x, nullptr, nullptr, 0.f, o, nullptr, n_tok, C, n_bits, status, st)) return true;
     return launch_smooth_half<false, 2>(x, nullptr, nullptr, 0.f, o, n_out, nullptr, n_tok, C, n_bits, status, st);
+}
+
+// the same for x [2, n_tok, C] with the grids of a token shared by its two samples, optionally behind LayerNorm + modulate
+// (shift / scale [2, C], both or neither): smooth_rowquant_multi_kernel<.., PAIR>
+bool vq_rowquant_smooth_multi_pair_fast(const half_t* x, const float* shift, const float* scale, float eps, int n_out,
+                                        const float* const* s, const float* const* s_rcp, int8_t* const* xq, float* const* sx,
+                                        int32_t* const* zx, int32_t* const* R, int n_tok, int C, int Kp, int n_bits,
+                                        int32_t* status, hipStream_t st) {
+    if (Kp != C || !rq_block_width(C) || n_out < 1 || n_out > 3) return false;
+    const LnqOut o = lnq_many(n_out, s, s_rcp, xq, sx, zx, R);
+    bool done = false;
+    vq_dispatch_bool(shift != nullptr, [&](auto ln) {
+        if (n_out == 3) done = launch_smooth_multi<ln(), 3, true>(x, shift, scale, eps, o, nullptr, n_tok, C, n_bits, status, st);
+        else if (n_out == 2) done = launch_smooth_multi<ln(), 2, true>(x, shift, scale, eps, o, nullptr, n_tok, C, n_bits, status, st);
+        else done = launch_smooth_multi<ln(), 1, true>(x, shift, scale, eps, o, nullptr, n_tok, C, n_bits, status, st);
+    });
+    return done;
 }

@@ -28,6 +28,10 @@ bool vq_lnq_pair_fast(const half_t* x, const float* shift, const float* scale, f
 bool vq_rowquant_smooth_multi_fast(const half_t* x, int n_out, const float* const* s, const float* const* s_rcp,
                                    int8_t* const* xq, float* const* sx, int32_t* const* zx, int32_t* const* R, int n_tok,
                                    int C, int Kp, int n_bits, int32_t* status, hipStream_t st);
+bool vq_rowquant_smooth_multi_pair_fast(const half_t* x, const float* shift, const float* scale, float eps, int n_out,
+                                        const float* const* s, const float* const* s_rcp, int8_t* const* xq, float* const* sx,
+                                        int32_t* const* zx, int32_t* const* R, int n_tok, int C, int Kp, int n_bits,
+                                        int32_t* status, hipStream_t st);
 // one-pass kernels for a static grid (rowquant_static.hip); false when the shape is not covered, else *rc = the result
 bool vq_rowquant_static_one(const half_t* x, const half_t* add_rows, int n_add, int add_div, const float* s, const float* s_rcp,
                             int8_t* xq, float* sx, int32_t* zx, int32_t* R, const float* delta, const float* zp, int n_param,

@@ -222,6 +222,60 @@ def rowquant_multi(x: torch.Tensor, smooth: Sequence[torch.Tensor], n_bits: int 
     return outs
 
 
+def rowquant_multi_shared_ok(B: int, n_tok: int, Cc: int, Kp: int, n_bits: int, n_out: int) -> bool:
+    """Whether vq_rowquant_smooth_multi_shared takes this launch: every refusal of the entry point (include/viditq.h) that
+    these six arguments decide, mirrored for callers that choose a route BEFORE they launch - a refused shape takes one
+    launch per output.  (The pointers, their alignment and the shift / scale pair stay with the entry point.)"""
+    if not (1 <= n_out <= 3) or min(B, n_tok, Cc) <= 0:              # VQ_EINVAL
+        return False
+    if Cc % 8 or Kp % 128 or Kp < Cc:                                 # VQ_ESHAPE
+        return False
+    if not (2 <= n_bits <= 8):                                        # VQ_EUNSUP: the code width
+        return False
+    return B == 2 and Cc in (768, 1024, 1152, 1280) and Kp == Cc     # VQ_EUNSUP: the half-wave pair kernel's shapes
+
+
+def rowquant_multi_shared(x: torch.Tensor, smooth: Sequence[torch.Tensor], n_bits: int = 8,
+                          status: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
+                          scale: Optional[torch.Tensor] = None, eps: float = 1e-6) -> Optional[List[QAct]]:
+    """One QAct of x [2, n_tok, C] (a joint forward: a token's grid is shared by its rows of both samples) per smoothing
+    vector, from ONE pass over the rows.  Plain: output j is ``rowquant(x, n_bits, s=smooth[j])``, bit for bit.  With
+    ``shift`` / ``scale`` [2, C] fp32: LayerNorm + modulate first, output j is ``ln_modulate_rowquant(x, shift, scale, eps,
+    smooth=[smooth[j]], n_bits)``, bit for bit.  None - nothing launched, nothing written - when the entry point would
+    refuse the shape (:func:`rowquant_multi_shared_ok`) or a vector has no exact reciprocal form."""
+    _req(x, torch.float16, "x")
+    assert x.dim() == 3
+    B, n_tok, Cc = x.shape
+    Kp = pad128(Cc)
+    G = len(smooth)
+    if (shift is None) != (scale is None):
+        raise VQError("rowquant_multi_shared: shift and scale come together")
+    if not rowquant_multi_shared_ok(B, n_tok, Cc, Kp, n_bits, G):
+        return None
+    for sm in smooth:
+        _req(sm, torch.float32, "smooth")
+        if sm.numel() != Cc:
+            raise VQError("rowquant_multi_shared: one smoothing entry per channel")
+    rcps = [smooth_rcp(sm) for sm in smooth]                      # kept alive until the launch is enqueued
+    if any(r is None for r in rcps):
+        return None
+    if shift is not None:
+        _req(shift, torch.float32, "shift")
+        _req(scale, torch.float32, "scale")
+        if shift.numel() != B * Cc or scale.numel() != B * Cc:
+            raise VQError("rowquant_multi_shared: shift / scale must be [B, C]")
+    rows, dev = B * n_tok, x.device
+    outs = [QAct(torch.empty((rows, Kp), dtype=torch.int8, device=dev), torch.empty(rows, dtype=torch.float32, device=dev),
+                 torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
+                 Cc, n_bits) for _ in range(G)]
+    keep = [_ptr_array([_p(sm) for sm in smooth]), _ptr_array([_p(r) for r in rcps])] + \
+           [_ptr_array([getattr(o, f).data_ptr() for o in outs]) for f in ("xq", "sx", "zx", "R")]
+    check(_L().vq_rowquant_smooth_multi_shared(_p(x), _p(shift), _p(scale), float(eps), G,
+                                               *[C.cast(k, C.c_void_p) for k in keep], B, n_tok, Cc, Kp, n_bits, _p(status),
+                                               _stream()), "vq_rowquant_smooth_multi_shared")
+    return outs
+
+
 STATIC_MAX_KP = 4608        # rows the one-pass static-grid kernels hold (csrc/rowquant_static.hip)
 
 

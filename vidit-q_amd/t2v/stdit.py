@@ -350,6 +350,25 @@ _STATIC_FUSED = True
 # fp16 attention outputs an ulp away from attn_temporal_kernel's, so a joint or sub-8-bit plan's
 # output moves inside its parity bound; VQ_ATTN_QUANT_JOINT=1 turns it on (DESIGN section 8 has the criterion for the default).
 _ATTN_QUANT_JOINT = __import__("os").environ.get("VQ_ATTN_QUANT_JOINT", "0") != "0"
+# the smoothed q | k | v quantizers of a joint forward (B = 2, cfg_split: False; dynamic per-token grids shared by the two
+# samples of a token, a smoothing vector per Linear: w8a8 / w4a8 / w6a6_smooth_quant) from ONE pass over the rows
+# (ops.rowquant_multi_shared) - behind LayerNorm + modulate instead of the generic B > 1 kernel, and in the temporal branch
+# instead of three launches.  Off by default: the LayerNorm arm sums a row in the half-wave order, the generic kernel in
+# the wave order, so a few codes of such a plan move by one step inside its parity bound; the plain arm
+# is bit-identical and rides on the same switch.  VQ_SMOOTH_JOINT=1 turns it on (DESIGN section 8 has the criterion).
+_SMOOTH_JOINT = __import__("os").environ.get("VQ_SMOOTH_JOINT", "0") != "0"
+
+
+def _smooth_joint(layers, svs, B, add_rows=False) -> bool:
+    """Whether ONE ops.rowquant_multi_shared launch serves the quantizers of ``layers`` (which share an input) behind their
+    smoothing vectors ``svs``: the switch, a joint forward, no added rows, dynamic quantizers of one bit width and a vector
+    on every Linear.  (The shape and the reciprocals are the launch's own: it answers None and the caller falls through.)"""
+    if not _SMOOTH_JOINT or B != 2 or add_rows or any(s is None for s in svs):
+        return False
+    aqs = [l.act_quantizer for l in layers]
+    return all(isinstance(a, DynamicActQuantizer) for a in aqs) and len({a.n_bits for a in aqs}) == 1
+
+
 # temporal attention + attn_temp.proj's static tensor-wise quantizer in one kernel (ops.attn_temporal_rowquant_static)
 # instead of attention + one quantizer pass.  Off by default: the fused kernel's fp16 output differs from
 # attn_temporal_kernel's by one ulp in a few elements (DESIGN section 1 row A8), so a static plan's output moves inside its
@@ -551,6 +570,11 @@ class STDiTBlock(nn.Module):
         modulated fp16 activation and every layer quantizes it on ITS calibrated (delta, zero_point)
         (base_quantizer.py:129-144) - never a silently substituted dynamic grid."""
         l0 = layers[0]
+        if len(layers) > 1 and _smooth_joint(layers, svs, x3.shape[0]):    # (one output, fc1: the pair kernel below)
+            qas = ops.rowquant_multi_shared(x3, svs, n_bits=l0.act_quantizer.n_bits, status=status, shift=shift, scale=scale,
+                                            eps=1e-6)
+            if qas is not None:
+                return qas
         if all(isinstance(l.act_quantizer, DynamicActQuantizer) for l in layers):
             smooth = [None] if all(s is None for s in svs) else list(svs)
             return ops.ln_modulate_rowquant(x3, shift, scale, 1e-6, smooth=smooth, n_bits=l0.act_quantizer.n_bits,
@@ -683,7 +707,13 @@ class STDiTBlock(nn.Module):
         # ---- temporal branch on the un-modulated x (+tpe in block 0)          (stdit.py:112-118)
         svs = [svec(l) for l in (a2.q, a2.k, a2.v)]
         tpe2 = None if tpe is None else tpe.reshape(T, C).contiguous()
-        if all(s is None for s in svs) and isinstance(a2.q.act_quantizer, DynamicActQuantizer):
+        qas = None
+        if _smooth_joint((a2.q, a2.k, a2.v), svs, B, add_rows=tpe2 is not None):
+            # a joint forward's three smoothed copies from one pass (None: refused, today's launches below)
+            qas = ops.rowquant_multi_shared(x3, svs, n_bits=a2.q.act_quantizer.n_bits, status=a2.q.status)
+        if qas is not None:
+            pass
+        elif all(s is None for s in svs) and isinstance(a2.q.act_quantizer, DynamicActQuantizer):
             qas = [a2.q.quantize_input(x3, None, add_rows=tpe2, add_div=S)]
         elif tpe2 is None and B == 1 and all(s is not None for s in svs) and all(
                 isinstance(l.act_quantizer, DynamicActQuantizer) for l in (a2.q, a2.k, a2.v)) and len(
