@@ -275,3 +275,54 @@ def dpm_mode_model(x, t, y, **kw):
     w = torch.cos(t.float() * (3.0 / 1000.0)).reshape(-1, 1, 1, 1)
     c = y.float().mean(dim=(1, 2, 3)).reshape(-1, 1, 1, 1)
     return 0.35 * w * x + 0.2 * torch.tanh(x * 0.5 + c) + 0.1 * c
+
+
+# ---- launch traces of the fused block route (tests/block_trace_cases.py, tests/golden/make_block_traces.py)
+def _describe_arg(v):
+    """What a launch depends on, without addresses: a tensor's shape / dtype / strides, a scalar's value; containers and
+    the ops dataclasses (QAct, PackedWeight, ...) member by member."""
+    import dataclasses
+    if isinstance(v, torch.Tensor):
+        return ["tensor", list(v.shape), str(v.dtype), list(v.stride())]
+    if v is None or isinstance(v, (bool, int, float, str)):
+        return v
+    if isinstance(v, (list, tuple)):
+        return [_describe_arg(e) for e in v]
+    if dataclasses.is_dataclass(v):
+        return [type(v).__name__, {f.name: _describe_arg(getattr(v, f.name)) for f in dataclasses.fields(v)}]
+    if isinstance(v, (torch.dtype, torch.device)):
+        return str(v)
+    return "<%s>" % type(v).__name__
+
+
+class trace_ops:
+    """Context manager: wraps every plain public function of ``viditq_amd.ops`` and records the ordered list of
+    ``[name, {parameter: description}]`` of the calls made while it is open (calls one ops function makes to another
+    included).  Arguments are bound to the function's signature with its defaults applied, so a value passed by position
+    and the same value passed by keyword give the same record."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __enter__(self):
+        import inspect
+        import types
+        from viditq_amd import ops
+        self.ops, self.saved = ops, {}
+        for name, fn in list(vars(ops).items()):
+            if name.startswith("_") or not isinstance(fn, types.FunctionType) or fn.__module__ != ops.__name__:
+                continue
+            self.saved[name] = fn
+
+            def traced(*a, _fn=fn, _name=name, _sig=inspect.signature(fn), **k):
+                bound = _sig.bind(*a, **k)
+                bound.apply_defaults()
+                self.calls.append([_name, {p: _describe_arg(v) for p, v in bound.arguments.items()}])
+                return _fn(*a, **k)
+            setattr(ops, name, traced)
+        return self.calls
+
+    def __exit__(self, *exc):
+        for name, fn in self.saved.items():
+            setattr(self.ops, name, fn)
+        return False

@@ -8,9 +8,10 @@ name routing of QuantModel(model_type='pixart') applies unchanged:
   x_embedder.proj (Conv2d) -> QuantLayer, kept FP by the t2i FP list (quant_txt2img.py:293-295).
 Unlike t2v, final_layer.linear is NOT in the t2i FP list and is quantized.
 
-Block = STDiT block without the temporal branch (PixArtMS.py:71-79); the fused route reuses the same
-kernels: LN+modulate+quant -> fused-qkv int8 GEMM -> flash attention over N tokens (4096 at 1024^2)
--> proj GEMM (+gate, +residual) -> varlen cross attention -> MLP.  kv-compression (sr_ratio > 1) and
+Block = STDiT block without the temporal branch (PixArtMS.py:71-79); the fused route is the stage functions of
+t2v/stdit.py behind this model's own front end: LN+modulate+quant -> fused-qkv int8 GEMM -> flash attention over N tokens
+(4096 at 1024^2) -> proj GEMM (+gate, +residual) [attn_proj_stage] -> varlen cross attention [cross_stage] -> MLP [mlp_stage];
+the route rules and switches are stdit's as well (fused_rules, takes_fused).  kv-compression (sr_ratio > 1) and
 qk_norm are not used by the quantized configs; they are implemented (round 6) with their FP parts as torch ops around the HIP attention.
 """
 from __future__ import annotations
@@ -25,9 +26,9 @@ import torch.nn.functional as F
 from .. import ops
 from ..qdiff.models.quant_block import QuantAttention
 from ..qdiff.models.quant_layer import QuantLayer
-from ..qdiff.quantizer.dynamic_quantizer import DynamicActQuantizer
-from ..t2v.stdit import (CaptionEmbedder, Mlp, fp_edge_linear, MultiHeadCrossAttention, STDiTBlock, T2IFinalLayer, TimestepEmbedder,
-                         approx_gelu, fused_running_rules, get_1d_sincos_pos_embed_from_grid, seq_offsets, t2i_modulate,
+from ..t2v.stdit import (CaptionEmbedder, Mlp, fp_edge_linear, MultiHeadCrossAttention, T2IFinalLayer, TimestepEmbedder,
+                         approx_gelu, attn_proj_stage, cross_stage, fused_rules, fwd_attn_quantized_static,
+                         get_1d_sincos_pos_embed_from_grid, ln_quant, mlp_stage, prompt_kv_exact_fill, seq_offsets, t2i_modulate,
                          takes_fused)
 
 
@@ -185,24 +186,12 @@ class PixArtMSBlock(nn.Module):
                 self.cross_attn.proj, self.mlp.fc1, self.mlp.fc2]
 
     def fused_ok(self) -> bool:
-        # (twin: fused_running_ok / t2v/stdit.py fused_running_rules restate these rules for the opt-in route of a running
-        # statistic on mlp.fc2 - a rule added here belongs there too)
-        for m in self.hot_layers():
-            if not (isinstance(m, QuantLayer) and m.int_route_ok()):
-                return False
-            if not isinstance(m.act_quantizer, DynamicActQuantizer) and m.act_quantizer.per_group:
-                return False
-            if getattr(m, "smooth_quant_running_stat", False):
-                # the released t2i script leaves the running act-scale statistic ON for blocks.27.mlp.fc2 at inference
-                # (quant_txt2img.py:297-300): that layer re-derives s from every input, which is QuantLayer.forward's
-                # job (host-visible statistics) - such a block takes the reference data flow, layer by layer
-                return False
-        return True
+        return fused_rules(self)
 
     def fused_running_ok(self) -> bool:
-        """:meth:`fused_ok` with a running smooth-quant statistic tolerated on ``mlp.fc2`` (served on the device by
-        QuantLayer.running_stat_step); consulted only under VQ_RUNNING_SMOOTH_DEVICE (t2v/stdit.py)."""
-        return fused_running_rules(self)
+        """:meth:`fused_ok` with a running smooth-quant statistic tolerated on ``mlp.fc2``; consulted only under
+        VQ_RUNNING_SMOOTH_DEVICE (t2v/stdit.py takes_fused)."""
+        return fused_rules(self, running=True)
 
     def forward(self, x, y, t, mask=None, HW=None, **kwargs):
         """PixArtMS.py:71-79 (reference data flow)."""
@@ -214,68 +203,37 @@ class PixArtMSBlock(nn.Module):
         x = x + gate_mlp * self.mlp(t2i_modulate(self.norm2(x), shift_mlp, scale_mlp))
         return x
 
+    def _kv_of_prompt(self, y2):
+        """kv_linear of the prompt tokens y2 [sum_L, C] on the integer route -> [sum_L, 2C] fp16 (computed per forward)."""
+        kvl = self.cross_attn.kv_linear
+        r, alpha = kvl._range_and_alpha()
+        s = kvl.smooth_vector(r, alpha)
+        return prompt_kv_exact_fill(kvl, y2.view(1, -1, self.hidden_size), r, s, kvl.packed_weight(r, s))
+
     def forward_fused(self, x2, y2, t0, kv_off, B, HW=None):
-        """In-place update of x2 [B*N, C] fp16 (hot path; same kernel sequence as the STDiT block minus
-        the temporal branch)."""
+        """In-place update of x2 [B*N, C] fp16 (hot path): the stages of t2v/stdit.py minus the temporal branch, every packed
+        weight for its own layer's time range (``r`` = None)."""
         C = self.hidden_size
-        M = x2.shape[0]
-        N = M // B
-        a1, ca, fc1, fc2 = self.attn, self.cross_attn, self.mlp.fc1, self.mlp.fc2
-
-        def sv(layer):
-            r, alpha = layer._range_and_alpha()
-            return r, layer.smooth_vector(r, alpha)
-
+        N = x2.shape[0] // B
+        a1, qkv_l = self.attn, self.attn.qkv
+        # ---- AdaLN table
         mod = ops.adaln_table(self.scale_shift_table.detach(), t0.reshape(B, -1))
         shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp = [mod[j] for j in range(6)]
         x3 = x2.view(B, N, C)
-        st = a1.qkv.status
-        r, s = sv(a1.qkv)
-        qa = STDiTBlock._ln_quant(x3, shift_msa, scale_msa, (a1.qkv,), [s], st)[0]   # dynamic or calibrated static grid
-        qkv = ops.gemm_i8(qa, a1.qkv.packed_weight(r, s), bias=a1.qkv.bias_f32())
-        from ..t2v.stdit import fwd_attn_quantized_static, prompt_kv_exact_fill
-        r, s = sv(a1.proj)
-        att_o, qa = None, None
-        if a1.plain:                                       # attention + proj's static tensor-wise quantizer, when switched on
-            qa = fwd_attn_quantized_static(a1.proj, s, lambda d, z, nb, sm: a1.core.spatial_quantized_static(
-                qkv, B, N, d, z, nb, s=sm))
-        if qa is None:
-            att_o = a1.attend(qkv, B, N, HW)               # (plain: the HIP kernel straight on the q | k | v buffer)
-            qa = a1.proj.quantize_input(att_o.view(B, N, C), s)
-        ops.gemm_i8(qa, a1.proj.packed_weight(r, s), bias=a1.proj.bias_f32(), out=x2, epilogue=ops.EPI_GATE_RESID,
-                    resid=x2, gate=gate_msa, rows_per_gate=N)
-        r, s = sv(ca.q_linear)
-        q = ops.gemm_i8(ca.q_linear.quantize_input(x3, s), ca.q_linear.packed_weight(r, s), bias=ca.q_linear.bias_f32())
-        r, s = sv(ca.kv_linear)
-        kv = prompt_kv_exact_fill(ca.kv_linear, y2.view(1, -1, C), r, s, ca.kv_linear.packed_weight(r, s))
-        r, s = sv(ca.proj)
-        qa = fwd_attn_quantized_static(ca.proj, s, lambda d, z, nb, sm: ca.core.cross_quantized_static(
-            q, kv, kv_off, B, N, d, z, nb, s=sm))
-        if qa is None:
-            att_o = ca.core.cross(q, kv, kv_off, B, N, out=att_o)
-            qa = ca.proj.quantize_input(att_o.view(B, N, C), s)
-        ops.gemm_i8(qa, ca.proj.packed_weight(r, s), bias=ca.proj.bias_f32(), out=x2, epilogue=ops.EPI_RESID, resid=x2)
-        r, s = sv(fc1)
-        qa = STDiTBlock._ln_quant(x3, shift_mlp, scale_mlp, (fc1,), [s], st)[0]
-        from ..t2v.stdit import _GELU_QUANT
-        if getattr(fc2, "smooth_quant_running_stat", False):
-            # a running statistic needs the activation itself before s exists: GELU in fc1's epilogue, then fc2's device step
-            h = ops.gemm_i8(qa, fc1.packed_weight(r, s), bias=fc1.bias_f32(), epilogue=ops.EPI_GELU)
-            qa, pw2 = fc2.running_stat_step(h.view(B, N, -1))
-        else:
-            r2, s2 = sv(fc2)
-            from ..t2v.stdit import mlp_quantized_static
-            pw1 = fc1.packed_weight(r, s)
-            qa2 = mlp_quantized_static(fc1, fc2, qa, pw1, s2)      # fc2's static quantizer in fc1's epilogue, when switched on
-            if qa2 is None:
-                # GELU inside fc2's quantizer pass (see t2v/stdit.py), also for the uncond | cond pair of the t2i loop
-                one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, s2)
-                h = ops.gemm_i8(qa, pw1, bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
-                qa2 = fc2.quantize_gelu_input(h.view(B, N, -1), s2) if one_pass else fc2.quantize_input(h.view(B, N, -1), s2)
-            r, s, qa = r2, s2, qa2
-            pw2 = fc2.packed_weight(r, s)
-        ops.gemm_i8(qa, pw2, bias=fc2.bias_f32(), out=x2,
-                    epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate_mlp, rows_per_gate=N)
+        st = qkv_l.status
+        # ---- self-attention: one fused qkv Linear; attention + proj's static tensor-wise quantizer when switched on and plain
+        r, alpha = qkv_l._range_and_alpha()
+        s = qkv_l.smooth_vector(r, alpha)
+        qa = ln_quant(x3, shift_msa, scale_msa, (qkv_l,), [s], st)[0]      # dynamic or calibrated static grid
+        qkv = ops.gemm_i8(qa, qkv_l.packed_weight(r, s), bias=qkv_l.bias_f32())
+        att_o = attn_proj_stage(
+            a1.proj, None, x2, B, N,
+            lambda sv: fwd_attn_quantized_static(a1.proj, sv, lambda d, z, nb, sm: a1.core.spatial_quantized_static(
+                qkv, B, N, d, z, nb, s=sm)) if a1.plain else None,
+            lambda o: a1.attend(qkv, B, N, HW), None, gate_msa)   # (plain: the HIP kernel straight on the q | k | v buffer)
+        # ---- cross attention, MLP
+        cross_stage(self.cross_attn, None, x2, x3, B, N, kv_off, lambda: self._kv_of_prompt(y2), att_o)
+        mlp_stage(self.mlp, None, x2, x3, B, N, shift_mlp, scale_mlp, gate_mlp, st)
         return x2
 
 

@@ -10,14 +10,17 @@ t2v/opensora/models/layers/blocks.py so that reference state-dicts, quant-param 
 Two routes through a block:
 * ``forward_fused`` (hot path; taken when every Linear of the block is on the integer route):
   fused LN+modulate+quant -> int8 GEMMs with fused epilogues -> HIP attention, rows kept in one
-  canonical [B][T][S] order, residual stream updated in place.  ~20 kernels per block, no torch op.
+  canonical [B][T][S] order, residual stream updated in place.  ~20 kernels per block, no torch op.  It is a sequence of
+  stage functions (AdaLN table, spatial, temporal, cross attention, MLP) defined at module level here and shared with the
+  PixArt blocks (t2i/pixart.py), together with the route rules (``fused_rules``) and the route switches.
 * ``forward_layerwise``: the reference's data flow (stdit.py:96-133) module by module - used for
   FP inference and PTQ / calibration states; Linears are QuantLayers (or nn.Linear), attention is
   the HIP kernel, the elementwise glue is torch.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+import os
+from typing import List
 
 import numpy as np
 import torch
@@ -332,84 +335,62 @@ class MultiHeadCrossAttention(nn.Module):
 
 
 # --------------------------------------------------------------------------- block
-# GELU inside fc2's quantizer pass (vq_gelu_rowquant: an HBM-bound kernel whose VALU is idle) instead of the fc1 GEMM
-# epilogue (22.0 M VALU instructions for 5.3 M MFMAs there, matrix pipe 31 % busy: profiles/r02_gemm_pmc.md).  It is what
-# the reference's fp16 mode computes - act() on the fp16-rounded fc1 output (quant_layer.py:211, blocks.py:27) - and
-# neutral for the step (24.81 vs 24.76 steps/s A/B on one box, round 3; round 1 measured -1 %), while the fc1 launch
-# gets ~20 % shorter.  On by default since round 3; VQ_GELU_QUANT=0 restores the GELU epilogue.
-_ATTN_QUANT = __import__("os").environ.get("VQ_ATTN_QUANT", "1") != "0"   # attention kernels that also run the next quantizer
-_GELU_QUANT = __import__('os').environ.get('VQ_GELU_QUANT', '1') != '0'
-# static (calibrated) tensor-wise grids: the quantizers of Linears that share an input, and what precedes them
-# (LayerNorm + modulate, the temporal position embedding), in ONE pass (ops.rowquant_static) instead of one generic
-# pass per Linear behind a LayerNorm launch.  Bit-identical; False restores that route (tests compare the two).
-_STATIC_FUSED = True
-
-# temporal attention + attn_temp.proj's DYNAMIC per-token quantizer in one kernel for what the B == 1, 8-bit route above does
-# not take: a joint cond | uncond forward (B = 2, cfg_split: False) and code widths of 2..7 bits, T <= 16
-# (ops.attn_temporal_rowquant_shared).  Off by default for the reason VQ_STATIC_ATTN_QUANT is: the fused kernels round a few
-# fp16 attention outputs an ulp away from attn_temporal_kernel's, so a joint or sub-8-bit plan's
-# output moves inside its parity bound; VQ_ATTN_QUANT_JOINT=1 turns it on (DESIGN section 8 has the criterion for the default).
-_ATTN_QUANT_JOINT = __import__("os").environ.get("VQ_ATTN_QUANT_JOINT", "0") != "0"
-# the smoothed q | k | v quantizers of a joint forward (B = 2, cfg_split: False; dynamic per-token grids shared by the two
-# samples of a token, a smoothing vector per Linear: w8a8 / w4a8 / w6a6_smooth_quant) from ONE pass over the rows
-# (ops.rowquant_multi_shared) - behind LayerNorm + modulate instead of the generic B > 1 kernel, and in the temporal branch
-# instead of three launches.  Off by default: the LayerNorm arm sums a row in the half-wave order, the generic kernel in
-# the wave order, so a few codes of such a plan move by one step inside its parity bound; the plain arm
-# is bit-identical and rides on the same switch.  VQ_SMOOTH_JOINT=1 turns it on (DESIGN section 8 has the criterion).
-_SMOOTH_JOINT = __import__("os").environ.get("VQ_SMOOTH_JOINT", "0") != "0"
+# The fused route of a block is five stages - AdaLN table, spatial attention, temporal attention (STDiT only), cross
+# attention, MLP - written once, below, as module-level functions; STDiTBlock.forward_fused and PixArtMSBlock.forward_fused
+# (t2i/pixart.py) are straight sequences of calls to them.
+#
+# ---- route switches.  Read from the environment once, at import; tests and tools patch the module globals HERE, and the
+# stages read them at launch time.  What each reroutes, why it is on or off and what decides a flip: the switch table of
+# DESIGN section 9.
+def _switch(name: str, default: bool) -> bool:
+    return os.environ.get(name, "1" if default else "0") != "0"
 
 
-def _smooth_joint(layers, svs, B, add_rows=False) -> bool:
-    """Whether ONE ops.rowquant_multi_shared launch serves the quantizers of ``layers`` (which share an input) behind their
-    smoothing vectors ``svs``: the switch, a joint forward, no added rows, dynamic quantizers of one bit width and a vector
-    on every Linear.  (The shape and the reciprocals are the launch's own: it answers None and the caller falls through.)"""
-    if not _SMOOTH_JOINT or B != 2 or add_rows or any(s is None for s in svs):
-        return False
+_ATTN_QUANT = _switch("VQ_ATTN_QUANT", True)                          # temporal attention + proj's quantizer, B = 1, 8 bits
+_GELU_QUANT = _switch("VQ_GELU_QUANT", True)                          # GELU inside fc2's quantizer pass
+_STATIC_FUSED = True                                                  # one-pass quantizers of static grids (no variable)
+_ATTN_QUANT_JOINT = _switch("VQ_ATTN_QUANT_JOINT", False)             # the same for B = 2 and 2..7 bits
+_SMOOTH_JOINT = _switch("VQ_SMOOTH_JOINT", False)                     # a joint forward's smoothed q | k | v codes in one pass
+_STATIC_ATTN_QUANT = _switch("VQ_STATIC_ATTN_QUANT", False)           # temporal attention + proj's static quantizer
+_STATIC_FWD_ATTN_QUANT = _switch("VQ_STATIC_FWD_ATTN_QUANT", False)   # spatial / cross attention + proj's static quantizer
+_STATIC_GEMM_QUANT = _switch("VQ_STATIC_GEMM_QUANT", False)           # fc1's GEMM + fc2's static quantizer
+_RUNNING_SMOOTH_DEVICE = _switch("VQ_RUNNING_SMOOTH_DEVICE", False)   # a running statistic on mlp.fc2, on the device
+EXACT_KV_EPS_FILL = _switch("VQ_EXACT_KV_EPS_FILL", True)             # the reference's global eps fill of the prompt's K / V
+
+
+# ---- what a quantizer is, asked in one place each
+def _tensorwise_static(aq) -> bool:
+    """A calibrated grid with one (delta, zero_point) for the whole tensor: not dynamic, not per token."""
+    return not isinstance(aq, DynamicActQuantizer) and aq.delta.numel() == 1 and aq.zero_point.numel() == 1
+
+
+def _same_dynamic(layers) -> bool:
+    """Every layer's quantizer dynamic per token, all of one bit width."""
     aqs = [l.act_quantizer for l in layers]
     return all(isinstance(a, DynamicActQuantizer) for a in aqs) and len({a.n_bits for a in aqs}) == 1
 
 
-# temporal attention + attn_temp.proj's static tensor-wise quantizer in one kernel (ops.attn_temporal_rowquant_static)
-# instead of attention + one quantizer pass.  Off by default: the fused kernel's fp16 output differs from
-# attn_temporal_kernel's by one ulp in a few elements (DESIGN section 1 row A8), so a static plan's output moves inside its
-# parity bound, and two tests pin today's launches and outputs of a static block; VQ_STATIC_ATTN_QUANT=1 turns it on.
-_STATIC_ATTN_QUANT = __import__("os").environ.get("VQ_STATIC_ATTN_QUANT", "0") != "0"
+# ---- which launches serve a plan
+def _smooth_joint(layers, svs, B, add_rows=False) -> bool:
+    """Whether ONE ops.rowquant_multi_shared launch serves the quantizers of ``layers`` (which share an input) behind their
+    smoothing vectors ``svs``: the switch, a joint forward, no added rows, dynamic quantizers of one bit width and a vector
+    on every Linear.  (The shape and the reciprocals are the launch's own: it answers None and the caller falls through.)"""
+    return _SMOOTH_JOINT and B == 2 and not add_rows and all(s is not None for s in svs) and _same_dynamic(layers)
 
 
 def _static_attn_quant(proj, T, H, D) -> bool:
     """Whether the temporal attention in front of ``proj`` also runs proj's quantizer: the switch, a calibrated
     tensor-wise grid, the one-pass static route, and nothing the entry point would refuse."""
     aq = proj.act_quantizer
-    if not (_STATIC_ATTN_QUANT and _STATIC_FUSED) or isinstance(aq, DynamicActQuantizer):
-        return False
-    if aq.delta.numel() != 1 or aq.zero_point.numel() != 1:
-        return False
-    return ops.attn_temporal_static_ok(T, H, D, ops.pad128(H * D), aq.n_bits)
-
-
-# spatial / cross attention + proj's static tensor-wise quantizer in one kernel (ops.attn_fwd_rowquant_static) instead of
-# attention + one quantizer pass.  The fused kernel's fp16 output IS attn_fwd's, so a static plan's output does not move;
-# off by default until the timing table (DESIGN section 4.1) decides: two tests pin today's launches of a static block.
-# VQ_STATIC_FWD_ATTN_QUANT=1 turns it on; independent of VQ_STATIC_ATTN_QUANT.
-_STATIC_FWD_ATTN_QUANT = __import__("os").environ.get("VQ_STATIC_FWD_ATTN_QUANT", "0") != "0"
+    return _STATIC_ATTN_QUANT and _STATIC_FUSED and _tensorwise_static(aq) and ops.attn_temporal_static_ok(
+        T, H, D, ops.pad128(H * D), aq.n_bits)
 
 
 def _static_fwd_attn_quant(proj) -> bool:
     """Whether the spatial / cross attention in front of ``proj`` may also run proj's quantizer: the switch, a calibrated
     tensor-wise grid and the one-pass static route.  (Whether the entry point takes the launch is asked by
     QuantAttention.spatial_quantized_static / cross_quantized_static, which return None when it does not.)"""
-    aq = proj.act_quantizer
-    if not (_STATIC_FWD_ATTN_QUANT and _STATIC_FUSED) or isinstance(aq, DynamicActQuantizer):
-        return False
-    return aq.delta.numel() == 1 and aq.zero_point.numel() == 1
-
-
-# mlp.fc1's GEMM with GELU and fc2's static tensor-wise quantizer in its epilogue (ops.gemm_i8_rowquant_static) instead of
-# the GELU epilogue + one quantizer pass over the [M, 4608] fp16 activation, which is then never written.  The codes are
-# those of the two launches bit for bit, so a static plan's output does not move; off by default until the timing table
-# (DESIGN section 4.1) decides: tests pin today's launches of a static block.  VQ_STATIC_GEMM_QUANT=1 turns it on;
-# independent of the two attention switches.
-_STATIC_GEMM_QUANT = __import__("os").environ.get("VQ_STATIC_GEMM_QUANT", "0") != "0"
+    return _STATIC_FWD_ATTN_QUANT and _STATIC_FUSED and _tensorwise_static(proj.act_quantizer)
 
 
 def _static_gemm_quant(pw1, fc2, M: int) -> bool:
@@ -417,11 +398,20 @@ def _static_gemm_quant(pw1, fc2, M: int) -> bool:
     static route, a calibrated tensor-wise grid on fc2, no running statistic there, and nothing the entry point would
     refuse."""
     aq = fc2.act_quantizer
-    if not (_STATIC_GEMM_QUANT and _STATIC_FUSED) or isinstance(aq, DynamicActQuantizer):
-        return False
-    if aq.delta.numel() != 1 or aq.zero_point.numel() != 1 or getattr(fc2, "smooth_quant_running_stat", False):
-        return False
-    return ops.gemm_rowquant_static_ok(M, pw1.N, pw1.K, pw1.n_bits, aq.n_bits)
+    return _STATIC_GEMM_QUANT and _STATIC_FUSED and _tensorwise_static(aq) and not getattr(
+        fc2, "smooth_quant_running_stat", False) and ops.gemm_rowquant_static_ok(M, pw1.N, pw1.K, pw1.n_bits, aq.n_bits)
+
+
+def _static_one_pass(layers, C, add_rows=False, ln=False) -> bool:
+    """Whether ONE ops.rowquant_static launch serves the calibrated quantizers of ``layers`` (which share an input):
+    the route switch, tensor-wise grids of one bit width, and nothing the entry point would refuse."""
+    aqs = [l.act_quantizer for l in layers]
+    return _STATIC_FUSED and all(_tensorwise_static(a) for a in aqs) and len({a.n_bits for a in aqs}) == 1 and \
+        ops.rowquant_static_ok(C, ops.pad128(C), aqs[0].n_bits, len(aqs), add_rows=add_rows, ln=ln)
+
+
+def _static_grids(layers):
+    return [l.act_quantizer.delta.float() for l in layers], [l.act_quantizer.zero_point.float() for l in layers]
 
 
 def mlp_quantized_static(fc1, fc2, qa, pw1, s2):
@@ -433,33 +423,6 @@ def mlp_quantized_static(fc1, fc2, qa, pw1, s2):
     return ops.gemm_i8_rowquant_static(qa, pw1, fc1.bias_f32(), aq.delta.float(), aq.zero_point.float(), aq.n_bits, s=s2)
 
 
-# a running smooth-quant statistic on mlp.fc2 (the released t2i script leaves it on for blocks.27.mlp.fc2 at inference,
-# quant_txt2img.py:297-300) served on the fused route by QuantLayer.running_stat_step: statistic, s, W*s and the quantizer
-# on the device, no host read.  Off by default: a test pins today's layer-by-layer route of such a block, and the timing
-# table decides the flip.  VQ_RUNNING_SMOOTH_DEVICE=1 turns it on.
-_RUNNING_SMOOTH_DEVICE = __import__("os").environ.get("VQ_RUNNING_SMOOTH_DEVICE", "0") != "0"
-
-
-def fused_running_rules(block) -> bool:
-    """``fused_ok()``'s per-layer rules for ``block`` (STDiTBlock or a PixArt block), with a running statistic tolerated on
-    ``mlp.fc2`` only and only where QuantLayer.running_stat_device_ok() holds.  A twin of the loops in both ``fused_ok()``
-    bodies, which stay as they are (tests pin them): a rule added there belongs here too."""
-    for m in block.hot_layers():
-        if not (isinstance(m, QuantLayer) and m.int_route_ok()):
-            return False
-        aq = m.act_quantizer
-        if not isinstance(aq, DynamicActQuantizer) and aq.per_group:
-            return False
-        if getattr(m, "smooth_quant_running_stat", False) and not (m is block.mlp.fc2 and m.running_stat_device_ok()):
-            return False
-    return True
-
-
-def takes_fused(block) -> bool:
-    """The route of ``block``: ``fused_ok()``, or - switched on - ``fused_running_ok()`` (never consulted otherwise)."""
-    return block.fused_ok() or (_RUNNING_SMOOTH_DEVICE and block.fused_running_ok())
-
-
 def fwd_attn_quantized_static(proj, sv, fused_call):
     """proj's input codes from ``fused_call(delta, zp, n_bits, s)`` - attention with proj's static quantizer fused in -
     or None when the route is off or refuses (the caller then runs attention and proj's quantizer separately)."""
@@ -469,34 +432,175 @@ def fwd_attn_quantized_static(proj, sv, fused_call):
     return fused_call(aq.delta.float(), aq.zero_point.float(), aq.n_bits, sv)
 
 
-
-def _static_one_pass(layers, C, add_rows=False, ln=False) -> bool:
-    """Whether ONE ops.rowquant_static launch serves the calibrated quantizers of ``layers`` (which share an input):
-    the route switch, tensor-wise grids of one bit width, and nothing the entry point would refuse."""
-    aqs = [l.act_quantizer for l in layers]
-    if not _STATIC_FUSED or any(isinstance(a, DynamicActQuantizer) for a in aqs):
-        return False
-    if len({a.n_bits for a in aqs}) != 1 or any(a.delta.numel() != 1 or a.zero_point.numel() != 1 for a in aqs):
-        return False
-    return ops.rowquant_static_ok(C, ops.pad128(C), aqs[0].n_bits, len(aqs), add_rows=add_rows, ln=ln)
-
-
-def _static_grids(layers):
-    return [l.act_quantizer.delta.float() for l in layers], [l.act_quantizer.zero_point.float() for l in layers]
-
-
-# The one activation of the block that no LayerNorm precedes is the prompt (cross_attn.kv_linear): a (near-)constant
-# prompt token there triggers the reference's GLOBAL eps fill (base_quantizer.py:219-223), which the integer route does
-# not express.  With this on (default) one small kernel follows the integer route (vq_epsfill_fixup): it reads the
-# quantizer's private status word, returns at once when it is clear and otherwise overwrites the K/V rows with the
-# reference's fp16-mode result on the 1e-6 grid: outputs then equal the reference's, nothing synchronises (round 3's
-# first form - both routes computed with torch ops and a device-side select - cost PixArt-Sigma 5 % of its step).
-EXACT_KV_EPS_FILL = __import__("os").environ.get("VQ_EXACT_KV_EPS_FILL", "1") != "0"
+# ---- which route a block takes
+def fused_rules(block, running=False) -> bool:
+    """The per-layer rules of the fused route, for ``block`` (STDiTBlock or a PixArt block): every hot layer a QuantLayer on
+    the integer route; no static per-group grid (static per-token grids need the reference's [B, n_prompt, C] views); no
+    running smooth-quant statistic - a live act-scale statistic is QuantLayer.forward's job (host-visible state; the released
+    t2i script leaves it on for blocks.27.mlp.fc2 at inference, quant_txt2img.py:297-300: such a block takes the reference
+    data flow, layer by layer).  ``running``: a statistic is tolerated on ``mlp.fc2``, and only there, where
+    QuantLayer.running_stat_device_ok() holds (QuantLayer.running_stat_step serves it on the device)."""
+    for m in block.hot_layers():
+        if not (isinstance(m, QuantLayer) and m.int_route_ok()):
+            return False
+        aq = m.act_quantizer
+        if not isinstance(aq, DynamicActQuantizer) and aq.per_group:
+            return False
+        if getattr(m, "smooth_quant_running_stat", False) and not (
+                running and m is block.mlp.fc2 and m.running_stat_device_ok()):
+            return False
+    return True
 
 
+def fused_running_rules(block) -> bool:
+    return fused_rules(block, running=True)
+
+
+def takes_fused(block) -> bool:
+    """The route of ``block``: ``fused_ok()``, or - switched on - ``fused_running_ok()`` (never consulted otherwise)."""
+    return block.fused_ok() or (_RUNNING_SMOOTH_DEVICE and block.fused_running_ok())
+
+
+# ---- the stages
+def _svec(layer):
+    """The layer's smoothing vector for the step's time range (None without smooth quant)."""
+    r, alpha = layer._range_and_alpha()
+    return layer.smooth_vector(r, alpha)
+
+
+def _range_of(layer, r):
+    """The time range a layer's weight is packed for: ``r`` when the block names one for all its Linears (STDiT: attn.q's),
+    the layer's own for None (PixArt) - the two models differ here, DESIGN section 9 open questions."""
+    return layer._range_and_alpha()[0] if r is None else r
+
+
+def ln_quant(x3, shift, scale, layers, svs, status):
+    """LayerNorm + modulate + the activation quantizer(s) of ``layers`` (which share the input).  Dynamic
+    per-token quantizers: ONE fused kernel, one output per distinct smoothing vector.  Static calibrated grids
+    (``dynamic: False``, the *_naive / *_ptqd plans): the fused kernel computes min-max grids only, so it emits the
+    modulated fp16 activation and every layer quantizes it on ITS calibrated (delta, zero_point)
+    (base_quantizer.py:129-144) - never a silently substituted dynamic grid."""
+    l0 = layers[0]
+    if len(layers) > 1 and _smooth_joint(layers, svs, x3.shape[0]):    # (one output, fc1: the pair kernel below)
+        qas = ops.rowquant_multi_shared(x3, svs, n_bits=l0.act_quantizer.n_bits, status=status, shift=shift, scale=scale,
+                                        eps=1e-6)
+        if qas is not None:
+            return qas
+    if all(isinstance(l.act_quantizer, DynamicActQuantizer) for l in layers):
+        smooth = [None] if all(s is None for s in svs) else list(svs)
+        return ops.ln_modulate_rowquant(x3, shift, scale, 1e-6, smooth=smooth, n_bits=l0.act_quantizer.n_bits,
+                                        status=status)
+    if _static_one_pass(layers, x3.shape[-1], ln=True):
+        delta, zp = _static_grids(layers)
+        return ops.rowquant_static(x3, delta, zp, n_bits=l0.act_quantizer.n_bits, smooth=svs, shift=shift, scale=scale,
+                                   eps=1e-6)
+    _, xm = ops.ln_modulate_rowquant(x3, shift, scale, 1e-6, smooth=[None], n_bits=8, want_xm=True)
+    # one pass per layer: each has its own calibrated grid tensor (comparing them would be a host sync)
+    return [l.quantize_input(xm, s) for l, s in zip(layers, svs)]
+
+
+def temporal_qkv_codes(att, x3, svs, tpe2, B, S):
+    """The input codes of attn_temp.q | k | v from the un-modulated x3 [B, N, C] (+ the position rows ``tpe2`` [T, C] in block
+    0), behind their smoothing vectors ``svs``: one QAct when the three share it, else three."""
+    layers = (att.q, att.k, att.v)
+    aq, st = att.q.act_quantizer, att.q.status
+    if _smooth_joint(layers, svs, B, add_rows=tpe2 is not None):
+        # a joint forward's three smoothed copies from one pass (None: refused, today's launches below)
+        qas = ops.rowquant_multi_shared(x3, svs, n_bits=aq.n_bits, status=st)
+        if qas is not None:
+            return qas
+    if all(s is None for s in svs) and isinstance(aq, DynamicActQuantizer):
+        return [att.q.quantize_input(x3, None, add_rows=tpe2, add_div=S)]
+    if tpe2 is None and B == 1 and all(s is not None for s in svs) and _same_dynamic(layers):
+        return ops.rowquant_multi(x3, svs, n_bits=aq.n_bits, status=st)                           # one launch
+    if _static_one_pass(layers, x3.shape[-1], add_rows=tpe2 is not None):
+        delta, zp = _static_grids(layers)
+        return ops.rowquant_static(x3, delta, zp, n_bits=aq.n_bits, smooth=svs, add_rows=tpe2, add_div=S)
+    return [l.quantize_input(x3, s, add_rows=tpe2, add_div=S) for l, s in zip(layers, svs)]
+
+
+def temporal_proj_codes(att, qkv, B, T, S, sv):
+    """attn_temp.proj's input codes (behind its smoothing vector ``sv``, if any) from a temporal attention kernel that also
+    runs proj's quantizer; None when the plan has no such kernel or the kernel refuses (attn_proj_stage then runs the plain
+    attention and proj's own quantizer)."""
+    proj, aq = att.proj, att.proj.act_quantizer
+    dynamic = isinstance(aq, DynamicActQuantizer)
+    if _ATTN_QUANT and dynamic and aq.n_bits == 8 and (B == 1 or not _ATTN_QUANT_JOINT):
+        return att.core.temporal_quantized(qkv, B, T, S, status=proj.status, s=sv)
+    if _ATTN_QUANT and _ATTN_QUANT_JOINT and dynamic:
+        # the same for a joint forward (B = 2) and for code widths below 8 bits: one grid per token over the samples
+        return att.core.temporal_quantized_shared(qkv, B, T, S, aq.n_bits, status=proj.status, s=sv)
+    if _static_attn_quant(proj, T, att.core.num_heads, att.core.head_dim):
+        return att.core.temporal_quantized_static(qkv, B, T, S, aq.delta.float(), aq.zero_point.float(), aq.n_bits, s=sv)
+    return None
+
+
+def proj_into_resid(layer, r, qa, x2, gate=None, rows_per_gate=None, pw=None):
+    """x2 += [gate *] layer(qa): the GEMM of a branch's last Linear with the residual add (and the AdaLN gate, one row of
+    ``gate`` per ``rows_per_gate`` rows) in its epilogue.  ``pw``: the packed weight, when the caller already holds it."""
+    if pw is None:
+        pw = layer.packed_weight(_range_of(layer, r), _svec(layer))
+    if gate is None:
+        return ops.gemm_i8(qa, pw, bias=layer.bias_f32(), out=x2, epilogue=ops.EPI_RESID, resid=x2)
+    return ops.gemm_i8(qa, pw, bias=layer.bias_f32(), out=x2, epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate,
+                       rows_per_gate=rows_per_gate)
+
+
+def attn_proj_stage(proj, r, x2, B, N, fused, plain, att_o, gate=None):
+    """The tail of an attention branch.  proj's input codes come from ``fused(sv)`` - an attention launch with proj's
+    quantizer fused in, None when there is none or it refuses - or else from the plain attention ``plain(att_o)`` (into the
+    block's one [B*N, C] attention buffer, allocated by the first branch that needs it) and proj's own quantizer; then proj's
+    GEMM goes into the residual stream.  Returns the attention buffer for the next branch."""
+    sv = _svec(proj)
+    qa = fused(sv)
+    if qa is None:
+        att_o = plain(att_o)
+        qa = proj.quantize_input(att_o.view(B, N, -1), sv)
+    proj_into_resid(proj, r, qa, x2, gate, N)
+    return att_o
+
+
+def cross_stage(ca, r, x2, x3, B, N, y_lens, prompt_kv, att_o):
+    """x += proj(attn(q_linear(x), K | V of the prompt))  (stdit.py:121, PixArtMS.py:77).  q_linear's quantizer and GEMM are
+    launched first; ``prompt_kv()`` then hands over the caller's [sum_L, 2C] K | V (STDiT: batched over the blocks, cached, or
+    computed here; PixArt: computed here)."""
+    ql, sv = ca.q_linear, _svec(ca.q_linear)
+    q = ops.gemm_i8(ql.quantize_input(x3, sv), ql.packed_weight(_range_of(ql, r), sv), bias=ql.bias_f32())
+    kv = prompt_kv()
+    return attn_proj_stage(
+        ca.proj, r, x2, B, N,
+        lambda s: fwd_attn_quantized_static(ca.proj, s, lambda d, z, nb, sm: ca.core.cross_quantized_static(
+            q, kv, y_lens, B, N, d, z, nb, s=sm)),
+        lambda o: ca.core.cross(q, kv, y_lens, B, N, out=o), att_o)
+
+
+def mlp_stage(mlp, r, x2, x3, B, N, shift, scale, gate, status):
+    """x += gate * fc2(gelu(fc1(LN-mod(x))))  (stdit.py:124-128, PixArtMS.py:78).  Between fc1's codes and fc2's GEMM, one of:
+    a running statistic on fc2 (it needs the activation itself before s exists: GELU in fc1's epilogue, then fc2's device
+    step); fc2's static codes from fc1's epilogue, when switched on; GELU inside fc2's quantizer pass (also for the uncond |
+    cond pair of the t2i loop) or, where that pass does not apply, in fc1's epilogue."""
+    fc1, fc2 = mlp.fc1, mlp.fc2
+    s1 = _svec(fc1)
+    qa = ln_quant(x3, shift, scale, (fc1,), [s1], status)[0]
+    pw1 = fc1.packed_weight(_range_of(fc1, r), s1)
+    if getattr(fc2, "smooth_quant_running_stat", False):
+        h = ops.gemm_i8(qa, pw1, bias=fc1.bias_f32(), epilogue=ops.EPI_GELU)
+        qa, pw2 = fc2.running_stat_step(h.view(B, N, -1))
+        return proj_into_resid(fc2, r, qa, x2, gate, N, pw=pw2)
+    s2 = _svec(fc2)
+    qa2 = mlp_quantized_static(fc1, fc2, qa, pw1, s2)
+    if qa2 is None:
+        one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, s2)
+        h = ops.gemm_i8(qa, pw1, bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
+        h3 = h.view(B, N, -1)
+        qa2 = fc2.quantize_gelu_input(h3, s2) if one_pass else fc2.quantize_input(h3, s2)
+    return proj_into_resid(fc2, r, qa2, x2, gate, N)
+
+
+# ---- the prompt's K / V
 def prompt_kv_exact_fill(layer, y3, r, sv, pw):
     """kv_linear on prompt tokens y3 [1, L, C]: integer route, replaced on the device by the exact eps-fill result when
-    the quantizer flagged a token with step < 1e-6."""
+    the quantizer flagged a token with step < 1e-6 (EXACT_KV_EPS_FILL: DESIGN section 9)."""
     aq = layer.act_quantizer
     if not (EXACT_KV_EPS_FILL and isinstance(aq, DynamicActQuantizer)):
         return ops.gemm_i8(layer.quantize_input(y3, sv), pw, bias=layer.bias_f32())
@@ -532,60 +636,22 @@ class STDiTBlock(nn.Module):
                 self.cross_attn.q_linear, self.cross_attn.kv_linear, self.cross_attn.proj,
                 self.mlp.fc1, self.mlp.fc2]
 
-    def fused_ok(self) -> bool:
-        # (twin: fused_running_ok / t2v/stdit.py fused_running_rules restate these rules for the opt-in route of a running
-        # statistic on mlp.fc2 - a rule added here belongs there too)
-        for m in self.hot_layers():
-            if not (isinstance(m, QuantLayer) and m.int_route_ok()):
-                return False
-            aq = m.act_quantizer
-            if not isinstance(aq, DynamicActQuantizer) and aq.per_group:
-                return False  # static per-token grids need the reference's [B, n_prompt, C] views
-            if getattr(m, "smooth_quant_running_stat", False):
-                return False  # a live act-scale statistic is QuantLayer.forward's job (host-visible state)
+    def _qkv_share_quantizer(self) -> bool:
+        """q, k and v are quantized from ONE pass over their common input: that needs one activation bit-width and one kind
+        of quantizer per attention (a mixed-precision YAML may set them apart: then the layerwise route runs)."""
         for att in (self.attn, self.attn_temp):
-            # q, k and v are quantized from ONE pass over their common input: that needs one activation bit-width
-            # and one kind of quantizer (a mixed-precision YAML may set them apart: then the layerwise route runs)
             aqs = [l.act_quantizer for l in (att.q, att.k, att.v)]
             if len({(a.n_bits, isinstance(a, DynamicActQuantizer)) for a in aqs}) != 1:
                 return False
         return True
+
+    def fused_ok(self) -> bool:
+        return fused_rules(self) and self._qkv_share_quantizer()
 
     def fused_running_ok(self) -> bool:
-        """:meth:`fused_ok` with a running smooth-quant statistic tolerated on ``mlp.fc2`` (served on the device by
-        QuantLayer.running_stat_step); consulted only under VQ_RUNNING_SMOOTH_DEVICE."""
-        if not fused_running_rules(self):
-            return False
-        for att in (self.attn, self.attn_temp):
-            aqs = [l.act_quantizer for l in (att.q, att.k, att.v)]
-            if len({(a.n_bits, isinstance(a, DynamicActQuantizer)) for a in aqs}) != 1:
-                return False
-        return True
-
-    @staticmethod
-    def _ln_quant(x3, shift, scale, layers, svs, status):
-        """LayerNorm + modulate + the activation quantizer(s) of ``layers`` (which share the input).  Dynamic
-        per-token quantizers: ONE fused kernel, one output per distinct smoothing vector.  Static calibrated grids
-        (``dynamic: False``, the *_naive / *_ptqd plans): the fused kernel computes min-max grids only, so it emits the
-        modulated fp16 activation and every layer quantizes it on ITS calibrated (delta, zero_point)
-        (base_quantizer.py:129-144) - never a silently substituted dynamic grid."""
-        l0 = layers[0]
-        if len(layers) > 1 and _smooth_joint(layers, svs, x3.shape[0]):    # (one output, fc1: the pair kernel below)
-            qas = ops.rowquant_multi_shared(x3, svs, n_bits=l0.act_quantizer.n_bits, status=status, shift=shift, scale=scale,
-                                            eps=1e-6)
-            if qas is not None:
-                return qas
-        if all(isinstance(l.act_quantizer, DynamicActQuantizer) for l in layers):
-            smooth = [None] if all(s is None for s in svs) else list(svs)
-            return ops.ln_modulate_rowquant(x3, shift, scale, 1e-6, smooth=smooth, n_bits=l0.act_quantizer.n_bits,
-                                            status=status)
-        if _static_one_pass(layers, x3.shape[-1], ln=True):
-            delta, zp = _static_grids(layers)
-            return ops.rowquant_static(x3, delta, zp, n_bits=l0.act_quantizer.n_bits, smooth=svs, shift=shift, scale=scale,
-                                       eps=1e-6)
-        _, xm = ops.ln_modulate_rowquant(x3, shift, scale, 1e-6, smooth=[None], n_bits=8, want_xm=True)
-        # one pass per layer: each has its own calibrated grid tensor (comparing them would be a host sync)
-        return [l.quantize_input(xm, s) for l, s in zip(layers, svs)]
+        """:meth:`fused_ok` with a running smooth-quant statistic tolerated on ``mlp.fc2``; consulted only under
+        VQ_RUNNING_SMOOTH_DEVICE (:func:`takes_fused`)."""
+        return fused_rules(self, running=True) and self._qkv_share_quantizer()
 
     def forward(self, x, y, t, mask=None, tpe=None):
         if x.is_cuda and x.dtype == torch.float16 and takes_fused(self):
@@ -656,124 +722,53 @@ class STDiTBlock(nn.Module):
                 self._kv_cache.put(kkey, kv)
         return kv
 
+    def _qkv_gemm(self, att, r, svs, qas, M):
+        """q | k | v of ``att`` into one new [M, 3C] fp16 buffer, from one QAct (shared codes) or three (one per smoothing vector)."""
+        layers = (att.q, att.k, att.v)
+        fused, pws = self._qkv_weights(att, r, svs)
+        C = self.hidden_size
+        qkv = torch.empty((M, 3 * C), dtype=torch.float16, device=qas[0].xq.device)
+        if fused is not None and len(qas) == 1:
+            ops.gemm_i8(qas[0], fused[0], bias=fused[1], out=qkv)
+        elif len({(p.N, p.K, p.Kp, p.n_bits) for p in pws}) == 1 and len({(a.K, a.Kp) for a in qas}) == 1:
+            # three smoothing vectors -> three quantized copies of the input: one grouped launch (q | k | v blocks)
+            ops.gemm_i8_grouped([qas[j if len(qas) > 1 else 0] for j in range(3)], pws, [l.bias_f32() for l in layers], out=qkv)
+        else:
+            for j, l in enumerate(layers):
+                ops.gemm_i8(qas[j if len(qas) > 1 else 0], pws[j], bias=l.bias_f32(), out=qkv[:, j * C:(j + 1) * C])
+        return qkv
+
     def forward_fused(self, x2, y2, t0, y_lens, tpe, B, kv_ready=None, mod=None):
         """In-place update of the residual stream x2 [B*T*S, C] fp16, rows ordered (b, t, s)."""
         T, S, C = self.d_t, self.d_s, self.hidden_size
         N = T * S
-        M = B * N
-        dev = x2.device
-        a1, a2, ca = self.attn, self.attn_temp, self.cross_attn
-        r, _ = a1.q._range_and_alpha()
-
-        def svec(layer):
-            rr, alpha = layer._range_and_alpha()
-            return layer.smooth_vector(rr, alpha)
-
+        a1, a2 = self.attn, self.attn_temp
+        r, _ = a1.q._range_and_alpha()          # ONE time range - attn.q's - for every packed weight of the block
+        # ---- AdaLN table (batched over the blocks by STDiT.forward)
         if mod is None:
             mod = ops.adaln_table(self.scale_shift_table.detach(), t0.reshape(B, -1))   # [6, B, C] fp32
         shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp = [mod[j] for j in range(6)]
         x3 = x2.view(B, N, C)
         st = a1.q.status
-
-        def qkv_proj(att, qas):
-            svs = [svec(l) for l in (att.q, att.k, att.v)]
-            fused, pws = self._qkv_weights(att, r, svs)
-            qkv = torch.empty((M, 3 * C), dtype=torch.float16, device=dev)
-            if fused is not None and len(qas) == 1:
-                ops.gemm_i8(qas[0], fused[0], bias=fused[1], out=qkv)
-            elif len({(p.N, p.K, p.Kp, p.n_bits) for p in pws}) == 1 and len({(a.K, a.Kp) for a in qas}) == 1:
-                # three smoothing vectors -> three quantized copies of the input: one grouped launch (q | k | v blocks)
-                ops.gemm_i8_grouped([qas[j if len(qas) > 1 else 0] for j in range(3)], pws,
-                                    [l.bias_f32() for l in (att.q, att.k, att.v)], out=qkv)
-            else:
-                for j, l in enumerate((att.q, att.k, att.v)):
-                    ops.gemm_i8(qas[j if len(qas) > 1 else 0], pws[j], bias=l.bias_f32(),
-                                out=qkv[:, j * C:(j + 1) * C])
-            return qkv
-
         # ---- spatial branch: x += gate_msa * proj(attn(LN-mod(x)))          (stdit.py:103-109)
-        svs = [svec(l) for l in (a1.q, a1.k, a1.v)]
-        qas = self._ln_quant(x3, shift_msa, scale_msa, (a1.q, a1.k, a1.v), svs, st)
-        qkv = qkv_proj(a1, qas)
-        att_o = None
-        qa = fwd_attn_quantized_static(a1.proj, svec(a1.proj), lambda d, z, nb, s: a1.core.spatial_quantized_static(
-            qkv, B * T, S, d, z, nb, s=s))
-        if qa is None:
-            att_o = a1.core.spatial(qkv, B * T, S)
-            qa = a1.proj.quantize_input(att_o.view(B, N, C), svec(a1.proj))
-        ops.gemm_i8(qa, a1.proj.packed_weight(r, svec(a1.proj)), bias=a1.proj.bias_f32(), out=x2,
-                    epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate_msa, rows_per_gate=N)
-
+        svs = [_svec(l) for l in (a1.q, a1.k, a1.v)]
+        qkv = self._qkv_gemm(a1, r, svs, ln_quant(x3, shift_msa, scale_msa, (a1.q, a1.k, a1.v), svs, st), B * N)
+        att_o = attn_proj_stage(
+            a1.proj, r, x2, B, N,
+            lambda s: fwd_attn_quantized_static(a1.proj, s, lambda d, z, nb, sm: a1.core.spatial_quantized_static(
+                qkv, B * T, S, d, z, nb, s=sm)),
+            lambda o: a1.core.spatial(qkv, B * T, S), None, gate_msa)
         # ---- temporal branch on the un-modulated x (+tpe in block 0)          (stdit.py:112-118)
-        svs = [svec(l) for l in (a2.q, a2.k, a2.v)]
+        svs = [_svec(l) for l in (a2.q, a2.k, a2.v)]
         tpe2 = None if tpe is None else tpe.reshape(T, C).contiguous()
-        qas = None
-        if _smooth_joint((a2.q, a2.k, a2.v), svs, B, add_rows=tpe2 is not None):
-            # a joint forward's three smoothed copies from one pass (None: refused, today's launches below)
-            qas = ops.rowquant_multi_shared(x3, svs, n_bits=a2.q.act_quantizer.n_bits, status=a2.q.status)
-        if qas is not None:
-            pass
-        elif all(s is None for s in svs) and isinstance(a2.q.act_quantizer, DynamicActQuantizer):
-            qas = [a2.q.quantize_input(x3, None, add_rows=tpe2, add_div=S)]
-        elif tpe2 is None and B == 1 and all(s is not None for s in svs) and all(
-                isinstance(l.act_quantizer, DynamicActQuantizer) for l in (a2.q, a2.k, a2.v)) and len(
-                {l.act_quantizer.n_bits for l in (a2.q, a2.k, a2.v)}) == 1:
-            qas = ops.rowquant_multi(x3, svs, n_bits=a2.q.act_quantizer.n_bits, status=a2.q.status)   # one launch
-        elif _static_one_pass((a2.q, a2.k, a2.v), C, add_rows=tpe2 is not None):
-            delta, zp = _static_grids((a2.q, a2.k, a2.v))
-            qas = ops.rowquant_static(x3, delta, zp, n_bits=a2.q.act_quantizer.n_bits, smooth=svs, add_rows=tpe2, add_div=S)
-        else:
-            qas = [l.quantize_input(x3, s, add_rows=tpe2, add_div=S) for l, s in zip((a2.q, a2.k, a2.v), svs)]
-        qkv = qkv_proj(a2, qas)
-        qa = None
-        if _ATTN_QUANT and isinstance(a2.proj.act_quantizer, DynamicActQuantizer) and a2.proj.act_quantizer.n_bits == 8 \
-                and (B == 1 or not _ATTN_QUANT_JOINT):
-            # attention + proj's quantizer (behind proj's smoothing vector, if any) in one kernel
-            qa = a2.core.temporal_quantized(qkv, B, T, S, status=a2.proj.status, s=svec(a2.proj))
-        elif _ATTN_QUANT and _ATTN_QUANT_JOINT and isinstance(a2.proj.act_quantizer, DynamicActQuantizer):
-            # the same for a joint forward (B = 2) and for code widths below 8 bits: one grid per token over the samples
-            qa = a2.core.temporal_quantized_shared(qkv, B, T, S, a2.proj.act_quantizer.n_bits, status=a2.proj.status,
-                                                   s=svec(a2.proj))
-        elif _static_attn_quant(a2.proj, T, a2.core.num_heads, a2.core.head_dim):
-            aq = a2.proj.act_quantizer
-            qa = a2.core.temporal_quantized_static(qkv, B, T, S, aq.delta.float(), aq.zero_point.float(), aq.n_bits,
-                                                   s=svec(a2.proj))
-        if qa is None:
-            att_o = a2.core.temporal(qkv, B, T, S, out=att_o)
-            qa = a2.proj.quantize_input(att_o.view(B, N, C), svec(a2.proj))
-        ops.gemm_i8(qa, a2.proj.packed_weight(r, svec(a2.proj)), bias=a2.proj.bias_f32(), out=x2,
-                    epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate_msa, rows_per_gate=N)
-
+        qkv = self._qkv_gemm(a2, r, svs, temporal_qkv_codes(a2, x3, svs, tpe2, B, S), B * N)
+        att_o = attn_proj_stage(a2.proj, r, x2, B, N, lambda s: temporal_proj_codes(a2, qkv, B, T, S, s),
+                                lambda o: a2.core.temporal(qkv, B, T, S, out=o), att_o, gate_msa)
         # ---- cross attention: x += proj(attn(q(x), kv(y)))                    (stdit.py:121)
-        qa = ca.q_linear.quantize_input(x3, svec(ca.q_linear))
-        q = ops.gemm_i8(qa, ca.q_linear.packed_weight(r, svec(ca.q_linear)), bias=ca.q_linear.bias_f32())
-        kv = kv_ready if kv_ready is not None else self.prompt_kv(y2)   # batched over the blocks by STDiT.forward
-        qa = fwd_attn_quantized_static(ca.proj, svec(ca.proj), lambda d, z, nb, s: ca.core.cross_quantized_static(
-            q, kv, y_lens, B, N, d, z, nb, s=s))
-        if qa is None:
-            att_o = ca.core.cross(q, kv, y_lens, B, N, out=att_o)
-            qa = ca.proj.quantize_input(att_o.view(B, N, C), svec(ca.proj))
-        ops.gemm_i8(qa, ca.proj.packed_weight(r, svec(ca.proj)), bias=ca.proj.bias_f32(), out=x2,
-                    epilogue=ops.EPI_RESID, resid=x2)
-
+        cross_stage(self.cross_attn, r, x2, x3, B, N, y_lens,
+                    lambda: kv_ready if kv_ready is not None else self.prompt_kv(y2), att_o)
         # ---- MLP: x += gate_mlp * fc2(gelu(fc1(LN-mod(x))))                   (stdit.py:124-128)
-        fc1, fc2 = self.mlp.fc1, self.mlp.fc2
-        qa = self._ln_quant(x3, shift_mlp, scale_mlp, (fc1,), [svec(fc1)], st)[0]
-        if getattr(fc2, "smooth_quant_running_stat", False):
-            # a running statistic needs the activation itself before s exists: GELU in fc1's epilogue, then fc2's device step
-            h = ops.gemm_i8(qa, fc1.packed_weight(r, svec(fc1)), bias=fc1.bias_f32(), epilogue=ops.EPI_GELU)
-            qa, pw2 = fc2.running_stat_step(h.view(B, N, -1))
-        else:
-            pw1 = fc1.packed_weight(r, svec(fc1))
-            qa2 = mlp_quantized_static(fc1, fc2, qa, pw1, svec(fc2))     # fc2's static quantizer in fc1's epilogue, when switched on
-            if qa2 is None:
-                one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, svec(fc2))
-                h = ops.gemm_i8(qa, pw1, bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
-                qa2 = fc2.quantize_gelu_input(h.view(B, N, -1), svec(fc2)) if one_pass else fc2.quantize_input(h.view(B, N, -1), svec(fc2))
-            qa = qa2
-            pw2 = fc2.packed_weight(r, svec(fc2))
-        ops.gemm_i8(qa, pw2, bias=fc2.bias_f32(), out=x2,
-                    epilogue=ops.EPI_GATE_RESID, resid=x2, gate=gate_mlp, rows_per_gate=N)
+        mlp_stage(self.mlp, r, x2, x3, B, N, shift_mlp, scale_mlp, gate_mlp, st)
         return x2
 
 
