@@ -488,6 +488,61 @@ int vq_cfg_ddim_step(const float* cond, const float* uncond, const float* x, flo
                      int n, int C, int inner, float cfg, float one_plus_k,
                      float A, float Bc, float abar_prev, void* stream);
 
+/* Fused CFG + data-prediction DPM-Solver++ multistep update: ONE launch per model call of the PixArt sampling loop.
+ * Replaces model_wrapper's guidance (t2i/diffusion/model/dpm_solver_sigma.py:318-332: noise_uncond + scale * (noise -
+ * noise_uncond)), data_prediction_fn (:435-444: x0 = (x - sigma_t * noise) / alpha_t) and the update that follows the
+ * call: dpm_solver_first_update (:551-596), multistep_dpm_solver_second_update (:805-862, solver_type 'dpmsolver' and
+ * 'taylor') or multistep_dpm_solver_third_update (:864-915), algorithm_type 'dpmsolver++'.
+ * For call number k (0-based) = clamp(row + (step ? *step : 0), 0, n_rows - 1), per element of [n, C, inner]:
+ *   u = eps[b], c = eps[n + b]       eps: the model's output for the (uncond | cond) batch, [2n] x [C*inner], batch pitch
+ *                                    ld_eps elements (2*C*inner for the chunk(2, dim=1)[0] view of forward_with_dpmsolver:
+ *                                    the learned-sigma channels are never read); fp32 (eps_f16 = 0) or fp16 (1)
+ *   e   = u + cfg * (c - u)
+ *   m_k = (x - sigma_t * e) * inv_alpha_t            -> hist[k % 3]         hist: [3, n*C*inner] fp32
+ *   order 1: x_out = a*x - b*m_k
+ *   order 2: D1_0 = inv_r0 * (m_k - m_{k-1});  x_out = a*x - b*m_k - c1*D1_0 ('dpmsolver') / + c1*D1_0 ('taylor')
+ *   order 3: D1_0 as above, D1_1 = inv_r1 * (m_{k-1} - m_{k-2}), dd = D1_0 - D1_1, D1 = D1_0 + r0_frac * dd,
+ *            D2 = inv_r01 * dd;  x_out = a*x - b*m_k + c1*D1 - c2*D2
+ *   with m_{k-1} = hist[(k - 1) % 3], m_{k-2} = hist[(k - 2) % 3], each expression evaluated left to right.
+ * x_out fp32 [n, C, inner], may alias x.  x_model: NULL, or the next forward's input [2n, C, inner] in fp32 (xm_f16 = 0) or
+ * fp16 (1): both halves receive x_out (torch.cat([x, x]) and the model's cast).
+ * Coefficient row (VQ_DPMPP_ROW floats, device memory, n_rows rows): the indices below.  step: NULL (an eager launch of
+ * row `row`) or a device counter: the same captured launch then serves every timestep (vq_dpmpp_advance moves it).
+ * Numerics: bit-identical to the eager torch expressions on the same device.  Every operation is one fp32 rounding and
+ * nothing is contracted into an fma; with fp16 eps, c - u, cfg * (.), u + (.) and sigma_t * e are each rounded to fp16 (the
+ * eager path's fp16 tensors).  The division by alpha_t is the product with VQ_DPMPP_INV_ALPHA = RN_fp32(1 / alpha_t): torch
+ * divides a GPU tensor by a host scalar that way (on the CPU it divides; VQ_DPMPP_ALPHA is kept in the row for that form).
+ * VQ_EINVAL: a null eps / x / hist / coef / x_out, n / C / inner / n_rows <= 0, row outside [0, n_rows).  Then VQ_ESHAPE:
+ * ld_eps < C*inner; the kernel moves 4 elements per access when inner % 4 == 0 (else 1): ld_eps not a multiple of that, or
+ * eps / x / hist / x_out / x_model not aligned to that many elements; coef / step off 4 bytes.  Then VQ_EUNSUP: eps_f16 or
+ * xm_f16 outside {0, 1}.  All before any HIP call or dereference. */
+#define VQ_DPMPP_ROW 16        /* floats per row */
+#define VQ_DPMPP_ORDER 0       /* 1, 2 or 3 */
+#define VQ_DPMPP_TAYLOR 1      /* 0 'dpmsolver', 1 'taylor' (order 2) */
+#define VQ_DPMPP_CFG 2         /* guidance scale */
+#define VQ_DPMPP_SIGMA 3       /* sigma_t of this call's time (data_prediction_fn) */
+#define VQ_DPMPP_ALPHA 4       /* alpha_t of this call's time (not read by the kernel) */
+#define VQ_DPMPP_INV_ALPHA 5   /* RN_fp32(1 / alpha_t) */
+#define VQ_DPMPP_X 6           /* a  = sigma_next / sigma_t */
+#define VQ_DPMPP_M0 7          /* b  = alpha_next * phi_1 */
+#define VQ_DPMPP_D1 8          /* c1 = 0.5 * (alpha_next * phi_1) | alpha_next * (phi_1 / h + 1) | alpha_next * phi_2 */
+#define VQ_DPMPP_D2 9          /* c2 = alpha_next * phi_3 */
+#define VQ_DPMPP_INV_R0 10     /* 1 / r0 */
+#define VQ_DPMPP_INV_R1 11     /* 1 / r1 */
+#define VQ_DPMPP_R0_FRAC 12    /* r0 / (r0 + r1) */
+#define VQ_DPMPP_INV_R01 13    /* 1 / (r0 + r1) */
+#define VQ_DPMPP_T_NEXT 14     /* model-input time of the NEXT forward: (t_next - 1/N) * 1000 */
+                               /* 15: zero */
+int vq_cfg_dpmpp_step(const void* eps, const float* x, float* hist, const float* coef, const int32_t* step,
+                      float* x_out, void* x_model, int n, int C, int inner, long ld_eps, int row, int n_rows,
+                      int eps_f16, int xm_f16, void* stream);
+
+/* One workgroup, enqueued after vq_cfg_dpmpp_step: t_out[0 .. n_t) (fp32) = VQ_DPMPP_T_NEXT of row clamp(*step, 0,
+ * n_rows - 1), then *step = min(*step + 1, n_rows - 1).  A launch of its own, so that no workgroup of the step kernel can
+ * read a counter another one has already moved.  VQ_EINVAL: a null pointer, n_rows or n_t <= 0; VQ_ESHAPE: a pointer off
+ * 4 bytes. */
+int vq_dpmpp_advance(int32_t* step, const float* coef, int n_rows, float* t_out, int n_t, void* stream);
+
 /* ---- floating-point Linears at the edges of a forward -------------------------------------
  * out[m, n] = act_out( sum_k act_in(x[m, k]) * w[n, k] + bias[n] ): fp16 operands and result, fp32 accumulation (MFMA),
  * act: 0 none, 1 SiLU, 2 GELU(tanh).  Replaces F.linear of the layers the reference's FP lists keep out of quantization

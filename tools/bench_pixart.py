@@ -25,6 +25,13 @@ ap.add_argument("--steps", type=int, default=6)
 ap.add_argument("--depth", type=int, default=28)
 ap.add_argument("--size", type=int, default=1024)
 ap.add_argument("--graph", action="store_true", help="replay the forward as one captured HIP graph (graph.GraphedModel) instead of eager launches")
+ap.add_argument("--fused-step", action="store_true",
+                help="guidance + x0 + multistep update in one launch per model call (ops.cfg_dpmpp_step); with --graph the whole "
+                     "step {forward, fused step, counter advance} is ONE captured graph replayed per timestep (graph.DPMStepGraph)")
+ap.add_argument("--alternate", type=int, default=0,
+                help="N > 0: time the arms eager / fused-step / graph / fused-step+graph N times in turn in THIS process "
+                     "(same weights, same latent) and print one JSON line with every figure, the GEMM clock probe and the "
+                     "copy probe of bench.py beside them")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 lat = a.size // 8
@@ -54,17 +61,60 @@ with torch.no_grad():
     mask[0, :180] = 1
     z = torch.randn(1, 4, lat, lat, generator=g).to(dev)
     from viditq_amd.graph import GraphedModel
-    solver = DPMS_sigma(GraphedModel(qnn.forward_with_dpmsolver, qnn=qnn) if a.graph else qnn.forward_with_dpmsolver, condition=y, uncondition=null_y, cfg_scale=4.5,
-                        model_kwargs=dict(data_info=None, mask=mask))
-    solver.sample(z, steps=2, order=2)                     # warm-up: packing, caches
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = solver.sample(z, steps=a.steps, order=2)
-    t_host = time.perf_counter() - t0                      # host done enqueuing (the GPU may still be running)
-    torch.cuda.synchronize()
-    el = time.perf_counter() - t0
-    assert torch.isfinite(out).all()
-    print(json.dumps({"workload": "PixArt-Sigma %dx%d W%dA8, %d tokens, Lp %d, DPM-Solver++ 2M, cfg 4.5, batched uncond|cond forward" % (
-        a.size, a.size, a.w_bits, (lat // 2) ** 2, Lp), "steps": a.steps, "depth": a.depth, "hip_graph": a.graph,
-        "steps_per_s": a.steps / el, "ms_per_step": el / a.steps * 1e3,
-        "host_enqueue_ms_per_step": t_host / a.steps * 1e3, "status_word": qnn.check_status()}))
+    kw = dict(condition=y, uncondition=null_y, cfg_scale=4.5, model_kwargs=dict(data_info=None, mask=mask))
+
+    def make_arm(graph, fused):
+        """sample(steps) -> latent for one arm; built (and its graphs captured) once."""
+        if graph and fused:
+            s = DPMS_sigma(qnn.forward_with_dpmsolver, **kw)
+            s.model_input_dtype = torch.float16
+            sgs = {}
+
+            def run(steps):
+                if steps not in sgs:
+                    sgs[steps] = s.step_graph(z, steps=steps, order=2)
+                return sgs[steps].run(z)
+            return run
+        s = DPMS_sigma(GraphedModel(qnn.forward_with_dpmsolver, qnn=qnn) if graph else qnn.forward_with_dpmsolver, **kw)
+        if fused:
+            s.model_input_dtype = torch.float16
+        return lambda steps: s.sample(z, steps=steps, order=2, fused=fused)
+
+    def timed(run, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = run(steps)
+        t_host = time.perf_counter() - t0                  # host done enqueuing (the GPU may still be running)
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        assert torch.isfinite(out).all()
+        return out, {"ms_per_step": el / steps * 1e3, "host_enqueue_ms_per_step": t_host / steps * 1e3}
+
+    workload = "PixArt-Sigma %dx%d W%dA8, %d tokens, Lp %d, DPM-Solver++ 2M, cfg 4.5, batched uncond|cond forward" % (
+        a.size, a.size, a.w_bits, (lat // 2) ** 2, Lp)
+    if a.alternate > 0:
+        import bench
+        arms = {"eager": make_arm(False, False), "fused_step": make_arm(False, True), "graph": make_arm(True, False),
+                "fused_step_graph": make_arm(True, True)}
+        outs = {}
+        for name, run in arms.items():                     # warm-up: packing, caches, captures (at the timed step count)
+            run(2)
+            outs[name] = run(a.steps)
+        torch.cuda.synchronize()
+        res = {name: [] for name in arms}
+        for _ in range(a.alternate):
+            for name, run in arms.items():
+                res[name].append(timed(run, a.steps)[1])
+        print(json.dumps({"workload": workload, "steps": a.steps, "depth": a.depth, "alternations": a.alternate,
+                          "arms": res, "bit_identical_to_eager": {n: bool(torch.equal(o, outs["eager"])) for n, o in outs.items()},
+                          "gemm_shader_clock": bench.gemm_clock_probe(dev), "memory": bench.memory_probe(dev),
+                          "status_word": qnn.check_status()}))
+        sys.exit(0)
+    run = make_arm(a.graph, a.fused_step)
+    run(2)                                                 # warm-up: packing, caches
+    if a.graph and a.fused_step:
+        run(a.steps)                                       # the capture for the timed step count
+    out, t = timed(run, a.steps)
+    print(json.dumps({"workload": workload, "steps": a.steps, "depth": a.depth, "hip_graph": a.graph,
+                      "fused_step": a.fused_step, "steps_per_s": 1e3 / t["ms_per_step"], "ms_per_step": t["ms_per_step"],
+                      "host_enqueue_ms_per_step": t["host_enqueue_ms_per_step"], "status_word": qnn.check_status()}))

@@ -1,4 +1,5 @@
-// sampler.hip - fused classifier-free-guidance + DDIM(eta=0) update for gfx950 (HBM-bound elementwise).
+// sampler.hip - the device-resident sampler steps for gfx950 (HBM-bound elementwise): fused classifier-free guidance +
+// DDIM(eta=0) update (STDiT loop), and further down guidance + x0 + DPM-Solver++ multistep update (PixArt loop).
 //
 // Replaces, for the first (kept) half of the duplicated batch, the tail of forward_with_cfg
 // (t2v/opensora/schedulers/iddpm/__init__.py:168-184: PTQD division, CFG on eps[:, :3] only) and
@@ -40,5 +41,175 @@ extern "C" int vq_cfg_ddim_step(const float* cond, const float* uncond, const fl
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(cfg_ddim_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, cond, uncond, x, x_out, n, C,
                        (long)inner, cfg, one_plus_k, A, Bc, abar_prev);
+    return vq_check_launch();
+}
+
+// ---- fused CFG + data-prediction DPM-Solver++ multistep update (the PixArt sampling loop) ---------------------------
+// One launch per model call k of t2i/diffusion/model/dpm_solver_sigma.py: model_wrapper's guidance (:318-332),
+// data_prediction_fn (:435-444) and dpm_solver_first_update (:551-596) / multistep_dpm_solver_second_update (:805-862) /
+// multistep_dpm_solver_third_update (:864-915).  Row layout and contract: include/viditq.h (vq_cfg_dpmpp_step).
+// Every operation is rounded on its own, as the eager torch expressions round it: no contraction (the pragma below; -O3
+// would otherwise fuse a*x - b*m into an fma), and with an fp16 model the four fp16 roundings of c - u, cfg * (.),
+// u + (.) and sigma_t * e.  The division by alpha_t is the product with the fp32 reciprocal the row holds (what torch's
+// GPU division by a host scalar computes).
+template <typename T, int V> struct dpm_vec;
+template <> struct dpm_vec<float, 4> { typedef float4v type; };
+template <> struct dpm_vec<float, 1> { typedef float type; };
+template <> struct dpm_vec<half_t, 4> { typedef half4 type; };
+template <> struct dpm_vec<half_t, 1> { typedef half_t type; };
+
+template <typename T, int V>
+__device__ __forceinline__ void dpm_load(const T* p, float (&v)[V]) {
+    typename dpm_vec<T, V>::type r = *reinterpret_cast<const typename dpm_vec<T, V>::type*>(p);
+    if constexpr (V == 1) {
+        v[0] = (float)r;
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = (float)r[j];
+    }
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void dpm_store(T* p, const float (&v)[V]) {
+    typename dpm_vec<T, V>::type r;
+    if constexpr (V == 1) {
+        r = (T)v[0];
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) r[j] = (T)v[j];
+    }
+    *reinterpret_cast<typename dpm_vec<T, V>::type*>(p) = r;
+}
+
+// T: the model output's type; V: elements per thread and access (4 needs inner % 4 == 0, so a group never spans two
+// batch elements).  x_out may alias x: an element is read and written by the same thread.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const T* __restrict__ eps, const float* x, float* hist,
+                                                        const float* __restrict__ coef, const int32_t* __restrict__ step,
+                                                        float* xo, void* xm, int xm_f16, int n, long CI, long ld_eps,
+                                                        int row, int n_rows) {
+#pragma clang fp contract(off)
+    int k = row + (step ? *step : 0);
+    k = k < 0 ? 0 : (k < n_rows - 1 ? k : n_rows - 1);          // a counter can never index outside the table
+    const float* r = coef + (long)k * VQ_DPMPP_ROW;
+    const int order = (int)r[VQ_DPMPP_ORDER];
+    const bool taylor = r[VQ_DPMPP_TAYLOR] != 0.0f;
+    const float cfg = r[VQ_DPMPP_CFG], sigma = r[VQ_DPMPP_SIGMA], inv_alpha = r[VQ_DPMPP_INV_ALPHA];
+    const float a = r[VQ_DPMPP_X], b = r[VQ_DPMPP_M0], c1 = r[VQ_DPMPP_D1], c2 = r[VQ_DPMPP_D2];
+    const float ir0 = r[VQ_DPMPP_INV_R0], ir1 = r[VQ_DPMPP_INV_R1], f = r[VQ_DPMPP_R0_FRAC], g = r[VQ_DPMPP_INV_R01];
+    const long total = (long)n * CI;
+    float* h0 = hist + (long)(k % 3) * total;                    // written: m_k
+    const float* h1 = hist + (long)((k + 2) % 3) * total;        // m_{k-1}
+    const float* h2 = hist + (long)((k + 1) % 3) * total;        // m_{k-2}
+    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V; i < total; i += (long)gridDim.x * blockDim.x * V) {
+        const long bi = i / CI, ri = i - bi * CI;
+        float u[V], c[V], xv[V], m1[V], m2[V], m0[V], out[V];
+        dpm_load<T, V>(eps + bi * ld_eps + ri, u);
+        dpm_load<T, V>(eps + (bi + n) * ld_eps + ri, c);
+        dpm_load<float, V>(x + i, xv);
+        if (order >= 2) dpm_load<float, V>(h1 + i, m1);
+        if (order >= 3) dpm_load<float, V>(h2 + i, m2);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float se;
+            if constexpr (std::is_same<T, half_t>::value) {
+                const half_t d = (half_t)(c[j] - u[j]);
+                const half_t p = (half_t)(cfg * (float)d);
+                const half_t e = (half_t)(u[j] + (float)p);
+                se = (float)(half_t)(sigma * (float)e);
+            } else {
+                const float d = c[j] - u[j];
+                const float p = cfg * d;
+                const float e = u[j] + p;
+                se = sigma * e;
+            }
+            const float t = xv[j] - se;
+            const float m = t * inv_alpha;
+            m0[j] = m;
+            const float ax = a * xv[j];
+            const float bm = b * m;
+            float o = ax - bm;
+            if (order == 2) {
+                const float dm = m - m1[j];
+                const float D1_0 = ir0 * dm;
+                const float cd = c1 * D1_0;
+                o = taylor ? o + cd : o - cd;
+            } else if (order >= 3) {
+                const float dm0 = m - m1[j];
+                const float D1_0 = ir0 * dm0;
+                const float dm1 = m1[j] - m2[j];
+                const float D1_1 = ir1 * dm1;
+                const float dd = D1_0 - D1_1;
+                const float fd = f * dd;
+                const float D1 = D1_0 + fd;
+                const float D2 = g * dd;
+                const float p2 = c1 * D1;
+                const float p3 = c2 * D2;
+                o = o + p2;
+                o = o - p3;
+            }
+            out[j] = o;
+        }
+        dpm_store<float, V>(h0 + i, m0);
+        dpm_store<float, V>(xo + i, out);
+        if (xm) {
+            if (xm_f16) {
+                dpm_store<half_t, V>((half_t*)xm + i, out);
+                dpm_store<half_t, V>((half_t*)xm + total + i, out);
+            } else {
+                dpm_store<float, V>((float*)xm + i, out);
+                dpm_store<float, V>((float*)xm + total + i, out);
+            }
+        }
+    }
+}
+
+static inline bool dpm_aligned(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
+
+extern "C" int vq_cfg_dpmpp_step(const void* eps, const float* x, float* hist, const float* coef, const int32_t* step,
+                                 float* x_out, void* x_model, int n, int C, int inner, long ld_eps, int row, int n_rows,
+                                 int eps_f16, int xm_f16, void* stream) {
+    if (!eps || !x || !hist || !coef || !x_out || n <= 0 || C <= 0 || inner <= 0 || row < 0 || n_rows <= 0 || row >= n_rows)
+        return VQ_EINVAL;
+    const long CI = (long)C * inner;
+    if (ld_eps < CI) return VQ_ESHAPE;
+    const int V = inner % 4 == 0 ? 4 : 1;
+    const bool e16 = eps_f16 == 1, m16 = xm_f16 == 1;            // (a flag outside {0, 1} is refused below, after the shapes)
+    if (ld_eps % V != 0 || !dpm_aligned(eps, (e16 ? 2 : 4) * V) || !dpm_aligned(x, 4 * V) || !dpm_aligned(hist, 4 * V) ||
+        !dpm_aligned(x_out, 4 * V) || !dpm_aligned(x_model, (m16 ? 2 : 4) * V) || !dpm_aligned(coef, 4) ||
+        !dpm_aligned(step, 4))
+        return VQ_ESHAPE;
+    if (eps_f16 < 0 || eps_f16 > 1 || xm_f16 < 0 || xm_f16 > 1) return VQ_EUNSUP;
+    const long total = (long)n * CI;
+    long blocks = ((total + V - 1) / V + 255) / 256;
+    if (blocks > 1024) blocks = 1024;                            // 16 waves per CU in flight; larger latents loop
+#define VQ_DPM_LAUNCH(T_, V_)                                                                                          \
+    hipLaunchKernelGGL((cfg_dpmpp_kernel<T_, V_>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,          \
+                       (const T_*)eps, x, hist, coef, step, x_out, x_model, xm_f16, n, CI, ld_eps, row, n_rows)
+    if (e16) {
+        if (V == 4) VQ_DPM_LAUNCH(half_t, 4); else VQ_DPM_LAUNCH(half_t, 1);
+    } else {
+        if (V == 4) VQ_DPM_LAUNCH(float, 4); else VQ_DPM_LAUNCH(float, 1);
+    }
+#undef VQ_DPM_LAUNCH
+    return vq_check_launch();
+}
+
+// One workgroup, after the step kernel in stream order: t_out[0 .. n_t) = the row's next model-input time, then the
+// counter moves on (saturating).  Every thread reads the counter before the barrier; thread 0 writes it after.
+__global__ __launch_bounds__(256) void dpmpp_advance_kernel(int32_t* step, const float* __restrict__ coef, int n_rows,
+                                                            float* __restrict__ t_out, int n_t) {
+    int k = *step;
+    k = k < 0 ? 0 : (k < n_rows - 1 ? k : n_rows - 1);
+    const float t = coef[(long)k * VQ_DPMPP_ROW + VQ_DPMPP_T_NEXT];
+    for (int i = threadIdx.x; i < n_t; i += blockDim.x) t_out[i] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) *step = k < n_rows - 1 ? k + 1 : n_rows - 1;
+}
+
+extern "C" int vq_dpmpp_advance(int32_t* step, const float* coef, int n_rows, float* t_out, int n_t, void* stream) {
+    if (!step || !coef || !t_out || n_rows <= 0 || n_t <= 0) return VQ_EINVAL;
+    if (!dpm_aligned(step, 4) || !dpm_aligned(coef, 4) || !dpm_aligned(t_out, 4)) return VQ_ESHAPE;
+    hipLaunchKernelGGL(dpmpp_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, step, coef, n_rows, t_out, n_t);
     return vq_check_launch();
 }

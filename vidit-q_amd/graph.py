@@ -230,3 +230,58 @@ class GraphedModel:
             if self._epoch != PACK_EPOCH[0]:             # the first pass packed weights: the capture came after it
                 self._epoch = PACK_EPOCH[0]
         return g.run(x, t, y).clone()
+
+
+class DPMStepGraph:
+    """The guided DPM-Solver++ multistep loop of t2i/dpm_solver.py as ONE captured step: {forward(x_model, t, text),
+    ops.cfg_dpmpp_step(step=counter), ops.dpmpp_advance} recorded once and replayed for every timestep.  What changes
+    from step to step lives in device memory: the latent, the model-input time, the x0 history, and a counter that
+    selects the row of the coefficient table uploaded before the loop.  The captured graph is one linear chain.
+    A forward that moves host-visible state (a running smooth-quant statistic) cannot be captured and is refused."""
+
+    def __init__(self, fn, text, kwargs, x, rows, t_first: float, model_dtype=torch.float32, warmup: int = 2):
+        from . import ops
+        from ._lib import VQError
+        if GraphedModel(fn)._state(kwargs.get("timestep_id"))[2]:
+            raise VQError("DPMStepGraph: a layer keeps a running smooth-quant statistic; its forward is not capturable")
+        n = x.shape[0]
+        dev = x.device
+        self.steps, self.t_first = rows.shape[0], float(t_first)
+        self.rows = rows.to(dev)
+        self.x = x.float().contiguous().clone()
+        self.xm = torch.cat([self.x, self.x]).to(model_dtype)
+        self.t = torch.full((2 * n,), self.t_first, dtype=torch.float32, device=dev)
+        self.hist = torch.zeros((3, self.x.numel()), dtype=torch.float32, device=dev)
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+
+        def one():
+            eps = fn(self.xm, self.t, text, **kwargs)
+            if not ops.cfg_dpmpp_step_ok(eps, self.x):
+                raise VQError("DPMStepGraph: vq_cfg_dpmpp_step does not take this model output")
+            ops.cfg_dpmpp_step(eps, self.x, self.hist, self.rows, 0, step=self.step, x_out=self.x, x_model=self.xm)
+            ops.dpmpp_advance(self.step, self.rows, self.t)
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(warmup + 1):                  # packs weights, fills the host-side caches
+                one()
+            side.synchronize()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+            one()
+
+    @torch.no_grad()
+    def run(self, x, step_callback=None):
+        n = x.shape[0]
+        self.x.copy_(x)
+        self.xm[:n].copy_(x)
+        self.xm[n:].copy_(x)
+        self.t.fill_(self.t_first)
+        self.step.zero_()
+        for k in range(self.steps):
+            self.graph.replay()
+            if step_callback is not None:
+                step_callback(k + 1, self.x.clone())
+        return self.x.clone()

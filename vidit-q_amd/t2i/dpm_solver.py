@@ -28,10 +28,18 @@ dynamic thresholding / ``correcting_x0_fn`` / ``correcting_xt_fn`` hooks and the
 """
 from __future__ import annotations
 
+import os
 from typing import Callable, Optional
 
 import numpy as np
 import torch
+
+
+def _switch(name: str, default: bool) -> bool:
+    return os.environ.get(name, "1" if default else "0") != "0"
+
+
+_DPM_FUSED = _switch("VQ_DPM_FUSED", False)          # guidance + x0 + multistep update in one launch per model call
 
 
 def linear_betas(diffusion_steps: int = 1000) -> np.ndarray:
@@ -99,6 +107,8 @@ class DPMSolverPP:
         self.model_kwargs = dict(model_kwargs or {})
         self.ns = NoiseScheduleVP(linear_betas(diffusion_steps))
         self._c2 = None                                   # (uncond | cond) text embedding, concatenated once
+        self.model_input_dtype = torch.float32            # fused route: dtype of the latent handed to the model (it casts)
+        self._tables = {}                                 # fused route: device coefficient tables by configuration
 
     # ---- model_wrapper: continuous time -> model input time, classifier-free guidance (:273-332)
     def _noise(self, x, t_cont: torch.Tensor):
@@ -106,69 +116,104 @@ class DPMSolverPP:
         # the model-input time is computed on the host in fp32 (the same two roundings as the reference's tensor
         # expression) and materialised by a fill kernel: a `.to(device)` of a host tensor here is a pageable copy that
         # makes the host wait for ALL queued GPU work once per step
-        t_val = float((t_cont.float() - 1.0 / self.ns.total_N) * 1000.0)
+        t_val = self._t_val(t_cont)
         if self.cfg_scale == 1.0 or self.uncondition is None:
             return self.model(x, torch.full((n,), t_val, dtype=torch.float32, device=x.device), self.condition,
                               **self.model_kwargs)
         x2 = torch.cat([x, x])
+        out = self.model(x2, torch.full((2 * n,), t_val, dtype=torch.float32, device=x.device), self._joint_text(),
+                         **self.model_kwargs)
+        return self._guide(out)
+
+    def _t_val(self, t_cont) -> float:
+        """Model-input time of a continuous time (:273-279), fp32 on the host."""
+        return float((t_cont.float() - 1.0 / self.ns.total_N) * 1000.0)
+
+    def _joint_text(self):
         c, u = self.condition, self.uncondition
         hit = self._c2
         if hit is None or hit[0][0] is not c or hit[0][2] is not u or hit[0][1] != c._version or hit[0][3] != u._version:
             self._c2 = ((c, c._version, u, u._version), torch.cat([u, c]))
-        out = self.model(x2, torch.full((2 * n,), t_val, dtype=torch.float32, device=x.device), self._c2[1],
-                         **self.model_kwargs)
+        return self._c2[1]
+
+    def _guide(self, out):
+        """Classifier-free guidance on the (uncond | cond) output of one batched forward (:318-332)."""
         noise_uncond, noise = out.chunk(2)
         return noise_uncond + self.cfg_scale * (noise - noise_uncond)
 
-    def _x0(self, x, t):
-        """data_prediction_fn (:435-444)."""
-        noise = self._noise(x, t)
-        alpha_t, sigma_t = float(self.ns.marginal_alpha(t)), float(self.ns.marginal_std(t))
+    def _x0_coefs(self, t):
+        """(sigma_t, alpha_t) of data_prediction_fn (:435-444)."""
+        return float(self.ns.marginal_std(t)), float(self.ns.marginal_alpha(t))
+
+    def _x0_of_noise(self, x, t, noise):
+        sigma_t, alpha_t = self._x0_coefs(t)
         return (x - sigma_t * noise) / alpha_t
 
-    # ---- updates (host scalars in fp32 as in the reference, applied to device tensors)
-    def _first(self, x, s, t, model_s):
+    def _x0(self, x, t):
+        """data_prediction_fn (:435-444)."""
+        return self._x0_of_noise(x, t, self._noise(x, t))
+
+    # ---- updates (host scalars in fp32 as in the reference, applied to device tensors).  The scalars of each update
+    # come from ONE function, which the eager expressions below and the coefficient table of the fused step
+    # (multistep_rows) both read
+    def _first_coefs(self, s, t):
+        """(sigma_t / sigma_s, alpha_t * phi_1) of dpm_solver_first_update (:551-596)."""
         ns = self.ns
         h = ns.marginal_lambda(t) - ns.marginal_lambda(s)
         sigma_s, sigma_t = ns.marginal_std(s), ns.marginal_std(t)
         alpha_t = torch.exp(ns.marginal_log_mean_coeff(t))
         phi_1 = torch.expm1(-h)
-        return float(sigma_t / sigma_s) * x - float(alpha_t * phi_1) * model_s
+        return float(sigma_t / sigma_s), float(alpha_t * phi_1)
 
-    def _second(self, x, model_prev, t_prev, t, solver_type="dpmsolver"):
+    def _first(self, x, s, t, model_s):
+        a, b = self._first_coefs(s, t)
+        return a * x - b * model_s
+
+    def _second_coefs(self, t1, t0, t, solver_type="dpmsolver"):
+        """(sigma_t / sigma0, alpha_t * phi_1, the multiplier of D1_0, 1 / r0) of multistep_dpm_solver_second_update
+        (:805-862); the third is added for 'taylor' (:839-844) and subtracted for 'dpmsolver'."""
         ns = self.ns
-        m1, m0 = model_prev[-2], model_prev[-1]
-        t1, t0 = t_prev[-2], t_prev[-1]
         l1, l0, lt = ns.marginal_lambda(t1), ns.marginal_lambda(t0), ns.marginal_lambda(t)
         sigma0, sigma_t = ns.marginal_std(t0), ns.marginal_std(t)
         alpha_t = torch.exp(ns.marginal_log_mean_coeff(t))
         h_0, h = l0 - l1, lt - l0
         r0 = h_0 / h
         phi_1 = torch.expm1(-h)
-        D1_0 = float(1.0 / r0) * (m0 - m1)
-        if solver_type == "taylor":                                    # (:839-844)
-            return float(sigma_t / sigma0) * x - float(alpha_t * phi_1) * m0 + float(alpha_t * (phi_1 / h + 1.0)) * D1_0
-        return float(sigma_t / sigma0) * x - float(alpha_t * phi_1) * m0 - float(0.5 * (alpha_t * phi_1)) * D1_0
+        c = float(alpha_t * (phi_1 / h + 1.0)) if solver_type == "taylor" else float(0.5 * (alpha_t * phi_1))
+        return float(sigma_t / sigma0), float(alpha_t * phi_1), c, float(1.0 / r0)
 
-    def _third(self, x, model_prev, t_prev, t):
-        """multistep_dpm_solver_third_update (:864-915), data prediction."""
+    def _second(self, x, model_prev, t_prev, t, solver_type="dpmsolver"):
+        m1, m0 = model_prev[-2], model_prev[-1]
+        a, b, c, inv_r0 = self._second_coefs(t_prev[-2], t_prev[-1], t, solver_type)
+        D1_0 = inv_r0 * (m0 - m1)
+        if solver_type == "taylor":
+            return a * x - b * m0 + c * D1_0
+        return a * x - b * m0 - c * D1_0
+
+    def _third_coefs(self, t2, t1, t0, t):
+        """(sigma_t / sigma0, alpha_t * phi_1, alpha_t * phi_2, alpha_t * phi_3, 1 / r0, 1 / r1, r0 / (r0 + r1),
+        1 / (r0 + r1)) of multistep_dpm_solver_third_update (:864-915)."""
         ns = self.ns
-        m2, m1, m0 = model_prev
-        t2, t1, t0 = t_prev
         l2, l1, l0, lt = ns.marginal_lambda(t2), ns.marginal_lambda(t1), ns.marginal_lambda(t0), ns.marginal_lambda(t)
         sigma0, sigma_t = ns.marginal_std(t0), ns.marginal_std(t)
         alpha_t = torch.exp(ns.marginal_log_mean_coeff(t))
         h_1, h_0, h = l1 - l2, l0 - l1, lt - l0
         r0, r1 = h_0 / h, h_1 / h
-        D1_0 = float(1.0 / r0) * (m0 - m1)
-        D1_1 = float(1.0 / r1) * (m1 - m2)
-        D1 = D1_0 + float(r0 / (r0 + r1)) * (D1_0 - D1_1)
-        D2 = float(1.0 / (r0 + r1)) * (D1_0 - D1_1)
         phi_1 = torch.expm1(-h)
         phi_2 = phi_1 / h + 1.0
         phi_3 = phi_2 / h - 0.5
-        return (float(sigma_t / sigma0) * x - float(alpha_t * phi_1) * m0 + float(alpha_t * phi_2) * D1
-                - float(alpha_t * phi_3) * D2)
+        return (float(sigma_t / sigma0), float(alpha_t * phi_1), float(alpha_t * phi_2), float(alpha_t * phi_3),
+                float(1.0 / r0), float(1.0 / r1), float(r0 / (r0 + r1)), float(1.0 / (r0 + r1)))
+
+    def _third(self, x, model_prev, t_prev, t):
+        """multistep_dpm_solver_third_update (:864-915), data prediction."""
+        m2, m1, m0 = model_prev
+        a, b, c1, c2, inv_r0, inv_r1, frac, inv_r01 = self._third_coefs(*t_prev, t)
+        D1_0 = inv_r0 * (m0 - m1)
+        D1_1 = inv_r1 * (m1 - m2)
+        D1 = D1_0 + frac * (D1_0 - D1_1)
+        D2 = inv_r01 * (D1_0 - D1_1)
+        return a * x - b * m0 + c1 * D1 - c2 * D2
 
     def _multistep(self, x, model_prev, t_prev, t, order, solver_type="dpmsolver"):
         if order == 1:
@@ -296,12 +341,107 @@ class DPMSolverPP:
             self.nfe += order
         return x
 
+    # ---- the fused step (ops.cfg_dpmpp_step): one launch per model call instead of the elementwise ops above
+    @staticmethod
+    def multistep_orders(steps, order, lower_order_final=True):
+        """Order of the update that follows model call k = 0 .. steps - 1 of the multistep loop (:1183-1230): k + 1 during
+        the warm-up, then ``min(order, steps - k)`` under ``lower_order_final``, else ``order``."""
+        return [k + 1 if k + 1 < order else (min(order, steps - k) if lower_order_final else order) for k in range(steps)]
+
+    def multistep_rows(self, steps, order=2, skip_type="time_uniform", t_T=None, t_0=None, lower_order_final=True,
+                       solver_type="dpmsolver"):
+        """The coefficient table of the fused step: [steps, DPMPP_ROW] fp32 (host), row k for model call k at time ts[k]
+        and the update to ts[k + 1] (layout: include/viditq.h, VQ_DPMPP_*).  Every scalar is the one the eager update
+        uses (_x0_coefs, _first_coefs, _second_coefs, _third_coefs, _t_val)."""
+        from .. import _lib as L
+        t_0 = 1.0 / self.ns.total_N if t_0 is None else t_0
+        t_T = self.ns.T if t_T is None else t_T
+        assert steps >= order and order in (1, 2, 3) and solver_type in ("dpmsolver", "taylor")
+        ts = self.time_steps(skip_type, t_T, t_0, steps)
+        rows = np.zeros((steps, L.DPMPP_ROW), dtype=np.float32)
+        for k, o in enumerate(self.multistep_orders(steps, order, lower_order_final)):
+            r = rows[k]
+            r[L.DPMPP_ORDER], r[L.DPMPP_TAYLOR], r[L.DPMPP_CFG] = o, float(solver_type == "taylor"), self.cfg_scale
+            r[L.DPMPP_SIGMA], r[L.DPMPP_ALPHA] = self._x0_coefs(ts[k])
+            # torch divides a GPU tensor by a host scalar as the product with this fp32 reciprocal
+            r[L.DPMPP_INV_ALPHA] = np.float32(1.0) / r[L.DPMPP_ALPHA]
+            if o == 1:
+                r[L.DPMPP_X], r[L.DPMPP_M0] = self._first_coefs(ts[k], ts[k + 1])
+            elif o == 2:
+                r[L.DPMPP_X], r[L.DPMPP_M0], r[L.DPMPP_D1], r[L.DPMPP_INV_R0] = self._second_coefs(
+                    ts[k - 1], ts[k], ts[k + 1], solver_type)
+            else:
+                (r[L.DPMPP_X], r[L.DPMPP_M0], r[L.DPMPP_D1], r[L.DPMPP_D2], r[L.DPMPP_INV_R0], r[L.DPMPP_INV_R1],
+                 r[L.DPMPP_R0_FRAC], r[L.DPMPP_INV_R01]) = self._third_coefs(ts[k - 2], ts[k - 1], ts[k], ts[k + 1])
+            r[L.DPMPP_T_NEXT] = self._t_val(ts[k + 1])
+        return torch.from_numpy(rows)
+
+    def _fused_wanted(self, x, method, fused):
+        if fused is None:
+            fused = _DPM_FUSED
+        return bool(fused) and method == "multistep" and self.cfg_scale != 1.0 and self.uncondition is not None and x.is_cuda
+
+    def _device_table(self, dev, n, args):
+        """(coefficient table, model-input times of calls 1 .. steps - 1 as [steps, 2n]) on the device for one sampling
+        configuration ``args`` = the arguments of multistep_rows; kept, so that the next sample() with the same
+        configuration uploads nothing."""
+        from .. import _lib
+        key = (args, self.cfg_scale, str(dev), n)
+        hit = self._tables.get(key)
+        if hit is None:
+            rows = self.multistep_rows(*args)
+            t_next = rows[:, _lib.DPMPP_T_NEXT][:, None].expand(rows.shape[0], 2 * n).contiguous()
+            # pinned and non-blocking: a pageable upload makes the host wait for the forward that is already queued
+            hit = (rows.pin_memory().to(dev, non_blocking=True), t_next.pin_memory().to(dev, non_blocking=True))
+            if len(self._tables) >= 8:
+                self._tables.clear()
+            self._tables[key] = hit
+        return hit
+
+    def _multistep_fused(self, x, ts, args, step_callback):
+        """The multistep loop with one launch behind each model call.  Returns (x, None), or (None, eps) when the first
+        model output is not one the kernel takes (ops.cfg_dpmpp_step_ok): the caller goes on eagerly from it."""
+        from .. import ops
+        n, steps, order = x.shape[0], args[0], args[1]
+        x = x.float().contiguous() if x.dtype != torch.float32 or not x.is_contiguous() else x
+        xm = torch.cat([x, x]).to(self.model_input_dtype)
+        hist = torch.empty((3, x.numel()), dtype=torch.float32, device=x.device)
+        text = self._joint_text()
+        t = torch.full((2 * n,), self._t_val(ts[0]), dtype=torch.float32, device=x.device)
+        for k in range(steps):
+            eps = self.model(xm, t, text, **self.model_kwargs)
+            if k == 0:
+                if not ops.cfg_dpmpp_step_ok(eps, x):
+                    return None, eps
+                # the table is built (host work) and uploaded behind the first forward's launches, not in front of them
+                rows, t_next = self._device_table(x.device, n, args)
+            # a fresh x_out per step: what a step_callback was handed is never written again
+            x = ops.cfg_dpmpp_step(eps, x, hist, rows, k, x_model=xm)
+            t = t_next[k]
+            if step_callback is not None and k + 1 >= order:
+                step_callback(k + 1, x)
+        return x, None
+
+    def step_graph(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type="time_uniform", lower_order_final=True,
+                   solver_type="dpmsolver"):
+        """The counter form of the fused multistep loop: {model call, fused step, counter advance} captured once as a HIP
+        graph and replayed ``steps`` times (graph.DPMStepGraph); ``.run(x)`` samples."""
+        from ..graph import DPMStepGraph
+        assert self.cfg_scale != 1.0 and self.uncondition is not None, "the fused step is the guided one"
+        rows = self.multistep_rows(steps, order, skip_type, t_start, t_end, lower_order_final, solver_type)
+        ts = self.time_steps(skip_type, self.ns.T if t_start is None else t_start,
+                             1.0 / self.ns.total_N if t_end is None else t_end, steps)
+        return DPMStepGraph(self.model, self._joint_text(), self.model_kwargs, x, rows, self._t_val(ts[0]),
+                            self.model_input_dtype)
+
     @torch.no_grad()
     def sample(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type="time_uniform", method="multistep",
                lower_order_final=True, denoise_to_zero=False, solver_type="dpmsolver", atol=0.0078, rtol=0.05,
-               step_callback=None):
+               step_callback=None, fused=None):
         """``DPM_Solver.sample`` (:1069-1279) for data-prediction DPM-Solver++.  ``method``: 'multistep' (order 1-3),
-        'singlestep', 'singlestep_fixed', 'adaptive' (order 2 / 3)."""
+        'singlestep', 'singlestep_fixed', 'adaptive' (order 2 / 3).  ``fused``: the guided multistep loop on GPU tensors
+        with ops.cfg_dpmpp_step behind each model call (None: the VQ_DPM_FUSED switch, off by default); bit-identical
+        to the eager expressions, which every other case runs."""
         if solver_type not in ("dpmsolver", "taylor"):
             raise ValueError("'solver_type' is 'dpmsolver' or 'taylor', got %r" % (solver_type,))
         if order not in (1, 2, 3):
@@ -315,7 +455,14 @@ class DPMSolverPP:
             assert steps >= order
             ts = self.time_steps(skip_type, t_T, t_0, steps)           # fp32, get_time_steps :455
             t = ts[0]
-            t_prev, model_prev = [t], [self._x0(x, t)]
+            eps0 = None
+            if self._fused_wanted(x, method, fused):
+                x_f, eps0 = self._multistep_fused(
+                    x, ts, (steps, order, skip_type, t_T, t_0, bool(lower_order_final), solver_type), step_callback)
+                if x_f is not None:
+                    return self._x0(x_f, torch.tensor(t_0, dtype=torch.float32)) if denoise_to_zero else x_f
+            t_prev = [t]
+            model_prev = [self._x0(x, t) if eps0 is None else self._x0_of_noise(x, t, self._guide(eps0))]
             for step in range(1, order):                               # warm-up with the lower orders
                 t = ts[step]
                 x = self._multistep(x, model_prev, t_prev, t, step, solver_type)
