@@ -543,6 +543,51 @@ int vq_cfg_dpmpp_step(const void* eps, const float* x, float* hist, const float*
  * 4 bytes. */
 int vq_dpmpp_advance(int32_t* step, const float* coef, int n_rows, float* t_out, int n_t, void* stream);
 
+/* Fused CFG + learned-range variance + ancestral posterior step: ONE launch per model call of the PixArt IDDPM loop
+ * (p_sample_loop(model.forward_with_cfg, ...), quant_txt2img.py:154-166).  Replaces, for the kept first half of the
+ * duplicated batch, the tail of forward_with_cfg (t2i/diffusion/model/nets/PixArtMS.py:221-234), p_mean_variance
+ * (t2i/diffusion/model/gaussian_diffusion.py:303-318), _predict_xstart_from_eps (:363-368), q_posterior_mean_variance
+ * (:264-267) and p_sample (:439-445).  For row k = clamp(row + (step ? *step : 0), 0, n_rows - 1), per element of
+ * [n, C, inner]:
+ *   c = eps[b, ch], u = eps[n + b, ch]   eps: the model's output for the (cond | uncond) batch - the OPPOSITE order of
+ *                                        vq_cfg_dpmpp_step -, [2n] x [2C * inner], batch pitch ld_eps elements; fp32
+ *                                        (eps_f16 = 0) or fp16 (1)
+ *   e    = ch < guided ? u + cfg * (c - u) : c          (guided = 3 in the reference)
+ *   v    = eps[b, C + ch]                               cond's variance channel; uncond's channels >= guided and its
+ *                                                       variance channels are never read
+ *   frac = (v + 1) * 0.5
+ *   lv   = frac * max_log + (1 - frac) * min_log
+ *   x0   = A * x - B * e;  clamped into [-1, 1] when CLIP   -> x0_out (NULL or fp32 [n, C, inner]: 'pred_xstart')
+ *   mean = c1 * x0 + c2 * x
+ *   out  = mean + ((nonzero * exp(0.5 * lv)) * noise)   -> x_out fp32 [n, C, inner], may alias x
+ * noise: fp32 [n, C, inner], required on every row (the reference draws it on the last one too, where nonzero = 0).
+ * x_model: NULL, or the next forward's input [2n, C, inner] in fp32 (xm_f16 = 0) or fp16 (1): both halves receive out.
+ * Coefficient row: VQ_DDPM_ROW floats, the indices below; unused slots are zero.  The row has the size of the DPM-Solver++
+ * row and keeps the next model-input time in the same slot (VQ_DDPM_T_NEXT == VQ_DPMPP_T_NEXT), so vq_dpmpp_advance serves
+ * as the counter and time kernel of this step unchanged.  step: as for vq_cfg_dpmpp_step.
+ * Numerics: every operation is rounded on its own, nothing is contracted; with fp16 eps, c - u, cfg * (.), u + (.), v + 1,
+ * (.) * 0.5 and 1 - frac are each rounded to fp16 (the eager path's fp16 tensors) and everything that meets a coefficient
+ * is fp32; exp is expf.
+ * Refusals, in this order, before any HIP call or dereference.  VQ_EINVAL: a null eps / x / noise / coef / x_out; n / C /
+ * inner / n_rows <= 0; row outside [0, n_rows); guided < 0.  VQ_ESHAPE: ld_eps < 2*C*inner; guided > C; the kernel moves 4
+ * elements per access when inner % 4 == 0 (else 1): ld_eps not a multiple of that, or eps / x / noise / x_out / x0_out /
+ * x_model not aligned to that many elements; coef / step off 4 bytes.  VQ_EUNSUP: eps_f16 or xm_f16 outside {0, 1}. */
+#define VQ_DDPM_ROW 16         /* floats per row (== VQ_DPMPP_ROW) */
+#define VQ_DDPM_CFG 0          /* guidance scale */
+#define VQ_DDPM_A 1            /* sqrt_recip_alphas_cumprod[i] */
+#define VQ_DDPM_B 2            /* sqrt_recipm1_alphas_cumprod[i] */
+#define VQ_DDPM_C1 3           /* posterior_mean_coef1[i] */
+#define VQ_DDPM_C2 4           /* posterior_mean_coef2[i] */
+#define VQ_DDPM_MIN_LOG 5      /* posterior_log_variance_clipped[i] */
+#define VQ_DDPM_MAX_LOG 6      /* log(betas[i]) */
+#define VQ_DDPM_NONZERO 7      /* 1, on the row of i == 0: 0 */
+#define VQ_DDPM_CLIP 8         /* clip_denoised: 0 or 1 */
+#define VQ_DDPM_T_NEXT 14      /* model-input time of the NEXT forward (== VQ_DPMPP_T_NEXT) */
+                               /* 9 - 13, 15: zero */
+int vq_cfg_ddpm_step(const void* eps, const float* x, const float* noise, const float* coef, const int32_t* step,
+                     float* x_out, float* x0_out, void* x_model, int n, int C, int inner, long ld_eps, int guided,
+                     int row, int n_rows, int eps_f16, int xm_f16, void* stream);
+
 /* ---- floating-point Linears at the edges of a forward -------------------------------------
  * out[m, n] = act_out( sum_k act_in(x[m, k]) * w[n, k] + bias[n] ): fp16 operands and result, fp32 accumulation (MFMA),
  * act: 0 none, 1 SiLU, 2 GELU(tanh).  Replaces F.linear of the layers the reference's FP lists keep out of quantization

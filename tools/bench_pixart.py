@@ -17,7 +17,7 @@ import viditq_amd  # noqa
 from viditq_amd import synth
 from viditq_amd.config import to_config
 from viditq_amd.qdiff.models import QuantModel
-from viditq_amd.t2i import DPMS_sigma, PixArtMS_XL_2
+from viditq_amd.t2i import DPMS_sigma, IDDPM, PixArtMS_XL_2
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--w-bits", type=int, default=4)
@@ -28,6 +28,9 @@ ap.add_argument("--graph", action="store_true", help="replay the forward as one 
 ap.add_argument("--fused-step", action="store_true",
                 help="guidance + x0 + multistep update in one launch per model call (ops.cfg_dpmpp_step); with --graph the whole "
                      "step {forward, fused step, counter advance} is ONE captured graph replayed per timestep (graph.DPMStepGraph)")
+ap.add_argument("--sampler", choices=("dpm", "iddpm"), default="dpm",
+                help="iddpm: the ancestral loop of --sampling_algo iddpm (t2i/iddpm.py, IDDPM(str(steps)).p_sample_loop("
+                     "forward_with_cfg)); --fused-step is then ops.cfg_ddpm_step and --fused-step --graph graph.DDPMStepGraph")
 ap.add_argument("--alternate", type=int, default=0,
                 help="N > 0: time the arms eager / fused-step / graph / fused-step+graph N times in turn in THIS process "
                      "(same weights, same latent) and print one JSON line with every figure, the GEMM clock probe and the "
@@ -63,8 +66,34 @@ with torch.no_grad():
     from viditq_amd.graph import GraphedModel
     kw = dict(condition=y, uncondition=null_y, cfg_scale=4.5, model_kwargs=dict(data_info=None, mask=mask))
 
+    def make_iddpm_arm(graph, fused):
+        """The same four arms for the IDDPM loop.  Every run draws its noise from a generator seeded alike, so the arms
+        see the same stack (the eager arms and the fused ones then differ by their exp only)."""
+        z2 = z.repeat(2, 1, 1, 1)
+        kw2 = dict(y=torch.cat([y, null_y]), cfg_scale=4.5, data_info=None, mask=mask)
+        ds, sgs = {}, {}
+        gm = GraphedModel(qnn.forward_with_cfg, qnn=qnn)
+        model = (lambda x, timestep, y, **k: gm(x, timestep, y, **k)) if graph and not fused else qnn.forward_with_cfg
+
+        def run(steps):
+            d = ds.get(steps)
+            if d is None:
+                d = ds[steps] = IDDPM(str(steps))
+                if fused:
+                    d.model_input_dtype = torch.float16
+            gen = torch.Generator(device=dev).manual_seed(3)
+            if graph and fused:
+                if steps not in sgs:
+                    sgs[steps] = d.p_sample_graph(qnn.forward_with_cfg, z2, clip_denoised=False, model_kwargs=kw2)
+                return sgs[steps].run(z2, generator=gen).chunk(2, dim=0)[0]
+            return d.p_sample_loop(model, z2.shape, z2, clip_denoised=False, model_kwargs=kw2, fused=fused,
+                                   generator=gen).chunk(2, dim=0)[0]
+        return run
+
     def make_arm(graph, fused):
         """sample(steps) -> latent for one arm; built (and its graphs captured) once."""
+        if a.sampler == "iddpm":
+            return make_iddpm_arm(graph, fused)
         if graph and fused:
             s = DPMS_sigma(qnn.forward_with_dpmsolver, **kw)
             s.model_input_dtype = torch.float16
@@ -90,8 +119,10 @@ with torch.no_grad():
         assert torch.isfinite(out).all()
         return out, {"ms_per_step": el / steps * 1e3, "host_enqueue_ms_per_step": t_host / steps * 1e3}
 
-    workload = "PixArt-Sigma %dx%d W%dA8, %d tokens, Lp %d, DPM-Solver++ 2M, cfg 4.5, batched uncond|cond forward" % (
-        a.size, a.size, a.w_bits, (lat // 2) ** 2, Lp)
+    workload = "PixArt-Sigma %dx%d W%dA8, %d tokens, Lp %d, %s, cfg 4.5, batched %s forward" % (
+        a.size, a.size, a.w_bits, (lat // 2) ** 2, Lp,
+        "DPM-Solver++ 2M" if a.sampler == "dpm" else "IDDPM ancestral (learned-range variance)",
+        "uncond|cond" if a.sampler == "dpm" else "cond|uncond")
     if a.alternate > 0:
         import bench
         arms = {"eager": make_arm(False, False), "fused_step": make_arm(False, True), "graph": make_arm(True, False),
@@ -107,6 +138,7 @@ with torch.no_grad():
                 res[name].append(timed(run, a.steps)[1])
         print(json.dumps({"workload": workload, "steps": a.steps, "depth": a.depth, "alternations": a.alternate,
                           "arms": res, "bit_identical_to_eager": {n: bool(torch.equal(o, outs["eager"])) for n, o in outs.items()},
+                          "max_abs_diff_to_eager": {n: float((o - outs["eager"]).abs().max()) for n, o in outs.items()},
                           "gemm_shader_clock": bench.gemm_clock_probe(dev), "memory": bench.memory_probe(dev),
                           "status_word": qnn.check_status()}))
         sys.exit(0)

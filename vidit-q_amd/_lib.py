@@ -59,12 +59,17 @@ SIGNATURES = {
     "vq_cfg_ddim_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
     "vq_cfg_dpmpp_step": (_i, [_vp] * 7 + [_i, _i, _i, _l, _i, _i, _i, _i, _vp]),
     "vq_dpmpp_advance": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    "vq_cfg_ddpm_step": (_i, [_vp] * 8 + [_i, _i, _i, _l, _i, _i, _i, _i, _i, _vp]),
 }
 
 # the coefficient row of vq_cfg_dpmpp_step (include/viditq.h, VQ_DPMPP_*)
 DPMPP_ROW = 16
 (DPMPP_ORDER, DPMPP_TAYLOR, DPMPP_CFG, DPMPP_SIGMA, DPMPP_ALPHA, DPMPP_INV_ALPHA, DPMPP_X, DPMPP_M0, DPMPP_D1, DPMPP_D2,
  DPMPP_INV_R0, DPMPP_INV_R1, DPMPP_R0_FRAC, DPMPP_INV_R01, DPMPP_T_NEXT) = range(15)
+# the coefficient row of vq_cfg_ddpm_step (include/viditq.h, VQ_DDPM_*): the same size, the next time in the same slot
+DDPM_ROW = 16
+(DDPM_CFG, DDPM_A, DDPM_B, DDPM_C1, DDPM_C2, DDPM_MIN_LOG, DDPM_MAX_LOG, DDPM_NONZERO, DDPM_CLIP) = range(9)
+DDPM_T_NEXT = 14
 
 _lib = None
 

@@ -1,5 +1,6 @@
 // sampler.hip - the device-resident sampler steps for gfx950 (HBM-bound elementwise): fused classifier-free guidance +
-// DDIM(eta=0) update (STDiT loop), and further down guidance + x0 + DPM-Solver++ multistep update (PixArt loop).
+// DDIM(eta=0) update (STDiT loop), and further down guidance + x0 + DPM-Solver++ multistep update and guidance +
+// learned-range variance + ancestral (IDDPM) posterior step (PixArt loops).
 //
 // Replaces, for the first (kept) half of the duplicated batch, the tail of forward_with_cfg
 // (t2v/opensora/schedulers/iddpm/__init__.py:168-184: PTQD division, CFG on eps[:, :3] only) and
@@ -211,5 +212,120 @@ extern "C" int vq_dpmpp_advance(int32_t* step, const float* coef, int n_rows, fl
     if (!step || !coef || !t_out || n_rows <= 0 || n_t <= 0) return VQ_EINVAL;
     if (!dpm_aligned(step, 4) || !dpm_aligned(coef, 4) || !dpm_aligned(t_out, 4)) return VQ_ESHAPE;
     hipLaunchKernelGGL(dpmpp_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, step, coef, n_rows, t_out, n_t);
+    return vq_check_launch();
+}
+
+// ---- fused CFG + learned-range variance + ancestral posterior step (the PixArt IDDPM sampling loop) -----------------
+// One launch per model call of p_sample_loop(model.forward_with_cfg, ...): the tail of forward_with_cfg
+// (t2i/diffusion/model/nets/PixArtMS.py:221-234), p_mean_variance (t2i/diffusion/model/gaussian_diffusion.py:303-318),
+// _predict_xstart_from_eps (:363-368), q_posterior_mean_variance (:264-267) and p_sample (:439-445) for the kept first half
+// of the duplicated batch.  Row layout and contract: include/viditq.h (vq_cfg_ddpm_step).  As above nothing is contracted
+// and an fp16 model output gets the fp16 roundings of the eager tensors: c - u, cfg * (.), u + (.), v + 1, (.) * 0.5 and
+// 1 - frac; whatever meets a coefficient is fp32.  exp is the library expf.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_ddpm_kernel(const T* __restrict__ eps, const float* x,
+                                                       const float* __restrict__ noise, const float* __restrict__ coef,
+                                                       const int32_t* __restrict__ step, float* xo, float* x0o, void* xm,
+                                                       int xm_f16, int n, long inner, long CI, long ld_eps, int guided,
+                                                       int row, int n_rows) {
+#pragma clang fp contract(off)
+    int k = row + (step ? *step : 0);
+    k = k < 0 ? 0 : (k < n_rows - 1 ? k : n_rows - 1);          // a counter can never index outside the table
+    const float* r = coef + (long)k * VQ_DDPM_ROW;
+    const float cfg = r[VQ_DDPM_CFG], A = r[VQ_DDPM_A], B = r[VQ_DDPM_B], c1 = r[VQ_DDPM_C1], c2 = r[VQ_DDPM_C2];
+    const float min_log = r[VQ_DDPM_MIN_LOG], max_log = r[VQ_DDPM_MAX_LOG], nonzero = r[VQ_DDPM_NONZERO];
+    const bool clip = r[VQ_DDPM_CLIP] != 0.0f;
+    const long total = (long)n * CI;
+    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V; i < total; i += (long)gridDim.x * blockDim.x * V) {
+        const long bi = i / CI, ri = i - bi * CI;
+        const bool guide = ri / inner < guided;                  // V == 4 has inner % 4 == 0: a group lies in one channel
+        float c[V], u[V], v[V], xv[V], z[V], x0[V], out[V];
+        dpm_load<T, V>(eps + bi * ld_eps + ri, c);
+        dpm_load<T, V>(eps + bi * ld_eps + CI + ri, v);
+        if (guide) dpm_load<T, V>(eps + (bi + n) * ld_eps + ri, u);
+        dpm_load<float, V>(x + i, xv);
+        dpm_load<float, V>(noise + i, z);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float e = c[j], frac, rest;
+            if constexpr (std::is_same<T, half_t>::value) {
+                if (guide) {
+                    const half_t d = (half_t)(c[j] - u[j]);
+                    const half_t p = (half_t)(cfg * (float)d);
+                    e = (float)(half_t)(u[j] + (float)p);
+                }
+                const half_t v1 = (half_t)(v[j] + 1.0f);
+                const half_t f = (half_t)((float)v1 * 0.5f);
+                frac = (float)f;
+                rest = (float)(half_t)(1.0f - frac);
+            } else {
+                if (guide) {
+                    const float d = c[j] - u[j];
+                    const float p = cfg * d;
+                    e = u[j] + p;
+                }
+                const float v1 = v[j] + 1.0f;
+                frac = v1 * 0.5f;
+                rest = 1.0f - frac;
+            }
+            const float lmax = frac * max_log;
+            const float lmin = rest * min_log;
+            const float lv = lmax + lmin;
+            const float ax = A * xv[j];
+            const float be = B * e;
+            float p0 = ax - be;
+            if (clip) p0 = p0 < -1.0f ? -1.0f : (p0 > 1.0f ? 1.0f : p0);      // a NaN stays one, as torch.clamp leaves it
+            x0[j] = p0;
+            const float m1 = c1 * p0;
+            const float m2 = c2 * xv[j];
+            const float mean = m1 + m2;
+            const float h = 0.5f * lv;
+            const float s = expf(h);
+            const float ns = nonzero * s;
+            const float nz = ns * z[j];
+            out[j] = mean + nz;
+        }
+        dpm_store<float, V>(xo + i, out);
+        if (x0o) dpm_store<float, V>(x0o + i, x0);
+        if (xm) {
+            if (xm_f16) {
+                dpm_store<half_t, V>((half_t*)xm + i, out);
+                dpm_store<half_t, V>((half_t*)xm + total + i, out);
+            } else {
+                dpm_store<float, V>((float*)xm + i, out);
+                dpm_store<float, V>((float*)xm + total + i, out);
+            }
+        }
+    }
+}
+
+extern "C" int vq_cfg_ddpm_step(const void* eps, const float* x, const float* noise, const float* coef, const int32_t* step,
+                                float* x_out, float* x0_out, void* x_model, int n, int C, int inner, long ld_eps, int guided,
+                                int row, int n_rows, int eps_f16, int xm_f16, void* stream) {
+    if (!eps || !x || !noise || !coef || !x_out || n <= 0 || C <= 0 || inner <= 0 || n_rows <= 0 || row < 0 ||
+        row >= n_rows || guided < 0)
+        return VQ_EINVAL;
+    const long CI = (long)C * inner;
+    if (ld_eps < 2 * CI || guided > C) return VQ_ESHAPE;
+    const int V = inner % 4 == 0 ? 4 : 1;
+    const bool e16 = eps_f16 == 1, m16 = xm_f16 == 1;            // (a flag outside {0, 1} is refused below, after the shapes)
+    if (ld_eps % V != 0 || !dpm_aligned(eps, (e16 ? 2 : 4) * V) || !dpm_aligned(x, 4 * V) || !dpm_aligned(noise, 4 * V) ||
+        !dpm_aligned(x_out, 4 * V) || !dpm_aligned(x0_out, 4 * V) || !dpm_aligned(x_model, (m16 ? 2 : 4) * V) ||
+        !dpm_aligned(coef, 4) || !dpm_aligned(step, 4))
+        return VQ_ESHAPE;
+    if (eps_f16 < 0 || eps_f16 > 1 || xm_f16 < 0 || xm_f16 > 1) return VQ_EUNSUP;
+    const long total = (long)n * CI;
+    long blocks = ((total + V - 1) / V + 255) / 256;
+    if (blocks > 1024) blocks = 1024;                            // as vq_cfg_dpmpp_step: larger latents loop
+#define VQ_DDPM_LAUNCH(T_, V_)                                                                                         \
+    hipLaunchKernelGGL((cfg_ddpm_kernel<T_, V_>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,           \
+                       (const T_*)eps, x, noise, coef, step, x_out, x0_out, x_model, xm_f16, n, (long)inner, CI, ld_eps, \
+                       guided, row, n_rows)
+    if (e16) {
+        if (V == 4) VQ_DDPM_LAUNCH(half_t, 4); else VQ_DDPM_LAUNCH(half_t, 1);
+    } else {
+        if (V == 4) VQ_DDPM_LAUNCH(float, 4); else VQ_DDPM_LAUNCH(float, 1);
+    }
+#undef VQ_DDPM_LAUNCH
     return vq_check_launch();
 }

@@ -285,3 +285,66 @@ class DPMStepGraph:
             if step_callback is not None:
                 step_callback(k + 1, self.x.clone())
         return self.x.clone()
+
+
+class DDPMStepGraph:
+    """The fused IDDPM loop of t2i/iddpm.py as ONE captured step, as DPMStepGraph is for DPM-Solver++: {forward(x_model, t,
+    y, mask), ops.cfg_ddpm_step(step=counter), ops.dpmpp_advance} recorded once as a linear chain and replayed for every
+    timestep.  The step's noise lives in a static buffer of the duplicated shape, which ``run`` refills eagerly before each
+    replay - from ``noise_steps`` or with the draw the eager-launched loop makes - so a replay is bit-identical to that
+    loop.  A forward that moves host-visible state (a running smooth-quant statistic) is refused."""
+
+    def __init__(self, fn, y, mask, kwargs, x, rows, t_first: float, model_dtype=torch.float32, guided: int = 3,
+                 warmup: int = 2):
+        from . import ops
+        from ._lib import VQError
+        if GraphedModel(fn)._state(kwargs.get("timestep_id"))[2]:
+            raise VQError("DDPMStepGraph: a layer keeps a running smooth-quant statistic; its forward is not capturable")
+        n = x.shape[0]
+        dev = x.device
+        self.steps, self.t_first = rows.shape[0], float(t_first)
+        self.rows = rows.to(dev)
+        self.x = x.float().contiguous().clone()
+        self.x0 = torch.empty_like(self.x)
+        self.xm = torch.cat([self.x, self.x]).to(model_dtype)
+        self.noise = torch.zeros((2 * n,) + tuple(x.shape[1:]), dtype=torch.float32, device=dev)
+        self.t = torch.full((2 * n,), self.t_first, dtype=torch.float32, device=dev)
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+
+        def one():
+            eps = fn(self.xm, self.t, y, mask, **kwargs)
+            if not ops.cfg_ddpm_step_ok(eps, self.x):
+                raise VQError("DDPMStepGraph: vq_cfg_ddpm_step does not take this model output")
+            ops.cfg_ddpm_step(eps, self.x, self.noise[:n], self.rows, 0, step=self.step, x_out=self.x, x0_out=self.x0,
+                              x_model=self.xm, guided=guided)
+            ops.dpmpp_advance(self.step, self.rows, self.t)
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(warmup + 1):                  # packs weights, fills the host-side caches
+                one()
+            side.synchronize()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+            one()
+
+    @torch.no_grad()
+    def run(self, x, noise_steps=None, generator=None, step_callback=None):
+        """``x``: the duplicated start latent [2n, ...] (its first half is read) -> ``cat([x, x])`` of the sample."""
+        n = self.x.shape[0]
+        self.x.copy_(x[:n])
+        self.xm[:n].copy_(x[:n])
+        self.xm[n:].copy_(x[:n])
+        self.t.fill_(self.t_first)
+        self.step.zero_()
+        for k in range(self.steps):
+            if noise_steps is not None:
+                self.noise.copy_(noise_steps[k])
+            else:
+                self.noise.normal_(generator=generator)
+            self.graph.replay()
+            if step_callback is not None:
+                step_callback(self.steps - 1 - k, self.x.clone(), self.x0.clone())
+        return torch.cat([self.x, self.x])

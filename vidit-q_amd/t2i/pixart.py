@@ -44,6 +44,9 @@ def get_2d_sincos_pos_embed(embed_dim, grid_size, pe_interpolation=1.0, base_siz
     return np.concatenate([emb_h, emb_w], axis=1)
 
 
+CFG_GUIDED_CHANNELS = 3          # forward_with_cfg guides eps[:, :3] (PixArt.py:193, PixArtMS.py:230)
+
+
 class PatchEmbed(nn.Module):
     def __init__(self, patch_size=2, in_chans=4, embed_dim=1152, bias=True):
         super().__init__()
@@ -351,8 +354,12 @@ class _PixArtBase(nn.Module):
         """PixArt.py:183-196: one batched (cond | uncond) forward, guidance on the first three channels."""
         half = x[: len(x) // 2]
         combined = torch.cat([half, half], dim=0)
-        model_out = self.forward(combined, timestep, y, mask, **kwargs)
-        eps, rest = model_out[:, :3], model_out[:, 3:]
+        return self.guide_cfg(self.forward(combined, timestep, y, mask, **kwargs), cfg_scale)
+
+    @staticmethod
+    def guide_cfg(model_out, cfg_scale):
+        """The tail of forward_with_cfg on the (cond | uncond) output of one forward (PixArt.py:192-196)."""
+        eps, rest = model_out[:, :CFG_GUIDED_CHANNELS], model_out[:, CFG_GUIDED_CHANNELS:]
         cond_eps, uncond_eps = torch.split(eps, len(eps) // 2, dim=0)
         half_eps = uncond_eps + cfg_scale * (cond_eps - uncond_eps)
         eps = torch.cat([half_eps, half_eps], dim=0)
