@@ -325,6 +325,29 @@ int vq_gemm_i8_rowquant_static(const int8_t* xq, const float* sx, const int32_t*
                                int M, int N, int K, int Kp, int Kp_out, int w_bits, int n_bits,
                                int variant, void* stream);
 
+/* cross_attn.q_linear AND cross attention against the prompt's keys in ONE launch: the GEMM's 256 x 288 tile is 256 queries
+ * x 4 heads of 72, the keys are <= 128 prompt tokens, so a workgroup holds everything its (query, head) pairs need and the
+ * attention runs in the GEMM's epilogue.  Replaces F.linear(x_hat, W_hat, bias) (qdiff/models/quant_layer.py:211) +
+ * xformers memory_efficient_attention with a block-diagonal mask (opensora/models/layers/blocks.py:302-304).  q [M, N] is
+ * never written.
+ * xq .. bias, M, N, K, Kp, w_bits: as vq_gemm_i8 (VQ_EPI_NONE; 8-bit and nibble weight storage).
+ * k, v, o, n_seq, Lq, Lk, H, D, kv_*_stride, o_*_stride, kv_off, scale: as vq_attn_fwd, q being the GEMM's output: row
+ *   i * Lq + t of the GEMM is token t of sequence i, its columns h * D .. h * D + D - 1 head h.
+ * Contract: o is bit-identical to vq_gemm_i8(..., VQ_EPI_NONE, VQ_GEMM_DEFAULT) into a dense [M, N] buffer followed by
+ *   vq_attn_fwd on it.
+ * Shapes (VQ_ESHAPE otherwise, nothing launched): M % 256 == 0, N == H * D with N % 288 == 0, M == n_seq * Lq with
+ *   Lq % 256 == 0 (every 256-row tile inside one sequence), Kp % 128 == 0, Kp >= K, K <= 16384, operand images below
+ *   2^32 bytes, 0 < Lk <= 128 (with kv_off: the caller's bound on every sequence's key count), Lk * kv_tok_stride below
+ *   2^30, strides multiples of 8 with kv_tok_stride >= D and o_tok_stride >= N, xq, wq, k, v, o 16-byte aligned.
+ *   VQ_EUNSUP: D != 72, w_bits outside 2..8.  VQ_EINVAL: a null required pointer (all but bias, kv_off), a non-positive
+ *   extent.  All checks come before any HIP call or dereference. */
+int vq_gemm_i8_cross_attn(const int8_t* xq, const float* sx, const int32_t* zx, const int32_t* R, const void* wq,
+                          const float* sw, const int32_t* zw, const int32_t* cs, const float* bias,
+                          const void* k, const void* v, void* o,
+                          int M, int N, int K, int Kp, int w_bits, int n_seq, int Lq, int Lk, int H, int D,
+                          long kv_seq_stride, long kv_tok_stride, long o_seq_stride, long o_tok_stride,
+                          const int32_t* kv_off, float scale, void* stream);
+
 /* ---- fp16 attention (fp32 online softmax) -----------------------------------
  * Replaces flash_attn_func / the softmax branch of Attention.forward
  * (opensora/models/layers/blocks.py:169-187), xformers block-diagonal

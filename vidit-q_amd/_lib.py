@@ -44,6 +44,7 @@ SIGNATURES = {
     "vq_gemm_i8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp,
                         _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "vq_gemm_i8_rowquant_static": (_i, [_vp] * 17 + [_i] * 8 + [_vp]),
+    "vq_gemm_i8_cross_attn": (_i, [_vp] * 12 + [_i] * 10 + [_l] * 4 + [_vp, _f, _vp]),
     "vq_gemm_i8_stamped": (_i, [_vp] * 10 + [_i] * 5 + [_vp, _l, _vp]),
     "vq_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _l, _l, _l, _l, _vp, _f, _vp]),
     "vq_attn_fwd_route": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _l, _l, _l, _l, _vp, _f, _vp]),

@@ -40,8 +40,6 @@
 #include "attn_rowquant.h"
 #include "attn_tile.h"
 
-#define ATT_LOG2E 1.4426950408889634f
-
 template <int D>
 struct AttCfg {
     static constexpr int KS = (D + 15) / 16;       // QK^T k-steps (16 dims each)

@@ -10,6 +10,8 @@
 #include "vq_common.h"
 #include "attn_rowquant.h"
 
+#define ATT_LOG2E 1.4426950408889634f
+
 // The argument block of every vq_attn_fwd kernel (filled by attn_fwd_args of attention.hip); it lives here because the
 // geometry steps below take it.
 struct AttnArgs {

@@ -6,6 +6,7 @@
 #include <type_traits>
 #include "vq_common.h"
 #include "attn_rowquant.h"   // tq_isum4rows; rowquant_shared.h: rqs_grid / rqs_quant, the one copy of the static rounding rule
+#include "attn_tile.h"       // the attention steps of the cross-attention epilogue (ring_epilogue_cross)
 
 template <int BK>
 __device__ __forceinline__ int swz(int row) {
@@ -266,7 +267,9 @@ __device__ __forceinline__ float ring_dequant(int acc, float sx, int nzx, int Rm
 // wave-instruction, two waves per SIMD = the 6.5 k cycles the stamps show).  The integer form is exact; this one rounds
 // the three products separately - the terms are up to ~50 x the result, so outputs move by <= 2e-5 relative, 1/25 of
 // the fp16 rounding that follows (rel-L2 vs the fp32 reference unchanged, asserted by the GEMM tests).
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int PAD = 16, bool FP = false, int SROWS = 0>
+// STORE = false: the tile stays parked in the waves' slabs (every slab row one token, WTN halves) and nothing is stored -
+// the first step of ring_epilogue_cross, which consumes it there.
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int PAD = 16, bool FP = false, int SROWS = 0, bool STORE = true>
 __device__ __forceinline__ void ring_epilogue_interior(const GemmArgs& a, uint8_t* smem,
                                                        int4v (&acc)[BN / WAVES_N / 16][BM / WAVES_M / 16], int m0, int n0,
                                                        int tid) {
@@ -304,6 +307,7 @@ __device__ __forceinline__ void ring_epilogue_interior(const GemmArgs& a, uint8_
     constexpr int NH = (TM % 2 == 0 && NITER % 2 == 0 && ((WTM / 2) * CPR) % 64 == 0) ? 2 : 1;
     constexpr int TMH = TM / NH, NITH = NITER / NH;
     static_assert(!HALF_SLAB || (NH == 2 && SROWS == WTM / 2), "half slabs need the two half passes");
+    static_assert(STORE || (!HALF_SLAB && !HAS_RES), "a parked tile: whole slabs, no residual");
     // the residual operand: requested during the dequant phase (its HBM latency hides under the VALU work)
     half8 rres[HAS_RES ? NITH : 1];
     int pcc = cc0;
@@ -355,7 +359,7 @@ __device__ __forceinline__ void ring_epilogue_interior(const GemmArgs& a, uint8_
         // store pass of this half: the wave's slab rows as row-major 16-byte chunks (same wave wrote them: LDS
         // operations are in order)
 #pragma unroll
-        for (int it = 0; it < NITH; ++it) {
+        for (int it = 0; STORE && it < NITH; ++it) {
             half8 y = *reinterpret_cast<const half8*>(slab + so);
             if constexpr (HAS_RES) {
                 const half8 rr = rres[it];
@@ -712,6 +716,144 @@ __device__ __forceinline__ void ring_epilogue_quant(const GemmQArgs& a, uint8_t*
             const int row = idx / padc, c = idx - row * padc;
             if (INTERIOR || m0 + row < a.M)
                 *reinterpret_cast<int2v*>(a.qxq + ((size_t)(m0 + row) * a.Kp_out + a.N + c * 8)) = int2v{0, 0};
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Cross-attention epilogue (vq_gemm_i8_cross_attn): the tile is cross_attn.q_linear's output, and the workgroup holds
+// everything its (query, head) pairs need - a 256 x 288 tile is 256 queries x 4 heads of 72, a wave's 64 x 144 block
+// 2 heads x 2 blocks of 32 queries, and the keys are the prompt's <= 128 tokens - so attention runs here and q is never
+// written.  att_o is bit-identical to vq_gemm_i8(VQ_EPI_NONE) followed by vq_attn_fwd (attn_cross32_kernel<72, 8, 2>):
+//   1. the tile is dequantised, rounded to fp16 and parked in the waves' slabs by the one copy of that step
+//      (ring_epilogue_interior<STORE = false>, the expression of the plain epilogue);
+//   2. every wave reads its own slab rows back as the B-operand fragments of its 2 heads x 2 query blocks (attn_q_frags
+//      on a slab row: 80 VGPRs; the int32 accumulators are dead);
+//   3. workgroup barrier: slabs and ring are free.  K | V of a head travel by LDS-DMA as the two 64-key images of
+//      attn_cross32_kernel (AttnKvDma, zero fill past the last key, ones column by attn_fill_pad): 42 KiB per head, so
+//      four heads (168 KiB) do not fit the 160 KiB of a CU and three (126 KiB) do.  Two phases, one head per wave column
+//      each: slots A, B, C receive the tile's heads 0, 2, 1 at once; phase 0 runs heads 0 | 2 (wave columns 0 | 1) from
+//      A | B; behind it head 3 goes into A, and phase 1 runs heads 1 | 3 from C | A.  So of phase 1's two heads one is
+//      delivered under phase 0's arithmetic and the other has to wait for the slot phase 0 frees: a fourth slot is what
+//      LDS does not allow.
+//   4. a (head, 32-query block) unit is attn_cross32_kernel's walk of one query tile: the 32-key half tiles in order,
+//      the same steps of attn_tile.h, the same 32 queries per rescale decision (query blocks start at multiples of 32 of
+//      the sample's tokens in both kernels), attn_store_rows straight to att_o.
+// No spin, no atomics, no traffic between workgroups.
+// ---------------------------------------------------------------------------------------------------------------
+#define VQ_EPI_CROSS_ATTN 9
+struct GemmXArgs : GemmArgs {
+    AttnArgs at;           // k, v, o with their strides, kv_off, Lq (tokens per sample), Lk (<= 128), H, c; q unused
+};
+
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+__device__ __forceinline__ void ring_epilogue_cross(const GemmArgs& a, const AttnArgs& at, uint8_t* smem,
+                                                    int4v (&acc)[BN / WAVES_N / 16][BM / WAVES_M / 16], int m0, int n0, int tid) {
+    constexpr int D = 72, NW = WAVES_M * WAVES_N;
+    constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
+    constexpr int HPW = WTN / D, QB = WTM / 32;                    // heads and 32-query blocks of a wave's block
+    static_assert(WTN % D == 0 && WTM % 32 == 0 && HPW == 2 && WAVES_N == 2, "two phases of one head per wave column");
+    // the image geometry of attn_cross32_kernel<72, 8, 2> (Att8Cfg<72, 8> of attention.hip)
+    constexpr int KS = (D + 15) / 16, DT = (D + 32) / 32, KROW = ((D / 8) | 1) * 16, VRB = 192;
+    constexpr int KT = 64, NT = 2, KTB = KT * KROW, VT = KT * VRB, SLOT = NT * (KTB + VT);
+    constexpr int ROWB = WTN * 2 + 16, SLAB = WTM * ROWB;          // the slabs of ring_epilogue_interior<PAD = 16>
+    static_assert(3 * SLOT <= NW * SLAB, "three head slots inside the vacated slabs");
+    static_assert(D * 2 + 2 <= VRB && DT * 64 <= VRB, "dims + ones column inside a row; every 32-dim tile readable");
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+    const int g = lane >> 5, l31 = lane & 31;
+
+    // 1. dequantise + park
+    ring_epilogue_interior<BM, BN, WAVES_M, WAVES_N, VQ_EPI_NONE, 16, true, 0, false>(a, smem, acc, m0, n0, tid);
+    // 2. q fragments of this wave's units from its own slab (same wave wrote it: LDS operations are in order)
+    half8 qf[HPW][QB][KS];
+    {
+        const uint8_t* slab = smem + wave * SLAB;
+#pragma unroll
+        for (int hh = 0; hh < HPW; ++hh)
+#pragma unroll
+            for (int b = 0; b < QB; ++b)
+                attn_q_frags<D>(reinterpret_cast<const half_t*>(slab + (b * 32 + l31) * ROWB + hh * D * 2), g, qf[hh][b]);
+#pragma unroll
+        for (int hh = 0; hh < HPW; ++hh)
+#pragma unroll
+            for (int b = 0; b < QB; ++b)
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[hh][b][ks]));   // read HERE, in front of the barrier
+    }
+    // 3. the slabs are free once every wave holds its fragments
+    attn_wg_barrier();
+    const int seq = __builtin_amdgcn_readfirstlane(m0 / at.Lq);    // all rows of the tile belong to one sample (launcher)
+    const int h0 = n0 / D;                                         // the tile's first head
+    const int strideB = (int)at.kv_tok_stride * 2;
+    AttnKvDma<D, NW, KT, KROW, VRB> dma;
+    dma.init(wave, lane, strideB);
+    const unsigned lds0 = attn_lds_addr(smem);
+    int kv_len = 0;
+    auto deliver = [&](int hl, int slot) __attribute__((always_inline)) {   // head h0 + hl -> slot
+        const half_t* kbase;
+        const half_t* vbase;
+        kv_len = attn_kv_base<D>(at, seq, h0 + hl, kbase, vbase, NT * KT);   // host guarantees <= 128
+        const unsigned nrec = kv_len > 0 ? (unsigned)(kv_len - 1) * (unsigned)strideB + D * 2 : 0u;
+#pragma unroll
+        for (int kt = 0; kt < NT; ++kt)
+            dma.template issue<true>(kbase, vbase, (unsigned)kt * (unsigned)KT * (unsigned)strideB, nrec,
+                                     lds0 + slot * SLOT + kt * KTB, lds0 + slot * SLOT + NT * KTB + kt * VT, wave);
+    };
+    deliver(0, 0);
+    deliver(2, 1);
+    deliver(1, 2);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) attn_fill_pad<D, VRB>(smem + s * SLOT + NT * KTB, NT * KT, tid, 64 * NW);
+    attn_wg_barrier();                                             // heads 0, 2, 1 have landed
+    const int nhalf = (kv_len + 31) / 32;                          // 32-key half tiles that hold keys (wave-uniform)
+    const int vtr0 = attn_vtr0<VRB>(lane, g);
+    half_t* otile = at.o + (long)seq * at.o_seq_stride + (long)(m0 - seq * at.Lq + wm * WTM + l31) * at.o_tok_stride + (h0 + wn * HPW) * D;
+#pragma unroll
+    for (int hh = 0; hh < HPW; ++hh) {
+        if (hh == 1) {
+            // every wave is done with phase 0: slot A takes head 3 (the LDS reads of phase 0 have returned - their MFMAs
+            // were issued; the stores of phase 0 stay in flight until the second barrier)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            deliver(3, 0);
+            attn_wg_barrier();
+        }
+        const int slot = hh == 0 ? wn : (wn == 0 ? 2 : 0);         // wave-uniform
+        const uint8_t* k_l = smem + slot * SLOT + l31 * KROW;
+        const uint8_t* v_l = smem + slot * SLOT + NT * KTB + vtr0;
+#pragma unroll
+        for (int b = 0; b < QB; ++b) {
+            float16v oacc[DT];
+            attn_zero(oacc);
+            float m_run = -INFINITY;
+#pragma nounroll
+            for (int hf = 0; hf < nhalf; ++hf) {                   // attn_cross32_kernel's walk of one query tile
+                float16v s;
+                const float16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                {
+                    half8 kf[KS];
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) kf[ks] = attn_frag<D, false>(k_l + hf * 32 * KROW, ks, g);
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks)
+                        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[hh][b][ks], ks == 0 ? zero16 : s, 0, 0, 0);
+                }
+                AttnVF vf[2 * DT];                                 // V^T fragments: requested here, they fly under the softmax
+#pragma unroll
+                for (int idx2 = 0; idx2 < 2 * DT; ++idx2) attn_vt_frag<DT, VRB>(v_l + hf * 32 * VRB, idx2, vf[idx2]);
+                if ((hf + 1) * 32 > kv_len) attn_mask(s, hf * 32, g, kv_len);   // wave-uniform: the ragged last half
+                const float mc = attn_lazy_rescale(attn_rowmax_swap(s), m_run, oacc, at.c);
+                half8 pf[2];
+                attn_exp_pack(s, at.c, mc, pf);
+#pragma unroll
+                for (int idx2 = 0; idx2 < 2 * DT; ++idx2)
+                    oacc[idx2 % DT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[idx2].v, pf[idx2 / DT], oacc[idx2 % DT], 0, 0, 0);
+            }
+            const float inv = attn_inv_row_sum<D>(oacc, l31);
+            attn_store_rows<D, DT>(oacc, inv, otile + (long)(b * 32) * at.o_tok_stride + hh * D, g, true);
         }
     }
 }

@@ -136,6 +136,39 @@ extern "C" int vq_gemm_i8_grouped(int ngroups, const int8_t* const* xq, const fl
     return launch_gemm_auto<false>(a, st, VQ_GEMM_DEFAULT);
 }
 
+// cross_attn.q_linear + cross attention against the prompt's <= 128 keys in ONE launch of the 256 x 288 interior tile with
+// the cross-attention epilogue (gemm_common.h, ring_epilogue_cross): q [M, N] is never written.  Replaces F.linear
+// (quant_layer.py:211) + the xformers block-diagonal attention of MultiHeadCrossAttention (blocks.py:302-304); o is
+// bit-identical to vq_gemm_i8(VQ_EPI_NONE) + vq_attn_fwd.  Every check comes before any HIP call or dereference.
+extern "C" int vq_gemm_i8_cross_attn(const int8_t* xq, const float* sx, const int32_t* zx, const int32_t* R, const void* wq,
+                                     const float* sw, const int32_t* zw, const int32_t* cs, const float* bias, const void* k,
+                                     const void* v, void* o, int M, int N, int K, int Kp, int w_bits, int n_seq, int Lq, int Lk,
+                                     int H, int D, long kv_seq_stride, long kv_tok_stride, long o_seq_stride, long o_tok_stride,
+                                     const int32_t* kv_off, float scale, void* stream) {
+    if (!xq || !sx || !zx || !R || !wq || !sw || !zw || !cs || !k || !v || !o) return VQ_EINVAL;
+    if (M <= 0 || N <= 0 || K <= 0 || n_seq <= 0 || Lq <= 0 || H <= 0 || Lk <= 0) return VQ_EINVAL;
+    // what vq_gemm_i8 refuses ...
+    if (Kp % 128 != 0 || Kp < K || K > 16384) return VQ_ESHAPE;
+    if ((long)M * Kp >= (1L << 32) || (long)N * Kp >= (1L << 32)) return VQ_ESHAPE;
+    if (w_bits < 2 || w_bits > 8) return VQ_EUNSUP;
+    // ... the tile: interior 256 x 288 tiles of 4 whole heads, every tile inside one sample
+    if (D != 72) return VQ_EUNSUP;
+    if (M % 256 != 0 || N % 288 != 0 || (long)N != (long)H * D || (long)M != (long)n_seq * Lq || Lq % 256 != 0) return VQ_ESHAPE;
+    // ... and the attention: resident images of <= 128 keys addressed with 32-bit byte offsets, 16-byte rows
+    if (Lk > 128 || (long)Lk * kv_tok_stride * 2 >= (1L << 31)) return VQ_ESHAPE;
+    if ((kv_tok_stride | kv_seq_stride | o_tok_stride | o_seq_stride) % 8 != 0 || kv_tok_stride < D || o_tok_stride < N) return VQ_ESHAPE;
+    if (((uintptr_t)xq | (uintptr_t)wq | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 != 0) return VQ_ESHAPE;
+    if (n_seq > 65535) return VQ_ESHAPE;
+    GemmXArgs a{};
+    static_cast<GemmArgs&>(a) = GemmArgs{xq, sx, zx, R, (const uint8_t*)wq, sw, zw, cs, bias, nullptr, nullptr, nullptr,
+                                         N, 1, M, N, K, Kp, VQ_EPI_NONE, 0};
+    a.at = AttnArgs{nullptr, (const half_t*)k, (const half_t*)v, (half_t*)o, 0, 0, kv_seq_stride, kv_tok_stride, o_seq_stride,
+                    o_tok_stride, kv_off, n_seq, Lq, Lk, H, scale * ATT_LOG2E};
+    hipStream_t st = (hipStream_t)stream;
+    if (w_bits <= 4) return launch_gemm_cross_attn<true>(a, st);
+    return launch_gemm_cross_attn<false>(a, st);
+}
+
 // R[0, n) = 0 in front of a quantizing launch (every wave adds its columns' part of a row's term).  A kernel, not
 // hipMemsetAsync: a memset node captured into a graph took effect in no replay (attention.hip, attn_zero_rows_kernel).
 __global__ void gemm_zero_rows_kernel(int32_t* R, int n) {

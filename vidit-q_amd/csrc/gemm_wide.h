@@ -41,11 +41,14 @@ struct WideCfg {
     static_assert(LDS <= 163840, "LDS budget of one CU");
 };
 
-// Args: GemmArgs, or GemmQArgs with EPI = VQ_EPI_GELU_QUANT (the quantizing epilogue, ring_epilogue_quant)
+// Args: GemmArgs, or GemmQArgs with EPI = VQ_EPI_GELU_QUANT (the quantizing epilogue, ring_epilogue_quant), or GemmXArgs with
+// EPI = VQ_EPI_CROSS_ATTN (the cross-attention epilogue, ring_epilogue_cross: interior form of the 256 x 288 tile only)
 template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool W4, bool STAMP = false, int INT = 0, class Args = GemmArgs>
 __device__ __forceinline__ void gemm_i8_wide_tile(const Args a0, const int vb, const int tid_) {
     constexpr bool QUANT = EPI == VQ_EPI_GELU_QUANT;
     static_assert(QUANT == std::is_same<Args, GemmQArgs>::value && !(QUANT && (W4 || STAMP)), "the quantizing epilogue: 8-bit weights");
+    constexpr bool CROSS = EPI == VQ_EPI_CROSS_ATTN;
+    static_assert(CROSS == std::is_same<Args, GemmXArgs>::value && !(CROSS && (STAMP || INT == 0)), "the cross-attention epilogue: interior tiles");
     using Cfg = WideCfg<BM, BN, WAVES_M, WAVES_N, W4>;
     constexpr int NW = Cfg::NW;
     constexpr bool ASYM = INT != 0;                   // one issuing wave per SIMD
@@ -97,7 +100,9 @@ __device__ __forceinline__ void gemm_i8_wide_tile(const Args a0, const int vb, c
     };
     // virtual block id -> the arguments of its problem (batched / grouped launches) and its tile
     auto select = [&](GemmArgs& a, int vb, TileSrc& t) {
-        if (a.nbatch > 1) {                            // batch-major grid: weight set = vb / tiles
+        // (the cross-attention form is one problem per launch: with the arms below compiled in, its larger argument block
+        //  stayed in scratch behind the groups' indexed selects and every DMA offset became a vector value)
+        if (!CROSS && a.nbatch > 1) {                  // batch-major grid: weight set = vb / tiles
             const int bt = vb / (MT_ * NT_);
             vb -= bt * (MT_ * NT_);
             a.wq += (size_t)bt * a.bs_w;
@@ -106,7 +111,7 @@ __device__ __forceinline__ void gemm_i8_wide_tile(const Args a0, const int vb, c
             a.cs += (size_t)bt * a.bs_ch;
             if (a.bias) a.bias += (size_t)bt * a.bs_ch;
             a.out += (size_t)bt * a.bs_out;
-        } else if (a.ngroups > 1) {                    // group-major grid; uniform selects, no indexed copy of the args
+        } else if (!CROSS && a.ngroups > 1) {          // group-major grid; uniform selects, no indexed copy of the args
             const int g = vb / (MT_ * NT_);
             vb -= g * (MT_ * NT_);
             if (g > 0) {
@@ -198,7 +203,8 @@ __device__ __forceinline__ void gemm_i8_wide_tile(const Args a0, const int vb, c
     };
     const int nkt = a0.Kp / 128;
 
-    Args a = a0;
+    // (the cross-attention form keeps its attention block in the kernel arguments: only the GEMM's part is a tile's own copy)
+    typename std::conditional<CROSS, GemmArgs, Args>::type a = a0;
     TileSrc src;
     select(a, vb, src);
     if constexpr (INT == 0) {
@@ -321,6 +327,8 @@ __device__ __forceinline__ void gemm_i8_wide_tile(const Args a0, const int vb, c
     __syncthreads();
     if constexpr (QUANT) {
         ring_epilogue_quant<BM, BN, WAVES_M, WAVES_N, INT != 0>(a, smem, acc, src.m0, src.n0, tid);
+    } else if constexpr (CROSS) {
+        ring_epilogue_cross<BM, BN, WAVES_M, WAVES_N>(a, a0.at, smem, acc, src.m0, src.n0, tid);
     } else {
         // (INT != 0: the launcher has checked what the interior epilogue needs for every tile - launch_gemm_wide_e)
         ring_epilogue<BM, BN, WAVES_M, WAVES_N, EPI, 16, true, 0, INT != 0 && !STAMP>(a, smem, acc, src.m0, src.n0, ts, tid,
@@ -337,6 +345,23 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_i8_wide_kernel(Gem
 template <int BM, int BN, int WAVES_M, int WAVES_N, int INT>
 __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_i8_wide_quant_kernel(GemmQArgs a) {
     gemm_i8_wide_tile<BM, BN, WAVES_M, WAVES_N, VQ_EPI_GELU_QUANT, false, false, INT>(a, blockIdx.x, threadIdx.x);
+}
+
+// the 256 x 288 interior tile with the cross-attention epilogue (vq_gemm_i8_cross_attn): 8-bit and nibble weights
+template <bool W4>
+__global__ __launch_bounds__(512) void gemm_i8_cross_attn_kernel(GemmXArgs a) {
+    gemm_i8_wide_tile<256, 288, 4, 2, VQ_EPI_CROSS_ATTN, W4, false, 1>(a, blockIdx.x, threadIdx.x);
+}
+
+template <bool W4>
+static int launch_gemm_cross_attn(const GemmXArgs& a, hipStream_t st) {
+    using Cfg = WideCfg<256, 288, 4, 2, W4>;
+    constexpr size_t LDS = Cfg::LDS;
+    if (a.M % 256 != 0 || a.N % 288 != 0) return VQ_ESHAPE;                 // interior tiles only
+    constexpr auto k = gemm_i8_cross_attn_kernel<W4>;
+    if (const int rc = vq_prepare_kernel<k>((int)LDS)) return rc;
+    hipLaunchKernelGGL(k, dim3((a.M / 256) * (a.N / 288)), dim3(512), LDS, st, a);
+    return vq_check_launch();
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int INT>

@@ -618,6 +618,33 @@ def gemm_i8_rowquant_static(a: QAct, w: PackedWeight, bias: Optional[torch.Tenso
     return QAct(xq, sx, zx, R, N, n_bits)
 
 
+def gemm_i8_cross_attn(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor], k: torch.Tensor, v: torch.Tensor,
+                       o: torch.Tensor, n_seq: int, Lq: int, Lk: int, H: int, D: int, kv_seq_stride: int, kv_tok_stride: int,
+                       o_seq_stride: int, o_tok_stride: int, kv_off: Optional[torch.Tensor] = None,
+                       scale: Optional[float] = None) -> torch.Tensor:
+    """cross_attn.q_linear's GEMM and cross attention against the prompt's <= 128 keys in ONE launch that never writes q:
+    ``o`` is, bit for bit, what ``attn_fwd(gemm_i8(a, w, bias), k, v, o, n_seq, Lq, Lk, H, D, Lq * N, N, ...)`` writes.
+    Shapes the entry point refuses (include/viditq.h) raise: callers choose the route before they launch."""
+    for t, n in ((a.xq, "a.xq"), (w.wq, "w.wq")):
+        if not t.is_cuda:
+            raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % n)
+    for t, n in ((k, "k"), (v, "v"), (o, "o")):
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise VQError("%s must be a GPU fp16 tensor" % n)
+    if a.K != w.K or a.Kp != w.Kp:
+        raise VQError("K mismatch: activation %d/%d weight %d/%d" % (a.K, a.Kp, w.K, w.Kp))
+    if bias is not None:
+        _req(bias, torch.float32, "bias")
+    if kv_off is not None:
+        _req(kv_off, torch.int32, "kv_off")
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    check(_L().vq_gemm_i8_cross_attn(_p(a.xq), _p(a.sx), _p(a.zx), _p(a.R), _p(w.wq), _p(w.sw), _p(w.zw), _p(w.cs), _p(bias),
+                                     _p(k), _p(v), _p(o), a.rows, w.N, a.K, a.Kp, w.n_bits, n_seq, Lq, Lk, H, D,
+                                     kv_seq_stride, kv_tok_stride, o_seq_stride, o_tok_stride, _p(kv_off), scale, _stream()),
+          "vq_gemm_i8_cross_attn")
+    return o
+
+
 def gemm_i8_stamped(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor] = None):
     """Diagnostics: ONE launch of the default 8-bit GEMM (256 x 288 tile, plain epilogue) with per-wave stamps.
     -> (out [M, N] fp16, stamps [tiles, 8, 10] int64: 0-6 shader cycles per phase boundary, 7 / 8 the chip's 100 MHz wall

@@ -356,6 +356,7 @@ _STATIC_FWD_ATTN_QUANT = _switch("VQ_STATIC_FWD_ATTN_QUANT", False)
 _STATIC_GEMM_QUANT = _switch("VQ_STATIC_GEMM_QUANT", False)           # fc1's GEMM + fc2's static quantizer
 _RUNNING_SMOOTH_DEVICE = _switch("VQ_RUNNING_SMOOTH_DEVICE", False)   # a running statistic on mlp.fc2, on the device
 EXACT_KV_EPS_FILL = _switch("VQ_EXACT_KV_EPS_FILL", True)             # the reference's global eps fill of the prompt's K / V
+_CROSS_Q_FUSED = _switch("VQ_CROSS_Q_FUSED", True)                    # cross attention inside q_linear's GEMM (q never written)
 
 
 # ---- what a quantizer is, asked in one place each
@@ -560,13 +561,55 @@ def attn_proj_stage(proj, r, x2, B, N, fused, plain, att_o, gate=None):
     return att_o
 
 
+def _cross_q_fused_shape(H, D, K, B, N, bound=None) -> bool:
+    """What vq_gemm_i8_cross_attn takes (include/viditq.h), in plain arithmetic - asked before any launch of the stage, so a
+    refused shape keeps today's order of launches: heads of 72 in whole 288-column tiles, 256-row tiles inside one sample,
+    operand images below 2^32 bytes and - once it is known - a bound of at most 128 keys per sample."""
+    C, Kp = H * D, (K + 127) // 128 * 128
+    return D == 72 and C % 288 == 0 and N > 0 and N % 256 == 0 and 0 < K <= 16384 and B * N * Kp < 1 << 32 and \
+        C * Kp < 1 << 32 and (bound is None or 0 < bound <= 128)
+
+
+# The fused launch is one 512-thread workgroup per 256 x 288 tile: it pays where its tiles fill whole rounds of the part's
+# 256 CUs (STDiT-XL/2's 16384 tokens: 256 tiles, 42.9 against 53.1 us; a joint forward, 512: 84.3 against 93.1) and loses
+# where most CUs stay idle (PixArt-alpha 512, 2 x 1024 tokens = 32 tiles: 33.4 against 24.4 us for the pair, whose GEMM takes
+# 128-row tiles there) - profiles/cross_q_fused/README.md.  Only whole rounds, the measured case, take the route.
+_CROSS_Q_FUSED_ROUND = 256
+
+
+def _cross_q_fused(ca, B, N) -> bool:
+    """Whether the cross stage runs attention inside q_linear's GEMM: the switch, the plain arm (proj's quantizer is not
+    served by the static fused attention launch), a shape the entry point takes and a tile count at which the launch was
+    measured faster than the pair; the prompt bound is asked again once K | V are there.  No launch and no call into
+    ``ops``."""
+    H, D = ca.core.num_heads, ca.core.head_dim
+    return _CROSS_Q_FUSED and not _static_fwd_attn_quant(ca.proj) and _cross_q_fused_shape(
+        H, D, ca.q_linear.in_features, B, N) and ((B * N // 256) * (H * D // 288)) % _CROSS_Q_FUSED_ROUND == 0
+
+
 def cross_stage(ca, r, x2, x3, B, N, y_lens, prompt_kv, att_o):
     """x += proj(attn(q_linear(x), K | V of the prompt))  (stdit.py:121, PixArtMS.py:77).  q_linear's quantizer and GEMM are
     launched first; ``prompt_kv()`` then hands over the caller's [sum_L, 2C] K | V (STDiT: batched over the blocks, cached, or
-    computed here; PixArt: computed here)."""
+    computed here; PixArt: computed here).  Where the fused launch applies (_cross_q_fused) the prompt's K | V are taken
+    FIRST and one launch runs q_linear's GEMM and the attention: q is never written."""
     ql, sv = ca.q_linear, _svec(ca.q_linear)
+    kv = None
+    if _cross_q_fused(ca, B, N):
+        kv = prompt_kv()
+        core = ca.core
+        C = core.num_heads * core.head_dim
+        bound = int(getattr(y_lens, "max_len", 0)) or kv.shape[0]
+        if _cross_q_fused_shape(core.num_heads, core.head_dim, ql.in_features, B, N, bound) and kv.stride(0) % 8 == 0:
+            def fused_q(o):
+                if o is None:
+                    o = torch.empty((B * N, C), dtype=torch.float16, device=x3.device)
+                return ops.gemm_i8_cross_attn(ql.quantize_input(x3, sv), ql.packed_weight(_range_of(ql, r), sv), ql.bias_f32(),
+                                              kv, kv[:, C:], o, B, N, bound, core.num_heads, core.head_dim, 0, kv.stride(0),
+                                              N * o.stride(0), o.stride(0), kv_off=y_lens, scale=core.scale)
+            return attn_proj_stage(ca.proj, r, x2, B, N, lambda s: None, fused_q, att_o)
     q = ops.gemm_i8(ql.quantize_input(x3, sv), ql.packed_weight(_range_of(ql, r), sv), bias=ql.bias_f32())
-    kv = prompt_kv()
+    if kv is None:
+        kv = prompt_kv()
     return attn_proj_stage(
         ca.proj, r, x2, B, N,
         lambda s: fwd_attn_quantized_static(ca.proj, s, lambda d, z, nb, sm: ca.core.cross_quantized_static(
