@@ -1189,7 +1189,7 @@ def test_gemm_i8_batched_interior_shape_equals_general_form_launches(ops, dev, M
 def test_gemm_full_size_against_the_library_integer_matmul(ops, dev, N, K, w_bits):
     """BASELINE size (16384 tokens): the int32 contraction of the codes recomputed by the vendor library
     (torch._int_mm), the rank-one zero-point terms exact in int64 and the dequantisation in fp64 - an independent route
-    to the same numbers.  The kernel's epilogue (round 4: packed fp32, gemm_common.h ring_dequant<true>) evaluates
+    to the same numbers.  The kernel's epilogue (round 4: packed fp32, gemm_common.h ring_dequant) evaluates
     y = (sx sw) acc + (sx R)(sw (-zw)) + (sx (-zx))(sw cs) + b with one fp32 rounding per product / sum, so it may sit a
     few fp32 ulps OF THE LARGEST TERM away from the exactly rounded value before the fp16 rounding: per output at most
     one fp16 ulp plus that, on a few per cent of the outputs, and the rel-L2 distance from the un-rounded result stays
@@ -1246,7 +1246,7 @@ def test_gemm_stamped_launch_equals_the_plain_one_and_reads_a_sane_clock(ops, de
 
 @pytest.mark.parametrize("w_bits", [8, 4])
 def test_gemm_fp_dequant_under_adversarial_cancellation(ops, dev, w_bits):
-    """Round-4 advisor finding on the packed-fp32 epilogue (gemm_common.h ring_dequant<true>): y = (sx sw) acc + U P + V Q + b
+    """Round-4 advisor finding on the packed-fp32 epilogue (gemm_common.h ring_dequant): y = (sx sw) acc + U P + V Q + b
     rounds three products separately, so the error is a few fp32 ulps OF THE LARGEST TERM, not of the result.  Worst case
     built on purpose: post-GELU rows (min -0.17, long positive tail: zero point near 0, centred codes near -128, |R| large),
     all-positive weights (|cs| large), K = 4608 (|acc| beyond 2^24: float(acc) itself inexact).  The guaranteed bound -

@@ -4,7 +4,7 @@
 // launched on gfx950: the VGPR allocation is ONE number per kernel (the descriptor's granulated count), every wave of the
 // dispatch gets it, and three waves per SIMD allow at most 168 registers each (512 / 3, granule 8) - the 64 x 144 wave tile
 // alone holds 144 accumulators + 44 fragment registers.  What CAN be built, and is built here from the product's stages,
-// fragment rings and epilogue code (gemm_common.h), interior tiles of 8-bit weights only:
+// fragment rings and epilogue code (gemm_common_lab.h), interior tiles of 8-bit weights only:
 //   MODE 0 (dedicated loaders): 8 MFMA waves of 64 x 96 (TM 4, TN 6: 96 accumulators, <= 168 VGPRs) on a 256 x 192 block
 //           tile + 4 loader waves (one per SIMD) that own every `buffer_load ... lds` piece and its vmcnt; the MFMA waves see
 //           only the stage barrier.  Tests the hypothesis itself: does the main loop become MFMA-bound (768 cycles per

@@ -38,7 +38,7 @@
 // edge.
 #pragma once
 #include <utility>
-#include "../../vidit-q_amd/csrc/gemm_common.h"
+#include "gemm_common_lab.h"
 
 struct PPSchedBlock {
     int cnt[8];       // per-XCD: units handed out beyond the static first ones

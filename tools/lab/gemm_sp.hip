@@ -9,7 +9,7 @@
 // What no earlier overlap design did: no second workgroup, no second accumulator set, no role split between the
 // waves of a SIMD - same stages, same bytes per MAC as the non-persistent 256 x 192 tile (gemm_loader.hip mode 2).
 // 8-bit weights, interior tiles, K >= 1152 (nine stages: eight carry the previous tile's stores), epilogues none / resid /
-// gate*y + resid (gate folded).  Dequantisation = ring_dequant<true> (gemm_common.h), residual add = packed fp16: bit-identical
+// gate*y + resid (gate folded).  Dequantisation = ring_dequant<true> (gemm_common_lab.h), residual add = packed fp16: bit-identical
 // to the product kernel (checked by tools/gemm_sp.py).
 #include "gemm_wide_lab.h"
 

@@ -3,9 +3,9 @@
 // the full-line ring kernel (256 x 288 tile, 8 waves of 64 x 144; 128 x 288 with 32 x 144 wave tiles for
 // launches that would otherwise leave half the CUs without a workgroup); see csrc/gemm_i8.hip for the design notes.
 #pragma once
-#include "gemm_common.h"
+#include "gemm_common_lab.h"
 
-// dequantisation of the ring kernel's epilogue: 1 = packed fp32 form (gemm_common.h: ring_dequant<true>), 0 = the exact
+// dequantisation of the ring kernel's epilogue: 1 = packed fp32 form (gemm_common_lab.h: ring_dequant<true>), 0 = the exact
 // integer correction (the form of rounds 1-3; kept for A/B builds: -DVQ_GEMM_FP_DEQUANT=0)
 #ifndef VQ_GEMM_FP_DEQUANT
 #define VQ_GEMM_FP_DEQUANT true

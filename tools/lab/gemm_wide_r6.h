@@ -5,7 +5,7 @@
 // Product forms only (round 6): the measurement arms of rounds 1-5 (main-loop ablations, issuer / prefetch-distance / slab
 // switches, the twelve-wave tile) live in tools/lab/gemm_wide_lab.h and are compiled into tools/lab/libviditq_lab.so.
 #pragma once
-#include "gemm_common.h"
+#include "gemm_common_lab.h"
 
 // ---------------------------------------------------------------------------
 // Full-line ring kernel.  tools/dma_depth.py: the L2 -> LDS fill rate of a CU is bound by cache-line REQUESTS, not bytes:

@@ -17,7 +17,7 @@ VGPR_FORM = {"attention.hip", "gemm_i8.hip", "clock_probe.hip"}
 def _flags(src: str):
     env = os.environ.get("VQ_VGPR_FORM")
     vg = set(env.split(",")) if env is not None else VGPR_FORM
-    extra = os.environ.get("VQ_EXTRA_HIPCC_FLAGS", "").split()       # A/B builds (e.g. -DVQ_GEMM_FP_DEQUANT=0 into out_dir)
+    extra = os.environ.get("VQ_EXTRA_HIPCC_FLAGS", "").split()       # A/B builds (e.g. -DVQ_XCD_SM=4 -DVQ_XCD_SN=8 into out_dir)
     return FLAGS + (["-mllvm", "-amdgpu-mfma-vgpr-form"] if src in vg else []) + extra
 
 

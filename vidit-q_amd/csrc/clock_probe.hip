@@ -10,8 +10,7 @@ extern "C" int vq_gemm_i8_stamped(const int8_t* xq, const float* sx, const int32
                                   int ldo, int M, int N, int K, int Kp, void* stamps, long n_stamps, void* stream) {
     if (!xq || !sx || !zx || !R || !wq || !sw || !zw || !cs || !out || !stamps) return VQ_EINVAL;
     if (M <= 0 || N <= 0 || K <= 0) return VQ_EINVAL;
-    if (Kp % 128 != 0 || Kp < K || N % 4 != 0 || ldo % 4 != 0 || ldo < N) return VQ_ESHAPE;
-    if (K > 16384 || (long)M * Kp >= (1L << 32) || (long)N * Kp >= (1L << 32)) return VQ_ESHAPE;
+    if (vq_gemm_operand_check(M, N, K, Kp) != VQ_GEMM_OPS_OK || N % 4 != 0 || ldo % 4 != 0 || ldo < N) return VQ_ESHAPE;
     const long tiles = (long)((M + 255) / 256) * ((N + 287) / 288);
     if (n_stamps < tiles * 8 * 10) return VQ_ESHAPE;
     GemmArgs a{xq, sx, zx, R, (const uint8_t*)wq, sw, zw, cs, bias, (half_t*)out, nullptr,

@@ -1,17 +1,12 @@
 // gemm_common.h - shared pieces of the int8 GEMM kernels: argument block, XCD-aware tile map, per-tile dequant
-// parameter staging and the LDS-transposed store epilogue.  Included by csrc/gemm_i8.hip (product kernels) and by
-// tools/lab/gemm_lab.hip (retired kernel generations kept as measurement equipment).
+// parameter staging and the epilogues (plain, quantizing, cross-attention) of the kernels csrc/gemm_i8.hip ships.  Product
+// forms only: the retired kernel generations and what they needed of this header live in tools/lab/gemm_common_lab.h.
 #pragma once
 #include <stdlib.h>
 #include <type_traits>
 #include "vq_common.h"
 #include "attn_rowquant.h"   // tq_isum4rows; rowquant_shared.h: rqs_grid / rqs_quant, the one copy of the static rounding rule
 #include "attn_tile.h"       // the attention steps of the cross-attention epilogue (ring_epilogue_cross)
-
-template <int BK>
-__device__ __forceinline__ int swz(int row) {
-    return BK == 64 ? ((row >> 2) & 3) : ((row >> 1) & 7);
-}
 
 __device__ __forceinline__ float gelu_tanh_f(float x) {
     // nn.GELU(approximate='tanh'): 0.5*x*(1+tanh(u)), u = sqrt(2/pi)*(x+0.044715 x^3)
@@ -89,95 +84,70 @@ __device__ __forceinline__ void xcd_tile(int bid, int MT, int NTl, int& mt, int&
     nt = ng * SN + r2 / smr;
 }
 
-// ===========================================================================
-// v3 ("pipe"): 3-stage LDS-DMA ring + register-level fragment prefetch across k-tiles
-// ===========================================================================
-// Ablations of v2 (profiles/r01_notes.md) showed DMA, LDS fragment reads and MFMAs each cost ~0.9 us
-// per 64-byte k-tile and did NOT overlap: the 8 waves of the workgroup run in lockstep between
-// barriers, so "all read LDS", "all issue MFMA" and "all wait for the DMA" were serial phases.
-// Here every wave overlaps them itself:
-//   - fragment reads run TWO 4-MFMA groups ahead (W ring of 3 registers sets) and roll over into the
-//     NEXT k-tile (X fragments double-buffered), so LDS latency sits under the MFMAs;
-//   - ONE barrier per k-tile, placed after MFMA group 6 of 9: by then DMA(kt+1) (issued a full tile
-//     earlier) has landed and every wave has issued its last read of stage kt-1, so the same point
-//     re-issues DMA(kt+2) into that stage; the vmcnt(0) of the barrier only ever waits for a transfer
-//     that had a whole tile of MFMAs to complete.
-// Per-channel dequant parameters of a tile (sw, -zw, cs, bias): loaded into registers BEFORE the first DMA
-// batch is issued and parked in the LDS block behind the epilogue slabs AFTER it (PAR_OFF lies past the end
-// of every ring), so neither the load latency nor the staging sits on the critical path.
-struct ColParams1 {
+// ---------------------------------------------------------------------------------------------------------------
+// Epilogue layer.  After the main loop the workgroup's LDS holds, in this order (EpiGeom, the one place that knows):
+//   one fp16 slab per wave (its WTM x WTN block of the tile, row stride ROWB) | per-channel terms sw, P, Q, b (BN floats
+//   each) | per-token terms sx, V, U (BM floats each); the quantizing epilogue parks the consuming Linear's smoothing vector
+//   (s, 1/s) in the 8 * BN bytes in front of the channel terms.
+// The zero-point terms are parked as fp32 PRODUCTS with the scale - P = sw * (-zw), Q = sw * cs per channel, V = sx * (-zx),
+// U = sx * R per token - for the float form of the dequantisation (ring_dequant).
+// ---------------------------------------------------------------------------------------------------------------
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+struct EpiGeom {
+    static constexpr int NW = WAVES_M * WAVES_N, NT = 64 * NW;
+    static constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;   // a wave's block of the tile
+    static constexpr int TM = WTM / 16, TN = WTN / 16;             // ... in 16 x 16 accumulator quads
+    static constexpr int ROWB = WTN * 2 + 16;                      // slab row stride in bytes (16 B aligned; pad 16: 2-way write conflicts)
+    static constexpr int SLAB = WTM * ROWB;
+    static constexpr int PAR_OFF = NW * SLAB;                      // channel terms behind the slabs
+    static constexpr int ROW_OFF = PAR_OFF + 16 * BN;              // token terms behind them
+    static constexpr int QS_OFF = PAR_OFF - 8 * BN;                // smoothing vector in front of them
+    static constexpr int BYTES = ROW_OFF + 12 * BM;
+    static_assert(BN <= NT && BM <= NT, "one channel and one token row per thread");
+    static_assert(BYTES <= 163840, "LDS budget");
+};
+
+// Per-channel dequant parameters of a tile (sw, -zw, cs, bias) and per-token ones (sx, -zx, R): one channel and one token
+// row per thread, loaded into registers behind the main loop and parked in LDS as the terms above.
+struct ColParams {
     float sw, b;
     int nzw, cs;
 };
-// NPT = channels per thread: 1 for the 512-thread workgroups (288 channels), 2 for a 256-thread workgroup
-template <int NPT = 1>
-struct ColParamsT {
-    ColParams1 c[NPT];
-};
-using ColParams = ColParamsT<1>;
-template <int BN, int NT = 512>
-__device__ __forceinline__ ColParamsT<(BN + NT - 1) / NT> ring_load_col_params(const GemmArgs& a, int n0, int tid_in = -1,
-                                                                                const float* gate_row = nullptr) {
-    constexpr int NPT = (BN + NT - 1) / NT;
-    ColParamsT<NPT> r;
-    const int tx0 = tid_in >= 0 ? tid_in : (int)threadIdx.x;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-        ColParams1 c{0.f, 0.f, 0, 0};
-        const int tx = tx0 + u * NT;
-        const int gn = n0 + tx;
-        if (tx < BN && gn < a.N) {
-            c.sw = a.sw[gn];
-            c.nzw = -a.zw[gn];
-            c.cs = a.cs[gn];
-            c.b = a.bias ? a.bias[gn] : 0.f;
-            if (gate_row) {                            // gate * (sx*sw*t + b): folded into the per-channel terms
-                const float g = gate_row[gn];
-                c.sw *= g;
-                c.b *= g;
-            }
+template <int BN>
+__device__ __forceinline__ ColParams ring_load_col_params(const GemmArgs& a, int n0, int tx, const float* gate_row) {
+    ColParams c{0.f, 0.f, 0, 0};
+    const int gn = n0 + tx;
+    if (tx < BN && gn < a.N) {
+        c.sw = a.sw[gn];
+        c.nzw = -a.zw[gn];
+        c.cs = a.cs[gn];
+        c.b = a.bias ? a.bias[gn] : 0.f;
+        if (gate_row) {                                // gate * (sx*sw*t + b): folded into the per-channel terms
+            const float g = gate_row[gn];
+            c.sw *= g;
+            c.b *= g;
         }
-        r.c[u] = c;
     }
-    return r;
+    return c;
 }
-// FP (round 4): the zero-point terms are parked as fp32 PRODUCTS with the scale - P = sw * (-zw), Q = sw * cs per
-// channel, U = sx * R, V = sx * (-zx) per token - for the float form of the dequantisation (ring_dequant below).
-// SROWS: rows of a wave's epilogue slab when it is smaller than the wave tile (half slabs: the 12-wave lab kernel, whose full
-// slabs would not fit beside the parameter blocks); 0 = the whole wave tile.
-template <int BM, int BN, int WAVES_M, int WAVES_N, int PAD = 16, bool FP = false, int SROWS = 0, int NPT = 1>
-__device__ __forceinline__ void ring_park_col_params(const ColParamsT<NPT>& c, uint8_t* smem, int tid_in = -1) {
-    constexpr int NT = 64 * WAVES_M * WAVES_N, NW = WAVES_M * WAVES_N;
-    static_assert(BN <= NPT * NT, "NPT channels per thread");
-    constexpr int PAR_OFF = NW * (SROWS ? SROWS : BM / WAVES_M) * ((BN / WAVES_N) * 2 + PAD);
-    const int tx0 = tid_in >= 0 ? tid_in : (int)threadIdx.x;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) {
-        const int tx = tx0 + u * NT;
-        if (tx < BN) {
-            reinterpret_cast<float*>(smem + PAR_OFF)[tx] = c.c[u].sw;
-            if constexpr (FP) {
-                reinterpret_cast<float*>(smem + PAR_OFF)[BN + tx] = c.c[u].sw * (float)c.c[u].nzw;
-                reinterpret_cast<float*>(smem + PAR_OFF)[2 * BN + tx] = c.c[u].sw * (float)c.c[u].cs;
-            } else {
-                reinterpret_cast<int*>(smem + PAR_OFF)[BN + tx] = c.c[u].nzw;
-                reinterpret_cast<int*>(smem + PAR_OFF)[2 * BN + tx] = c.c[u].cs;
-            }
-            reinterpret_cast<float*>(smem + PAR_OFF)[3 * BN + tx] = c.c[u].b;
-        }
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+__device__ __forceinline__ void ring_park_col_params(const ColParams& c, uint8_t* smem, int tx) {
+    constexpr int PAR_OFF = EpiGeom<BM, BN, WAVES_M, WAVES_N>::PAR_OFF;
+    if (tx < BN) {
+        reinterpret_cast<float*>(smem + PAR_OFF)[tx] = c.sw;
+        reinterpret_cast<float*>(smem + PAR_OFF)[BN + tx] = c.sw * (float)c.nzw;
+        reinterpret_cast<float*>(smem + PAR_OFF)[2 * BN + tx] = c.sw * (float)c.cs;
+        reinterpret_cast<float*>(smem + PAR_OFF)[3 * BN + tx] = c.b;
     }
 }
 
-// Per-token dequant parameters (sx, -zx, R) of the tile's BM token rows travel the same way: one row per
-// thread, loaded before the first DMA batch, parked behind the channel block (BM * 12 bytes).
 struct RowParams {
     float sx;
     int nzx, R;
 };
 template <int BM>
-__device__ __forceinline__ RowParams ring_load_row_params(const GemmArgs& a, int m0, int tid_in = -1) {
+__device__ __forceinline__ RowParams ring_load_row_params(const GemmArgs& a, int m0, int tx) {
     RowParams r{0.f, 0, 0};
-    const int tx = tid_in >= 0 ? tid_in : (int)threadIdx.x;
     if (tx < BM) {
         const int m = m0 + tx;
         const int mc = m < a.M ? m : a.M - 1;
@@ -187,22 +157,13 @@ __device__ __forceinline__ RowParams ring_load_row_params(const GemmArgs& a, int
     }
     return r;
 }
-template <int BM, int BN, int WAVES_M, int WAVES_N, int PAD = 16, bool FP = false, int SROWS = 0>
-__device__ __forceinline__ void ring_park_row_params(const RowParams& r, uint8_t* smem, int tid_in = -1) {
-    constexpr int NT = 64 * WAVES_M * WAVES_N, NW = WAVES_M * WAVES_N;
-    static_assert(BM <= NT, "one token row per thread");
-    constexpr int ROW_OFF = NW * (SROWS ? SROWS : BM / WAVES_M) * ((BN / WAVES_N) * 2 + PAD) + 16 * BN;
-    static_assert(ROW_OFF + 12 * BM <= 163840, "LDS budget");
-    const int tx = tid_in >= 0 ? tid_in : (int)threadIdx.x;
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+__device__ __forceinline__ void ring_park_row_params(const RowParams& r, uint8_t* smem, int tx) {
+    constexpr int ROW_OFF = EpiGeom<BM, BN, WAVES_M, WAVES_N>::ROW_OFF;
     if (tx < BM) {
         reinterpret_cast<float*>(smem + ROW_OFF)[tx] = r.sx;
-        if constexpr (FP) {
-            reinterpret_cast<float*>(smem + ROW_OFF)[BM + tx] = r.sx * (float)r.nzx;
-            reinterpret_cast<float*>(smem + ROW_OFF)[2 * BM + tx] = r.sx * (float)r.R;
-        } else {
-            reinterpret_cast<int*>(smem + ROW_OFF)[BM + tx] = r.nzx;
-            reinterpret_cast<int*>(smem + ROW_OFF)[2 * BM + tx] = r.R;
-        }
+        reinterpret_cast<float*>(smem + ROW_OFF)[BM + tx] = r.sx * (float)r.nzx;
+        reinterpret_cast<float*>(smem + ROW_OFF)[2 * BM + tx] = r.sx * (float)r.R;
     }
 }
 
@@ -218,17 +179,6 @@ __device__ __forceinline__ const float* ring_tile_gate_row(const GemmArgs& a, in
     return s0 == s1 ? a.gate + (size_t)s0 * a.N : nullptr;
 }
 
-// Stage both parameter blocks (called once all fragment reads of the main loop are issued; the blocks lie
-// past the end of every ring, so no barrier is needed before writing them, only before reading them).
-template <int BM, int BN, int WAVES_M, int WAVES_N, int PAD = 16>
-__device__ __forceinline__ void ring_stage_params(const GemmArgs& a, uint8_t* smem, int m0, int n0, int tid_in = -1,
-                                                  const float* gate_row = nullptr) {
-    const auto colp = ring_load_col_params<BN, 64 * WAVES_M * WAVES_N>(a, n0, tid_in, gate_row);
-    const RowParams rowp = ring_load_row_params<BM>(a, m0, tid_in);
-    ring_park_col_params<BM, BN, WAVES_M, WAVES_N, PAD>(colp, smem, tid_in);
-    ring_park_row_params<BM, BN, WAVES_M, WAVES_N, PAD>(rowp, smem, tid_in);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Epilogue of an INTERIOR tile (all BM x BN outputs inside the matrix, N % 8 == 0, gate - if any - folded into the
 // staged scale / bias): the same arithmetic and the same LDS-transposed store pattern as ring_epilogue below, minus
@@ -241,43 +191,26 @@ __device__ __forceinline__ void ring_stage_params(const GemmArgs& a, uint8_t* sm
 // ---------------------------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(2))) _Float16 half2v;
 
-// One output of the dequantisation, y = sx sw (acc - zw R - zx cs) + b.
-//   FP = false: the correction exact in int32 - two v_mad_i32_i24 (|zw|, |zx| < 2^8, |R|, |cs| < 2^23; written as asm
-//               because the compiler otherwise emits 2 x v_mul_i32_i24 + v_add3_u32), one conversion, mul + fma;
-//   FP = true:  nzx / Rm / nzw / ics carry the BIT PATTERNS of the parked fp32 products V = sx (-zx), U = sx R,
-//               P = sw (-zw), Q = sw cs: y = (sx sw) float(acc) + (U P + (V Q + b)) - the compiler packs the four
-//               operations of neighbouring outputs into v_pk_mul_f32 / v_pk_fma_f32.
-template <bool FP>
-__device__ __forceinline__ float ring_dequant(int acc, float sx, int nzx, int Rm, float sw, int nzw, int ics, float b) {
-    if constexpr (FP) {
-        const float V = __builtin_bit_cast(float, nzx), U = __builtin_bit_cast(float, Rm);
-        const float P = __builtin_bit_cast(float, nzw), Q = __builtin_bit_cast(float, ics);
-        return __builtin_fmaf(sx * sw, (float)acc, __builtin_fmaf(U, P, __builtin_fmaf(V, Q, b)));
-    } else {
-        int t1, tt;
-        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(t1) : "v"(nzw), "v"(Rm), "v"(acc));
-        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(tt) : "v"(nzx), "v"(ics), "v"(t1));
-        return (sx * sw) * (float)tt + b;
-    }
+// One output of the dequantisation, y = sx sw (acc - zw R - zx cs) + b, in floating point on the parked products V = sx (-zx),
+// U = sx R, P = sw (-zw), Q = sw cs: y = (sx sw) float(acc) + (U P + (V Q + b)) - the compiler packs the four operations of
+// neighbouring outputs into v_pk_mul_f32 / v_pk_fma_f32: 1 conversion + 4 packed fp32 operations per PAIR of outputs, 3.5
+// VALU issue slots per output where the exact integer correction took 4.5, in a phase that is VALU-bound (144 outputs per
+// lane, 4 cycles per wave-instruction, two waves per SIMD = the 6.5 k cycles the stamps show).  The three products are rounded
+// separately - the terms are up to ~50 x the result, so outputs move by <= 2e-5 relative against the integer form, 1/25 of the
+// fp16 rounding that follows (rel-L2 vs the fp32 reference unchanged, asserted by the GEMM tests).
+__device__ __forceinline__ float ring_dequant(int acc, float sx, float V, float U, float sw, float P, float Q, float b) {
+    return __builtin_fmaf(sx * sw, (float)acc, __builtin_fmaf(U, P, __builtin_fmaf(V, Q, b)));
 }
 
-// FP: the dequantisation in floating point - y = (sx sw) acc + U P + V Q + b with the parked products (ring_park_*<FP>):
-// 1 conversion + 4 packed fp32 operations per PAIR of outputs instead of 2 x (2 v_mad_i32_i24 + conversion) + 2 packed
-// ones: 3.5 instead of 4.5 VALU issue slots per output in a phase that is VALU-bound (144 outputs per lane, 4 cycles per
-// wave-instruction, two waves per SIMD = the 6.5 k cycles the stamps show).  The integer form is exact; this one rounds
-// the three products separately - the terms are up to ~50 x the result, so outputs move by <= 2e-5 relative, 1/25 of
-// the fp16 rounding that follows (rel-L2 vs the fp32 reference unchanged, asserted by the GEMM tests).
 // STORE = false: the tile stays parked in the waves' slabs (every slab row one token, WTN halves) and nothing is stored -
 // the first step of ring_epilogue_cross, which consumes it there.
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int PAD = 16, bool FP = false, int SROWS = 0, bool STORE = true>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool STORE = true>
 __device__ __forceinline__ void ring_epilogue_interior(const GemmArgs& a, uint8_t* smem,
                                                        int4v (&acc)[BN / WAVES_N / 16][BM / WAVES_M / 16], int m0, int n0,
                                                        int tid) {
-    constexpr int NW = WAVES_M * WAVES_N;
-    constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
-    constexpr int TM = WTM / 16, TN = WTN / 16;
-    constexpr int ROWB = WTN * 2 + PAD, SLAB = (SROWS ? SROWS : WTM) * ROWB, PAR_OFF = NW * SLAB;
-    constexpr bool HALF_SLAB = SROWS != 0 && SROWS < WTM;   // the second half pass re-uses the slab rows of the first
+    using G = EpiGeom<BM, BN, WAVES_M, WAVES_N>;
+    constexpr int WTM = G::WTM, WTN = G::WTN, TM = G::TM, TN = G::TN;
+    constexpr int ROWB = G::ROWB, SLAB = G::SLAB, PAR_OFF = G::PAR_OFF;
     constexpr int CPR = WTN / 8, NCH = WTM * CPR, NITER = NCH / 64;
     constexpr int QS = 64 / CPR, RS = 64 % CPR;       // chunk c + 64: QS rows further (+1 on wrap), RS chunks to the right
     static_assert(NCH % 64 == 0 && CPR < 64, "whole passes");
@@ -287,12 +220,12 @@ __device__ __forceinline__ void ring_epilogue_interior(const GemmArgs& a, uint8_
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int frow = lane & 15, fc = lane >> 4;
     const float* l_sw = reinterpret_cast<const float*>(smem + PAR_OFF);
-    const int* l_nzw = reinterpret_cast<const int*>(smem + PAR_OFF) + BN;
-    const int* l_cs = reinterpret_cast<const int*>(smem + PAR_OFF) + 2 * BN;
+    const float* l_P = reinterpret_cast<const float*>(smem + PAR_OFF) + BN;
+    const float* l_Q = reinterpret_cast<const float*>(smem + PAR_OFF) + 2 * BN;
     const float* l_b = reinterpret_cast<const float*>(smem + PAR_OFF) + 3 * BN;
     const float* l_sx = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN);
-    const int* l_nzx = reinterpret_cast<const int*>(smem + PAR_OFF + 16 * BN) + BM;
-    const int* l_R = reinterpret_cast<const int*>(smem + PAR_OFF + 16 * BN) + 2 * BM;
+    const float* l_V = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN) + BM;
+    const float* l_U = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN) + 2 * BM;
     uint8_t* slab = smem + wave * SLAB;
     // wave-uniform byte bases of this wave's 64 x WTN output block; lane offsets stay 32-bit
     const size_t tile_off = ((size_t)(m0 + wm * WTM) * a.ldo + (n0 + wn * WTN)) * 2;
@@ -306,8 +239,7 @@ __device__ __forceinline__ void ring_epilogue_interior(const GemmArgs& a, uint8_
     // is dequantised, instead of all VALU work first and all stores after it.
     constexpr int NH = (TM % 2 == 0 && NITER % 2 == 0 && ((WTM / 2) * CPR) % 64 == 0) ? 2 : 1;
     constexpr int TMH = TM / NH, NITH = NITER / NH;
-    static_assert(!HALF_SLAB || (NH == 2 && SROWS == WTM / 2), "half slabs need the two half passes");
-    static_assert(STORE || (!HALF_SLAB && !HAS_RES), "a parked tile: whole slabs, no residual");
+    static_assert(STORE || !HAS_RES, "a parked tile: no residual");
     // the residual operand: requested during the dequant phase (its HBM latency hides under the VALU work)
     half8 rres[HAS_RES ? NITH : 1];
     int pcc = cc0;
@@ -319,13 +251,13 @@ __device__ __forceinline__ void ring_epilogue_interior(const GemmArgs& a, uint8_
         pgo += w ? step_g + wrap_g : step_g;
     };
     float sxm[TM];
-    int nzx[TM], Rm[TM];                              // (FP: the bit patterns of V = sx * (-zx) and U = sx * R)
+    float Vm[TM], Um[TM];                             // V = sx * (-zx), U = sx * R
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int rl = wm * WTM + i * 16 + frow;
         sxm[i] = l_sx[rl];
-        nzx[i] = l_nzx[rl];
-        Rm[i] = l_R[rl];
+        Vm[i] = l_V[rl];
+        Um[i] = l_U[rl];
     }
     int cc = cc0;
     uint32_t go = (uint32_t)(row0 * ldb + cc0 * 16), so = (uint32_t)(row0 * ROWB + cc0 * 16);
@@ -335,19 +267,19 @@ __device__ __forceinline__ void ring_epilogue_interior(const GemmArgs& a, uint8_
         for (int j = 0; j < TN; ++j) {
             const int nl = wn * WTN + j * 16 + 4 * fc;
             const float4v fsw_ = *reinterpret_cast<const float4v*>(l_sw + nl);
-            const int4v nzw = *reinterpret_cast<const int4v*>(l_nzw + nl);
-            const int4v ics = *reinterpret_cast<const int4v*>(l_cs + nl);
+            const float4v fP = *reinterpret_cast<const float4v*>(l_P + nl);
+            const float4v fQ = *reinterpret_cast<const float4v*>(l_Q + nl);
             const float4v fb = *reinterpret_cast<const float4v*>(l_b + nl);
 #pragma unroll
             for (int i = h * TMH; i < (h + 1) * TMH; ++i) {
                 half4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float y = ring_dequant<FP>(acc[j][i][e], sxm[i], nzx[i], Rm[i], fsw_[e], nzw[e], ics[e], fb[e]);
+                    float y = ring_dequant(acc[j][i][e], sxm[i], Vm[i], Um[i], fsw_[e], fP[e], fQ[e], fb[e]);
                     if constexpr (EPI == VQ_EPI_GELU) y = gelu_tanh_f(y);
                     o[e] = (half_t)y;
                 }
-                *reinterpret_cast<half4*>(slab + ((HALF_SLAB ? i - h * TMH : i) * 16 + frow) * ROWB + (j * 16 + 4 * fc) * 2) = o;
+                *reinterpret_cast<half4*>(slab + (i * 16 + frow) * ROWB + (j * 16 + 4 * fc) * 2) = o;
             }
             if constexpr (HAS_RES) {
                 constexpr int PER = (NITH + TN - 1) / TN;
@@ -376,41 +308,36 @@ __device__ __forceinline__ void ring_epilogue_interior(const GemmArgs& a, uint8_
             go += w ? step_g + wrap_g : step_g;
             so += w ? step_s + wrap_s : step_s;
         }
-        if constexpr (HALF_SLAB) so -= (uint32_t)((WTM / 2) * ROWB);   // (a half pass covers exactly WTM / 2 rows: cc is back at cc0)
     }
 }
 
-// Shared epilogue of the LDS-DMA ring kernels (called after a workgroup barrier; uses all of smem; the
-// parameter block must have been staged by ring_stage_params and made visible by that barrier).
+// Shared epilogue of the LDS-DMA ring kernels (called after the workgroup barrier that publishes the parked terms; uses all of
+// smem).
 // INTERIOR_ONLY: the launcher guarantees what the interior path needs for EVERY tile (interior tiles, 8-element aligned rows,
 // the gate folded into the staged scales) - the general path below is then not even compiled into the kernel: the resid
 // epilogues' 18 x 16-byte residual registers of that path were what put those kernels at 244 VGPRs (round 5).
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int PAD = 16, bool FP = false, int SROWS = 0, bool INTERIOR_ONLY = false>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool INTERIOR_ONLY>
 __device__ __forceinline__ void ring_epilogue(const GemmArgs& a, uint8_t* smem,
                                               int4v (&acc)[BN / WAVES_N / 16][BM / WAVES_M / 16], int m0, int n0,
-                                              long long* ts = nullptr, int tid_in = -1, bool gate_folded = false) {
+                                              long long* ts, int tid, bool gate_folded) {
     // gate_folded (workgroup-uniform): VQ_EPI_GATE_RESID with the gate already inside the staged scale / bias
-    // tid_in: the persistent kernel passes an opaque copy of threadIdx.x per tile so that the address arithmetic
-    // below is not hoisted out of its tile loop (and kept in registers through the main loop)
+    // ts: the stamped kernel's stamp block of this wave, else nullptr
     constexpr int NW = WAVES_M * WAVES_N;
     constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
     constexpr int TM = WTM / 16, TN = WTN / 16;
-    const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, lane = tid & 63;
+    const int lane = tid & 63;
     if constexpr ((BM / WAVES_M) * (BN / WAVES_N / 8) % 64 == 0) {
         if constexpr (INTERIOR_ONLY) {
-            ring_epilogue_interior<BM, BN, WAVES_M, WAVES_N, EPI, PAD, FP, SROWS>(a, smem, acc, m0, n0, tid);
+            ring_epilogue_interior<BM, BN, WAVES_M, WAVES_N, EPI>(a, smem, acc, m0, n0, tid);
             return;
         }
         // workgroup-uniform: every tile of the benchmark shapes is interior and takes the lean path
         const bool interior = m0 + BM <= a.M && n0 + BN <= a.N && (a.N & 7) == 0 && (a.ldo & 7) == 0 &&
                               (EPI != VQ_EPI_GATE_RESID || gate_folded);
         if (!ts && interior) {
-            ring_epilogue_interior<BM, BN, WAVES_M, WAVES_N, EPI, PAD, FP, SROWS>(a, smem, acc, m0, n0, tid);
+            ring_epilogue_interior<BM, BN, WAVES_M, WAVES_N, EPI>(a, smem, acc, m0, n0, tid);
             return;
         }
-    }
-    if constexpr (SROWS != 0 && SROWS < BM / WAVES_M) {   // half slabs exist for interior tiles only (lab kernels: the launcher checks)
-        __builtin_trap();
     }
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
@@ -421,16 +348,15 @@ __device__ __forceinline__ void ring_epilogue(const GemmArgs& a, uint8_t* smem,
     // parks its 64 x WTN fp16 sub-tile in its own LDS slab (row stride ROWB), then re-reads it as 16-byte
     // chunks in row-major order, so one store instruction covers contiguous WTN*2-byte runs of ~3.5 rows;
     // the residual / gate operands of the fused adds are read with the same coalesced pattern.
-    constexpr int ROWB = WTN * 2 + PAD;               // slab row stride in bytes (16 B aligned; PAD 16: 2-way write conflicts)
-    constexpr int SLAB = WTM * ROWB;
-    constexpr int PAR_OFF = NW * SLAB;                // per-channel parameter block behind the slabs
+    using G = EpiGeom<BM, BN, WAVES_M, WAVES_N>;
+    constexpr int ROWB = G::ROWB, SLAB = G::SLAB, PAR_OFF = G::PAR_OFF;
     const float* l_sw = reinterpret_cast<const float*>(smem + PAR_OFF);
-    const int* l_nzw = reinterpret_cast<const int*>(smem + PAR_OFF) + BN;
-    const int* l_cs = reinterpret_cast<const int*>(smem + PAR_OFF) + 2 * BN;
+    const float* l_P = reinterpret_cast<const float*>(smem + PAR_OFF) + BN;
+    const float* l_Q = reinterpret_cast<const float*>(smem + PAR_OFF) + 2 * BN;
     const float* l_b = reinterpret_cast<const float*>(smem + PAR_OFF) + 3 * BN;
     const float* l_sx = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN);
-    const int* l_nzx = reinterpret_cast<const int*>(smem + PAR_OFF + 16 * BN) + BM;
-    const int* l_R = reinterpret_cast<const int*>(smem + PAR_OFF + 16 * BN) + 2 * BM;
+    const float* l_V = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN) + BM;
+    const float* l_U = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN) + 2 * BM;
     uint8_t* slab = smem + wave * SLAB;
     if (ts) ts[3] = __builtin_readcyclecounter();
     constexpr int CPR = WTN / 8;                      // 16-byte chunks per slab row
@@ -460,27 +386,27 @@ __device__ __forceinline__ void ring_epilogue(const GemmArgs& a, uint8_t* smem,
     };
     {
         float sxm[TM];
-        int nzx[TM], Rm[TM];
+        float Vm[TM], Um[TM];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int rl = wm * WTM + i * 16 + frow;
             sxm[i] = l_sx[rl];
-            nzx[i] = l_nzx[rl];
-            Rm[i] = l_R[rl];
+            Vm[i] = l_V[rl];
+            Um[i] = l_U[rl];
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int nl = wn * WTN + j * 16 + 4 * fc;
             const float4v fsw_ = *reinterpret_cast<const float4v*>(l_sw + nl);
-            const int4v nzw = *reinterpret_cast<const int4v*>(l_nzw + nl);
-            const int4v ics = *reinterpret_cast<const int4v*>(l_cs + nl);
+            const float4v fP = *reinterpret_cast<const float4v*>(l_P + nl);
+            const float4v fQ = *reinterpret_cast<const float4v*>(l_Q + nl);
             const float4v fb = *reinterpret_cast<const float4v*>(l_b + nl);
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 half4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float y = ring_dequant<FP>(acc[j][i][e], sxm[i], nzx[i], Rm[i], fsw_[e], nzw[e], ics[e], fb[e]);
+                    float y = ring_dequant(acc[j][i][e], sxm[i], Vm[i], Um[i], fsw_[e], fP[e], fQ[e], fb[e]);
                     if constexpr (EPI == VQ_EPI_GELU) y = gelu_tanh_f(y);
                     o[e] = (half_t)y;
                 }
@@ -556,7 +482,7 @@ struct GemmQArgs : GemmArgs {
 };
 
 // The smoothing vector of a tile's BN columns travels like the channel parameters: one column per thread, loaded with them,
-// parked in the 8 * BN bytes in front of the parameter block.  The codes' slabs (below) end far in front of it.
+// parked in the 8 * BN bytes in front of the parameter block (EpiGeom::QS_OFF).  The codes' slabs (below) end far in front of it.
 struct SmoothParams {
     float s, r;
 };
@@ -571,8 +497,7 @@ __device__ __forceinline__ SmoothParams ring_load_smooth(const GemmQArgs& a, int
 }
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 __device__ __forceinline__ void ring_park_smooth(const GemmQArgs& a, const SmoothParams& p, uint8_t* smem, int tid) {
-    constexpr int QS_OFF = WAVES_M * WAVES_N * (BM / WAVES_M) * ((BN / WAVES_N) * 2 + 16) - 8 * BN;
-    static_assert(BN <= 64 * WAVES_M * WAVES_N, "one column per thread");
+    constexpr int QS_OFF = EpiGeom<BM, BN, WAVES_M, WAVES_N>::QS_OFF;
     if (a.qs && tid < BN) {
         reinterpret_cast<float*>(smem + QS_OFF)[tid] = p.s;
         reinterpret_cast<float*>(smem + QS_OFF)[BN + tid] = p.r;
@@ -593,7 +518,7 @@ __device__ __forceinline__ void ring_epilogue_quant(const GemmQArgs& a, uint8_t*
     constexpr int NW = WAVES_M * WAVES_N, NT = 64 * NW;
     constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
     constexpr int TM = WTM / 16, TN = WTN / 16;
-    constexpr int PAR_OFF = NW * WTM * (WTN * 2 + 16), QS_OFF = PAR_OFF - 8 * BN;
+    constexpr int PAR_OFF = EpiGeom<BM, BN, WAVES_M, WAVES_N>::PAR_OFF, QS_OFF = EpiGeom<BM, BN, WAVES_M, WAVES_N>::QS_OFF;
     constexpr int SLAB = WTM * WTN;
     constexpr int CPR = WTN / 16, NCH = WTM * CPR, NITER = (NCH + 63) / 64;
     static_assert(WTN % 16 == 0 && NW * SLAB <= QS_OFF, "whole chunks; slabs in front of the smoothing vector");
@@ -602,12 +527,12 @@ __device__ __forceinline__ void ring_epilogue_quant(const GemmQArgs& a, uint8_t*
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int frow = lane & 15, fc = lane >> 4;
     const float* l_sw = reinterpret_cast<const float*>(smem + PAR_OFF);
-    const int* l_nzw = reinterpret_cast<const int*>(smem + PAR_OFF) + BN;
-    const int* l_cs = reinterpret_cast<const int*>(smem + PAR_OFF) + 2 * BN;
+    const float* l_P = reinterpret_cast<const float*>(smem + PAR_OFF) + BN;
+    const float* l_Q = reinterpret_cast<const float*>(smem + PAR_OFF) + 2 * BN;
     const float* l_b = reinterpret_cast<const float*>(smem + PAR_OFF) + 3 * BN;
     const float* l_sx = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN);
-    const int* l_nzx = reinterpret_cast<const int*>(smem + PAR_OFF + 16 * BN) + BM;
-    const int* l_R = reinterpret_cast<const int*>(smem + PAR_OFF + 16 * BN) + 2 * BM;
+    const float* l_V = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN) + BM;
+    const float* l_U = reinterpret_cast<const float*>(smem + PAR_OFF + 16 * BN) + 2 * BM;
     const float* l_qs = reinterpret_cast<const float*>(smem + QS_OFF);
     uint8_t* slab = smem + wave * SLAB;
     const int mrow0 = m0 + wm * WTM, ncol0 = n0 + wn * WTN;
@@ -618,14 +543,14 @@ __device__ __forceinline__ void ring_epilogue_quant(const GemmQArgs& a, uint8_t*
     const bool smooth = a.qs != nullptr;              // kernel-uniform
 
     float sxm[TM];
-    int nzx[TM], Rm[TM];                              // (the bit patterns of V = sx * (-zx) and U = sx * R: ring_dequant<true>)
+    float Vm[TM], Um[TM];                             // V = sx * (-zx), U = sx * R
     uint32_t csum[TM];
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int rl = wm * WTM + i * 16 + frow;
         sxm[i] = l_sx[rl];
-        nzx[i] = l_nzx[rl];
-        Rm[i] = l_R[rl];
+        Vm[i] = l_V[rl];
+        Um[i] = l_U[rl];
         csum[i] = 0;
     }
     // one kernel-uniform branch on the code width and one on the smoothing vector around the whole phase
@@ -635,8 +560,8 @@ __device__ __forceinline__ void ring_epilogue_quant(const GemmQArgs& a, uint8_t*
         for (int j = 0; j < TN; ++j) {
             const int nl = wn * WTN + j * 16 + 4 * fc;
             const float4v fsw_ = *reinterpret_cast<const float4v*>(l_sw + nl);
-            const int4v nzw = *reinterpret_cast<const int4v*>(l_nzw + nl);
-            const int4v ics = *reinterpret_cast<const int4v*>(l_cs + nl);
+            const float4v fP = *reinterpret_cast<const float4v*>(l_P + nl);
+            const float4v fQ = *reinterpret_cast<const float4v*>(l_Q + nl);
             const float4v fb = *reinterpret_cast<const float4v*>(l_b + nl);
             float4v s4 = {1.f, 1.f, 1.f, 1.f}, r4 = {1.f, 1.f, 1.f, 1.f};
             if constexpr (SM_) {
@@ -649,7 +574,7 @@ __device__ __forceinline__ void ring_epilogue_quant(const GemmQArgs& a, uint8_t*
                 float x4[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float y = ring_dequant<true>(acc[j][i][e], sxm[i], nzx[i], Rm[i], fsw_[e], nzw[e], ics[e], fb[e]);
+                    float y = ring_dequant(acc[j][i][e], sxm[i], Vm[i], Um[i], fsw_[e], fP[e], fQ[e], fb[e]);
                     y = gelu_tanh_f(y);
                     x4[e] = (float)(half_t)y;         // the value VQ_EPI_GELU stores: the quantizer's input
                     if constexpr (SM_) x4[e] = rq_div_rcp(x4[e], s4[e], r4[e]);
@@ -756,7 +681,7 @@ __device__ __forceinline__ void ring_epilogue_cross(const GemmArgs& a, const Att
     // the image geometry of attn_cross32_kernel<72, 8, 2> (Att8Cfg<72, 8> of attention.hip)
     constexpr int KS = (D + 15) / 16, DT = (D + 32) / 32, KROW = ((D / 8) | 1) * 16, VRB = 192;
     constexpr int KT = 64, NT = 2, KTB = KT * KROW, VT = KT * VRB, SLOT = NT * (KTB + VT);
-    constexpr int ROWB = WTN * 2 + 16, SLAB = WTM * ROWB;          // the slabs of ring_epilogue_interior<PAD = 16>
+    constexpr int ROWB = EpiGeom<BM, BN, WAVES_M, WAVES_N>::ROWB, SLAB = EpiGeom<BM, BN, WAVES_M, WAVES_N>::SLAB;   // the waves' fp16 slabs
     static_assert(3 * SLOT <= NW * SLAB, "three head slots inside the vacated slabs");
     static_assert(D * 2 + 2 <= VRB && DT * 64 <= VRB, "dims + ones column inside a row; every 32-dim tile readable");
     const int lane = tid & 63;
@@ -765,7 +690,7 @@ __device__ __forceinline__ void ring_epilogue_cross(const GemmArgs& a, const Att
     const int g = lane >> 5, l31 = lane & 31;
 
     // 1. dequantise + park
-    ring_epilogue_interior<BM, BN, WAVES_M, WAVES_N, VQ_EPI_NONE, 16, true, 0, false>(a, smem, acc, m0, n0, tid);
+    ring_epilogue_interior<BM, BN, WAVES_M, WAVES_N, VQ_EPI_NONE, false>(a, smem, acc, m0, n0, tid);
     // 2. q fragments of this wave's units from its own slab (same wave wrote it: LDS operations are in order)
     half8 qf[HPW][QB][KS];
     {

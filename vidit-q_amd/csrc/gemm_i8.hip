@@ -42,17 +42,38 @@ static bool vq_half_tiles(int M, int N, int sets) {
 // kernel with asymmetric DMA issue (gemm_wide.h, INT 1: waves 0-3 issue every stage piece): `variant` 19, and the library's
 // own choice for such shapes - every Linear of the benchmarked STDiT / PixArt-Sigma configurations.  Bit-identical to the
 // general form (tested).
+// The tile form of a launch.  ldo and gate_rows are what the interior form's EPILOGUE needs beyond interior tiles: 8-element
+// aligned output rows, and - gate epilogue - rows_per_gate a multiple of the tile height, so that the gate folds into the
+// staged scales for every tile; an epilogue without output rows / without a gate passes 0.  VQ_ESHAPE: `variant` 19 on a
+// shape the interior form does not cover.
+struct GemmForm {
+    bool half, interior;
+};
+static int vq_gemm_form(int M, int N, int sets, int variant, int ldo, int gate_rows, GemmForm& f) {
+    f.half = variant == 16 || (variant == VQ_GEMM_DEFAULT && vq_half_tiles(M, N, sets));
+    const int bm = f.half ? 128 : 256;
+    const bool interior = M % bm == 0 && N % 288 == 0 && (ldo & 7) == 0 && gate_rows % bm == 0;
+    if (variant == 19 && !interior) return VQ_ESHAPE;          // (variant 19 is never a half tile)
+    f.interior = variant == 19 || (variant == VQ_GEMM_DEFAULT && interior);
+    return VQ_OK;
+}
+// go(tile height, INT) as integral constants
+template <class F>
+static int vq_gemm_dispatch_form(const GemmForm& f, F&& go) {
+    using H = std::integral_constant<int, 128>;
+    using T = std::integral_constant<int, 256>;
+    if (f.interior) return f.half ? go(H{}, std::integral_constant<int, 1>{}) : go(T{}, std::integral_constant<int, 1>{});
+    return f.half ? go(H{}, std::integral_constant<int, 0>{}) : go(T{}, std::integral_constant<int, 0>{});
+}
 template <bool W4>
 static int launch_gemm_auto(const GemmArgs& a, hipStream_t st, int variant) {
     const int sets = a.nbatch > 1 ? a.nbatch : a.ngroups > 1 ? a.ngroups : 1;
-    const bool half = variant == 16 || (variant == VQ_GEMM_DEFAULT && vq_half_tiles(a.M, a.N, sets));
-    const int bm = half ? 128 : 256;
-    const bool interior = a.M % bm == 0 && a.N % 288 == 0 && (a.ldo & 7) == 0 &&
-                          (a.epilogue != VQ_EPI_GATE_RESID || a.rows_per_gate % bm == 0);   // what the interior form's epilogue needs
-    if (variant == 19 && (!interior || half)) return VQ_ESHAPE;
-    if (variant == 19 || (variant == VQ_GEMM_DEFAULT && interior))
-        return half ? launch_gemm_wide<128, 288, 4, 2, W4, 1>(a, st) : launch_gemm_wide<256, 288, 4, 2, W4, 1>(a, st);
-    return half ? launch_gemm_wide<128, 288, 4, 2, W4>(a, st) : launch_gemm_wide<256, 288, 4, 2, W4>(a, st);
+    GemmForm f;
+    if (const int rc = vq_gemm_form(a.M, a.N, sets, variant, a.ldo, a.epilogue == VQ_EPI_GATE_RESID ? a.rows_per_gate : 0, f))
+        return rc;
+    return vq_gemm_dispatch_form(f, [&](auto bm, auto interior) {
+        return launch_gemm_wide<decltype(bm)::value, 288, 4, 2, W4, decltype(interior)::value>(a, st);
+    });
 }
 extern "C" int vq_gemm_i8(const int8_t* xq, const float* sx, const int32_t* zx, const int32_t* R, const void* wq,
                           const float* sw, const int32_t* zw, const int32_t* cs, const float* bias, void* out,
@@ -60,15 +81,13 @@ extern "C" int vq_gemm_i8(const int8_t* xq, const float* sx, const int32_t* zx, 
                           int Kp, int w_bits, int epilogue, int variant, void* stream) {
     if (!xq || !sx || !zx || !R || !wq || !sw || !zw || !cs || !out) return VQ_EINVAL;
     if (M <= 0 || N <= 0 || K <= 0) return VQ_EINVAL;
-    if (Kp % 128 != 0 || Kp < K || N % 4 != 0 || ldo % 4 != 0 || ldo < N) return VQ_ESHAPE;
+    const int ops = vq_gemm_operand_check(M, N, K, Kp);
+    if (ops == VQ_GEMM_OPS_KP || N % 4 != 0 || ldo % 4 != 0 || ldo < N) return VQ_ESHAPE;
     if (w_bits < 2 || w_bits > 8) return VQ_EUNSUP;
     if (epilogue < VQ_EPI_NONE || epilogue > VQ_EPI_RESID) return VQ_EUNSUP;
     if ((epilogue == VQ_EPI_GATE_RESID || epilogue == VQ_EPI_RESID) && !resid) return VQ_EINVAL;
     if (epilogue == VQ_EPI_GATE_RESID && (!gate || rows_per_gate <= 0)) return VQ_EINVAL;
-    // 24-bit multiplies in the epilogue: |R| < 2^23 needs K <= 2^14
-    if (K > 16384) return VQ_ESHAPE;
-    // LDS-DMA offsets are 32-bit (buffer addressing, gemm_wide.h): both operand images must fit
-    if ((long)M * Kp >= (1L << 32) || (long)N * Kp >= (1L << 32)) return VQ_ESHAPE;
+    if (ops != VQ_GEMM_OPS_OK) return VQ_ESHAPE;
     GemmArgs a{xq, sx, zx, R, (const uint8_t*)wq, sw, zw, cs, bias, (half_t*)out, (const half_t*)resid, gate,
                ldo, rows_per_gate > 0 ? rows_per_gate : 1, M, N, K, Kp, epilogue, 0};
     hipStream_t st = (hipStream_t)stream;
@@ -93,11 +112,10 @@ extern "C" int vq_gemm_i8_batched(const int8_t* xq, const float* sx, const int32
                                   int nbatch, int M, int N, int K, int Kp, int w_bits, void* stream) {
     if (!xq || !sx || !zx || !R || !wq || !sw || !zw || !cs || !out) return VQ_EINVAL;
     if (M <= 0 || N <= 0 || K <= 0 || nbatch <= 0) return VQ_EINVAL;
-    if (Kp % 128 != 0 || Kp < K || N % 4 != 0) return VQ_ESHAPE;
+    const int ops = vq_gemm_operand_check(M, N, K, Kp);
+    if (ops == VQ_GEMM_OPS_KP || N % 4 != 0) return VQ_ESHAPE;
     if (w_bits <= 4 || w_bits > 8) return VQ_EUNSUP;
-    if (K > 16384) return VQ_ESHAPE;
-    // LDS-DMA offsets are 32-bit (buffer addressing, gemm_wide.h): both operand images must fit
-    if ((long)M * Kp >= (1L << 32) || (long)N * Kp >= (1L << 32)) return VQ_ESHAPE;
+    if (ops != VQ_GEMM_OPS_OK) return VQ_ESHAPE;
     GemmArgs a{xq, sx, zx, R, (const uint8_t*)wq, sw, zw, cs, bias, (half_t*)out, nullptr, nullptr,
                N, 1, M, N, K, Kp, VQ_EPI_NONE, 0};
     a.nbatch = nbatch;
@@ -118,11 +136,10 @@ extern "C" int vq_gemm_i8_grouped(int ngroups, const int8_t* const* xq, const fl
                                   int ldo, int M, int N, int K, int Kp, int w_bits, void* stream) {
     if (ngroups < 1 || ngroups > 3 || !xq || !sx || !zx || !R || !wq || !sw || !zw || !cs || !out) return VQ_EINVAL;
     if (M <= 0 || N <= 0 || K <= 0) return VQ_EINVAL;
-    if (Kp % 128 != 0 || Kp < K || N % 4 != 0 || ldo % 4 != 0 || ldo < ngroups * N) return VQ_ESHAPE;
+    const int ops = vq_gemm_operand_check(M, N, K, Kp);
+    if (ops == VQ_GEMM_OPS_KP || N % 4 != 0 || ldo % 4 != 0 || ldo < ngroups * N) return VQ_ESHAPE;
     if (w_bits < 2 || w_bits > 8) return VQ_EUNSUP;
-    if (K > 16384) return VQ_ESHAPE;
-    // LDS-DMA offsets are 32-bit (buffer addressing, gemm_wide.h): both operand images must fit
-    if ((long)M * Kp >= (1L << 32) || (long)N * Kp >= (1L << 32)) return VQ_ESHAPE;
+    if (ops != VQ_GEMM_OPS_OK) return VQ_ESHAPE;
     for (int g = 0; g < ngroups; ++g)
         if (!xq[g] || !sx[g] || !zx[g] || !R[g] || !wq[g] || !sw[g] || !zw[g] || !cs[g]) return VQ_EINVAL;
     GemmArgs a{xq[0], sx[0], zx[0], R[0], (const uint8_t*)wq[0], sw[0], zw[0], cs[0], bias ? bias[0] : nullptr,
@@ -148,8 +165,7 @@ extern "C" int vq_gemm_i8_cross_attn(const int8_t* xq, const float* sx, const in
     if (!xq || !sx || !zx || !R || !wq || !sw || !zw || !cs || !k || !v || !o) return VQ_EINVAL;
     if (M <= 0 || N <= 0 || K <= 0 || n_seq <= 0 || Lq <= 0 || H <= 0 || Lk <= 0) return VQ_EINVAL;
     // what vq_gemm_i8 refuses ...
-    if (Kp % 128 != 0 || Kp < K || K > 16384) return VQ_ESHAPE;
-    if ((long)M * Kp >= (1L << 32) || (long)N * Kp >= (1L << 32)) return VQ_ESHAPE;
+    if (vq_gemm_operand_check(M, N, K, Kp) != VQ_GEMM_OPS_OK) return VQ_ESHAPE;
     if (w_bits < 2 || w_bits > 8) return VQ_EUNSUP;
     // ... the tile: interior 256 x 288 tiles of 4 whole heads, every tile inside one sample
     if (D != 72) return VQ_EUNSUP;
@@ -165,8 +181,8 @@ extern "C" int vq_gemm_i8_cross_attn(const int8_t* xq, const float* sx, const in
     a.at = AttnArgs{nullptr, (const half_t*)k, (const half_t*)v, (half_t*)o, 0, 0, kv_seq_stride, kv_tok_stride, o_seq_stride,
                     o_tok_stride, kv_off, n_seq, Lq, Lk, H, scale * ATT_LOG2E};
     hipStream_t st = (hipStream_t)stream;
-    if (w_bits <= 4) return launch_gemm_cross_attn<true>(a, st);
-    return launch_gemm_cross_attn<false>(a, st);
+    if (w_bits <= 4) return launch_gemm_tiles<gemm_i8_cross_attn_kernel<true>, 256, 288, 4, 2, true>(a, st);
+    return launch_gemm_tiles<gemm_i8_cross_attn_kernel<false>, 256, 288, 4, 2, false>(a, st);
 }
 
 // R[0, n) = 0 in front of a quantizing launch (every wave adds its columns' part of a row's term).  A kernel, not
@@ -191,15 +207,12 @@ extern "C" int vq_gemm_i8_rowquant_static(const int8_t* xq, const float* sx, con
         return VQ_EINVAL;
     if (M <= 0 || N <= 0 || K <= 0 || Kp <= 0 || Kp_out <= 0) return VQ_EINVAL;
     // what vq_gemm_i8 refuses (N % 8 covers its N % 4) ...
-    if (Kp % 128 != 0 || Kp < K || K > 16384) return VQ_ESHAPE;
-    if ((long)M * Kp >= (1L << 32) || (long)N * Kp >= (1L << 32)) return VQ_ESHAPE;
+    if (vq_gemm_operand_check(M, N, K, Kp) != VQ_GEMM_OPS_OK) return VQ_ESHAPE;
     // ... and the quantizer's: whole 8-byte runs of codes, rows the int8 GEMM reads, 16-byte chunk stores and float4 reads
     if (N % 8 != 0 || Kp_out % 128 != 0 || Kp_out < N) return VQ_ESHAPE;
     if ((((uintptr_t)xq_out | (uintptr_t)s | (uintptr_t)s_rcp) & 15u) != 0) return VQ_ESHAPE;
-    const bool half = variant == 16 || (variant == VQ_GEMM_DEFAULT && vq_half_tiles(M, N, 1));
-    const int bm = half ? 128 : 256;
-    const bool interior = M % bm == 0 && N % 288 == 0;
-    if (variant == 19 && (!interior || half)) return VQ_ESHAPE;
+    GemmForm f;                                                // (the quantizing epilogue: no output rows, no gate)
+    if (const int rc = vq_gemm_form(M, N, 1, variant, 0, 0, f)) return rc;
     if (w_bits <= 4 || w_bits > 8) return VQ_EUNSUP;           // nibble weights: no quantizing form
     if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
     if (s && !s_rcp) return VQ_EUNSUP;                         // the division exists in reciprocal form only
@@ -212,7 +225,8 @@ extern "C" int vq_gemm_i8_rowquant_static(const int8_t* xq, const float* sx, con
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(gemm_zero_rows_kernel, dim3((M + 255) / 256), dim3(256), 0, st, R_out, M);
     if (const int rc = vq_check_launch()) return rc;
-    if (variant == 19 || (variant == VQ_GEMM_DEFAULT && interior))
-        return half ? launch_gemm_wide_quant<128, 288, 4, 2, 1>(a, st) : launch_gemm_wide_quant<256, 288, 4, 2, 1>(a, st);
-    return half ? launch_gemm_wide_quant<128, 288, 4, 2, 0>(a, st) : launch_gemm_wide_quant<256, 288, 4, 2, 0>(a, st);
+    return vq_gemm_dispatch_form(f, [&](auto bm, auto interior) {
+        constexpr int BM = decltype(bm)::value;
+        return launch_gemm_tiles<gemm_i8_wide_quant_kernel<BM, 288, 4, 2, decltype(interior)::value>, BM, 288, 4, 2, false>(a, st);
+    });
 }

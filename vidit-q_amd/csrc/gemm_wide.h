@@ -32,13 +32,16 @@
 // ---------------------------------------------------------------------------
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool W4>
 struct WideCfg {
-    static constexpr int NW = WAVES_M * WAVES_N;
-    static constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
+    using Epi = EpiGeom<BM, BN, WAVES_M, WAVES_N>;             // epilogue slabs + parked terms (gemm_common.h)
+    static constexpr int NW = Epi::NW, WTM = Epi::WTM, WTN = Epi::WTN;
     static constexpr int WROW = W4 ? 64 : 128;                 // bytes per weight row and stage
     static constexpr int STAGE = BM * 128 + BN * WROW;
-    static constexpr int EPIL = NW * WTM * (WTN * 2 + 16) + 16 * BN + 12 * BM;   // epilogue slabs + parameter blocks
-    static constexpr int LDS = 2 * STAGE > EPIL ? 2 * STAGE : EPIL;
+    static constexpr int LDS = 2 * STAGE > Epi::BYTES ? 2 * STAGE : Epi::BYTES;
     static_assert(LDS <= 163840, "LDS budget of one CU");
+    // The terms are parked behind the epilogue slabs.  For the 256-row tile (and for W4 stages) that is past the end of the
+    // ring; for the 128-row tile with 128-byte weight rows the block lies INSIDE stage 1 (gemm_i8_wide_tile, behind its loop).
+    static constexpr bool PAR_IN_RING = Epi::PAR_OFF < 2 * STAGE;
+    static_assert(PAR_IN_RING || Epi::QS_OFF >= 2 * STAGE, "smoothing vector outside the live ring");
 };
 
 // Args: GemmArgs, or GemmQArgs with EPI = VQ_EPI_GELU_QUANT (the quantizing epilogue, ring_epilogue_quant), or GemmXArgs with
@@ -309,30 +312,28 @@ __device__ __forceinline__ void gemm_i8_wide_tile(const Args a0, const int vb, c
     // even (K = 256, 4608): parked before every wave had left the loop it overwrote weight rows under the last MFMAs
     // (found by test_gemm_low_bit_weights).  There the global loads are issued first and the LDS writes wait for a
     // workgroup barrier.
-    constexpr bool PAR_IN_RING = NW * WTM * (WTN * 2 + 16) < 2 * STAGE;
-    const auto colp = ring_load_col_params<BN, 64 * NW>(a, src.n0, tid, gate_row);
+    constexpr bool PAR_IN_RING = Cfg::PAR_IN_RING;
+    const ColParams colp = ring_load_col_params<BN>(a, src.n0, tid, gate_row);
     const RowParams rowp = ring_load_row_params<BM>(a, src.m0, tid);
     if constexpr (QUANT) {
         // the consuming Linear's smoothing vector, parked in front of the parameter block: past the ring, or behind the
-        // barrier that frees it
-        static_assert(PAR_IN_RING || NW * WTM * (WTN * 2 + 16) - 8 * BN >= 2 * STAGE, "smoothing vector outside the live ring");
+        // barrier that frees it (WideCfg asserts it)
         const SmoothParams smp = ring_load_smooth<BN>(a, src.n0, tid);
         if constexpr (PAR_IN_RING) __syncthreads();
         ring_park_smooth<BM, BN, WAVES_M, WAVES_N>(a, smp, smem, tid);
     } else {
         if constexpr (PAR_IN_RING) __syncthreads();
     }
-    ring_park_col_params<BM, BN, WAVES_M, WAVES_N, 16, true>(colp, smem, tid);
-    ring_park_row_params<BM, BN, WAVES_M, WAVES_N, 16, true>(rowp, smem, tid);
+    ring_park_col_params<BM, BN, WAVES_M, WAVES_N>(colp, smem, tid);
+    ring_park_row_params<BM, BN, WAVES_M, WAVES_N>(rowp, smem, tid);
     __syncthreads();
     if constexpr (QUANT) {
         ring_epilogue_quant<BM, BN, WAVES_M, WAVES_N, INT != 0>(a, smem, acc, src.m0, src.n0, tid);
     } else if constexpr (CROSS) {
         ring_epilogue_cross<BM, BN, WAVES_M, WAVES_N>(a, a0.at, smem, acc, src.m0, src.n0, tid);
     } else {
-        // (INT != 0: the launcher has checked what the interior epilogue needs for every tile - launch_gemm_wide_e)
-        ring_epilogue<BM, BN, WAVES_M, WAVES_N, EPI, 16, true, 0, INT != 0 && !STAMP>(a, smem, acc, src.m0, src.n0, ts, tid,
-                                                                                     gate_row != nullptr);
+        // (INT != 0: the launcher has checked what the interior epilogue needs for every tile - vq_gemm_form)
+        ring_epilogue<BM, BN, WAVES_M, WAVES_N, EPI, INT != 0 && !STAMP>(a, smem, acc, src.m0, src.n0, ts, tid, gate_row != nullptr);
     }
 }
 
@@ -353,53 +354,41 @@ __global__ __launch_bounds__(512) void gemm_i8_cross_attn_kernel(GemmXArgs a) {
     gemm_i8_wide_tile<256, 288, 4, 2, VQ_EPI_CROSS_ATTN, W4, false, 1>(a, blockIdx.x, threadIdx.x);
 }
 
-template <bool W4>
-static int launch_gemm_cross_attn(const GemmXArgs& a, hipStream_t st) {
-    using Cfg = WideCfg<256, 288, 4, 2, W4>;
-    constexpr size_t LDS = Cfg::LDS;
-    if (a.M % 256 != 0 || a.N % 288 != 0) return VQ_ESHAPE;                 // interior tiles only
-    constexpr auto k = gemm_i8_cross_attn_kernel<W4>;
-    if (const int rc = vq_prepare_kernel<k>((int)LDS)) return rc;
-    hipLaunchKernelGGL(k, dim3((a.M / 256) * (a.N / 288)), dim3(512), LDS, st, a);
-    return vq_check_launch();
+// ---- host side -----------------------------------------------------------------------------------------------------
+// What every GEMM entry point requires of its operand images; each failing clause is a VQ_ESHAPE of the entry point.  The two
+// groups are told apart because three entry points check a code width between them (and must keep refusing in that order):
+//   VQ_GEMM_OPS_KP:    whole 128-byte k-lines that cover K (a stage is 128 bytes of k per row);
+//   VQ_GEMM_OPS_RANGE: K <= 2^14 (|R| < 2^23: the row terms convert to fp32 exactly), and both images below 2^32 bytes -
+//                      LDS-DMA offsets are 32-bit (buffer addressing).
+enum { VQ_GEMM_OPS_OK = 0, VQ_GEMM_OPS_KP = 1, VQ_GEMM_OPS_RANGE = 2 };
+static inline int vq_gemm_operand_check(int M, int N, int K, int Kp) {
+    if (Kp % 128 != 0 || Kp < K) return VQ_GEMM_OPS_KP;
+    if (K > 16384 || (long)M * Kp >= (1L << 32) || (long)N * Kp >= (1L << 32)) return VQ_GEMM_OPS_RANGE;
+    return VQ_GEMM_OPS_OK;
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int INT>
-static int launch_gemm_wide_quant(const GemmQArgs& a, hipStream_t st) {
-    using Cfg = WideCfg<BM, BN, WAVES_M, WAVES_N, false>;
-    constexpr size_t LDS = Cfg::LDS;
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    if (INT != 0 && (a.M % BM != 0 || a.N % BN != 0)) return VQ_ESHAPE;     // interior tiles only
-    constexpr auto k = gemm_i8_wide_quant_kernel<BM, BN, WAVES_M, WAVES_N, INT>;
-    if (const int rc = vq_prepare_kernel<k>((int)LDS)) return rc;
-    hipLaunchKernelGGL(k, dim3(tiles), dim3(64 * WAVES_M * WAVES_N), LDS, st, a);
-    return vq_check_launch();
-}
-
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, bool W4, int INT = 0>
-static int launch_gemm_wide_e(const GemmArgs& a, hipStream_t st) {
-    using Cfg = WideCfg<BM, BN, WAVES_M, WAVES_N, W4>;
-    constexpr int NT = 64 * WAVES_M * WAVES_N;
-    constexpr size_t LDS = Cfg::LDS;
+// One launch of a tile kernel K: its dynamic LDS limit raised once per device, one workgroup per tile and weight set / group.
+template <auto K, int BM, int BN, int WAVES_M, int WAVES_N, bool W4, class Args>
+static int launch_gemm_tiles(const Args& a, hipStream_t st) {
+    constexpr size_t LDS = WideCfg<BM, BN, WAVES_M, WAVES_N, W4>::LDS;
     const int MT = (a.M + BM - 1) / BM, NTl = (a.N + BN - 1) / BN;
     const int tiles = MT * NTl * (a.nbatch > 1 ? a.nbatch : a.ngroups > 1 ? a.ngroups : 1);
-    // interior tiles only, and (its epilogue is the interior one, compiled alone) 8-element aligned rows and a gate that folds
-    // into the staged scales for every tile
-    if (INT != 0 && (a.M % BM != 0 || a.N % BN != 0 || (a.N & 7) != 0 || (a.ldo & 7) != 0 ||
-                     (EPI == VQ_EPI_GATE_RESID && a.rows_per_gate % BM != 0)))
-        return VQ_ESHAPE;
-    constexpr auto k = gemm_i8_wide_kernel<BM, BN, WAVES_M, WAVES_N, EPI, W4, false, INT>;
-    if (const int rc = vq_prepare_kernel<k>((int)LDS)) return rc;
-    hipLaunchKernelGGL(k, dim3(tiles), dim3(NT), LDS, st, a);
+    if (const int rc = vq_prepare_kernel<K>((int)LDS)) return rc;
+    hipLaunchKernelGGL(K, dim3(tiles), dim3(64 * WAVES_M * WAVES_N), LDS, st, a);
     return vq_check_launch();
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool W4 = false, int INT = 0>
+// the plain kernel by epilogue kind (INT != 0: the caller has checked what the interior form needs - vq_gemm_form)
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool W4, int INT>
 static int launch_gemm_wide(const GemmArgs& a, hipStream_t st) {
+    auto go = [&](auto epi) {
+        constexpr int EPI = decltype(epi)::value;
+        return launch_gemm_tiles<gemm_i8_wide_kernel<BM, BN, WAVES_M, WAVES_N, EPI, W4, false, INT>, BM, BN, WAVES_M, WAVES_N, W4>(a, st);
+    };
     switch (a.epilogue) {
-        case VQ_EPI_NONE: return launch_gemm_wide_e<BM, BN, WAVES_M, WAVES_N, VQ_EPI_NONE, W4, INT>(a, st);
-        case VQ_EPI_GELU: return launch_gemm_wide_e<BM, BN, WAVES_M, WAVES_N, VQ_EPI_GELU, W4, INT>(a, st);
-        case VQ_EPI_GATE_RESID: return launch_gemm_wide_e<BM, BN, WAVES_M, WAVES_N, VQ_EPI_GATE_RESID, W4, INT>(a, st);
-        default: return launch_gemm_wide_e<BM, BN, WAVES_M, WAVES_N, VQ_EPI_RESID, W4, INT>(a, st);
+        case VQ_EPI_NONE: return go(std::integral_constant<int, VQ_EPI_NONE>{});
+        case VQ_EPI_GELU: return go(std::integral_constant<int, VQ_EPI_GELU>{});
+        case VQ_EPI_GATE_RESID: return go(std::integral_constant<int, VQ_EPI_GATE_RESID>{});
+        default: return go(std::integral_constant<int, VQ_EPI_RESID>{});
     }
 }
