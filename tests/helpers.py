@@ -277,6 +277,49 @@ def dpm_mode_model(x, t, y, **kw):
     return 0.35 * w * x + 0.2 * torch.tanh(x * 0.5 + c) + 0.1 * c
 
 
+# ---- the fused sampler steps (tests/test_dpm_step_*.py, tests/test_ddpm_step_*.py)
+PAD = 64                                                 # elements of NaN on both sides of every Arena buffer
+
+
+class Arena:
+    """A buffer ``t`` inside a NaN-filled allocation; ``unchanged`` shows that nothing outside [lo, hi) moved by a bit."""
+
+    def __init__(self, dev, numel, dtype):
+        self.full = torch.full((numel + 2 * PAD,), float("nan"), dtype=dtype, device=dev)
+        self.t = self.full[PAD:PAD + numel]
+        self.before = None
+
+    def snapshot(self):
+        self.before = self.full.clone()
+
+    @staticmethod
+    def bits(t):
+        return t.view(torch.int16 if t.dtype == torch.float16 else torch.int32)
+
+    def unchanged(self, lo=None, hi=None):
+        """Everything outside [lo, hi) of the buffer (pads included; the whole allocation when lo is None)."""
+        a, b = self.bits(self.full), self.bits(self.before)
+        if lo is None:
+            return torch.equal(a, b)
+        return torch.equal(a[:PAD + lo], b[:PAD + lo]) and torch.equal(a[PAD + hi:], b[PAD + hi:])
+
+
+class _FakeTensor:
+    """Shape / stride / address / dtype of a GPU tensor, for the step predicates (which touch nothing else)."""
+
+    def __init__(self, shape, strides, ptr, dtype, cuda=True):
+        self.shape, self._st, self._ptr, self.dtype, self.is_cuda = tuple(shape), tuple(strides), ptr, dtype, cuda
+
+    def stride(self):
+        return self._st
+
+    def data_ptr(self):
+        return self._ptr
+
+    def element_size(self):
+        return {torch.float16: 2, torch.bfloat16: 2, torch.float32: 4, torch.float64: 8}[self.dtype]
+
+
 # ---- launch traces of the fused block route (tests/block_trace_cases.py, tests/golden/make_block_traces.py)
 def _describe_arg(v):
     """What a launch depends on, without addresses: a tensor's shape / dtype / strides, a scalar's value; containers and

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import ddpm_step_cases as pc
+from helpers import _FakeTensor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "t2i_iddpm.npz"))
@@ -199,22 +200,6 @@ def test_entry_point_refusal_table_and_order():
     null = [None if k in PTRS else 1 for k in ("eps", "x", "noise", "coef", "step", "x_out", "x0_out", "x_model", "n", "C",
                                                 "inner", "ld_eps", "guided", "row", "n_rows", "eps_f16", "xm_f16", "stream")]
     assert lib.vq_cfg_ddpm_step(*null) == -1
-
-
-class _FakeTensor:
-    """Shape / stride / address / dtype of a GPU tensor, for the predicate (which touches nothing else)."""
-
-    def __init__(self, shape, strides, ptr, dtype, cuda=True):
-        self.shape, self._st, self._ptr, self.dtype, self.is_cuda = tuple(shape), tuple(strides), ptr, dtype, cuda
-
-    def stride(self):
-        return self._st
-
-    def data_ptr(self):
-        return self._ptr
-
-    def element_size(self):
-        return {torch.float16: 2, torch.bfloat16: 2, torch.float32: 4, torch.float64: 8}[self.dtype]
 
 
 def _fakes(kw):

@@ -16,33 +16,11 @@ import pytest
 import torch
 
 import ddpm_step_cases as pc
+from helpers import Arena
 
 pytestmark = pytest.mark.gpu
-PAD = 64                                                 # elements of NaN on both sides of every buffer
 EXP_ULPS = 2                                             # E above; measured 1 (profiles/ddpm_step/README.md) + 1
 CFG = 4.5
-
-
-class Arena:
-    """A buffer inside a NaN-filled allocation; ``unchanged`` shows that nothing outside [lo, hi) moved by a bit."""
-
-    def __init__(self, dev, numel, dtype):
-        self.full = torch.full((numel + 2 * PAD,), float("nan"), dtype=dtype, device=dev)
-        self.t = self.full[PAD:PAD + numel]
-        self.before = None
-
-    def snapshot(self):
-        self.before = self.full.clone()
-
-    @staticmethod
-    def bits(t):
-        return t.view(torch.int16 if t.dtype == torch.float16 else torch.int32)
-
-    def unchanged(self, lo=None, hi=None):
-        a, b = self.bits(self.full), self.bits(self.before)
-        if lo is None:
-            return torch.equal(a, b)
-        return torch.equal(a[:PAD + lo], b[:PAD + lo]) and torch.equal(a[PAD + hi:], b[PAD + hi:])
 
 
 def launch(ops, dev, row, eps, x, noise, half, padded=False, alias=False, xm=None, guided=3, nan_unread=True, k=0):

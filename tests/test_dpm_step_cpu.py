@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import dpm_step_cases as dc
+from helpers import _FakeTensor
 
 
 @pytest.mark.parametrize("case", dc.d1_cases(), ids=lambda c: c.name)
@@ -120,22 +121,6 @@ def test_advance_entry_point_refusals():
     assert lib.vq_dpmpp_advance(p, p, 1, ctypes.c_void_p(GOOD + 1), 1, None) == -2
 
 
-class _FakeTensor:
-    """Shape / stride / address / dtype of a GPU tensor, for the predicate (which touches nothing else)."""
-
-    def __init__(self, shape, strides, ptr, dtype, cuda=True):
-        self.shape, self._st, self._ptr, self.dtype, self.is_cuda = tuple(shape), tuple(strides), ptr, dtype, cuda
-
-    def stride(self):
-        return self._st
-
-    def data_ptr(self):
-        return self._ptr
-
-    def element_size(self):
-        return {torch.float16: 2, torch.bfloat16: 2, torch.float32: 4, torch.float64: 8}[self.dtype]
-
-
 def _fakes(kw):
     a = dict(eps=GOOD, x=GOOD, n=1, C=4, inner=8, ld_eps=32, eps_f16=0)
     a.update({k: v for k, v in kw.items() if k in a})
@@ -172,6 +157,51 @@ def test_ok_predicate_agrees_with_the_entry_point():
     eps, x = _fakes({})
     eps.is_cuda = False
     assert ops.cfg_dpmpp_step_ok(eps, x) is False
+
+
+# Every layout the two ``_fakes`` tables (this file: eps [2n, C, inner]; test_ddpm_step_cpu.py: eps [2n, 2C, inner]) hand to
+# the predicates: (channel multiplier m of the layout, n, C, inner, ld_eps), then what the two geometry functions that
+# _step_geometry replaced returned for it - the DPM-Solver++ one (an element is C * inner) and the IDDPM one (2C * inner).
+GEOMETRIES = [
+    (1, 0, 4, 8, 32, (0, 4, 8, 32), None), (1, 1, 0, 8, 32, (1, 0, 8, 32), (1, 0, 8, 32)),
+    (1, 1, 4, 0, 32, (1, 4, 0, 32), None), (1, 1, 4, 8, 31, (1, 4, 8, 31), None), (1, 1, 4, 8, 34, (1, 4, 8, 34), None),
+    (1, 1, 4, 8, 32, (1, 4, 8, 32), None), (1, 1, 4, 7, 28, (1, 4, 7, 28), None), (1, 1, 4, 7, 27, (1, 4, 7, 27), None),
+    (1, 1, 4, 8, 64, (1, 4, 8, 64), None), (1, 1, 4, 1, 4, (1, 4, 1, 4), None), (1, 1, 4, 7, 56, (1, 4, 7, 56), None),
+    (1, 3, 3, 12, 72, (3, 3, 12, 72), None),
+    (2, 0, 4, 8, 64, None, (0, 4, 8, 64)), (2, 1, 0, 8, 64, (1, 0, 8, 64), (1, 0, 8, 64)),
+    (2, 1, 4, 0, 64, None, (1, 4, 0, 64)), (2, 1, 4, 8, 63, None, (1, 4, 8, 63)), (2, 1, 4, 8, 32, None, (1, 4, 8, 32)),
+    (2, 1, 4, 8, 66, None, (1, 4, 8, 66)), (2, 1, 4, 8, 64, None, (1, 4, 8, 64)), (2, 1, 4, 7, 56, None, (1, 4, 7, 56)),
+    (2, 1, 4, 7, 55, None, (1, 4, 7, 55)), (2, 1, 4, 8, 65, None, (1, 4, 8, 65)), (2, 1, 4, 8, 68, None, (1, 4, 8, 68)),
+    (2, 1, 4, 8, 72, None, (1, 4, 8, 72)),
+    (2, 2, 3, 7, 41, None, (2, 3, 7, 41)), (2, 2, 3, 7, 42, None, (2, 3, 7, 42)), (2, 2, 3, 7, 43, None, (2, 3, 7, 43)),
+    (2, 2, 3, 7, 44, None, (2, 3, 7, 44)), (2, 2, 3, 7, 46, None, (2, 3, 7, 46)), (2, 2, 3, 7, 50, None, (2, 3, 7, 50)),
+    (2, 3, 4, 12, 95, None, (3, 4, 12, 95)), (2, 3, 4, 12, 96, None, (3, 4, 12, 96)), (2, 3, 4, 12, 97, None, (3, 4, 12, 97)),
+    (2, 3, 4, 12, 98, None, (3, 4, 12, 98)), (2, 3, 4, 12, 100, None, (3, 4, 12, 100)),
+    (2, 3, 4, 12, 104, None, (3, 4, 12, 104)),
+    (2, 1, 1, 1, 1, None, (1, 1, 1, 1)), (2, 1, 1, 1, 2, None, (1, 1, 1, 2)), (2, 1, 1, 1, 3, None, (1, 1, 1, 3)),
+    (2, 1, 1, 1, 4, None, (1, 1, 1, 4)), (2, 1, 1, 1, 6, None, (1, 1, 1, 6)), (2, 1, 1, 1, 10, None, (1, 1, 1, 10)),
+    (2, 2, 4, 2, 15, None, (2, 4, 2, 15)), (2, 2, 4, 2, 16, None, (2, 4, 2, 16)), (2, 2, 4, 2, 17, None, (2, 4, 2, 17)),
+    (2, 2, 4, 2, 18, None, (2, 4, 2, 18)), (2, 2, 4, 2, 20, None, (2, 4, 2, 20)), (2, 2, 4, 2, 24, None, (2, 4, 2, 24)),
+]
+
+
+def test_merged_geometry_returns_what_the_two_geometry_functions_returned():
+    """ops._step_geometry(eps, x, 1) and (eps, x, 2) on every layout of GEOMETRIES, and None from both for strides that
+    are not dense within a batch element."""
+    import viditq_amd  # noqa: F401
+    from viditq_amd import ops
+    assert len(GEOMETRIES) == 48
+    for m, n, C, inner, ld, want1, want2 in GEOMETRIES:
+        eps = _FakeTensor((2 * n, m * C, inner), (ld, inner, 1), GOOD, torch.float32)
+        x = _FakeTensor((n, C, inner), (C * inner, inner, 1), GOOD, torch.float32)
+        assert ops._step_geometry(eps, x, 1) == want1, (m, n, C, inner, ld)
+        assert ops._step_geometry(eps, x, 2) == want2, (m, n, C, inner, ld)
+        eps._st = (ld, 1, m * C)
+        if inner > 1 and m * C > 1:
+            assert ops._step_geometry(eps, x, 1) is None and ops._step_geometry(eps, x, 2) is None
+    eps, x = _fakes({})
+    x._st = (64, 8, 1)
+    assert ops._step_geometry(eps, x, 1) is None                       # the latent itself is dense
 
 
 def test_ops_refuse_cpu_tensors():

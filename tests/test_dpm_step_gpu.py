@@ -10,33 +10,10 @@ import pytest
 import torch
 
 import dpm_step_cases as dc
-from helpers import load_npz, quant_params_of, rel_l2, state_dict_of
+from helpers import Arena, load_npz, quant_params_of, rel_l2, state_dict_of
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PAD = 64                                                 # elements of NaN on both sides of every buffer
-
-
-class Arena:
-    """A buffer inside a NaN-filled allocation; ``check`` shows that nothing outside ``written`` moved by a bit."""
-
-    def __init__(self, dev, numel, dtype):
-        self.full = torch.full((numel + 2 * PAD,), float("nan"), dtype=dtype, device=dev)
-        self.t = self.full[PAD:PAD + numel]
-        self.before = None
-
-    def snapshot(self):
-        self.before = self.full.clone()
-
-    def bits(self, t):
-        return t.view(torch.int16 if t.dtype == torch.float16 else torch.int32)
-
-    def unchanged(self, lo=None, hi=None):
-        """Everything outside [lo, hi) of the buffer (pads included; the whole allocation when lo is None)."""
-        a, b = self.bits(self.full), self.bits(self.before)
-        if lo is None:
-            return torch.equal(a, b)
-        return torch.equal(a[:PAD + lo], b[:PAD + lo]) and torch.equal(a[PAD + hi:], b[PAD + hi:])
 
 
 def launch(ops, dev, row, k, eps, x, hist, half, pitch2=False, alias=False, xm=None):

@@ -82,6 +82,38 @@ __device__ __forceinline__ void dpm_store(T* p, const float (&v)[V]) {
     *reinterpret_cast<typename dpm_vec<T, V>::type*>(p) = r;
 }
 
+// What the two table-driven step kernels (DPM-Solver++ here, IDDPM further down) share.  The contract pragma is scoped to
+// a function body: a helper with floating-point arithmetic carries its own.
+
+// The table row of a launch: ``row`` plus the device counter when there is one.
+__device__ __forceinline__ int step_row(int row, const int32_t* step, int n_rows) {
+    const int k = row + (step ? *step : 0);
+    return k < 0 ? 0 : (k < n_rows - 1 ? k : n_rows - 1);       // a counter can never index outside the table
+}
+
+// Classifier-free guidance u + cfg * (c - u) as the eager tensors round it: each of the three operations in the model
+// output's type T.  Returns e as a float that is exactly the fp16 value when T is half_t.
+template <typename T>
+__device__ __forceinline__ float step_guide(float c, float u, float cfg) {
+#pragma clang fp contract(off)
+    const T d = (T)(c - u);
+    const T p = (T)(cfg * (float)d);
+    return (float)(T)(u + (float)p);
+}
+
+// The sample for the next forward: both halves of the duplicated batch x_model, in its own type.
+template <int V>
+__device__ __forceinline__ void step_store_model(void* xm, int xm_f16, long i, long total, const float (&out)[V]) {
+    if (!xm) return;
+    if (xm_f16) {
+        dpm_store<half_t, V>((half_t*)xm + i, out);
+        dpm_store<half_t, V>((half_t*)xm + total + i, out);
+    } else {
+        dpm_store<float, V>((float*)xm + i, out);
+        dpm_store<float, V>((float*)xm + total + i, out);
+    }
+}
+
 // T: the model output's type; V: elements per thread and access (4 needs inner % 4 == 0, so a group never spans two
 // batch elements).  x_out may alias x: an element is read and written by the same thread.
 template <typename T, int V>
@@ -90,8 +122,7 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const T* __restrict__ ep
                                                         float* xo, void* xm, int xm_f16, int n, long CI, long ld_eps,
                                                         int row, int n_rows) {
 #pragma clang fp contract(off)
-    int k = row + (step ? *step : 0);
-    k = k < 0 ? 0 : (k < n_rows - 1 ? k : n_rows - 1);          // a counter can never index outside the table
+    const int k = step_row(row, step, n_rows);
     const float* r = coef + (long)k * VQ_DPMPP_ROW;
     const int order = (int)r[VQ_DPMPP_ORDER];
     const bool taylor = r[VQ_DPMPP_TAYLOR] != 0.0f;
@@ -112,18 +143,8 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const T* __restrict__ ep
         if (order >= 3) dpm_load<float, V>(h2 + i, m2);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            float se;
-            if constexpr (std::is_same<T, half_t>::value) {
-                const half_t d = (half_t)(c[j] - u[j]);
-                const half_t p = (half_t)(cfg * (float)d);
-                const half_t e = (half_t)(u[j] + (float)p);
-                se = (float)(half_t)(sigma * (float)e);
-            } else {
-                const float d = c[j] - u[j];
-                const float p = cfg * d;
-                const float e = u[j] + p;
-                se = sigma * e;
-            }
+            const float e = step_guide<T>(c[j], u[j], cfg);
+            const float se = (float)(T)(sigma * e);
             const float t = xv[j] - se;
             const float m = t * inv_alpha;
             m0[j] = m;
@@ -153,47 +174,64 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const T* __restrict__ ep
         }
         dpm_store<float, V>(h0 + i, m0);
         dpm_store<float, V>(xo + i, out);
-        if (xm) {
-            if (xm_f16) {
-                dpm_store<half_t, V>((half_t*)xm + i, out);
-                dpm_store<half_t, V>((half_t*)xm + total + i, out);
-            } else {
-                dpm_store<float, V>((float*)xm + i, out);
-                dpm_store<float, V>((float*)xm + total + i, out);
-            }
-        }
+        step_store_model<V>(xm, xm_f16, i, total, out);
     }
 }
 
-static inline bool dpm_aligned(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
+static inline bool vq_aligned(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
+
+// The refusals of both step entry points, in the order include/viditq.h documents: VQ_EINVAL (``einval``: the solver's own
+// nulls and ranges; then what both have), VQ_ESHAPE (an element of elem_mult * C * inner values within the pitch and the
+// solver's clause ``eshape``; then the pitch and every address on the V elements of an access: ``f32`` is the
+// null-terminated list of the fp32 operands moved V at a time, of which an optional one may only stand last), VQ_EUNSUP
+// (a flag outside {0, 1}).  Sets V and returns VQ_OK when the launch may go ahead.
+static int step_check(bool einval, bool eshape, const void* eps, const void* const* f32, const float* coef,
+                      const int32_t* step, const void* x_model, int n, int C, int inner, long ld_eps, int elem_mult, int row,
+                      int n_rows, int eps_f16, int xm_f16, int* V_out) {
+    if (einval || !eps || !coef || n <= 0 || C <= 0 || inner <= 0 || row < 0 || n_rows <= 0 || row >= n_rows) return VQ_EINVAL;
+    if (ld_eps < elem_mult * (long)C * inner || eshape) return VQ_ESHAPE;
+    const int V = *V_out = inner % 4 == 0 ? 4 : 1;
+    const bool e16 = eps_f16 == 1, m16 = xm_f16 == 1;            // (a flag outside {0, 1} is refused below, after the shapes)
+    bool aligned = ld_eps % V == 0 && vq_aligned(eps, (e16 ? 2 : 4) * V) && vq_aligned(x_model, (m16 ? 2 : 4) * V) &&
+                   vq_aligned(coef, 4) && vq_aligned(step, 4);
+    for (; *f32; ++f32) aligned = aligned && vq_aligned(*f32, 4 * V);
+    if (!aligned) return VQ_ESHAPE;
+    if (eps_f16 < 0 || eps_f16 > 1 || xm_f16 < 0 || xm_f16 > 1) return VQ_EUNSUP;
+    return VQ_OK;
+}
+
+// One launch of a step kernel template over n * CI elements: ``launch(T(), V, grid)`` is called with the model output's
+// type as a value and V as an integral constant, once.
+template <typename F>
+static int step_launch(int n, long CI, int V, int eps_f16, F launch) {
+    const long total = (long)n * CI;
+    long blocks = ((total + V - 1) / V + 255) / 256;
+    if (blocks > 1024) blocks = 1024;                            // 16 waves per CU in flight; larger latents loop
+    const dim3 grid((unsigned)blocks);
+    typedef std::integral_constant<int, 4> four;
+    typedef std::integral_constant<int, 1> one;
+    if (eps_f16) {
+        if (V == 4) launch(half_t(), four(), grid); else launch(half_t(), one(), grid);
+    } else {
+        if (V == 4) launch(float(), four(), grid); else launch(float(), one(), grid);
+    }
+    return vq_check_launch();
+}
 
 extern "C" int vq_cfg_dpmpp_step(const void* eps, const float* x, float* hist, const float* coef, const int32_t* step,
                                  float* x_out, void* x_model, int n, int C, int inner, long ld_eps, int row, int n_rows,
                                  int eps_f16, int xm_f16, void* stream) {
-    if (!eps || !x || !hist || !coef || !x_out || n <= 0 || C <= 0 || inner <= 0 || row < 0 || n_rows <= 0 || row >= n_rows)
-        return VQ_EINVAL;
+    const void* const f32[] = {x, hist, x_out, nullptr};
+    int V;
+    const int rc = step_check(!x || !hist || !x_out, false, eps, f32, coef, step, x_model, n, C, inner, ld_eps, 1, row, n_rows,
+                              eps_f16, xm_f16, &V);
+    if (rc != VQ_OK) return rc;
     const long CI = (long)C * inner;
-    if (ld_eps < CI) return VQ_ESHAPE;
-    const int V = inner % 4 == 0 ? 4 : 1;
-    const bool e16 = eps_f16 == 1, m16 = xm_f16 == 1;            // (a flag outside {0, 1} is refused below, after the shapes)
-    if (ld_eps % V != 0 || !dpm_aligned(eps, (e16 ? 2 : 4) * V) || !dpm_aligned(x, 4 * V) || !dpm_aligned(hist, 4 * V) ||
-        !dpm_aligned(x_out, 4 * V) || !dpm_aligned(x_model, (m16 ? 2 : 4) * V) || !dpm_aligned(coef, 4) ||
-        !dpm_aligned(step, 4))
-        return VQ_ESHAPE;
-    if (eps_f16 < 0 || eps_f16 > 1 || xm_f16 < 0 || xm_f16 > 1) return VQ_EUNSUP;
-    const long total = (long)n * CI;
-    long blocks = ((total + V - 1) / V + 255) / 256;
-    if (blocks > 1024) blocks = 1024;                            // 16 waves per CU in flight; larger latents loop
-#define VQ_DPM_LAUNCH(T_, V_)                                                                                          \
-    hipLaunchKernelGGL((cfg_dpmpp_kernel<T_, V_>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,          \
-                       (const T_*)eps, x, hist, coef, step, x_out, x_model, xm_f16, n, CI, ld_eps, row, n_rows)
-    if (e16) {
-        if (V == 4) VQ_DPM_LAUNCH(half_t, 4); else VQ_DPM_LAUNCH(half_t, 1);
-    } else {
-        if (V == 4) VQ_DPM_LAUNCH(float, 4); else VQ_DPM_LAUNCH(float, 1);
-    }
-#undef VQ_DPM_LAUNCH
-    return vq_check_launch();
+    return step_launch(n, CI, V, eps_f16, [&](auto t, auto v, dim3 grid) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((cfg_dpmpp_kernel<T, decltype(v)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)eps,
+                           x, hist, coef, step, x_out, x_model, xm_f16, n, CI, ld_eps, row, n_rows);
+    });
 }
 
 // One workgroup, after the step kernel in stream order: t_out[0 .. n_t) = the row's next model-input time, then the
@@ -210,7 +248,7 @@ __global__ __launch_bounds__(256) void dpmpp_advance_kernel(int32_t* step, const
 
 extern "C" int vq_dpmpp_advance(int32_t* step, const float* coef, int n_rows, float* t_out, int n_t, void* stream) {
     if (!step || !coef || !t_out || n_rows <= 0 || n_t <= 0) return VQ_EINVAL;
-    if (!dpm_aligned(step, 4) || !dpm_aligned(coef, 4) || !dpm_aligned(t_out, 4)) return VQ_ESHAPE;
+    if (!vq_aligned(step, 4) || !vq_aligned(coef, 4) || !vq_aligned(t_out, 4)) return VQ_ESHAPE;
     hipLaunchKernelGGL(dpmpp_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, step, coef, n_rows, t_out, n_t);
     return vq_check_launch();
 }
@@ -229,9 +267,7 @@ __global__ __launch_bounds__(256) void cfg_ddpm_kernel(const T* __restrict__ eps
                                                        int xm_f16, int n, long inner, long CI, long ld_eps, int guided,
                                                        int row, int n_rows) {
 #pragma clang fp contract(off)
-    int k = row + (step ? *step : 0);
-    k = k < 0 ? 0 : (k < n_rows - 1 ? k : n_rows - 1);          // a counter can never index outside the table
-    const float* r = coef + (long)k * VQ_DDPM_ROW;
+    const float* r = coef + (long)step_row(row, step, n_rows) * VQ_DDPM_ROW;
     const float cfg = r[VQ_DDPM_CFG], A = r[VQ_DDPM_A], B = r[VQ_DDPM_B], c1 = r[VQ_DDPM_C1], c2 = r[VQ_DDPM_C2];
     const float min_log = r[VQ_DDPM_MIN_LOG], max_log = r[VQ_DDPM_MAX_LOG], nonzero = r[VQ_DDPM_NONZERO];
     const bool clip = r[VQ_DDPM_CLIP] != 0.0f;
@@ -247,27 +283,10 @@ __global__ __launch_bounds__(256) void cfg_ddpm_kernel(const T* __restrict__ eps
         dpm_load<float, V>(noise + i, z);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            float e = c[j], frac, rest;
-            if constexpr (std::is_same<T, half_t>::value) {
-                if (guide) {
-                    const half_t d = (half_t)(c[j] - u[j]);
-                    const half_t p = (half_t)(cfg * (float)d);
-                    e = (float)(half_t)(u[j] + (float)p);
-                }
-                const half_t v1 = (half_t)(v[j] + 1.0f);
-                const half_t f = (half_t)((float)v1 * 0.5f);
-                frac = (float)f;
-                rest = (float)(half_t)(1.0f - frac);
-            } else {
-                if (guide) {
-                    const float d = c[j] - u[j];
-                    const float p = cfg * d;
-                    e = u[j] + p;
-                }
-                const float v1 = v[j] + 1.0f;
-                frac = v1 * 0.5f;
-                rest = 1.0f - frac;
-            }
+            const float e = guide ? step_guide<T>(c[j], u[j], cfg) : c[j];
+            const T v1 = (T)(v[j] + 1.0f);
+            const float frac = (float)(T)((float)v1 * 0.5f);
+            const float rest = (float)(T)(1.0f - frac);
             const float lmax = frac * max_log;
             const float lmin = rest * min_log;
             const float lv = lmax + lmin;
@@ -287,45 +306,23 @@ __global__ __launch_bounds__(256) void cfg_ddpm_kernel(const T* __restrict__ eps
         }
         dpm_store<float, V>(xo + i, out);
         if (x0o) dpm_store<float, V>(x0o + i, x0);
-        if (xm) {
-            if (xm_f16) {
-                dpm_store<half_t, V>((half_t*)xm + i, out);
-                dpm_store<half_t, V>((half_t*)xm + total + i, out);
-            } else {
-                dpm_store<float, V>((float*)xm + i, out);
-                dpm_store<float, V>((float*)xm + total + i, out);
-            }
-        }
+        step_store_model<V>(xm, xm_f16, i, total, out);
     }
 }
 
 extern "C" int vq_cfg_ddpm_step(const void* eps, const float* x, const float* noise, const float* coef, const int32_t* step,
                                 float* x_out, float* x0_out, void* x_model, int n, int C, int inner, long ld_eps, int guided,
                                 int row, int n_rows, int eps_f16, int xm_f16, void* stream) {
-    if (!eps || !x || !noise || !coef || !x_out || n <= 0 || C <= 0 || inner <= 0 || n_rows <= 0 || row < 0 ||
-        row >= n_rows || guided < 0)
-        return VQ_EINVAL;
+    const void* const f32[] = {x, noise, x_out, x0_out, nullptr};                 // (x0_out is optional: last)
+    int V;
+    const int rc = step_check(!x || !noise || !x_out || guided < 0, guided > C, eps, f32, coef, step, x_model, n, C, inner,
+                              ld_eps, 2, row, n_rows, eps_f16, xm_f16, &V);
+    if (rc != VQ_OK) return rc;
     const long CI = (long)C * inner;
-    if (ld_eps < 2 * CI || guided > C) return VQ_ESHAPE;
-    const int V = inner % 4 == 0 ? 4 : 1;
-    const bool e16 = eps_f16 == 1, m16 = xm_f16 == 1;            // (a flag outside {0, 1} is refused below, after the shapes)
-    if (ld_eps % V != 0 || !dpm_aligned(eps, (e16 ? 2 : 4) * V) || !dpm_aligned(x, 4 * V) || !dpm_aligned(noise, 4 * V) ||
-        !dpm_aligned(x_out, 4 * V) || !dpm_aligned(x0_out, 4 * V) || !dpm_aligned(x_model, (m16 ? 2 : 4) * V) ||
-        !dpm_aligned(coef, 4) || !dpm_aligned(step, 4))
-        return VQ_ESHAPE;
-    if (eps_f16 < 0 || eps_f16 > 1 || xm_f16 < 0 || xm_f16 > 1) return VQ_EUNSUP;
-    const long total = (long)n * CI;
-    long blocks = ((total + V - 1) / V + 255) / 256;
-    if (blocks > 1024) blocks = 1024;                            // as vq_cfg_dpmpp_step: larger latents loop
-#define VQ_DDPM_LAUNCH(T_, V_)                                                                                         \
-    hipLaunchKernelGGL((cfg_ddpm_kernel<T_, V_>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,           \
-                       (const T_*)eps, x, noise, coef, step, x_out, x0_out, x_model, xm_f16, n, (long)inner, CI, ld_eps, \
-                       guided, row, n_rows)
-    if (e16) {
-        if (V == 4) VQ_DDPM_LAUNCH(half_t, 4); else VQ_DDPM_LAUNCH(half_t, 1);
-    } else {
-        if (V == 4) VQ_DDPM_LAUNCH(float, 4); else VQ_DDPM_LAUNCH(float, 1);
-    }
-#undef VQ_DDPM_LAUNCH
-    return vq_check_launch();
+    return step_launch(n, CI, V, eps_f16, [&](auto t, auto v, dim3 grid) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((cfg_ddpm_kernel<T, decltype(v)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)eps,
+                           x, noise, coef, step, x_out, x0_out, x_model, xm_f16, n, (long)inner, CI, ld_eps, guided, row,
+                           n_rows);
+    });
 }

@@ -17,6 +17,31 @@ from typing import Dict, Hashable, Optional, Tuple
 import torch
 
 
+def _capture(fn, warmup: int, first=None, debug: bool = False):
+    """One call of ``fn`` recorded as a HIP graph.  Before the capture, on a side stream: ``first`` (when given, and waited
+    for) and ``warmup`` calls of ``fn`` - they pack weights and fill the host-side caches (fused qkv weights, prompt K/V,
+    mask selection) with the capture's own launch pattern.  ``debug``: the graph keeps what ``debug_dump`` needs.
+    Returns (graph, what the recorded call returned)."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side), torch.no_grad():
+        if first is not None:
+            first()
+            side.synchronize()
+        for _ in range(warmup):
+            fn()
+        side.synchronize()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    if debug:
+        graph.enable_debug_mode()
+    # thread_local: with a process group alive (N > 1) the RCCL watchdog thread polls events while we capture; in
+    # the default 'global' mode such a call from ANOTHER thread would invalidate the capture
+    with torch.no_grad(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        out = fn()
+    return graph, out
+
+
 class StepGraph:
     """cond/uncond forwards of a QuantModel for one prompt as a replayable HIP graph."""
 
@@ -34,30 +59,23 @@ class StepGraph:
         self.yc, self.yu = y_cond.clone(), y_uncond.clone()
         self.mask = mask
         self.cfg_split = bool(getattr(qnn, "cfg_split", False))
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            # first pass on ONE stream: it packs weights and fills the module-level caches (fused qkv weights, prompt
-            # K/V, mask selection).  Run on two streams that pass would let the cond chain read a cached tensor that the
-            # uncond chain's stream is still producing - and such a tensor would persist into the captured graph
-            self._forward(timestep_id, serial=True)
-            side.synchronize()
-            for _ in range(warmup):                      # then the capture's own launch pattern
-                self._forward(timestep_id)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        dump = os.environ.get("VQ_GRAPH_DUMP")          # measurement: a .dot file of the captured graph (node census, bench.py)
-        if dump:
-            self.graph.enable_debug_mode()
         from . import _lib
-        calls0 = _lib.CALLS[0]
-        # thread_local: with a process group alive (N > 1) the RCCL watchdog thread polls events while we capture; in
-        # the default 'global' mode such a call from ANOTHER thread would invalidate the capture
-        with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self.cond, self.uncond = self._forward(timestep_id)
-        # C-ABI calls recorded into the graph (= its HIP-kernel nodes from this library: one launch per entry point, the
-        # fast quantizer entry points included; the ~60 torch elementwise kernels of the FP edges come on top)
-        self.c_abi_calls = _lib.CALLS[0] - calls0
+        dump = os.environ.get("VQ_GRAPH_DUMP")          # measurement: a .dot file of the captured graph (node census, bench.py)
+
+        def counted():
+            # C-ABI calls of one step; the last call is the recorded one (= the graph's HIP-kernel nodes from this library:
+            # one launch per entry point, the fast quantizer entry points included; the ~60 torch elementwise kernels of
+            # the FP edges come on top)
+            calls0 = _lib.CALLS[0]
+            out = self._forward(timestep_id)
+            self.c_abi_calls = _lib.CALLS[0] - calls0
+            return out
+
+        # first pass on ONE stream: it packs weights and fills the module-level caches.  Run on two streams that pass would
+        # let the cond chain read a cached tensor that the uncond chain's stream is still producing - and such a tensor
+        # would persist into the captured graph
+        self.graph, (self.cond, self.uncond) = _capture(counted, warmup, debug=bool(dump),
+                                                        first=lambda: self._forward(timestep_id, serial=True))
         self.dot_path = None
         if dump:
             try:
@@ -142,16 +160,7 @@ class ForwardGraph:
     def __init__(self, fn, x, t, y, kwargs, warmup: int = 2):
         self.x, self.t, self.y = x.clone(), t.clone(), y.clone()
         self.kwargs = kwargs
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(warmup + 1):                  # packs weights, fills the host-side caches (mask selection, ...)
-                fn(self.x, self.t, self.y, **kwargs)
-            side.synchronize()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self.out = fn(self.x, self.t, self.y, **kwargs)
+        self.graph, self.out = _capture(lambda: fn(self.x, self.t, self.y, **kwargs), warmup + 1)
 
     def run(self, x, t, y):
         self.x.copy_(x)
@@ -232,18 +241,21 @@ class GraphedModel:
         return g.run(x, t, y).clone()
 
 
-class DPMStepGraph:
-    """The guided DPM-Solver++ multistep loop of t2i/dpm_solver.py as ONE captured step: {forward(x_model, t, text),
-    ops.cfg_dpmpp_step(step=counter), ops.dpmpp_advance} recorded once and replayed for every timestep.  What changes
-    from step to step lives in device memory: the latent, the model-input time, the x0 history, and a counter that
-    selects the row of the coefficient table uploaded before the loop.  The captured graph is one linear chain.
-    A forward that moves host-visible state (a running smooth-quant statistic) cannot be captured and is refused."""
+class _CounterStepGraph:
+    """A fused sampling loop as ONE captured step: {forward(x_model, t, ...), the solver's fused step(step=counter),
+    ops.dpmpp_advance} recorded once as a linear chain and replayed for every timestep.  What changes from step to step
+    lives in device memory: the latent ``x``, its duplicated copy ``xm`` in the model's dtype, the model-input time ``t``,
+    and a counter ``step`` that selects the row of the coefficient table ``rows`` uploaded before the loop.  A subclass
+    supplies ``_forward()`` and ``_step(eps)`` (with the buffers of its own, allocated before this constructor runs) and
+    its ``run``.  A forward that moves host-visible state (a running smooth-quant statistic) cannot be captured and is
+    refused."""
 
-    def __init__(self, fn, text, kwargs, x, rows, t_first: float, model_dtype=torch.float32, warmup: int = 2):
+    def __init__(self, fn, kwargs, x, rows, t_first: float, model_dtype, warmup: int):
         from . import ops
         from ._lib import VQError
         if GraphedModel(fn)._state(kwargs.get("timestep_id"))[2]:
-            raise VQError("DPMStepGraph: a layer keeps a running smooth-quant statistic; its forward is not capturable")
+            raise VQError("%s: a layer keeps a running smooth-quant statistic; its forward is not capturable"
+                          % type(self).__name__)
         n = x.shape[0]
         dev = x.device
         self.steps, self.t_first = rows.shape[0], float(t_first)
@@ -251,100 +263,90 @@ class DPMStepGraph:
         self.x = x.float().contiguous().clone()
         self.xm = torch.cat([self.x, self.x]).to(model_dtype)
         self.t = torch.full((2 * n,), self.t_first, dtype=torch.float32, device=dev)
-        self.hist = torch.zeros((3, self.x.numel()), dtype=torch.float32, device=dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
 
         def one():
-            eps = fn(self.xm, self.t, text, **kwargs)
-            if not ops.cfg_dpmpp_step_ok(eps, self.x):
-                raise VQError("DPMStepGraph: vq_cfg_dpmpp_step does not take this model output")
-            ops.cfg_dpmpp_step(eps, self.x, self.hist, self.rows, 0, step=self.step, x_out=self.x, x_model=self.xm)
+            self._step(self._forward())
             ops.dpmpp_advance(self.step, self.rows, self.t)
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(warmup + 1):                  # packs weights, fills the host-side caches
-                one()
-            side.synchronize()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            one()
+        self.graph, _ = _capture(one, warmup + 1)        # (the counter and the time are reset by every loop, not here)
 
-    @torch.no_grad()
-    def run(self, x, step_callback=None):
-        n = x.shape[0]
+    def _refuse_output(self, entry_point):
+        from ._lib import VQError
+        raise VQError("%s: %s does not take this model output" % (type(self).__name__, entry_point))
+
+    def _loop(self, x, before=None, after=None):
+        """Start from the latent ``x`` [n, ...] and replay every step; ``before(k)`` / ``after(k)`` around replay k."""
+        n = self.x.shape[0]
         self.x.copy_(x)
         self.xm[:n].copy_(x)
         self.xm[n:].copy_(x)
         self.t.fill_(self.t_first)
         self.step.zero_()
         for k in range(self.steps):
+            if before is not None:
+                before(k)
             self.graph.replay()
-            if step_callback is not None:
-                step_callback(k + 1, self.x.clone())
+            if after is not None:
+                after(k)
+
+
+class DPMStepGraph(_CounterStepGraph):
+    """The guided DPM-Solver++ multistep loop of t2i/dpm_solver.py in the counter form: the step is ops.cfg_dpmpp_step,
+    whose x0 history is one more device buffer."""
+
+    def __init__(self, fn, text, kwargs, x, rows, t_first: float, model_dtype=torch.float32, warmup: int = 2):
+        self.fn, self.text, self.kwargs = fn, text, kwargs
+        self.hist = torch.zeros((3, x.numel()), dtype=torch.float32, device=x.device)
+        super().__init__(fn, kwargs, x, rows, t_first, model_dtype, warmup)
+
+    def _forward(self):
+        return self.fn(self.xm, self.t, self.text, **self.kwargs)
+
+    def _step(self, eps):
+        from . import ops
+        if not ops.cfg_dpmpp_step_ok(eps, self.x):
+            self._refuse_output("vq_cfg_dpmpp_step")
+        ops.cfg_dpmpp_step(eps, self.x, self.hist, self.rows, 0, step=self.step, x_out=self.x, x_model=self.xm)
+
+    @torch.no_grad()
+    def run(self, x, step_callback=None):
+        self._loop(x, after=None if step_callback is None else lambda k: step_callback(k + 1, self.x.clone()))
         return self.x.clone()
 
 
-class DDPMStepGraph:
-    """The fused IDDPM loop of t2i/iddpm.py as ONE captured step, as DPMStepGraph is for DPM-Solver++: {forward(x_model, t,
-    y, mask), ops.cfg_ddpm_step(step=counter), ops.dpmpp_advance} recorded once as a linear chain and replayed for every
-    timestep.  The step's noise lives in a static buffer of the duplicated shape, which ``run`` refills eagerly before each
-    replay - from ``noise_steps`` or with the draw the eager-launched loop makes - so a replay is bit-identical to that
-    loop.  A forward that moves host-visible state (a running smooth-quant statistic) is refused."""
+class DDPMStepGraph(_CounterStepGraph):
+    """The fused IDDPM loop of t2i/iddpm.py in the counter form: the step is ops.cfg_ddpm_step.  Its noise lives in a
+    static buffer of the duplicated shape, which ``run`` refills eagerly before each replay - from ``noise_steps`` or with
+    the draw the eager-launched loop makes - so a replay is bit-identical to that loop."""
 
     def __init__(self, fn, y, mask, kwargs, x, rows, t_first: float, model_dtype=torch.float32, guided: int = 3,
                  warmup: int = 2):
+        self.fn, self.y, self.mask, self.kwargs, self.guided = fn, y, mask, kwargs, guided
+        self.x0 = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+        self.noise = torch.zeros((2 * x.shape[0],) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+        super().__init__(fn, kwargs, x, rows, t_first, model_dtype, warmup)
+
+    def _forward(self):
+        return self.fn(self.xm, self.t, self.y, self.mask, **self.kwargs)
+
+    def _step(self, eps):
         from . import ops
-        from ._lib import VQError
-        if GraphedModel(fn)._state(kwargs.get("timestep_id"))[2]:
-            raise VQError("DDPMStepGraph: a layer keeps a running smooth-quant statistic; its forward is not capturable")
-        n = x.shape[0]
-        dev = x.device
-        self.steps, self.t_first = rows.shape[0], float(t_first)
-        self.rows = rows.to(dev)
-        self.x = x.float().contiguous().clone()
-        self.x0 = torch.empty_like(self.x)
-        self.xm = torch.cat([self.x, self.x]).to(model_dtype)
-        self.noise = torch.zeros((2 * n,) + tuple(x.shape[1:]), dtype=torch.float32, device=dev)
-        self.t = torch.full((2 * n,), self.t_first, dtype=torch.float32, device=dev)
-        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
-
-        def one():
-            eps = fn(self.xm, self.t, y, mask, **kwargs)
-            if not ops.cfg_ddpm_step_ok(eps, self.x):
-                raise VQError("DDPMStepGraph: vq_cfg_ddpm_step does not take this model output")
-            ops.cfg_ddpm_step(eps, self.x, self.noise[:n], self.rows, 0, step=self.step, x_out=self.x, x0_out=self.x0,
-                              x_model=self.xm, guided=guided)
-            ops.dpmpp_advance(self.step, self.rows, self.t)
-
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(warmup + 1):                  # packs weights, fills the host-side caches
-                one()
-            side.synchronize()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            one()
+        if not ops.cfg_ddpm_step_ok(eps, self.x):
+            self._refuse_output("vq_cfg_ddpm_step")
+        ops.cfg_ddpm_step(eps, self.x, self.noise[:self.x.shape[0]], self.rows, 0, step=self.step, x_out=self.x,
+                          x0_out=self.x0, x_model=self.xm, guided=self.guided)
 
     @torch.no_grad()
     def run(self, x, noise_steps=None, generator=None, step_callback=None):
         """``x``: the duplicated start latent [2n, ...] (its first half is read) -> ``cat([x, x])`` of the sample."""
-        n = self.x.shape[0]
-        self.x.copy_(x[:n])
-        self.xm[:n].copy_(x[:n])
-        self.xm[n:].copy_(x[:n])
-        self.t.fill_(self.t_first)
-        self.step.zero_()
-        for k in range(self.steps):
+        def refill(k):
             if noise_steps is not None:
                 self.noise.copy_(noise_steps[k])
             else:
                 self.noise.normal_(generator=generator)
-            self.graph.replay()
-            if step_callback is not None:
-                step_callback(self.steps - 1 - k, self.x.clone(), self.x0.clone())
+
+        self._loop(x[:self.x.shape[0]], before=refill, after=None if step_callback is None else
+                   lambda k: step_callback(self.steps - 1 - k, self.x.clone(), self.x0.clone()))
         return torch.cat([self.x, self.x])
+

@@ -1070,7 +1070,10 @@ def cfg_ddim_step(cond: torch.Tensor, uncond: torch.Tensor, x: torch.Tensor, cfg
     return out
 
 
-# --------------------------------------------------------------------------- DPM-Solver++ step (t2i sampling loop)
+# --------------------------------------------------------------------------- the fused steps of the t2i sampling loops
+# DPM-Solver++ (vq_cfg_dpmpp_step) and the IDDPM posterior step (vq_cfg_ddpm_step) read the same kind of model output:
+# [2n] elements of elem_mult * C * inner values, an element dense, the batch pitch free.  elem_mult is 1 for DPM-Solver++
+# (eps [2n, C, ...]) and 2 for IDDPM (the learned-variance channels are in the element: eps [2n, 2C, ...]).
 def _dense_strides(shape):
     out, acc = [], 1
     for d in reversed(shape):
@@ -1079,11 +1082,11 @@ def _dense_strides(shape):
     return tuple(reversed(out))
 
 
-def _dpmpp_geometry(eps, x):
-    """(n, C, inner, ld_eps) of a step, or None when eps is not the [2n] x [C * inner] model output the kernel reads:
-    dense within a batch element, batch pitch free.  Shapes and strides only (no tensor is touched)."""
+def _step_geometry(eps, x, elem_mult):
+    """(n, C, inner, ld_eps) of a step, or None when eps is not the model output described above for the latent ``x``
+    [n, C, ...].  Shapes and strides only (no tensor is touched)."""
     es, xs = tuple(eps.shape), tuple(x.shape)
-    if len(xs) < 2 or len(es) != len(xs) or es[0] != 2 * xs[0] or es[1:] != xs[1:]:
+    if len(xs) < 2 or len(es) != len(xs) or es[0] != 2 * xs[0] or es[1] != elem_mult * xs[1] or es[2:] != xs[2:]:
         return None
     inner = 1
     for d in xs[2:]:
@@ -1093,47 +1096,43 @@ def _dpmpp_geometry(eps, x):
     return int(xs[0]), int(xs[1]), inner, int(eps.stride()[0])
 
 
-def cfg_dpmpp_step_ok(eps, x) -> bool:
-    """The refusals of vq_cfg_dpmpp_step (include/viditq.h) for a model output ``eps`` [2n, C, ...] and a latent ``x``
-    [n, C, ...], asked before the launch: GPU tensors, fp32 x, fp16 / fp32 eps (VQ_EUNSUP), positive extents (VQ_EINVAL),
-    and VQ_ESHAPE: the layout, ld_eps >= C * inner, and - the kernel moves 4 elements per access when inner % 4 == 0 -
-    the pitch and both base addresses on that many elements."""
+def _step_ok(eps, x, elem_mult) -> bool:
+    """The refusals of a step entry point (include/viditq.h) that depend on eps and x, asked before the launch: GPU
+    tensors, fp32 x, fp16 / fp32 eps (VQ_EUNSUP), positive extents (VQ_EINVAL), and VQ_ESHAPE: the layout, ld_eps >=
+    elem_mult * C * inner, and - the kernel moves 4 elements per access when inner % 4 == 0 - the pitch and both base
+    addresses on that many elements."""
     if not (eps.is_cuda and x.is_cuda):
         return False
     if x.dtype != torch.float32 or eps.dtype not in (torch.float16, torch.float32):
         return False
-    geo = _dpmpp_geometry(eps, x)
+    geo = _step_geometry(eps, x, elem_mult)
     if geo is None:
         return False
     n, Cc, inner, ld = geo
     if n <= 0 or Cc <= 0 or inner <= 0:
         return False
     V = 4 if inner % 4 == 0 else 1
-    return (ld >= Cc * inner and ld % V == 0 and eps.data_ptr() % (eps.element_size() * V) == 0
+    return (ld >= elem_mult * Cc * inner and ld % V == 0 and eps.data_ptr() % (eps.element_size() * V) == 0
             and x.data_ptr() % (4 * V) == 0)
 
 
-def cfg_dpmpp_step(eps: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, coef: torch.Tensor, row: int,
-                   step: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None,
-                   x_model: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """One call of the fused guidance + x0 + DPM-Solver++ multistep update (vq_cfg_dpmpp_step): ``eps`` [2n, C, ...] the
-    (uncond | cond) model output (fp16 / fp32, batch pitch free), ``x`` [n, C, ...] fp32, ``hist`` [3, n*C*inner] fp32,
-    ``coef`` [n_rows, DPMPP_ROW] fp32 on the device; the row is ``row`` plus the device counter ``step`` (int32, one
-    element) when given.  Returns x_out (may be ``x`` itself); ``x_model`` [2n, C, ...] (fp16 / fp32) receives it twice."""
-    for t, name in ((eps, "eps"), (x, "x"), (hist, "hist"), (coef, "coef")):
+def _step_front(eps, x, aux, aux_name, coef, elem_mult, layout, refuse, step, x_out, x_model):
+    """What both step wrappers do before their launch: GPU tensors, fp32 x / ``aux`` (hist or noise) / coef, fp16 / fp32
+    eps, the geometry (else the solver's ``layout`` message), the solver's own clause ``refuse`` = (bad, message), the
+    counter, x_out (allocated when None) and x_model.  Returns (n, C, inner, ld_eps, x_out, xm_f16)."""
+    for t, name in ((eps, "eps"), (x, "x"), (aux, aux_name), (coef, "coef")):
         if not t.is_cuda:
             raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % name)
     _req(x, torch.float32, "x")
-    _req(hist, torch.float32, "hist")
+    _req(aux, torch.float32, aux_name)
     _req(coef, torch.float32, "coef")
     if eps.dtype not in (torch.float16, torch.float32):
         raise VQError("eps must be float16 or float32, got %s" % eps.dtype)
-    geo = _dpmpp_geometry(eps, x)
+    geo = _step_geometry(eps, x, elem_mult)
     if geo is None:
-        raise VQError("eps must be [2n, C, ...] for x [n, C, ...], dense within a batch element")
-    n, Cc, inner, ld = geo
-    if hist.numel() != 3 * x.numel() or coef.dim() != 2 or coef.shape[1] != _lib.DPMPP_ROW:
-        raise VQError("hist must hold 3 x %d fp32 and coef rows of %d floats" % (x.numel(), _lib.DPMPP_ROW))
+        raise VQError("eps must be %s for x [n, C, ...], dense within a batch element" % layout)
+    if refuse[0]:
+        raise VQError(refuse[1])
     if step is not None:
         _req(step, torch.int32, "step")
     if x_out is None:
@@ -1147,6 +1146,25 @@ def cfg_dpmpp_step(eps: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, coef:
             raise VQError("x_model must be a contiguous float16 or float32 GPU tensor")
         assert x_model.numel() == 2 * x.numel()
         xm16 = int(x_model.dtype == torch.float16)
+    return (*geo, x_out, xm16)
+
+
+def cfg_dpmpp_step_ok(eps, x) -> bool:
+    """Whether vq_cfg_dpmpp_step takes a model output ``eps`` [2n, C, ...] and a latent ``x`` [n, C, ...] (_step_ok)."""
+    return _step_ok(eps, x, 1)
+
+
+def cfg_dpmpp_step(eps: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, coef: torch.Tensor, row: int,
+                   step: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None,
+                   x_model: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One call of the fused guidance + x0 + DPM-Solver++ multistep update (vq_cfg_dpmpp_step): ``eps`` [2n, C, ...] the
+    (uncond | cond) model output (fp16 / fp32, batch pitch free), ``x`` [n, C, ...] fp32, ``hist`` [3, n*C*inner] fp32,
+    ``coef`` [n_rows, DPMPP_ROW] fp32 on the device; the row is ``row`` plus the device counter ``step`` (int32, one
+    element) when given.  Returns x_out (may be ``x`` itself); ``x_model`` [2n, C, ...] (fp16 / fp32) receives it twice."""
+    bad = hist.numel() != 3 * x.numel() or coef.dim() != 2 or coef.shape[1] != _lib.DPMPP_ROW
+    n, Cc, inner, ld, x_out, xm16 = _step_front(
+        eps, x, hist, "hist", coef, 1, "[2n, C, ...]",
+        (bad, "hist must hold 3 x %d fp32 and coef rows of %d floats" % (x.numel(), _lib.DPMPP_ROW)), step, x_out, x_model)
     check(_L().vq_cfg_dpmpp_step(_p(eps), _p(x), _p(hist), _p(coef), _p(step), _p(x_out), _p(x_model), n, Cc, inner, ld,
                                  int(row), coef.shape[0], int(eps.dtype == torch.float16), xm16, _stream()),
           "vq_cfg_dpmpp_step")
@@ -1155,7 +1173,8 @@ def cfg_dpmpp_step(eps: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, coef:
 
 def dpmpp_advance(step: torch.Tensor, coef: torch.Tensor, t_out: torch.Tensor) -> None:
     """t_out[:] = the counter's row's next model-input time, then the counter moves on (saturating at the last row):
-    vq_dpmpp_advance, enqueued after cfg_dpmpp_step(step=counter)."""
+    vq_dpmpp_advance, enqueued after cfg_dpmpp_step(step=counter) or cfg_ddpm_step(step=counter) (T_NEXT is the same
+    column in both row layouts)."""
     _req(step, torch.int32, "step")
     _req(coef, torch.float32, "coef")
     _req(t_out, torch.float32, "t_out")
@@ -1163,39 +1182,9 @@ def dpmpp_advance(step: torch.Tensor, coef: torch.Tensor, t_out: torch.Tensor) -
     check(_L().vq_dpmpp_advance(_p(step), _p(coef), coef.shape[0], _p(t_out), t_out.numel(), _stream()), "vq_dpmpp_advance")
 
 
-# --------------------------------------------------------------------------- IDDPM posterior step (t2i sampling loop)
-def _ddpm_geometry(eps, x):
-    """(n, C, inner, ld_eps) of a step, or None when eps is not the [2n] x [2C * inner] model output the kernel reads:
-    an element (2C * inner) dense, batch pitch free - _dpmpp_geometry with the learned-variance channels in the element."""
-    es, xs = tuple(eps.shape), tuple(x.shape)
-    if len(xs) < 2 or len(es) != len(xs) or es[0] != 2 * xs[0] or es[1] != 2 * xs[1] or es[2:] != xs[2:]:
-        return None
-    inner = 1
-    for d in xs[2:]:
-        inner *= int(d)
-    if tuple(x.stride()) != _dense_strides(xs) or tuple(eps.stride())[1:] != _dense_strides(es)[1:]:
-        return None
-    return int(xs[0]), int(xs[1]), inner, int(eps.stride()[0])
-
-
 def cfg_ddpm_step_ok(eps, x) -> bool:
-    """The refusals of vq_cfg_ddpm_step (include/viditq.h) for a model output ``eps`` [2n, 2C, ...] and a latent ``x``
-    [n, C, ...], asked before the launch: GPU tensors, fp32 x, fp16 / fp32 eps (VQ_EUNSUP), positive extents (VQ_EINVAL),
-    and VQ_ESHAPE: the layout, ld_eps >= 2 * C * inner, and - four elements per access when inner % 4 == 0 - the pitch and
-    both base addresses on that many elements."""
-    if not (eps.is_cuda and x.is_cuda):
-        return False
-    if x.dtype != torch.float32 or eps.dtype not in (torch.float16, torch.float32):
-        return False
-    geo = _ddpm_geometry(eps, x)
-    if geo is None:
-        return False
-    n, Cc, inner, ld = geo
-    if n <= 0 or Cc <= 0 or inner <= 0:
-        return False
-    V = 4 if inner % 4 == 0 else 1
-    return (ld >= 2 * Cc * inner and ld % V == 0 and eps.data_ptr() % (eps.element_size() * V) == 0
-            and x.data_ptr() % (4 * V) == 0)
+    """Whether vq_cfg_ddpm_step takes a model output ``eps`` [2n, 2C, ...] and a latent ``x`` [n, C, ...] (_step_ok)."""
+    return _step_ok(eps, x, 2)
 
 
 def cfg_ddpm_step(eps: torch.Tensor, x: torch.Tensor, noise: torch.Tensor, coef: torch.Tensor, row: int,
@@ -1207,37 +1196,15 @@ def cfg_ddpm_step(eps: torch.Tensor, x: torch.Tensor, noise: torch.Tensor, coef:
     [n_rows, DDPM_ROW] fp32 on the device; the row is ``row`` plus the device counter ``step`` (int32, one element) when
     given.  Returns x_out (may be ``x`` itself); ``x0_out`` receives pred_xstart, ``x_model`` [2n, C, ...] (fp16 / fp32)
     the sample twice."""
-    for t, name in ((eps, "eps"), (x, "x"), (noise, "noise"), (coef, "coef")):
-        if not t.is_cuda:
-            raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % name)
-    _req(x, torch.float32, "x")
-    _req(noise, torch.float32, "noise")
-    _req(coef, torch.float32, "coef")
-    if eps.dtype not in (torch.float16, torch.float32):
-        raise VQError("eps must be float16 or float32, got %s" % eps.dtype)
-    geo = _ddpm_geometry(eps, x)
-    if geo is None:
-        raise VQError("eps must be [2n, 2C, ...] for x [n, C, ...], dense within a batch element")
-    n, Cc, inner, ld = geo
-    if noise.shape != x.shape or coef.dim() != 2 or coef.shape[1] != _lib.DDPM_ROW:
-        raise VQError("noise must have x's shape and coef rows of %d floats" % _lib.DDPM_ROW)
-    if step is not None:
-        _req(step, torch.int32, "step")
-    if x_out is None:
-        x_out = torch.empty_like(x)
-    else:
-        _req(x_out, torch.float32, "x_out")
-        assert x_out.shape == x.shape
+    bad = noise.shape != x.shape or coef.dim() != 2 or coef.shape[1] != _lib.DDPM_ROW
+    n, Cc, inner, ld, x_out, xm16 = _step_front(
+        eps, x, noise, "noise", coef, 2, "[2n, 2C, ...]",
+        (bad, "noise must have x's shape and coef rows of %d floats" % _lib.DDPM_ROW), step, x_out, x_model)
     if x0_out is not None:
         _req(x0_out, torch.float32, "x0_out")
         assert x0_out.shape == x.shape
-    xm16 = 0
-    if x_model is not None:
-        if not x_model.is_cuda or not x_model.is_contiguous() or x_model.dtype not in (torch.float16, torch.float32):
-            raise VQError("x_model must be a contiguous float16 or float32 GPU tensor")
-        assert x_model.numel() == 2 * x.numel()
-        xm16 = int(x_model.dtype == torch.float16)
     check(_L().vq_cfg_ddpm_step(_p(eps), _p(x), _p(noise), _p(coef), _p(step), _p(x_out), _p(x0_out), _p(x_model), n, Cc,
                                 inner, ld, int(guided), int(row), coef.shape[0], int(eps.dtype == torch.float16), xm16,
                                 _stream()), "vq_cfg_ddpm_step")
     return x_out
+

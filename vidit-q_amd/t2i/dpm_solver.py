@@ -381,46 +381,34 @@ class DPMSolverPP:
             fused = _DPM_FUSED
         return bool(fused) and method == "multistep" and self.cfg_scale != 1.0 and self.uncondition is not None and x.is_cuda
 
-    def _device_table(self, dev, n, args):
-        """(coefficient table, model-input times of calls 1 .. steps - 1 as [steps, 2n]) on the device for one sampling
-        configuration ``args`` = the arguments of multistep_rows; kept, so that the next sample() with the same
-        configuration uploads nothing."""
-        from .. import _lib
-        key = (args, self.cfg_scale, str(dev), n)
-        hit = self._tables.get(key)
-        if hit is None:
-            rows = self.multistep_rows(*args)
-            t_next = rows[:, _lib.DPMPP_T_NEXT][:, None].expand(rows.shape[0], 2 * n).contiguous()
-            # pinned and non-blocking: a pageable upload makes the host wait for the forward that is already queued
-            hit = (rows.pin_memory().to(dev, non_blocking=True), t_next.pin_memory().to(dev, non_blocking=True))
-            if len(self._tables) >= 8:
-                self._tables.clear()
-            self._tables[key] = hit
-        return hit
-
     def _multistep_fused(self, x, ts, args, step_callback):
-        """The multistep loop with one launch behind each model call.  Returns (x, None), or (None, eps) when the first
-        model output is not one the kernel takes (ops.cfg_dpmpp_step_ok): the caller goes on eagerly from it."""
+        """The multistep loop with one launch behind each model call (fused_loop).  ``args``: the arguments of
+        multistep_rows, which with the guidance scale, the device and n name the device table.  Returns (x, None), or
+        (None, eps) when the first model output is not one the kernel takes (ops.cfg_dpmpp_step_ok): the caller goes on
+        eagerly from it."""
         from .. import ops
+        from .fused_loop import device_table, fused_loop
         n, steps, order = x.shape[0], args[0], args[1]
         x = x.float().contiguous() if x.dtype != torch.float32 or not x.is_contiguous() else x
         xm = torch.cat([x, x]).to(self.model_input_dtype)
         hist = torch.empty((3, x.numel()), dtype=torch.float32, device=x.device)
         text = self._joint_text()
         t = torch.full((2 * n,), self._t_val(ts[0]), dtype=torch.float32, device=x.device)
-        for k in range(steps):
-            eps = self.model(xm, t, text, **self.model_kwargs)
-            if k == 0:
-                if not ops.cfg_dpmpp_step_ok(eps, x):
-                    return None, eps
-                # the table is built (host work) and uploaded behind the first forward's launches, not in front of them
-                rows, t_next = self._device_table(x.device, n, args)
+
+        def table(eps, x):
+            if not ops.cfg_dpmpp_step_ok(eps, x):
+                return None
+            return device_table(self._tables, (args, self.cfg_scale, str(x.device), n),
+                                lambda: self.multistep_rows(*args), x.device, n)
+
+        def step(k, eps, x, rows):
             # a fresh x_out per step: what a step_callback was handed is never written again
             x = ops.cfg_dpmpp_step(eps, x, hist, rows, k, x_model=xm)
-            t = t_next[k]
             if step_callback is not None and k + 1 >= order:
                 step_callback(k + 1, x)
-        return x, None
+            return x
+
+        return fused_loop(steps, x, xm, t, lambda xm, t: self.model(xm, t, text, **self.model_kwargs), table, step)
 
     def step_graph(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type="time_uniform", lower_order_final=True,
                    solver_type="dpmsolver"):

@@ -225,22 +225,6 @@ class SpacedDiffusion:
             return None
         return net
 
-    def _device_table(self, dev, n, cfg_scale, clip_denoised):
-        """(coefficient table, model-input times of the following forwards as [steps, 2n]) on the device; kept, so that
-        the next loop with the same configuration uploads nothing."""
-        from .. import _lib
-        key = (float(cfg_scale), bool(clip_denoised), str(dev), n)
-        hit = self._tables.get(key)
-        if hit is None:
-            rows = self.step_rows(cfg_scale, clip_denoised)
-            t_next = rows[:, _lib.DDPM_T_NEXT][:, None].expand(rows.shape[0], 2 * n).contiguous()
-            # pinned and non-blocking: a pageable upload makes the host wait for the forward that is already queued
-            hit = (rows.pin_memory().to(dev, non_blocking=True), t_next.pin_memory().to(dev, non_blocking=True))
-            if len(self._tables) >= 8:
-                self._tables.clear()
-            self._tables[key] = hit
-        return hit
-
     @staticmethod
     def _split_kwargs(model_kwargs):
         kw = dict(model_kwargs)
@@ -248,9 +232,10 @@ class SpacedDiffusion:
 
     @torch.no_grad()
     def _loop_fused(self, net, img, clip_denoised, model_kwargs, noise_steps, generator, step_callback):
-        """The loop with one launch behind each model call.  Returns (x, None), or (None, model output) when the first
-        model output is not one the kernel takes (ops.cfg_ddpm_step_ok): the caller goes on eagerly from it."""
+        """The loop with one launch behind each model call (fused_loop).  Returns (x, None), or (None, model output) when
+        the first model output is not one the kernel takes (ops.cfg_ddpm_step_ok): the caller goes on eagerly from it."""
         from .. import ops
+        from .fused_loop import device_table, fused_loop
         n = img.shape[0] // 2
         y, cfg_scale, mask, kw = self._split_kwargs(model_kwargs)
         x = img[:n].contiguous()
@@ -258,23 +243,25 @@ class SpacedDiffusion:
         # the model-input time as fp32, which the counter form writes on the device; the nets cast it to their own dtype,
         # as they cast the reference's int64
         t = torch.full((2 * n,), float(self.timestep_map[-1]), dtype=torch.float32, device=x.device)
-        for k in range(self.num_timesteps):
-            eps = net.forward(xm, t, y, mask, **kw)
-            if k == 0:
-                if not ops.cfg_ddpm_step_ok(eps, x):
-                    return None, eps
-                # the table is built (host work) and uploaded behind the first forward's launches, not in front of them
-                rows, t_next = self._device_table(x.device, n, cfg_scale, clip_denoised)
+
+        def table(eps, x):
+            if not ops.cfg_ddpm_step_ok(eps, x):
+                return None
+            return device_table(self._tables, (float(cfg_scale), bool(clip_denoised), str(x.device), n),
+                                lambda: self.step_rows(cfg_scale, clip_denoised), x.device, n)
+
+        def step(k, eps, x, rows):
             # the draw of the duplicated shape, as randn_like(x) of the reference: the RNG stream is the eager route's
             z = noise_steps[k] if noise_steps is not None else torch.randn(
                 img.shape, generator=generator, device=x.device, dtype=torch.float32)
             x0 = torch.empty_like(x) if step_callback is not None else None
             # a fresh x_out per step: what a step_callback was handed is never written again
             x = ops.cfg_ddpm_step(eps, x, z[:n], rows, k, x0_out=x0, x_model=xm, guided=GUIDED)
-            t = t_next[k]
             if step_callback is not None:
                 step_callback(self.num_timesteps - 1 - k, x, x0)
-        return x, None
+            return x
+
+        return fused_loop(self.num_timesteps, x, xm, t, lambda xm, t: net.forward(xm, t, y, mask, **kw), table, step)
 
     def p_sample_graph(self, model, noise, clip_denoised=True, model_kwargs=None):
         """The counter form of the fused loop: {forward, fused step, counter advance} captured once as a HIP graph and
