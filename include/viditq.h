@@ -611,6 +611,60 @@ int vq_cfg_ddpm_step(const void* eps, const float* x, const float* noise, const 
                      float* x_out, float* x0_out, void* x_model, int n, int C, int inner, long ld_eps, int guided,
                      int row, int n_rows, int eps_f16, int xm_f16, void* stream);
 
+/* Fused CFG + x0 + SA-Solver corrector + next predictor: ONE launch per model call of the PixArt SA-Solver loop
+ * (SASolverSampler.sample, t2i/diffusion/sa_sampler.py:75-92: 'few_steps', PEC, predictor 2, corrector 2).  Replaces
+ * model_wrapper's guidance (t2i/diffusion/model/sa_solver.py:297-322), data_prediction_fn (:377-386), the corrector
+ * adams_moulton_update_few_steps (:700-753) of loop step k and the predictor adams_bashforth_update_few_steps (:644-698) of
+ * loop step k + 1 (sample_few_steps :755-909); the final, predictor-only step (tau = 0, order 1, no model call) is the
+ * predictor half of the last call, so S launches serve S model calls and the last launch's xp_out is the result.
+ * For call number k (0-based) = clamp(row + (step ? *step : 0), 0, n_rows - 1), per element of [n, C, inner]:
+ *   u = eps[b], c = eps[n + b]           eps: the model's output for the (uncond | cond) batch, [2n] x [C*inner], batch
+ *                                        pitch ld_eps elements; fp32 (eps_f16 = 0) or fp16 (1)
+ *   e   = u + cfg * (c - u)
+ *   m_k = (xp - sigma * e) / alpha                                          -> hist[k % 2]     hist: [2, n*C*inner] fp32
+ *   OC == 0 (call 0):  xc = x
+ *   OC >= 1:           g  = CG0 * m_k;  if OC == 2: g = g + CG1 * m_{k-1}
+ *                      xc = (CX * x + g) + CN * noise[k % 2]                -> x_out
+ *   OP >= 1:           q  = PG0 * m_k;  if OP == 2: q = q + PG1 * m_{k-1}
+ *                      xq = (PX * xc + q) + PN * noise[(k + 1) % 2]         -> xp_out, x_model   (OP == 0: xq = xc)
+ *   with m_{k-1} = hist[(k - 1) % 2], each expression evaluated left to right.
+ * x: the corrected sample of the previous loop step, xp: the predicted sample the model just saw, both fp32 [n, C, inner];
+ * x_out may alias x and xp_out may alias xp.  noise: fp32 [2, n*C*inner], a ring: slot (k + 1) % 2 holds the draw of loop
+ * step k + 1, written by the host before call k.  m_{k-1} is read only when an order is 2, noise[k % 2] only when OC >= 1.
+ * x_model: NULL, or the next forward's input [2n, C, inner] in fp32 (xm_f16 = 0) or fp16 (1): both halves receive xq.
+ * Coefficient row: VQ_SA_ROW floats, the indices below; unused slots are zero.  The row has the size of the DPM-Solver++ row
+ * and keeps the next model-input time in the same slot (VQ_SA_T_NEXT == VQ_DPMPP_T_NEXT), so vq_dpmpp_advance serves as
+ * the counter and time kernel of this step unchanged - which is why the orders stop at 2 (the released configuration);
+ * an order outside {0, 1, 2} in the table is the host's to avoid.  step: as for vq_cfg_dpmpp_step.
+ * Numerics: bit-identical to the eager torch expressions on the same device and to an fp32 model that rounds every
+ * operation on its own.  Nothing is contracted; with fp16 eps, c - u, cfg * (.) and u + (.) are each rounded to fp16,
+ * sigma * e is an fp32 product (sigma_t is a one-element fp32 tensor in the eager path: it promotes) and the division by
+ * alpha is the correctly rounded fp32 division.  No transcendental.
+ * Refusals, in this order, before any HIP call or dereference.  VQ_EINVAL: a null eps / x / xp / hist / noise / coef /
+ * x_out / xp_out; n / C / inner / n_rows <= 0; row outside [0, n_rows).  VQ_ESHAPE: ld_eps < C*inner; the kernel moves 4
+ * elements per access when inner % 4 == 0 (else 1): ld_eps not a multiple of that, or eps / x / xp / hist / noise / x_out /
+ * xp_out / x_model not aligned to that many elements; coef / step off 4 bytes.  VQ_EUNSUP: eps_f16 or xm_f16 outside
+ * {0, 1}. */
+#define VQ_SA_ROW 16           /* floats per row (== VQ_DPMPP_ROW) */
+#define VQ_SA_CFG 0            /* guidance scale */
+#define VQ_SA_SIGMA 1          /* sigma_t of this call's time (data_prediction_fn) */
+#define VQ_SA_ALPHA 2          /* alpha_t of this call's time */
+#define VQ_SA_OC 3             /* corrector order of loop step k: 0 (call 0: none), 1 or 2 */
+#define VQ_SA_CX 4             /* exp(-tau^2 h) * (sigma_t / sigma_prev), step k-1 -> k */
+#define VQ_SA_CG0 5            /* ((1 + tau^2) * sigma_t) * exp(-tau^2 lambda_t) * gc[0] */
+#define VQ_SA_CG1 6            /* ... * gc[1] (OC == 2) */
+#define VQ_SA_CN 7             /* sigma_t * sqrt(1 - exp(-2 tau^2 h)) */
+#define VQ_SA_OP 8             /* predictor order of loop step k + 1: 1 or 2 */
+#define VQ_SA_PX 9             /* as CX, for the step k -> k+1 with that step's tau (last row: tau = 0) */
+#define VQ_SA_PG0 10           /* as CG0 */
+#define VQ_SA_PG1 11           /* as CG1 (OP == 2) */
+#define VQ_SA_PN 12            /* as CN */
+#define VQ_SA_T_NEXT 14        /* model-input time of the NEXT forward (== VQ_DPMPP_T_NEXT) */
+                               /* 13, 15: zero */
+int vq_cfg_sa_step(const void* eps, const float* x, const float* xp, float* hist, const float* noise, const float* coef,
+                   const int32_t* step, float* x_out, float* xp_out, void* x_model, int n, int C, int inner, long ld_eps,
+                   int row, int n_rows, int eps_f16, int xm_f16, void* stream);
+
 /* ---- floating-point Linears at the edges of a forward -------------------------------------
  * out[m, n] = act_out( sum_k act_in(x[m, k]) * w[n, k] + bias[n] ): fp16 operands and result, fp32 accumulation (MFMA),
  * act: 0 none, 1 SiLU, 2 GELU(tanh).  Replaces F.linear of the layers the reference's FP lists keep out of quantization

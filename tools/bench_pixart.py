@@ -17,7 +17,7 @@ import viditq_amd  # noqa
 from viditq_amd import synth
 from viditq_amd.config import to_config
 from viditq_amd.qdiff.models import QuantModel
-from viditq_amd.t2i import DPMS_sigma, IDDPM, PixArtMS_XL_2
+from viditq_amd.t2i import DPMS_sigma, IDDPM, PixArtMS_XL_2, SASolverSampler
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--w-bits", type=int, default=4)
@@ -28,9 +28,12 @@ ap.add_argument("--graph", action="store_true", help="replay the forward as one 
 ap.add_argument("--fused-step", action="store_true",
                 help="guidance + x0 + multistep update in one launch per model call (ops.cfg_dpmpp_step); with --graph the whole "
                      "step {forward, fused step, counter advance} is ONE captured graph replayed per timestep (graph.DPMStepGraph)")
-ap.add_argument("--sampler", choices=("dpm", "iddpm"), default="dpm",
+ap.add_argument("--sampler", choices=("dpm", "iddpm", "sa"), default="dpm",
                 help="iddpm: the ancestral loop of --sampling_algo iddpm (t2i/iddpm.py, IDDPM(str(steps)).p_sample_loop("
-                     "forward_with_cfg)); --fused-step is then ops.cfg_ddpm_step and --fused-step --graph graph.DDPMStepGraph")
+                     "forward_with_cfg)); --fused-step is then ops.cfg_ddpm_step and --fused-step --graph graph.DDPMStepGraph.  "
+                     "sa: the SA-Solver loop of --sampling_algo sa-solver (t2i/sa_solver.py, SASolverSampler.sample: few_steps, "
+                     "PEC, predictor 2, corrector 2, eta 1); --fused-step is then ops.cfg_sa_step and --fused-step --graph "
+                     "graph.SAStepGraph")
 ap.add_argument("--alternate", type=int, default=0,
                 help="N > 0: time the arms eager / fused-step / graph / fused-step+graph N times in turn in THIS process "
                      "(same weights, same latent) and print one JSON line with every figure, the GEMM clock probe and the "
@@ -90,10 +93,33 @@ with torch.no_grad():
                                    generator=gen).chunk(2, dim=0)[0]
         return run
 
+    def make_sa_arm(graph, fused):
+        """The same four arms for the SA-Solver loop.  Every run draws its noise from a generator seeded alike, so the arms
+        see the same 1 + steps draws."""
+        gm = GraphedModel(qnn.forward_with_dpmsolver, qnn=qnn)
+        smp = SASolverSampler(gm if graph and not fused else qnn.forward_with_dpmsolver, device=dev)
+        if fused:
+            smp.model_input_dtype = torch.float16
+        sgs = {}
+        tau = lambda t: 1 if 0.2 <= t <= 0.8 else 0   # noqa: E731  (sa_sampler.py:90 with eta = 1)
+
+        def run(steps):
+            gen = torch.Generator(device=dev).manual_seed(3)
+            if graph and fused:
+                if steps not in sgs:
+                    sgs[steps] = smp.solver(y, null_y, 4.5, kw["model_kwargs"]).step_graph(z, tau, steps)
+                return sgs[steps].run(z, generator=gen)
+            return smp.sample(steps, z.shape[0], tuple(z.shape[1:]), conditioning=y, unconditional_conditioning=null_y,
+                              unconditional_guidance_scale=4.5, eta=1, x_T=z, model_kwargs=kw["model_kwargs"], fused=fused,
+                              generator=gen)[0]
+        return run
+
     def make_arm(graph, fused):
         """sample(steps) -> latent for one arm; built (and its graphs captured) once."""
         if a.sampler == "iddpm":
             return make_iddpm_arm(graph, fused)
+        if a.sampler == "sa":
+            return make_sa_arm(graph, fused)
         if graph and fused:
             s = DPMS_sigma(qnn.forward_with_dpmsolver, **kw)
             s.model_input_dtype = torch.float16
@@ -121,8 +147,8 @@ with torch.no_grad():
 
     workload = "PixArt-Sigma %dx%d W%dA8, %d tokens, Lp %d, %s, cfg 4.5, batched %s forward" % (
         a.size, a.size, a.w_bits, (lat // 2) ** 2, Lp,
-        "DPM-Solver++ 2M" if a.sampler == "dpm" else "IDDPM ancestral (learned-range variance)",
-        "uncond|cond" if a.sampler == "dpm" else "cond|uncond")
+        {"dpm": "DPM-Solver++ 2M", "iddpm": "IDDPM ancestral (learned-range variance)",
+         "sa": "SA-Solver few_steps PEC P2/C2 eta 1"}[a.sampler], "cond|uncond" if a.sampler == "iddpm" else "uncond|cond")
     if a.alternate > 0:
         import bench
         arms = {"eager": make_arm(False, False), "fused_step": make_arm(False, True), "graph": make_arm(True, False),

@@ -61,6 +61,7 @@ SIGNATURES = {
     "vq_cfg_dpmpp_step": (_i, [_vp] * 7 + [_i, _i, _i, _l, _i, _i, _i, _i, _vp]),
     "vq_dpmpp_advance": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     "vq_cfg_ddpm_step": (_i, [_vp] * 8 + [_i, _i, _i, _l, _i, _i, _i, _i, _i, _vp]),
+    "vq_cfg_sa_step": (_i, [_vp] * 10 + [_i, _i, _i, _l, _i, _i, _i, _i, _vp]),
 }
 
 # the coefficient row of vq_cfg_dpmpp_step (include/viditq.h, VQ_DPMPP_*)
@@ -71,6 +72,10 @@ DPMPP_ROW = 16
 DDPM_ROW = 16
 (DDPM_CFG, DDPM_A, DDPM_B, DDPM_C1, DDPM_C2, DDPM_MIN_LOG, DDPM_MAX_LOG, DDPM_NONZERO, DDPM_CLIP) = range(9)
 DDPM_T_NEXT = 14
+# the coefficient row of vq_cfg_sa_step (include/viditq.h, VQ_SA_*): the same size, the next time in the same slot
+SA_ROW = 16
+(SA_CFG, SA_SIGMA, SA_ALPHA, SA_OC, SA_CX, SA_CG0, SA_CG1, SA_CN, SA_OP, SA_PX, SA_PG0, SA_PG1, SA_PN) = range(13)
+SA_T_NEXT = 14
 
 _lib = None
 

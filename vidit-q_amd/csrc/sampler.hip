@@ -1,6 +1,7 @@
 // sampler.hip - the device-resident sampler steps for gfx950 (HBM-bound elementwise): fused classifier-free guidance +
 // DDIM(eta=0) update (STDiT loop), and further down guidance + x0 + DPM-Solver++ multistep update and guidance +
-// learned-range variance + ancestral (IDDPM) posterior step (PixArt loops).
+// learned-range variance + ancestral (IDDPM) posterior step and guidance + x0 + SA-Solver corrector + predictor (PixArt
+// loops).
 //
 // Replaces, for the first (kept) half of the duplicated batch, the tail of forward_with_cfg
 // (t2v/opensora/schedulers/iddpm/__init__.py:168-184: PTQD division, CFG on eps[:, :3] only) and
@@ -82,7 +83,7 @@ __device__ __forceinline__ void dpm_store(T* p, const float (&v)[V]) {
     *reinterpret_cast<typename dpm_vec<T, V>::type*>(p) = r;
 }
 
-// What the two table-driven step kernels (DPM-Solver++ here, IDDPM further down) share.  The contract pragma is scoped to
+// What the table-driven step kernels (DPM-Solver++ here, IDDPM and SA-Solver further down) share.  The contract pragma is scoped to
 // a function body: a helper with floating-point arithmetic carries its own.
 
 // The table row of a launch: ``row`` plus the device counter when there is one.
@@ -180,7 +181,7 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const T* __restrict__ ep
 
 static inline bool vq_aligned(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
 
-// The refusals of both step entry points, in the order include/viditq.h documents: VQ_EINVAL (``einval``: the solver's own
+// The refusals of the step entry points, in the order include/viditq.h documents: VQ_EINVAL (``einval``: the solver's own
 // nulls and ranges; then what both have), VQ_ESHAPE (an element of elem_mult * C * inner values within the pitch and the
 // solver's clause ``eshape``; then the pitch and every address on the V elements of an access: ``f32`` is the
 // null-terminated list of the fp32 operands moved V at a time, of which an optional one may only stand last), VQ_EUNSUP
@@ -324,5 +325,96 @@ extern "C" int vq_cfg_ddpm_step(const void* eps, const float* x, const float* no
         hipLaunchKernelGGL((cfg_ddpm_kernel<T, decltype(v)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)eps,
                            x, noise, coef, step, x_out, x0_out, x_model, xm_f16, n, (long)inner, CI, ld_eps, guided, row,
                            n_rows);
+    });
+}
+
+// ---- fused CFG + x0 + SA-Solver corrector + next predictor (the PixArt SA-Solver sampling loop) ---------------------
+// One launch per model call k of the PEC loop of t2i/diffusion/model/sa_solver.py sample_few_steps (:755-909) as
+// sa_sampler.py:75-92 runs it: model_wrapper's guidance (:297-322), data_prediction_fn (:377-386), the corrector
+// adams_moulton_update_few_steps (:700-753) of loop step k and the predictor adams_bashforth_update_few_steps (:644-698) of
+// loop step k + 1, so the sample the next forward reads leaves the same launch.  Row layout and contract: include/viditq.h
+// (vq_cfg_sa_step).  As above nothing is contracted; the guidance is rounded in the model output's type, sigma_t * e is an
+// fp32 product (sigma_t is a one-element fp32 tensor in the eager path, which promotes) and the division by alpha_t is the
+// correctly rounded fp32 division of a tensor / tensor division.  There is no transcendental.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_sa_kernel(const T* __restrict__ eps, const float* x, const float* xp, float* hist,
+                                                     const float* __restrict__ noise, const float* __restrict__ coef,
+                                                     const int32_t* __restrict__ step, float* xo, float* xpo, void* xm,
+                                                     int xm_f16, int n, long CI, long ld_eps, int row, int n_rows) {
+#pragma clang fp contract(off)
+    const int k = step_row(row, step, n_rows);
+    const float* r = coef + (long)k * VQ_SA_ROW;
+    const int oc = (int)r[VQ_SA_OC], op = (int)r[VQ_SA_OP];
+    const float cfg = r[VQ_SA_CFG], sigma = r[VQ_SA_SIGMA], alpha = r[VQ_SA_ALPHA];
+    const float cx = r[VQ_SA_CX], cg0 = r[VQ_SA_CG0], cg1 = r[VQ_SA_CG1], cn = r[VQ_SA_CN];
+    const float px = r[VQ_SA_PX], pg0 = r[VQ_SA_PG0], pg1 = r[VQ_SA_PG1], pn = r[VQ_SA_PN];
+    const long total = (long)n * CI;
+    float* h0 = hist + (long)(k % 2) * total;                    // written: m_k
+    const float* h1 = hist + (long)((k + 1) % 2) * total;        // m_{k-1}
+    const float* z0 = noise + (long)(k % 2) * total;             // the draw of loop step k (corrector)
+    const float* z1 = noise + (long)((k + 1) % 2) * total;       // the draw of loop step k + 1 (predictor)
+    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V; i < total; i += (long)gridDim.x * blockDim.x * V) {
+        const long bi = i / CI, ri = i - bi * CI;
+        float u[V], c[V], xv[V], pv[V], m1[V], zc[V], zp[V], m0[V], xc[V], xq[V];
+        dpm_load<T, V>(eps + bi * ld_eps + ri, u);
+        dpm_load<T, V>(eps + (bi + n) * ld_eps + ri, c);
+        dpm_load<float, V>(x + i, xv);
+        dpm_load<float, V>(xp + i, pv);
+        if (oc == 2 || op == 2) dpm_load<float, V>(h1 + i, m1);
+        if (oc >= 1) dpm_load<float, V>(z0 + i, zc);
+        if (op >= 1) dpm_load<float, V>(z1 + i, zp);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float e = step_guide<T>(c[j], u[j], cfg);
+            const float se = sigma * e;
+            const float t = pv[j] - se;
+            const float m = __fdiv_rn(t, alpha);
+            m0[j] = m;
+            float v = xv[j];
+            if (oc >= 1) {
+                float g = cg0 * m;
+                if (oc == 2) {
+                    const float g1 = cg1 * m1[j];
+                    g = g + g1;
+                }
+                const float a = cx * v;
+                const float ag = a + g;
+                const float nz = cn * zc[j];
+                v = ag + nz;
+            }
+            xc[j] = v;
+            if (op >= 1) {
+                float q = pg0 * m;
+                if (op == 2) {
+                    const float q1 = pg1 * m1[j];
+                    q = q + q1;
+                }
+                const float a = px * v;
+                const float aq = a + q;
+                const float nz = pn * zp[j];
+                v = aq + nz;
+            }
+            xq[j] = v;
+        }
+        dpm_store<float, V>(h0 + i, m0);
+        dpm_store<float, V>(xo + i, xc);
+        dpm_store<float, V>(xpo + i, xq);
+        step_store_model<V>(xm, xm_f16, i, total, xq);
+    }
+}
+
+extern "C" int vq_cfg_sa_step(const void* eps, const float* x, const float* xp, float* hist, const float* noise,
+                              const float* coef, const int32_t* step, float* x_out, float* xp_out, void* x_model, int n, int C,
+                              int inner, long ld_eps, int row, int n_rows, int eps_f16, int xm_f16, void* stream) {
+    const void* const f32[] = {x, xp, hist, noise, x_out, xp_out, nullptr};
+    int V;
+    const int rc = step_check(!x || !xp || !hist || !noise || !x_out || !xp_out, false, eps, f32, coef, step, x_model, n, C,
+                              inner, ld_eps, 1, row, n_rows, eps_f16, xm_f16, &V);
+    if (rc != VQ_OK) return rc;
+    const long CI = (long)C * inner;
+    return step_launch(n, CI, V, eps_f16, [&](auto t, auto v, dim3 grid) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((cfg_sa_kernel<T, decltype(v)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)eps, x,
+                           xp, hist, noise, coef, step, x_out, xp_out, x_model, xm_f16, n, CI, ld_eps, row, n_rows);
     });
 }

@@ -350,3 +350,41 @@ class DDPMStepGraph(_CounterStepGraph):
                    lambda k: step_callback(self.steps - 1 - k, self.x.clone(), self.x0.clone()))
         return torch.cat([self.x, self.x])
 
+
+
+class SAStepGraph(_CounterStepGraph):
+    """The fused SA-Solver PEC loop of t2i/sa_solver.py in the counter form: the step is ops.cfg_sa_step.  Beside the
+    corrected latent ``x`` it keeps the predicted one ``xp`` (what the model saw; the result after the last replay), the
+    two-slot x0 history and the two-slot noise ring, of which ``run`` refills slot (k + 1) % 2 eagerly before replay k -
+    from ``noise_steps`` or with the draw the eager-launched loop makes - so a replay is bit-identical to that loop."""
+
+    def __init__(self, fn, text, kwargs, x, rows, t_first: float, model_dtype=torch.float32, warmup: int = 2):
+        self.fn, self.text, self.kwargs = fn, text, kwargs
+        self.hist = torch.zeros((2, x.numel()), dtype=torch.float32, device=x.device)
+        self.noise = torch.zeros((2,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+        self.xp = x.float().contiguous().clone()
+        super().__init__(fn, kwargs, x, rows, t_first, model_dtype, warmup)
+
+    def _forward(self):
+        return self.fn(self.xm, self.t, self.text, **self.kwargs)
+
+    def _step(self, eps):
+        from . import ops
+        if not ops.cfg_sa_step_ok(eps, self.x):
+            self._refuse_output("vq_cfg_sa_step")
+        ops.cfg_sa_step(eps, self.x, self.xp, self.hist, self.noise, self.rows, 0, step=self.step, x_out=self.x,
+                        xp_out=self.xp, x_model=self.xm)
+
+    @torch.no_grad()
+    def run(self, x, noise_steps=None, generator=None):
+        """``noise_steps``: [1 + steps, ...], entry 0 unused (the draw the loop makes before its first model call), or the
+        1 + steps draws are made here, from ``generator`` when given."""
+        def draw(i, out=None):
+            if noise_steps is not None:
+                return None if out is None else out.copy_(noise_steps[i])
+            return (torch.empty_like(self.x) if out is None else out).normal_(generator=generator)
+
+        draw(0)
+        self.xp.copy_(x)
+        self._loop(x, before=lambda k: draw(k + 1, self.noise[(k + 1) % 2]))
+        return self.xp.clone()

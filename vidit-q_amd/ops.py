@@ -1208,3 +1208,35 @@ def cfg_ddpm_step(eps: torch.Tensor, x: torch.Tensor, noise: torch.Tensor, coef:
                                 _stream()), "vq_cfg_ddpm_step")
     return x_out
 
+
+
+def cfg_sa_step_ok(eps, x) -> bool:
+    """Whether vq_cfg_sa_step takes a model output ``eps`` [2n, C, ...] and a latent ``x`` [n, C, ...] (_step_ok)."""
+    return _step_ok(eps, x, 1)
+
+
+def cfg_sa_step(eps: torch.Tensor, x: torch.Tensor, xp: torch.Tensor, hist: torch.Tensor, noise: torch.Tensor,
+                coef: torch.Tensor, row: int, step: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None,
+                xp_out: Optional[torch.Tensor] = None, x_model: Optional[torch.Tensor] = None):
+    """One call of the fused guidance + x0 + SA-Solver corrector + next predictor (vq_cfg_sa_step): ``eps`` [2n, C, ...] the
+    (uncond | cond) model output (fp16 / fp32, batch pitch free), ``x`` (the corrected sample of the previous step) and
+    ``xp`` (the predicted sample the model saw) [n, C, ...] fp32, ``hist`` [2, n*C*inner] fp32, ``noise`` the ring
+    [2, n*C*inner] fp32, ``coef`` [n_rows, SA_ROW] fp32 on the device; the row is ``row`` plus the device counter ``step``
+    (int32, one element) when given.  Returns (x_out, xp_out) (may be ``x`` / ``xp`` themselves); ``x_model`` [2n, C, ...]
+    (fp16 / fp32) receives xp_out twice."""
+    bad = (hist.numel() != 2 * x.numel() or noise.numel() != 2 * x.numel() or xp.shape != x.shape or not xp.is_cuda
+           or xp.dtype != torch.float32 or not xp.is_contiguous() or not noise.is_cuda or noise.dtype != torch.float32
+           or not noise.is_contiguous() or coef.dim() != 2 or coef.shape[1] != _lib.SA_ROW)
+    n, Cc, inner, ld, x_out, xm16 = _step_front(
+        eps, x, hist, "hist", coef, 1, "[2n, C, ...]",
+        (bad, "xp must be an fp32 GPU tensor of x's shape, hist and the noise ring must hold 2 x %d fp32 and coef rows of "
+              "%d floats" % (x.numel(), _lib.SA_ROW)), step, x_out, x_model)
+    if xp_out is None:
+        xp_out = torch.empty_like(x)
+    else:
+        _req(xp_out, torch.float32, "xp_out")
+        assert xp_out.shape == x.shape
+    check(_L().vq_cfg_sa_step(_p(eps), _p(x), _p(xp), _p(hist), _p(noise), _p(coef), _p(step), _p(x_out), _p(xp_out),
+                              _p(x_model), n, Cc, inner, ld, int(row), coef.shape[0], int(eps.dtype == torch.float16), xm16,
+                              _stream()), "vq_cfg_sa_step")
+    return x_out, xp_out

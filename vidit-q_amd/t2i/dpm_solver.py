@@ -24,7 +24,7 @@ are here too, for the algorithm the wrappers fix (``algorithm_type="dpmsolver++"
 ``denoise_to_zero`` (:545-549), ``t_start`` / ``t_end``.  Pinned against the imported reference on an
 analytic noise model (tests/golden/dpm_solver_modes.npz, tests/test_oracle_golden_cpu.py).  Still absent:
 dynamic thresholding / ``correcting_x0_fn`` / ``correcting_xt_fn`` hooks and the noise-prediction
-``algorithm_type="dpmsolver"`` (no wrapper of the reference can select them), SA-Solver.
+``algorithm_type="dpmsolver"`` (no wrapper of the reference can select them).  SA-Solver is t2i/sa_solver.py.
 """
 from __future__ import annotations
 
@@ -65,8 +65,22 @@ class NoiseScheduleVP:
         log_alphas = 0.5 * torch.log(1 - b).cumsum(dim=0)
         self.T = 1.0
         self.log_alpha_array = self._clip(log_alphas).to(dtype)
+        self._set_times(dtype)
+
+    def _set_times(self, dtype):
         self.total_N = self.log_alpha_array.numel()
         self.t_array = torch.linspace(0.0, 1.0, self.total_N + 1)[1:].to(dtype)
+
+    @classmethod
+    def from_alphas_cumprod(cls, alphas_cumprod: torch.Tensor, dtype=torch.float32):
+        """The schedule SA-Solver builds (t2i/diffusion/model/sa_solver.py:81-90 with ``alphas_cumprod``, which
+        sa_sampler.py:19-22 has already cast to fp32): ``log_alphas = 0.5 * log(alphas_cumprod)`` and NO ``clipped_lambda``
+        cut, so total_N is the full length and t_0 = 1 / total_N."""
+        ns = cls.__new__(cls)
+        ns.T = 1.0
+        ns.log_alpha_array = (0.5 * torch.log(alphas_cumprod)).to(dtype)
+        ns._set_times(dtype)
+        return ns
 
     @staticmethod
     def _clip(log_alphas, clipped_lambda=-5.1):
@@ -95,20 +109,21 @@ class NoiseScheduleVP:
         log_alpha = -0.5 * torch.logaddexp(torch.zeros((1,), dtype=lamb.dtype), -2.0 * lamb)
         return interpolate_fn(log_alpha.reshape(-1), torch.flip(self.log_alpha_array, [0]), torch.flip(self.t_array, [0]))
 
+    def edm_sigma(self, t):
+        """sigma_t / alpha_t (sa_solver.py:162-163): the 'karras' spacing's axis."""
+        return self.marginal_std(t) / self.marginal_alpha(t)
 
-class DPMSolverPP:
-    """``DPM_Solver(model_wrapper(...), ns, algorithm_type='dpmsolver++')`` for the configuration above."""
+    def edm_inverse_sigma(self, edmsigma):
+        """t of an EDM sigma (sa_solver.py:165-170)."""
+        alpha = 1 / (edmsigma ** 2 + 1).sqrt()
+        sigma = alpha * edmsigma
+        return self.inverse_lambda(torch.log(alpha / sigma))
 
-    def __init__(self, model: Callable, condition: torch.Tensor, uncondition: Optional[torch.Tensor], cfg_scale: float,
-                 model_kwargs: Optional[dict] = None, diffusion_steps: int = 1000):
-        self.model = model
-        self.condition, self.uncondition = condition, uncondition
-        self.cfg_scale = float(cfg_scale)
-        self.model_kwargs = dict(model_kwargs or {})
-        self.ns = NoiseScheduleVP(linear_betas(diffusion_steps))
-        self._c2 = None                                   # (uncond | cond) text embedding, concatenated once
-        self.model_input_dtype = torch.float32            # fused route: dtype of the latent handed to the model (it casts)
-        self._tables = {}                                 # fused route: device coefficient tables by configuration
+
+class GuidedModel:
+    """``model_wrapper(model, ns, model_type='noise', guidance_type='classifier-free', ...)`` (:172-336; the same function in
+    sa_solver.py:173-322): continuous time -> model-input time and classifier-free guidance with one batched (uncond | cond)
+    forward.  A solver that derives from it sets model, condition, uncondition, cfg_scale, model_kwargs, ns and _c2."""
 
     # ---- model_wrapper: continuous time -> model input time, classifier-free guidance (:273-332)
     def _noise(self, x, t_cont: torch.Tensor):
@@ -140,6 +155,21 @@ class DPMSolverPP:
         """Classifier-free guidance on the (uncond | cond) output of one batched forward (:318-332)."""
         noise_uncond, noise = out.chunk(2)
         return noise_uncond + self.cfg_scale * (noise - noise_uncond)
+
+
+class DPMSolverPP(GuidedModel):
+    """``DPM_Solver(model_wrapper(...), ns, algorithm_type='dpmsolver++')`` for the configuration above."""
+
+    def __init__(self, model: Callable, condition: torch.Tensor, uncondition: Optional[torch.Tensor], cfg_scale: float,
+                 model_kwargs: Optional[dict] = None, diffusion_steps: int = 1000):
+        self.model = model
+        self.condition, self.uncondition = condition, uncondition
+        self.cfg_scale = float(cfg_scale)
+        self.model_kwargs = dict(model_kwargs or {})
+        self.ns = NoiseScheduleVP(linear_betas(diffusion_steps))
+        self._c2 = None                                   # (uncond | cond) text embedding, concatenated once
+        self.model_input_dtype = torch.float32            # fused route: dtype of the latent handed to the model (it casts)
+        self._tables = {}                                 # fused route: device coefficient tables by configuration
 
     def _x0_coefs(self, t):
         """(sigma_t, alpha_t) of data_prediction_fn (:435-444)."""

@@ -1,4 +1,5 @@
-"""What the two eager-launched fused sampling loops share (DPMSolverPP._multistep_fused, SpacedDiffusion._loop_fused): the
+"""What the eager-launched fused sampling loops share (DPMSolverPP._multistep_fused, SpacedDiffusion._loop_fused,
+SASolver._pec_fused): the
 device coefficient table and the loop that puts one fused launch behind each model call."""
 from __future__ import annotations
 
@@ -7,7 +8,7 @@ def device_table(cache: dict, key, build_rows, dev, n):
     """(coefficient table, its T_NEXT column - the model-input time of the forward that follows each row - as
     [steps, 2n]) on the device ``dev``; ``build_rows()`` gives the host table.  Kept in ``cache`` under ``key``, so that
     the next loop with the same configuration uploads nothing."""
-    from .._lib import DPMPP_T_NEXT as T_NEXT         # == DDPM_T_NEXT: the same column of both row layouts
+    from .._lib import DPMPP_T_NEXT as T_NEXT         # == DDPM_T_NEXT == SA_T_NEXT: the same column of every row layout
     hit = cache.get(key)
     if hit is None:
         rows = build_rows()
