@@ -371,7 +371,10 @@ def test_ln_modulate_rowquant(ops, dev, B, n_tok, C, nout, all_smooth):
         assert float((diff > 0).float().mean()) < 5e-3
         got_dq = (got.float() - (qa.zx.cpu().reshape(B, n_tok, 1) + 128)) * qa.sx.cpu().reshape(B, n_tok, 1)
         assert rel_l2(got_dq, dq) < 2e-3
-        assert torch.allclose(qa.sx.cpu().reshape(B, n_tok)[0], delta.reshape(-1), rtol=1e-5)
+        for b in range(B):                                # the step of every sample's rows (the grid is shared over B)
+            assert torch.allclose(qa.sx.cpu().reshape(B, n_tok)[b], delta.reshape(-1), rtol=1e-5)
+        # the row term the int8 GEMM's zero-point correction reads, from the kernel's own codes (rq_write_row's identity)
+        assert torch.equal(qa.R.cpu(), qa.xq.cpu().int().sum(-1).int() - C * qa.zx.cpu())
 
 
 # ----------------------------------------------------------------------------- smooth-quant division by reciprocal

@@ -406,5 +406,8 @@ def test_ln_modulate_rowquant_edges(ops, dev, B, C, nout, name):
         got_dq = (got.float() - (qa.zx.cpu().reshape(B, n_tok, 1) + 128)) * qa.sx.cpu().reshape(B, n_tok, 1)
         rel = float((got_dq.double() - dq.double()).norm() / dq.double().norm())
         assert rel < 2e-3, rel
-        assert torch.allclose(qa.sx.cpu().reshape(B, n_tok)[0], delta.reshape(-1), rtol=1e-5)
+        for b in range(B):                                # the step of every sample's rows (the grid is shared over B)
+            assert torch.allclose(qa.sx.cpu().reshape(B, n_tok)[b], delta.reshape(-1), rtol=1e-5)
+        # the row term the int8 GEMM's zero-point correction reads, from the kernel's own codes (rq_write_row's identity)
+        assert torch.equal(qa.R.cpu(), qa.xq.cpu().int().sum(-1).int() - C * qa.zx.cpu())
     assert int(st.item()) == 0
