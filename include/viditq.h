@@ -560,6 +560,31 @@ int vq_cfg_dpmpp_step(const void* eps, const float* x, float* hist, const float*
                       float* x_out, void* x_model, int n, int C, int inner, long ld_eps, int row, int n_rows,
                       int eps_f16, int xm_f16, void* stream);
 
+/* The same step for the STDiT sampling loop (t2v/opensora/schedulers/dpms/__init__.py: DMP_SOLVER.sample,
+ * forward_with_dpmsolver), reading the model output where final_layer left it instead of an unpatchified fp32 copy.
+ *   eps_u, eps_c: the uncond and the cond output, each [n, N_t*N_h*N_w, p_t*p_h*p_w*C_out] with N_t = T/p_t, N_h = H/p_h,
+ *                 N_w = W/p_w, sample pitch ld_eps elements, fp32 (eps_f16 = 0) or fp16 (1).  Two pointers: the two
+ *                 forwards of a cfg_split step write two buffers; a joint forward passes eps_c = eps_u + n*ld_eps.
+ *   latent element (b, c, t, h, w), c < C, is read from token ((t/p_t)*N_h + h/p_h)*N_w + w/p_w at column
+ *                 (((t%p_t)*p_h + h%p_h)*p_w + w%p_w)*C_out + c: the index map of STDiT.unpatchify.  Channels C .. C_out-1
+ *                 (the learned sigma that chunk(2, dim=1)[0] drops) are never read.
+ * Every value is widened to fp32 on load and ALL arithmetic is fp32, one rounding per operation, nothing contracted: what
+ * unpatchify, .to(float32) and the eager expressions compute (the fp16-typed guidance of vq_cfg_dpmpp_step is the PixArt
+ * loop's).  The formulas, hist (3 slots), the VQ_DPMPP_* row, row / n_rows / step are those of vq_cfg_dpmpp_step; x, hist
+ * slots and x_out are dense fp32 [n, C, T, H, W], x_out may alias x.  x_model: NULL, or [xm_copies, n, C, T, H, W] in fp32
+ * (xm_f16 = 0) or fp16 (1): xm_copies = 1 for the cfg_split forwards (both read the same n samples), 2 for a joint one.
+ * Access: C == 4, C_out % 4 == 0 and W % 2 == 0 read 4 channels per eps access and move 2 elements along w per fp32 /
+ * x_model access; every other shape moves one element per access.
+ * VQ_EINVAL: a null eps_u / eps_c / x / hist / coef / x_out, an extent, a patch extent or n_rows <= 0, row outside
+ * [0, n_rows).  Then VQ_ESHAPE: C > C_out, T % p_t, H % p_h or W % p_w != 0, ld_eps < T*H*W*C_out; ld_eps not a multiple of
+ * the channels per eps access, eps_u / eps_c not aligned to that many elements, x / hist / x_out / x_model not aligned to
+ * the elements per access along w; coef / step off 4 bytes.  Then VQ_EUNSUP: a patch extent outside {1, 2}, eps_f16 or
+ * xm_f16 outside {0, 1}, xm_copies outside {1, 2}.  All before any HIP call or dereference. */
+int vq_cfg_dpmpp_step_patch(const void* eps_u, const void* eps_c, const float* x, float* hist, const float* coef,
+                            const int32_t* step, float* x_out, void* x_model, int n, int C, int C_out, int T, int H, int W,
+                            int p_t, int p_h, int p_w, long ld_eps, int row, int n_rows, int eps_f16, int xm_f16,
+                            int xm_copies, void* stream);
+
 /* One workgroup, enqueued after vq_cfg_dpmpp_step: t_out[0 .. n_t) (fp32) = VQ_DPMPP_T_NEXT of row clamp(*step, 0,
  * n_rows - 1), then *step = min(*step + 1, n_rows - 1).  A launch of its own, so that no workgroup of the step kernel can
  * read a counter another one has already moved.  VQ_EINVAL: a null pointer, n_rows or n_t <= 0; VQ_ESHAPE: a pointer off

@@ -59,6 +59,7 @@ SIGNATURES = {
     "vq_linear_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _vp]),
     "vq_cfg_ddim_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
     "vq_cfg_dpmpp_step": (_i, [_vp] * 7 + [_i, _i, _i, _l, _i, _i, _i, _i, _vp]),
+    "vq_cfg_dpmpp_step_patch": (_i, [_vp] * 8 + [_i] * 9 + [_l] + [_i] * 5 + [_vp]),
     "vq_dpmpp_advance": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     "vq_cfg_ddpm_step": (_i, [_vp] * 8 + [_i, _i, _i, _l, _i, _i, _i, _i, _i, _vp]),
     "vq_cfg_sa_step": (_i, [_vp] * 10 + [_i, _i, _i, _l, _i, _i, _i, _i, _vp]),

@@ -1,7 +1,7 @@
 // sampler.hip - the device-resident sampler steps for gfx950 (HBM-bound elementwise): fused classifier-free guidance +
 // DDIM(eta=0) update (STDiT loop), and further down guidance + x0 + DPM-Solver++ multistep update and guidance +
 // learned-range variance + ancestral (IDDPM) posterior step and guidance + x0 + SA-Solver corrector + predictor (PixArt
-// loops).
+// loops).  The DPM-Solver++ step also exists reading final_layer's patch-major output (the STDiT DPM-Solver++ loop).
 //
 // Replaces, for the first (kept) half of the duplicated batch, the tail of forward_with_cfg
 // (t2v/opensora/schedulers/iddpm/__init__.py:168-184: PTQD division, CFG on eps[:, :3] only) and
@@ -54,10 +54,13 @@ extern "C" int vq_cfg_ddim_step(const float* cond, const float* uncond, const fl
 // would otherwise fuse a*x - b*m into an fma), and with an fp16 model the four fp16 roundings of c - u, cfg * (.),
 // u + (.) and sigma_t * e.  The division by alpha_t is the product with the fp32 reciprocal the row holds (what torch's
 // GPU division by a host scalar computes).
+typedef __attribute__((ext_vector_type(2))) _Float16 half2v;
 template <typename T, int V> struct dpm_vec;
 template <> struct dpm_vec<float, 4> { typedef float4v type; };
+template <> struct dpm_vec<float, 2> { typedef float2v type; };
 template <> struct dpm_vec<float, 1> { typedef float type; };
 template <> struct dpm_vec<half_t, 4> { typedef half4 type; };
+template <> struct dpm_vec<half_t, 2> { typedef half2v type; };
 template <> struct dpm_vec<half_t, 1> { typedef half_t type; };
 
 template <typename T, int V>
@@ -115,6 +118,60 @@ __device__ __forceinline__ void step_store_model(void* xm, int xm_f16, long i, l
     }
 }
 
+// The coefficient row of a DPM-Solver++ launch, read once per thread.
+struct dpmpp_row {
+    int order;
+    bool taylor;
+    float cfg, sigma, inv_alpha, a, b, c1, c2, ir0, ir1, f, g;
+};
+
+__device__ __forceinline__ dpmpp_row dpmpp_load_row(const float* __restrict__ coef, int k) {
+    const float* r = coef + (long)k * VQ_DPMPP_ROW;
+    dpmpp_row R;
+    R.order = (int)r[VQ_DPMPP_ORDER];
+    R.taylor = r[VQ_DPMPP_TAYLOR] != 0.0f;
+    R.cfg = r[VQ_DPMPP_CFG], R.sigma = r[VQ_DPMPP_SIGMA], R.inv_alpha = r[VQ_DPMPP_INV_ALPHA];
+    R.a = r[VQ_DPMPP_X], R.b = r[VQ_DPMPP_M0], R.c1 = r[VQ_DPMPP_D1], R.c2 = r[VQ_DPMPP_D2];
+    R.ir0 = r[VQ_DPMPP_INV_R0], R.ir1 = r[VQ_DPMPP_INV_R1], R.f = r[VQ_DPMPP_R0_FRAC], R.g = r[VQ_DPMPP_INV_R01];
+    return R;
+}
+
+// Guidance, x0 and the order 1 / 2 / 3 update of one element (the body both DPM-Solver++ kernels share).  T: the type the
+// eager tensors round the guidance and sigma_t * e in (half_t for an fp16 model output used as it is, float for one that
+// was widened first).  m1 / m2 are read for orders >= 2 / >= 3 only.  Returns x_out; m0 receives m_k.
+template <typename T>
+__device__ __forceinline__ float dpmpp_element(const dpmpp_row& R, float c, float u, float xv, float m1, float m2, float& m0) {
+#pragma clang fp contract(off)
+    const float e = step_guide<T>(c, u, R.cfg);
+    const float se = (float)(T)(R.sigma * e);
+    const float t = xv - se;
+    const float m = t * R.inv_alpha;
+    m0 = m;
+    const float ax = R.a * xv;
+    const float bm = R.b * m;
+    float o = ax - bm;
+    if (R.order == 2) {
+        const float dm = m - m1;
+        const float D1_0 = R.ir0 * dm;
+        const float cd = R.c1 * D1_0;
+        o = R.taylor ? o + cd : o - cd;
+    } else if (R.order >= 3) {
+        const float dm0 = m - m1;
+        const float D1_0 = R.ir0 * dm0;
+        const float dm1 = m1 - m2;
+        const float D1_1 = R.ir1 * dm1;
+        const float dd = D1_0 - D1_1;
+        const float fd = R.f * dd;
+        const float D1 = D1_0 + fd;
+        const float D2 = R.g * dd;
+        const float p2 = R.c1 * D1;
+        const float p3 = R.c2 * D2;
+        o = o + p2;
+        o = o - p3;
+    }
+    return o;
+}
+
 // T: the model output's type; V: elements per thread and access (4 needs inner % 4 == 0, so a group never spans two
 // batch elements).  x_out may alias x: an element is read and written by the same thread.
 template <typename T, int V>
@@ -122,57 +179,22 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_kernel(const T* __restrict__ ep
                                                         const float* __restrict__ coef, const int32_t* __restrict__ step,
                                                         float* xo, void* xm, int xm_f16, int n, long CI, long ld_eps,
                                                         int row, int n_rows) {
-#pragma clang fp contract(off)
     const int k = step_row(row, step, n_rows);
-    const float* r = coef + (long)k * VQ_DPMPP_ROW;
-    const int order = (int)r[VQ_DPMPP_ORDER];
-    const bool taylor = r[VQ_DPMPP_TAYLOR] != 0.0f;
-    const float cfg = r[VQ_DPMPP_CFG], sigma = r[VQ_DPMPP_SIGMA], inv_alpha = r[VQ_DPMPP_INV_ALPHA];
-    const float a = r[VQ_DPMPP_X], b = r[VQ_DPMPP_M0], c1 = r[VQ_DPMPP_D1], c2 = r[VQ_DPMPP_D2];
-    const float ir0 = r[VQ_DPMPP_INV_R0], ir1 = r[VQ_DPMPP_INV_R1], f = r[VQ_DPMPP_R0_FRAC], g = r[VQ_DPMPP_INV_R01];
+    const dpmpp_row R = dpmpp_load_row(coef, k);
     const long total = (long)n * CI;
     float* h0 = hist + (long)(k % 3) * total;                    // written: m_k
     const float* h1 = hist + (long)((k + 2) % 3) * total;        // m_{k-1}
     const float* h2 = hist + (long)((k + 1) % 3) * total;        // m_{k-2}
     for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V; i < total; i += (long)gridDim.x * blockDim.x * V) {
         const long bi = i / CI, ri = i - bi * CI;
-        float u[V], c[V], xv[V], m1[V], m2[V], m0[V], out[V];
+        float u[V], c[V], xv[V], m1[V] = {}, m2[V] = {}, m0[V], out[V];
         dpm_load<T, V>(eps + bi * ld_eps + ri, u);
         dpm_load<T, V>(eps + (bi + n) * ld_eps + ri, c);
         dpm_load<float, V>(x + i, xv);
-        if (order >= 2) dpm_load<float, V>(h1 + i, m1);
-        if (order >= 3) dpm_load<float, V>(h2 + i, m2);
+        if (R.order >= 2) dpm_load<float, V>(h1 + i, m1);
+        if (R.order >= 3) dpm_load<float, V>(h2 + i, m2);
 #pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const float e = step_guide<T>(c[j], u[j], cfg);
-            const float se = (float)(T)(sigma * e);
-            const float t = xv[j] - se;
-            const float m = t * inv_alpha;
-            m0[j] = m;
-            const float ax = a * xv[j];
-            const float bm = b * m;
-            float o = ax - bm;
-            if (order == 2) {
-                const float dm = m - m1[j];
-                const float D1_0 = ir0 * dm;
-                const float cd = c1 * D1_0;
-                o = taylor ? o + cd : o - cd;
-            } else if (order >= 3) {
-                const float dm0 = m - m1[j];
-                const float D1_0 = ir0 * dm0;
-                const float dm1 = m1[j] - m2[j];
-                const float D1_1 = ir1 * dm1;
-                const float dd = D1_0 - D1_1;
-                const float fd = f * dd;
-                const float D1 = D1_0 + fd;
-                const float D2 = g * dd;
-                const float p2 = c1 * D1;
-                const float p3 = c2 * D2;
-                o = o + p2;
-                o = o - p3;
-            }
-            out[j] = o;
-        }
+        for (int j = 0; j < V; ++j) out[j] = dpmpp_element<T>(R, c[j], u[j], xv[j], m1[j], m2[j], m0[j]);
         dpm_store<float, V>(h0 + i, m0);
         dpm_store<float, V>(xo + i, out);
         step_store_model<V>(xm, xm_f16, i, total, out);
@@ -233,6 +255,113 @@ extern "C" int vq_cfg_dpmpp_step(const void* eps, const float* x, float* hist, c
         hipLaunchKernelGGL((cfg_dpmpp_kernel<T, decltype(v)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)eps,
                            x, hist, coef, step, x_out, x_model, xm_f16, n, CI, ld_eps, row, n_rows);
     });
+}
+
+// ---- the same step reading final_layer's patch-major output (the STDiT sampling loop) -------------------------------
+// eps_u / eps_c: [n, N_t*N_h*N_w tokens, p_t*p_h*p_w*C_out columns], sample pitch ld_eps; latent element (b, c, t, h, w) is
+// at token ((t/p_t)*N_h + h/p_h)*N_w + w/p_w, column (((t%p_t)*p_h + h%p_h)*p_w + w%p_w)*C_out + c (STDiT.unpatchify).
+// Every value is widened to fp32 on load and the arithmetic is dpmpp_element<float>: what unpatchify, .to(float32) and
+// the eager fp32 expressions compute.  Patch extents are 1 or 2 and are passed as shifts.
+struct patch_geo {
+    int C, C_out, T, H, W;                       // latent channels read, channels per patch position, latent extents
+    int lt, lh, lw;                              // log2 of the patch extents
+    long ld_eps;
+};
+
+// VC x VW: channels per eps access x elements along w per fp32 access.  4 x 2 (C == 4: one thread owns the four channels
+// of two neighbouring w, the eps reads are 8 / 16 bytes and the dense streams run along w) or 1 x 1 (any C: one element per
+// thread).  x_out may alias x: an element is read and written by the same thread.
+template <typename T, int VC, int VW>
+__global__ __launch_bounds__(256) void cfg_dpmpp_patch_kernel(const T* __restrict__ eps_u, const T* __restrict__ eps_c,
+                                                              const float* x, float* hist, const float* __restrict__ coef,
+                                                              const int32_t* __restrict__ step, float* xo, void* xm,
+                                                              int xm_f16, int xm_copies, int n, patch_geo g, int row,
+                                                              int n_rows) {
+    const int k = step_row(row, step, n_rows);
+    const dpmpp_row R = dpmpp_load_row(coef, k);
+    const long HW = (long)g.H * g.W, total = (long)n * g.C * g.T * HW;
+    float* h0 = hist + (long)(k % 3) * total;                    // written: m_k
+    const float* h1 = hist + (long)((k + 2) % 3) * total;        // m_{k-1}
+    const float* h2 = hist + (long)((k + 1) % 3) * total;        // m_{k-2}
+    const int Wg = g.W / VW, Cg = VC == 1 ? g.C : 1;             // (VC == 4: the channels are inside the item)
+    const int Nh = g.H >> g.lh, Nw = g.W >> g.lw, ph = 1 << g.lh, pw = 1 << g.lw;
+    const long PC = (long)(1 << (g.lt + g.lh + g.lw)) * g.C_out; // columns of a token
+    const long items = (long)n * Cg * g.T * g.H * Wg;
+    for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (long)gridDim.x * blockDim.x) {
+        long r = it;
+        const int w0 = (int)(r % Wg) * VW;  r /= Wg;
+        const int h = (int)(r % g.H);       r /= g.H;
+        const int t = (int)(r % g.T);       r /= g.T;
+        const int c0 = (int)(r % Cg);       r /= Cg;
+        const long b = r;
+        const long tok = ((long)(t >> g.lt) * Nh + (h >> g.lh)) * Nw;
+        const int pos = ((t & ((1 << g.lt) - 1)) * ph + (h & (ph - 1))) * pw;
+        float u[VW][VC], c[VW][VC];
+#pragma unroll
+        for (int j = 0; j < VW; ++j) {
+            const int w = w0 + j;
+            const long e = b * g.ld_eps + (tok + (w >> g.lw)) * PC + (long)(pos + (w & (pw - 1))) * g.C_out + c0;
+            dpm_load<T, VC>(eps_u + e, u[j]);
+            dpm_load<T, VC>(eps_c + e, c[j]);
+        }
+#pragma unroll
+        for (int cc = 0; cc < VC; ++cc) {
+            const long i = ((b * g.C + c0 + cc) * g.T + t) * HW + (long)h * g.W + w0;
+            float xv[VW], m1[VW] = {}, m2[VW] = {}, m0[VW], out[VW];
+            dpm_load<float, VW>(x + i, xv);
+            if (R.order >= 2) dpm_load<float, VW>(h1 + i, m1);
+            if (R.order >= 3) dpm_load<float, VW>(h2 + i, m2);
+#pragma unroll
+            for (int j = 0; j < VW; ++j) out[j] = dpmpp_element<float>(R, c[j][cc], u[j][cc], xv[j], m1[j], m2[j], m0[j]);
+            dpm_store<float, VW>(h0 + i, m0);
+            dpm_store<float, VW>(xo + i, out);
+            for (int q = 0; q < (xm ? xm_copies : 0); ++q) {
+                if (xm_f16) dpm_store<half_t, VW>((half_t*)xm + q * total + i, out);
+                else dpm_store<float, VW>((float*)xm + q * total + i, out);
+            }
+        }
+    }
+}
+
+static inline int vq_log2_patch(int p) { return p == 1 ? 0 : (p == 2 ? 1 : -1); }
+
+extern "C" int vq_cfg_dpmpp_step_patch(const void* eps_u, const void* eps_c, const float* x, float* hist, const float* coef,
+                                       const int32_t* step, float* x_out, void* x_model, int n, int C, int C_out, int T, int H,
+                                       int W, int p_t, int p_h, int p_w, long ld_eps, int row, int n_rows, int eps_f16,
+                                       int xm_f16, int xm_copies, void* stream) {
+    if (!eps_u || !eps_c || !x || !hist || !coef || !x_out || n <= 0 || C <= 0 || C_out <= 0 || T <= 0 || H <= 0 || W <= 0 ||
+        p_t <= 0 || p_h <= 0 || p_w <= 0 || row < 0 || n_rows <= 0 || row >= n_rows)
+        return VQ_EINVAL;
+    if (C > C_out || T % p_t || H % p_h || W % p_w) return VQ_ESHAPE;
+    // one sample of the model output: T*H*W positions (tokens x patch positions) of C_out columns each
+    if (ld_eps < (long)T * H * W * C_out) return VQ_ESHAPE;
+    const bool wide = C == 4 && C_out % 4 == 0 && W % 2 == 0;
+    const int VC = wide ? 4 : 1, VW = wide ? 2 : 1;
+    const size_t e_sz = eps_f16 == 1 ? 2 : 4, m_sz = xm_f16 == 1 ? 2 : 4;     // (a flag outside {0, 1} is refused below)
+    if (ld_eps % VC || !vq_aligned(eps_u, e_sz * VC) || !vq_aligned(eps_c, e_sz * VC) || !vq_aligned(x, 4 * VW) ||
+        !vq_aligned(hist, 4 * VW) || !vq_aligned(x_out, 4 * VW) || !vq_aligned(x_model, m_sz * VW) || !vq_aligned(coef, 4) ||
+        !vq_aligned(step, 4))
+        return VQ_ESHAPE;
+    patch_geo g;
+    g.C = C, g.C_out = C_out, g.T = T, g.H = H, g.W = W, g.ld_eps = ld_eps;
+    g.lt = vq_log2_patch(p_t), g.lh = vq_log2_patch(p_h), g.lw = vq_log2_patch(p_w);
+    if (g.lt < 0 || g.lh < 0 || g.lw < 0 || eps_f16 < 0 || eps_f16 > 1 || xm_f16 < 0 || xm_f16 > 1 || xm_copies < 1 ||
+        xm_copies > 2)
+        return VQ_EUNSUP;
+    const long items = (long)n * (wide ? 1 : C) * T * H * (W / VW);
+    long blocks = (items + 255) / 256;
+    if (blocks > 1024) blocks = 1024;                            // 16 waves per CU in flight; larger latents loop
+    const dim3 grid((unsigned)blocks);
+#define VQ_PATCH_LAUNCH(T_, VC_, VW_)                                                                                    \
+    hipLaunchKernelGGL((cfg_dpmpp_patch_kernel<T_, VC_, VW_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)eps_u, \
+                       (const T_*)eps_c, x, hist, coef, step, x_out, x_model, xm_f16, xm_copies, n, g, row, n_rows)
+    if (eps_f16) {
+        if (wide) VQ_PATCH_LAUNCH(half_t, 4, 2); else VQ_PATCH_LAUNCH(half_t, 1, 1);
+    } else {
+        if (wide) VQ_PATCH_LAUNCH(float, 4, 2); else VQ_PATCH_LAUNCH(float, 1, 1);
+    }
+#undef VQ_PATCH_LAUNCH
+    return vq_check_launch();
 }
 
 // One workgroup, after the step kernel in stream order: t_out[0 .. n_t) = the row's next model-input time, then the

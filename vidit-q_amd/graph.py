@@ -250,39 +250,49 @@ class _CounterStepGraph:
     its ``run``.  A forward that moves host-visible state (a running smooth-quant statistic) cannot be captured and is
     refused."""
 
-    def __init__(self, fn, kwargs, x, rows, t_first: float, model_dtype, warmup: int):
-        from . import ops
+    def __init__(self, fn, kwargs, x, rows, t_first: float, model_dtype, warmup: int, copies: int = 2, first=None):
+        """``copies``: how many times ``xm`` and ``t`` hold the n samples (2: one duplicated-batch forward; 1: forwards of
+        n samples).  ``first``: a call made once, and waited for, before the warm-up passes (_capture)."""
         from ._lib import VQError
         if GraphedModel(fn)._state(kwargs.get("timestep_id"))[2]:
             raise VQError("%s: a layer keeps a running smooth-quant statistic; its forward is not capturable"
                           % type(self).__name__)
         n = x.shape[0]
         dev = x.device
-        self.steps, self.t_first = rows.shape[0], float(t_first)
+        self.steps, self.t_first, self.copies = rows.shape[0], float(t_first), copies
         self.rows = rows.to(dev)
         self.x = x.float().contiguous().clone()
-        self.xm = torch.cat([self.x, self.x]).to(model_dtype)
-        self.t = torch.full((2 * n,), self.t_first, dtype=torch.float32, device=dev)
+        self.xm = torch.cat([self.x] * copies).to(model_dtype)
+        self.t = torch.full((copies * n,), self.t_first, dtype=torch.float32, device=dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.graph = self._capture_step(warmup, first)   # (the counter and the time are reset by every loop, not here)
+
+    def _capture_step(self, warmup, first=None):
+        """One {forward, step, advance} of the buffers' current state, recorded."""
+        from . import ops
 
         def one():
             self._step(self._forward())
             ops.dpmpp_advance(self.step, self.rows, self.t)
 
-        self.graph, _ = _capture(one, warmup + 1)        # (the counter and the time are reset by every loop, not here)
+        return _capture(one, warmup + 1, first=first)[0]
 
     def _refuse_output(self, entry_point):
         from ._lib import VQError
         raise VQError("%s: %s does not take this model output" % (type(self).__name__, entry_point))
 
-    def _loop(self, x, before=None, after=None):
-        """Start from the latent ``x`` [n, ...] and replay every step; ``before(k)`` / ``after(k)`` around replay k."""
+    def _reset(self, x):
+        """The state a loop starts from: the latent ``x`` [n, ...] in ``x`` and ``xm``, the first time, the counter at 0."""
         n = self.x.shape[0]
         self.x.copy_(x)
-        self.xm[:n].copy_(x)
-        self.xm[n:].copy_(x)
+        for q in range(self.copies):
+            self.xm[q * n:(q + 1) * n].copy_(x)
         self.t.fill_(self.t_first)
         self.step.zero_()
+
+    def _loop(self, x, before=None, after=None):
+        """Start from the latent ``x`` [n, ...] and replay every step; ``before(k)`` / ``after(k)`` around replay k."""
+        self._reset(x)
         for k in range(self.steps):
             if before is not None:
                 before(k)
@@ -388,3 +398,51 @@ class SAStepGraph(_CounterStepGraph):
         self.xp.copy_(x)
         self._loop(x, before=lambda k: draw(k + 1, self.noise[(k + 1) % 2]))
         return self.xp.clone()
+
+
+class VideoDPMStepGraph(_CounterStepGraph):
+    """The fused DPM-Solver++ loop of t2v/dpm_solver.py in the counter form: {forward(patch_major=True) - once for the
+    joint route, twice for cfg_split, the two chains forked onto a side stream as StepGraph._forward does -,
+    ops.cfg_dpmpp_step_patch(step=counter), ops.dpmpp_advance}.  The smooth-quant time range of a forward is host state
+    that a capture bakes in, so there is one capture per range the schedule visits (GraphedSampler._range_of), ALL taken
+    here, before the first replay; the warm-up passes move x, xm, t, the counter and the history, which are reset
+    afterwards.  ``solver``: a t2v.dpm_solver.VideoDPMSolverPP; ``t_vals``: the model-input time of every call."""
+
+    def __init__(self, solver, x, rows, t_vals, warmup: int = 2):
+        from .qdiff.models.quant_model import QuantModel
+        self.solver, self.patch = solver, tuple(solver.net.patch_size)
+        self.side = torch.cuda.Stream() if solver.cfg_split else None
+        self.hist = torch.zeros((3, x.numel()), dtype=torch.float32, device=x.device)
+        ranged = GraphedSampler(solver.net, None, None, None) if isinstance(solver.net, QuantModel) else None
+        self.range_of = [0 if ranged is None else ranged._range_of(t) for t in t_vals]
+        self.t_id = t_vals[0]
+        kwargs = dict(solver.model_kwargs, timestep_id=t_vals[0])
+        # the first pass on ONE stream: it packs weights and fills the module-level caches (StepGraph)
+        super().__init__(solver.net.forward, kwargs, x, rows, t_vals[0], solver.model_input_dtype, warmup,
+                         copies=1 if solver.cfg_split else 2, first=lambda: self._forward(serial=True))
+        self.graphs = {self.range_of[0]: self.graph}
+        for k, r in enumerate(self.range_of):
+            if r not in self.graphs:
+                self.t_id = t_vals[k]
+                self.graphs[r] = self._capture_step(warmup, first=lambda: self._forward(serial=True))
+        self.hist.zero_()
+        self._reset(x)
+
+    def _forward(self, serial=False):
+        return self.solver._forward_patch(self.xm, self.t, self.t_id, side=None if serial else self.side)
+
+    def _step(self, eps):
+        from . import ops
+        if not ops.cfg_dpmpp_step_patch_ok(eps[0], eps[1], self.x, self.patch):
+            self._refuse_output("vq_cfg_dpmpp_step_patch")
+        ops.cfg_dpmpp_step_patch(eps[0], eps[1], self.x, self.hist, self.rows, 0, self.patch, step=self.step, x_out=self.x,
+                                 x_model=self.xm)
+
+    def _select(self, k):
+        self.graph = self.graphs[self.range_of[k]]
+
+    @torch.no_grad()
+    def run(self, x, step_callback=None):
+        self._loop(x, before=self._select,
+                   after=None if step_callback is None else lambda k: step_callback(k + 1, self.x.clone()))
+        return self.x.clone()

@@ -1171,6 +1171,90 @@ def cfg_dpmpp_step(eps: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, coef:
     return x_out
 
 
+def _patch_geometry(eps_u, eps_c, x, patch):
+    """(n, C, C_out, T, H, W, ld_eps) of a patch-major step, or None when eps_u / eps_c are not two final_layer outputs
+    [n, N_t*N_h*N_w, p_t*p_h*p_w*C_out] (same shape, strides and type, a sample dense, the sample pitch free) for the dense
+    latent ``x`` [n, C, T, H, W] and the patch (p_t, p_h, p_w).  Shapes and strides only (no tensor is touched)."""
+    es, xs = tuple(eps_u.shape), tuple(x.shape)
+    if len(xs) != 5 or len(es) != 3 or len(patch) != 3 or tuple(eps_c.shape) != es or eps_c.dtype != eps_u.dtype:
+        return None
+    pt, ph, pw = (int(p) for p in patch)
+    n, Cc, T, H, W = (int(d) for d in xs)
+    if min(pt, ph, pw) <= 0 or T % pt or H % ph or W % pw:
+        return None
+    P = pt * ph * pw
+    if es[0] != n or es[1] * P != T * H * W or es[2] % P:
+        return None
+    if tuple(x.stride()) != _dense_strides(xs) or tuple(eps_u.stride())[1:] != (es[2], 1) \
+            or tuple(eps_c.stride()) != tuple(eps_u.stride()):
+        return None
+    return n, Cc, int(es[2]) // P, T, H, W, int(eps_u.stride()[0])
+
+
+def cfg_dpmpp_step_patch_ok(eps_u, eps_c, x, patch) -> bool:
+    """Whether vq_cfg_dpmpp_step_patch takes the two model outputs and the latent (include/viditq.h), asked before the
+    launch from shapes, strides and addresses: GPU tensors, fp32 x, fp16 / fp32 eps and patch extents of 1 or 2 (VQ_EUNSUP),
+    positive extents (VQ_EINVAL), and VQ_ESHAPE: the layout, C <= C_out, ld_eps >= T*H*W*C_out and the pitch and the base
+    addresses on the elements of an access (4 channels x 2 along w when C == 4, C_out % 4 == 0 and W % 2 == 0, else 1 x 1)."""
+    if not (eps_u.is_cuda and eps_c.is_cuda and x.is_cuda):
+        return False
+    if x.dtype != torch.float32 or eps_u.dtype not in (torch.float16, torch.float32):
+        return False
+    geo = _patch_geometry(eps_u, eps_c, x, patch)
+    if geo is None or any(int(p) not in (1, 2) for p in patch):
+        return False
+    n, Cc, Co, T, H, W, ld = geo
+    if min(n, Cc, Co, T, H, W) <= 0 or Cc > Co or ld < T * H * W * Co:
+        return False
+    wide = Cc == 4 and Co % 4 == 0 and W % 2 == 0
+    VC, VW = (4, 2) if wide else (1, 1)
+    ea = eps_u.element_size() * VC
+    return ld % VC == 0 and eps_u.data_ptr() % ea == 0 and eps_c.data_ptr() % ea == 0 and x.data_ptr() % (4 * VW) == 0
+
+
+def cfg_dpmpp_step_patch(eps_u: torch.Tensor, eps_c: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, coef: torch.Tensor,
+                         row: int, patch, step: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None,
+                         x_model: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One call of the DPM-Solver++ step of cfg_dpmpp_step on the patch-major model output (vq_cfg_dpmpp_step_patch):
+    ``eps_u`` / ``eps_c`` the uncond / cond outputs of final_layer [n, tokens, p_t*p_h*p_w*C_out] (fp16 / fp32, sample pitch
+    free; the two halves of one joint output, or the outputs of two forwards), ``x`` [n, C, T, H, W] fp32, ``patch``
+    (p_t, p_h, p_w); hist, coef, row and step as for cfg_dpmpp_step.  All arithmetic is fp32.  Returns x_out (may be ``x``
+    itself); ``x_model`` [n or 2n, C, T, H, W] (fp16 / fp32) receives it once or twice."""
+    for t, name in ((eps_u, "eps_u"), (eps_c, "eps_c"), (x, "x"), (hist, "hist"), (coef, "coef")):
+        if not t.is_cuda:
+            raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % name)
+    _req(x, torch.float32, "x")
+    _req(hist, torch.float32, "hist")
+    _req(coef, torch.float32, "coef")
+    if eps_u.dtype not in (torch.float16, torch.float32):
+        raise VQError("eps must be float16 or float32, got %s" % eps_u.dtype)
+    geo = _patch_geometry(eps_u, eps_c, x, patch)
+    if geo is None:
+        raise VQError("eps_u / eps_c must be [n, tokens, p_t*p_h*p_w*C_out] with equal strides for x [n, C, T, H, W]")
+    if hist.numel() != 3 * x.numel() or coef.dim() != 2 or coef.shape[1] != _lib.DPMPP_ROW:
+        raise VQError("hist must hold 3 x %d fp32 and coef rows of %d floats" % (x.numel(), _lib.DPMPP_ROW))
+    if step is not None:
+        _req(step, torch.int32, "step")
+    if x_out is None:
+        x_out = torch.empty_like(x)
+    else:
+        _req(x_out, torch.float32, "x_out")
+        assert x_out.shape == x.shape
+    xm16, copies = 0, 1
+    if x_model is not None:
+        if not x_model.is_cuda or not x_model.is_contiguous() or x_model.dtype not in (torch.float16, torch.float32):
+            raise VQError("x_model must be a contiguous float16 or float32 GPU tensor")
+        copies = x_model.numel() // x.numel()
+        assert x_model.numel() == copies * x.numel()
+        xm16 = int(x_model.dtype == torch.float16)
+    n, Cc, Co, T, H, W, ld = geo
+    pt, ph, pw = (int(p) for p in patch)
+    check(_L().vq_cfg_dpmpp_step_patch(_p(eps_u), _p(eps_c), _p(x), _p(hist), _p(coef), _p(step), _p(x_out), _p(x_model), n,
+                                       Cc, Co, T, H, W, pt, ph, pw, ld, int(row), coef.shape[0],
+                                       int(eps_u.dtype == torch.float16), xm16, copies, _stream()), "vq_cfg_dpmpp_step_patch")
+    return x_out
+
+
 def dpmpp_advance(step: torch.Tensor, coef: torch.Tensor, t_out: torch.Tensor) -> None:
     """t_out[:] = the counter's row's next model-input time, then the counter moves on (saturating at the last row):
     vq_dpmpp_advance, enqueued after cfg_dpmpp_step(step=counter) or cfg_ddpm_step(step=counter) (T_NEXT is the same

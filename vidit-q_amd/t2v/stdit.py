@@ -1000,7 +1000,9 @@ class STDiT(nn.Module):
         return out
 
     # ---- forward (stdit.py:238-341) -------------------------------------------------------------
-    def forward(self, x, timestep, y, mask=None):
+    def forward(self, x, timestep, y, mask=None, patch_major=False):
+        """``patch_major``: return final_layer's output [B, N_t*N_h*N_w, p_t*p_h*p_w*out_channels] as it is, in the model's
+        dtype (no unpatchify copy, no cast): what ops.cfg_dpmpp_step_patch reads."""
         x = x.to(self.dtype)
         timestep = timestep.to(self.dtype)
         C = self.hidden_size
@@ -1031,6 +1033,8 @@ class STDiT(nn.Module):
             for i, block in enumerate(self.blocks):
                 x = block(x, y, t0, y_lens, self.pos_embed_temporal if i == 0 else None)
         x = self.final_layer(x, t)
+        if patch_major:
+            return x
         x = self.unpatchify(x)
         return x.to(torch.float32)
 
