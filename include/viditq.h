@@ -591,6 +591,48 @@ int vq_cfg_dpmpp_step_patch(const void* eps_u, const void* eps_c, const float* x
  * 4 bytes. */
 int vq_dpmpp_advance(int32_t* step, const float* coef, int n_rows, float* t_out, int n_t, void* stream);
 
+/* The DDIM(eta = 0) step of vq_cfg_ddim_step for the STDiT loop in the table-driven, patch-major form: it reads the model
+ * output where final_layer left it (no unpatchify copy, no fp32 cast) and its five scalars from a coefficient row.
+ *   eps_c, eps_u: the cond and the uncond output, each [n, N_t*N_h*N_w, p_t*p_h*p_w*C_out], sample pitch ld_eps elements,
+ *                 fp32 (eps_f16 = 0) or fp16 (1).  Two pointers: the two forwards of a cfg_split step write two buffers; a
+ *                 joint forward of this loop (text = cat([cond, null])) passes eps_u = eps_c + n*ld_eps.
+ *   The index map, patch extents, x_model / xm_copies, the access widths and their choice, and the grid are those of
+ *   vq_cfg_dpmpp_step_patch.  Channels C .. C_out-1 (the learned sigma, unused at eta = 0) and the pitch padding are never read.
+ * For row k = clamp(row + (step ? *step : 0), 0, n_rows - 1), per latent element (b, c, t, h, w), every value widened to
+ * fp32 on load, with fl() one fp32 rounding and fma() one rounding of the exact a*b + c:
+ *   cv = fl(cond / (1 + k)),  uv = fl(uncond / (1 + k))                         (IEEE division)
+ *   e  = c < guided ? fma(cfg, fl(cv - uv), uv) : cv                            (guided > C behaves as C)
+ *   be = fl(Bc * e);   x0 = fma(A, x, -be)
+ *   r  = fl(fl(A * x) - x0)               [paired: fma(A, x, -x0)]
+ *   e2 = fl(r / Bc)                                                             (IEEE division)
+ *   sa = sqrt(abar_prev),  sb = sqrt(fl(1 - abar_prev))                          (__fsqrt_rn)
+ *   x_next = fl(fl(sa * x0) + fl(sb * e2))  [paired: fma(sa, x0, fl(sb * e2))]
+ * This is, operation for operation, what the compiled cfg_ddim_kernel of vq_cfg_ddim_step performs (that kernel leaves
+ * contraction to the compiler; here every fma is written out and nothing else is contracted), so the result is bit for
+ * bit vq_cfg_ddim_step applied to unpatchify(out).to(float32).  That kernel has TWO compiled bodies: its grid-stride loop
+ * (4096 x 256 = 2^20 elements per pass) is unrolled by two, and the unrolled body contracts r and x_next (the bracketed
+ * 'paired' forms) where the remainder body does not.  A latent of n*C*T*H*W <= 2^20 elements - a 16 x 64 x 64 one has
+ * 2^18 per sample - is one pass, remainder body throughout.  Above that, the dense index i of an element decides: with
+ * first = i mod 2^20 and passes = floor((total - 1 - first) / 2^20) + 1, the element is 'paired' iff
+ * floor(i / 2^20) < passes - passes % 2.  This entry point evaluates the same rule per element (shifts, no division).
+ * Coefficient row: VQ_DDIM_ROW floats, the indices below; unused slots are zero.  The row has the size of the DPM-Solver++
+ * row and keeps the next model-input time in the same slot (VQ_DDIM_T_NEXT == VQ_DPMPP_T_NEXT), so vq_dpmpp_advance serves
+ * as this step's counter kernel.  PTQD's 1 + k is per row.
+ * x dense fp32 [n, C, T, H, W]; x_out the same, may alias x.
+ * Refusals: those of vq_cfg_dpmpp_step_patch in its order (there is no hist), and guided < 0 is VQ_EINVAL.  All before any
+ * HIP call or dereference. */
+#define VQ_DDIM_ROW 16         /* floats per row (== VQ_DPMPP_ROW) */
+#define VQ_DDIM_CFG 0          /* guidance scale */
+#define VQ_DDIM_ONE_PLUS_K 1   /* 1 + k (PTQD), 1 without */
+#define VQ_DDIM_A 2            /* sqrt_recip_alphas_cumprod[t] */
+#define VQ_DDIM_BC 3           /* sqrt_recipm1_alphas_cumprod[t] */
+#define VQ_DDIM_ABAR_PREV 4    /* alphas_cumprod_prev[t] */
+#define VQ_DDIM_T_NEXT 14      /* model-input time of the NEXT forward */
+int vq_cfg_ddim_step_patch(const void* eps_c, const void* eps_u, const float* x, const float* coef, const int32_t* step,
+                           float* x_out, void* x_model, int n, int C, int C_out, int T, int H, int W, int p_t, int p_h,
+                           int p_w, long ld_eps, int guided, int row, int n_rows, int eps_f16, int xm_f16, int xm_copies,
+                           void* stream);
+
 /* Fused CFG + learned-range variance + ancestral posterior step: ONE launch per model call of the PixArt IDDPM loop
  * (p_sample_loop(model.forward_with_cfg, ...), quant_txt2img.py:154-166).  Replaces, for the kept first half of the
  * duplicated batch, the tail of forward_with_cfg (t2i/diffusion/model/nets/PixArtMS.py:221-234), p_mean_variance

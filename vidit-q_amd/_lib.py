@@ -61,6 +61,7 @@ SIGNATURES = {
     "vq_cfg_dpmpp_step": (_i, [_vp] * 7 + [_i, _i, _i, _l, _i, _i, _i, _i, _vp]),
     "vq_cfg_dpmpp_step_patch": (_i, [_vp] * 8 + [_i] * 9 + [_l] + [_i] * 5 + [_vp]),
     "vq_dpmpp_advance": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    "vq_cfg_ddim_step_patch": (_i, [_vp] * 7 + [_i] * 9 + [_l] + [_i] * 6 + [_vp]),
     "vq_cfg_ddpm_step": (_i, [_vp] * 8 + [_i, _i, _i, _l, _i, _i, _i, _i, _i, _vp]),
     "vq_cfg_sa_step": (_i, [_vp] * 10 + [_i, _i, _i, _l, _i, _i, _i, _i, _vp]),
 }
@@ -77,6 +78,10 @@ DDPM_T_NEXT = 14
 SA_ROW = 16
 (SA_CFG, SA_SIGMA, SA_ALPHA, SA_OC, SA_CX, SA_CG0, SA_CG1, SA_CN, SA_OP, SA_PX, SA_PG0, SA_PG1, SA_PN) = range(13)
 SA_T_NEXT = 14
+# the coefficient row of vq_cfg_ddim_step_patch (include/viditq.h, VQ_DDIM_*): the same size, the next time in the same slot
+DDIM_ROW = 16
+(DDIM_CFG, DDIM_ONE_PLUS_K, DDIM_A, DDIM_BC, DDIM_ABAR_PREV) = range(5)
+DDIM_T_NEXT = 14
 
 _lib = None
 

@@ -1,7 +1,8 @@
 // sampler.hip - the device-resident sampler steps for gfx950 (HBM-bound elementwise): fused classifier-free guidance +
 // DDIM(eta=0) update (STDiT loop), and further down guidance + x0 + DPM-Solver++ multistep update and guidance +
 // learned-range variance + ancestral (IDDPM) posterior step and guidance + x0 + SA-Solver corrector + predictor (PixArt
-// loops).  The DPM-Solver++ step also exists reading final_layer's patch-major output (the STDiT DPM-Solver++ loop).
+// loops).  The DPM-Solver++ step and the DDIM step also exist reading final_layer's patch-major output (the STDiT
+// DPM-Solver++ loop; the STDiT DDIM loop in its table-driven form): one geometry walk, patch_walk, serves both.
 //
 // Replaces, for the first (kept) half of the duplicated batch, the tail of forward_with_cfg
 // (t2v/opensora/schedulers/iddpm/__init__.py:168-184: PTQD division, CFG on eps[:, :3] only) and
@@ -270,19 +271,16 @@ struct patch_geo {
 
 // VC x VW: channels per eps access x elements along w per fp32 access.  4 x 2 (C == 4: one thread owns the four channels
 // of two neighbouring w, the eps reads are 8 / 16 bytes and the dense streams run along w) or 1 x 1 (any C: one element per
-// thread).  x_out may alias x: an element is read and written by the same thread.
-template <typename T, int VC, int VW>
-__global__ __launch_bounds__(256) void cfg_dpmpp_patch_kernel(const T* __restrict__ eps_u, const T* __restrict__ eps_c,
-                                                              const float* x, float* hist, const float* __restrict__ coef,
-                                                              const int32_t* __restrict__ step, float* xo, void* xm,
-                                                              int xm_f16, int xm_copies, int n, patch_geo g, int row,
-                                                              int n_rows) {
-    const int k = step_row(row, step, n_rows);
-    const dpmpp_row R = dpmpp_load_row(coef, k);
-    const long HW = (long)g.H * g.W, total = (long)n * g.C * g.T * HW;
-    float* h0 = hist + (long)(k % 3) * total;                    // written: m_k
-    const float* h1 = hist + (long)((k + 2) % 3) * total;        // m_{k-1}
-    const float* h2 = hist + (long)((k + 1) % 3) * total;        // m_{k-2}
+// thread).
+//
+// The geometry walk of the patch-major step kernels (owner: this helper; both kernels below call it).  One item is VC
+// channels x VW neighbouring w of one (b, t, h); the grid-stride loop hands each to
+//   item(b, c0, t, h, w0, e, i):  e[j] the offset of (b, c0, t, h, w0 + j) in a model output, i the dense offset of
+//                                 (b, c0, t, h, w0) in [n, C, T, H, W]; channel c0 + cc is at i + cc * T*H*W.
+// An element is read and written by the same thread, so a dense output may alias a dense input.
+template <int VC, int VW, typename F>
+__device__ __forceinline__ void patch_walk(int n, const patch_geo& g, F item) {
+    const long HW = (long)g.H * g.W;
     const int Wg = g.W / VW, Cg = VC == 1 ? g.C : 1;             // (VC == 4: the channels are inside the item)
     const int Nh = g.H >> g.lh, Nw = g.W >> g.lw, ph = 1 << g.lh, pw = 1 << g.lw;
     const long PC = (long)(1 << (g.lt + g.lh + g.lw)) * g.C_out; // columns of a token
@@ -296,17 +294,56 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_patch_kernel(const T* __restric
         const long b = r;
         const long tok = ((long)(t >> g.lt) * Nh + (h >> g.lh)) * Nw;
         const int pos = ((t & ((1 << g.lt) - 1)) * ph + (h & (ph - 1))) * pw;
-        float u[VW][VC], c[VW][VC];
+        long e[VW];
 #pragma unroll
         for (int j = 0; j < VW; ++j) {
             const int w = w0 + j;
-            const long e = b * g.ld_eps + (tok + (w >> g.lw)) * PC + (long)(pos + (w & (pw - 1))) * g.C_out + c0;
-            dpm_load<T, VC>(eps_u + e, u[j]);
-            dpm_load<T, VC>(eps_c + e, c[j]);
+            e[j] = b * g.ld_eps + (tok + (w >> g.lw)) * PC + (long)(pos + (w & (pw - 1))) * g.C_out + c0;
         }
+        item(b, c0, t, h, w0, e, ((b * g.C + c0) * g.T + t) * HW + (long)h * g.W + w0);
+    }
+}
+
+// The uncond and the cond values of one item, widened to fp32.
+template <typename T, int VC, int VW>
+__device__ __forceinline__ void patch_load(const T* __restrict__ eps_u, const T* __restrict__ eps_c, const long (&e)[VW],
+                                           float (&u)[VW][VC], float (&c)[VW][VC]) {
+#pragma unroll
+    for (int j = 0; j < VW; ++j) {
+        dpm_load<T, VC>(eps_u + e[j], u[j]);
+        dpm_load<T, VC>(eps_c + e[j], c[j]);
+    }
+}
+
+// The sample for the next forward(s): xm_copies times [n, C, T, H, W] in x_model's own type.
+template <int VW>
+__device__ __forceinline__ void patch_store_model(void* xm, int xm_f16, int xm_copies, long total, long i,
+                                                  const float (&out)[VW]) {
+    for (int q = 0; q < (xm ? xm_copies : 0); ++q) {
+        if (xm_f16) dpm_store<half_t, VW>((half_t*)xm + q * total + i, out);
+        else dpm_store<float, VW>((float*)xm + q * total + i, out);
+    }
+}
+
+// x_out may alias x (patch_walk).
+template <typename T, int VC, int VW>
+__global__ __launch_bounds__(256) void cfg_dpmpp_patch_kernel(const T* __restrict__ eps_u, const T* __restrict__ eps_c,
+                                                              const float* x, float* hist, const float* __restrict__ coef,
+                                                              const int32_t* __restrict__ step, float* xo, void* xm,
+                                                              int xm_f16, int xm_copies, int n, patch_geo g, int row,
+                                                              int n_rows) {
+    const int k = step_row(row, step, n_rows);
+    const dpmpp_row R = dpmpp_load_row(coef, k);
+    const long CS = (long)g.T * g.H * g.W, total = (long)n * g.C * CS;
+    float* h0 = hist + (long)(k % 3) * total;                    // written: m_k
+    const float* h1 = hist + (long)((k + 2) % 3) * total;        // m_{k-1}
+    const float* h2 = hist + (long)((k + 1) % 3) * total;        // m_{k-2}
+    patch_walk<VC, VW>(n, g, [&](long, int, int, int, int, const long (&e)[VW], long i0) {
+        float u[VW][VC], c[VW][VC];
+        patch_load<T, VC, VW>(eps_u, eps_c, e, u, c);
 #pragma unroll
         for (int cc = 0; cc < VC; ++cc) {
-            const long i = ((b * g.C + c0 + cc) * g.T + t) * HW + (long)h * g.W + w0;
+            const long i = i0 + cc * CS;
             float xv[VW], m1[VW] = {}, m2[VW] = {}, m0[VW], out[VW];
             dpm_load<float, VW>(x + i, xv);
             if (R.order >= 2) dpm_load<float, VW>(h1 + i, m1);
@@ -315,34 +352,36 @@ __global__ __launch_bounds__(256) void cfg_dpmpp_patch_kernel(const T* __restric
             for (int j = 0; j < VW; ++j) out[j] = dpmpp_element<float>(R, c[j][cc], u[j][cc], xv[j], m1[j], m2[j], m0[j]);
             dpm_store<float, VW>(h0 + i, m0);
             dpm_store<float, VW>(xo + i, out);
-            for (int q = 0; q < (xm ? xm_copies : 0); ++q) {
-                if (xm_f16) dpm_store<half_t, VW>((half_t*)xm + q * total + i, out);
-                else dpm_store<float, VW>((float*)xm + q * total + i, out);
-            }
+            patch_store_model<VW>(xm, xm_f16, xm_copies, total, i, out);
         }
-    }
+    });
 }
 
 static inline int vq_log2_patch(int p) { return p == 1 ? 0 : (p == 2 ? 1 : -1); }
 
-extern "C" int vq_cfg_dpmpp_step_patch(const void* eps_u, const void* eps_c, const float* x, float* hist, const float* coef,
-                                       const int32_t* step, float* x_out, void* x_model, int n, int C, int C_out, int T, int H,
-                                       int W, int p_t, int p_h, int p_w, long ld_eps, int row, int n_rows, int eps_f16,
-                                       int xm_f16, int xm_copies, void* stream) {
-    if (!eps_u || !eps_c || !x || !hist || !coef || !x_out || n <= 0 || C <= 0 || C_out <= 0 || T <= 0 || H <= 0 || W <= 0 ||
-        p_t <= 0 || p_h <= 0 || p_w <= 0 || row < 0 || n_rows <= 0 || row >= n_rows)
+// The refusals of the patch-major entry points, in the order include/viditq.h documents: VQ_EINVAL (``einval``: the
+// solver's own nulls and ranges; then what both have), VQ_ESHAPE (the shapes, the pitch, then every address on the elements
+// of an access: ``f32`` is the null-terminated list of the dense fp32 operands, of which an optional one may only stand
+// last), VQ_EUNSUP (a patch extent outside {1, 2}, a flag outside {0, 1}, xm_copies outside {1, 2}).  Sets the geometry,
+// the access form and the grid, and returns VQ_OK when the launch may go ahead.
+static int patch_check(bool einval, const void* eps_u, const void* eps_c, const void* const* f32, const float* coef,
+                       const int32_t* step, const void* x_model, int n, int C, int C_out, int T, int H, int W, int p_t,
+                       int p_h, int p_w, long ld_eps, int row, int n_rows, int eps_f16, int xm_f16, int xm_copies,
+                       patch_geo* g_out, bool* wide_out, dim3* grid_out) {
+    if (einval || !eps_u || !eps_c || !coef || n <= 0 || C <= 0 || C_out <= 0 || T <= 0 || H <= 0 || W <= 0 || p_t <= 0 ||
+        p_h <= 0 || p_w <= 0 || row < 0 || n_rows <= 0 || row >= n_rows)
         return VQ_EINVAL;
     if (C > C_out || T % p_t || H % p_h || W % p_w) return VQ_ESHAPE;
     // one sample of the model output: T*H*W positions (tokens x patch positions) of C_out columns each
     if (ld_eps < (long)T * H * W * C_out) return VQ_ESHAPE;
-    const bool wide = C == 4 && C_out % 4 == 0 && W % 2 == 0;
+    const bool wide = *wide_out = C == 4 && C_out % 4 == 0 && W % 2 == 0;
     const int VC = wide ? 4 : 1, VW = wide ? 2 : 1;
     const size_t e_sz = eps_f16 == 1 ? 2 : 4, m_sz = xm_f16 == 1 ? 2 : 4;     // (a flag outside {0, 1} is refused below)
-    if (ld_eps % VC || !vq_aligned(eps_u, e_sz * VC) || !vq_aligned(eps_c, e_sz * VC) || !vq_aligned(x, 4 * VW) ||
-        !vq_aligned(hist, 4 * VW) || !vq_aligned(x_out, 4 * VW) || !vq_aligned(x_model, m_sz * VW) || !vq_aligned(coef, 4) ||
-        !vq_aligned(step, 4))
-        return VQ_ESHAPE;
-    patch_geo g;
+    bool aligned = ld_eps % VC == 0 && vq_aligned(eps_u, e_sz * VC) && vq_aligned(eps_c, e_sz * VC) &&
+                   vq_aligned(x_model, m_sz * VW) && vq_aligned(coef, 4) && vq_aligned(step, 4);
+    for (; *f32; ++f32) aligned = aligned && vq_aligned(*f32, 4 * VW);
+    if (!aligned) return VQ_ESHAPE;
+    patch_geo& g = *g_out;
     g.C = C, g.C_out = C_out, g.T = T, g.H = H, g.W = W, g.ld_eps = ld_eps;
     g.lt = vq_log2_patch(p_t), g.lh = vq_log2_patch(p_h), g.lw = vq_log2_patch(p_w);
     if (g.lt < 0 || g.lh < 0 || g.lw < 0 || eps_f16 < 0 || eps_f16 > 1 || xm_f16 < 0 || xm_f16 > 1 || xm_copies < 1 ||
@@ -351,17 +390,134 @@ extern "C" int vq_cfg_dpmpp_step_patch(const void* eps_u, const void* eps_c, con
     const long items = (long)n * (wide ? 1 : C) * T * H * (W / VW);
     long blocks = (items + 255) / 256;
     if (blocks > 1024) blocks = 1024;                            // 16 waves per CU in flight; larger latents loop
-    const dim3 grid((unsigned)blocks);
-#define VQ_PATCH_LAUNCH(T_, VC_, VW_)                                                                                    \
-    hipLaunchKernelGGL((cfg_dpmpp_patch_kernel<T_, VC_, VW_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)eps_u, \
-                       (const T_*)eps_c, x, hist, coef, step, x_out, x_model, xm_f16, xm_copies, n, g, row, n_rows)
+    *grid_out = dim3((unsigned)blocks);
+    return VQ_OK;
+}
+
+// One launch of a patch-major kernel template: ``launch(T(), VC, VW)`` is called once, with the model output's type as a
+// value and the access form as integral constants.
+template <typename F>
+static int patch_launch(bool wide, int eps_f16, F launch) {
+    typedef std::integral_constant<int, 4> four;
+    typedef std::integral_constant<int, 2> two;
+    typedef std::integral_constant<int, 1> one;
     if (eps_f16) {
-        if (wide) VQ_PATCH_LAUNCH(half_t, 4, 2); else VQ_PATCH_LAUNCH(half_t, 1, 1);
+        if (wide) launch(half_t(), four(), two()); else launch(half_t(), one(), one());
     } else {
-        if (wide) VQ_PATCH_LAUNCH(float, 4, 2); else VQ_PATCH_LAUNCH(float, 1, 1);
+        if (wide) launch(float(), four(), two()); else launch(float(), one(), one());
     }
-#undef VQ_PATCH_LAUNCH
     return vq_check_launch();
+}
+
+extern "C" int vq_cfg_dpmpp_step_patch(const void* eps_u, const void* eps_c, const float* x, float* hist, const float* coef,
+                                       const int32_t* step, float* x_out, void* x_model, int n, int C, int C_out, int T, int H,
+                                       int W, int p_t, int p_h, int p_w, long ld_eps, int row, int n_rows, int eps_f16,
+                                       int xm_f16, int xm_copies, void* stream) {
+    const void* const f32[] = {x, hist, x_out, nullptr};
+    patch_geo g;
+    bool wide;
+    dim3 grid;
+    const int rc = patch_check(!x || !hist || !x_out, eps_u, eps_c, f32, coef, step, x_model, n, C, C_out, T, H, W, p_t, p_h,
+                               p_w, ld_eps, row, n_rows, eps_f16, xm_f16, xm_copies, &g, &wide, &grid);
+    if (rc != VQ_OK) return rc;
+    return patch_launch(wide, eps_f16, [&](auto t, auto vc, auto vw) {
+        typedef decltype(t) T_;
+        hipLaunchKernelGGL((cfg_dpmpp_patch_kernel<T_, decltype(vc)::value, decltype(vw)::value>), grid, dim3(256), 0,
+                           (hipStream_t)stream, (const T_*)eps_u, (const T_*)eps_c, x, hist, coef, step, x_out, x_model,
+                           xm_f16, xm_copies, n, g, row, n_rows);
+    });
+}
+
+// ---- the DDIM(eta = 0) step of the STDiT loop on the same patch-major output, table-driven --------------------------
+// Contract and operation sequence: include/viditq.h (vq_cfg_ddim_step_patch).  The row of a launch, read once per thread;
+// the two square roots are cfg_ddim_kernel's expressions.
+struct ddim_row {
+    float cfg, opk, A, Bc, sa, sb;
+};
+
+__device__ __forceinline__ ddim_row ddim_load_row(const float* __restrict__ coef, int k) {
+    const float* r = coef + (long)k * VQ_DDIM_ROW;
+    ddim_row R;
+    R.cfg = r[VQ_DDIM_CFG], R.opk = r[VQ_DDIM_ONE_PLUS_K], R.A = r[VQ_DDIM_A], R.Bc = r[VQ_DDIM_BC];
+    const float abp = r[VQ_DDIM_ABAR_PREV];
+    R.sa = __fsqrt_rn(abp), R.sb = __fsqrt_rn(1.0f - abp - 0.0f);
+    return R;
+}
+
+// vq_cfg_ddim_step's kernel covers 4096 x 256 elements per pass of its grid-stride loop, and its compiled form rounds an
+// element in one of two ways (include/viditq.h): ``paired`` for the passes a thread takes two at a time, the other for a
+// thread's odd last pass - which is every element of a latent of up to 2^20 elements.  Which way element i of ``total`` goes:
+__device__ __forceinline__ bool ddim_paired(long i, long total) {
+    const long pass = 1L << 20;
+    if (total <= pass) return false;
+    const long first = i & (pass - 1);                           // the thread's first element
+    const long passes = ((total - 1 - first) >> 20) + 1;         // how many that thread takes
+    return (i >> 20) < (passes & ~1L);
+}
+
+// One element: PTQD division, guidance on the channels below ``guided``, x0, eps back from x0 and the eta = 0 update,
+// every operation spelled out.  Under the pragma a plain * / - / + is one rounding and is never fused; every fused
+// multiply-add is an explicit __fmaf_rn.  (The __fmul_rn / __fsub_rn / __fadd_rn intrinsics are NOT used for the unfused
+// operations: they are inline header functions compiled in the header's contraction mode, and hipcc fuses a product and a
+// sum written through them - measured here, where both forms of ``r`` came out as one v_fma_f32.)
+__device__ __forceinline__ float ddim_element(const ddim_row& R, float cnd, float unc, float xv, bool guide, bool paired) {
+#pragma clang fp contract(off)
+    const float cv = __fdiv_rn(cnd, R.opk);
+    const float uv = __fdiv_rn(unc, R.opk);
+    const float d = cv - uv;
+    const float e = guide ? __fmaf_rn(R.cfg, d, uv) : cv;
+    const float be = R.Bc * e;
+    const float x0 = __fmaf_rn(R.A, xv, -be);
+    const float ax = R.A * xv;
+    const float r = paired ? __fmaf_rn(R.A, xv, -x0) : ax - x0;
+    const float e2 = __fdiv_rn(r, R.Bc);
+    const float p2 = R.sb * e2;
+    const float p1 = R.sa * x0;
+    return paired ? __fmaf_rn(R.sa, x0, p2) : p1 + p2;
+}
+
+template <typename T, int VC, int VW>
+__global__ __launch_bounds__(256) void cfg_ddim_patch_kernel(const T* __restrict__ eps_c, const T* __restrict__ eps_u,
+                                                             const float* x, const float* __restrict__ coef,
+                                                             const int32_t* __restrict__ step, float* xo, void* xm,
+                                                             int xm_f16, int xm_copies, int n, patch_geo g, int guided,
+                                                             int row, int n_rows) {
+    const ddim_row R = ddim_load_row(coef, step_row(row, step, n_rows));
+    const long CS = (long)g.T * g.H * g.W, total = (long)n * g.C * CS;
+    patch_walk<VC, VW>(n, g, [&](long, int c0, int, int, int, const long (&e)[VW], long i0) {
+        float u[VW][VC], c[VW][VC];
+        patch_load<T, VC, VW>(eps_u, eps_c, e, u, c);
+#pragma unroll
+        for (int cc = 0; cc < VC; ++cc) {
+            const long i = i0 + cc * CS;
+            float xv[VW], out[VW];
+            dpm_load<float, VW>(x + i, xv);
+#pragma unroll
+            for (int j = 0; j < VW; ++j)
+                out[j] = ddim_element(R, c[j][cc], u[j][cc], xv[j], c0 + cc < guided, ddim_paired(i + j, total));
+            dpm_store<float, VW>(xo + i, out);
+            patch_store_model<VW>(xm, xm_f16, xm_copies, total, i, out);
+        }
+    });
+}
+
+extern "C" int vq_cfg_ddim_step_patch(const void* eps_c, const void* eps_u, const float* x, const float* coef,
+                                      const int32_t* step, float* x_out, void* x_model, int n, int C, int C_out, int T, int H,
+                                      int W, int p_t, int p_h, int p_w, long ld_eps, int guided, int row, int n_rows,
+                                      int eps_f16, int xm_f16, int xm_copies, void* stream) {
+    const void* const f32[] = {x, x_out, nullptr};
+    patch_geo g;
+    bool wide;
+    dim3 grid;
+    const int rc = patch_check(!x || !x_out || guided < 0, eps_u, eps_c, f32, coef, step, x_model, n, C, C_out, T, H, W, p_t,
+                               p_h, p_w, ld_eps, row, n_rows, eps_f16, xm_f16, xm_copies, &g, &wide, &grid);
+    if (rc != VQ_OK) return rc;
+    return patch_launch(wide, eps_f16, [&](auto t, auto vc, auto vw) {
+        typedef decltype(t) T_;
+        hipLaunchKernelGGL((cfg_ddim_patch_kernel<T_, decltype(vc)::value, decltype(vw)::value>), grid, dim3(256), 0,
+                           (hipStream_t)stream, (const T_*)eps_c, (const T_*)eps_u, x, coef, step, x_out, x_model, xm_f16,
+                           xm_copies, n, g, guided, row, n_rows);
+    });
 }
 
 // One workgroup, after the step kernel in stream order: t_out[0 .. n_t) = the row's next model-input time, then the

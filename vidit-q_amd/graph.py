@@ -400,33 +400,52 @@ class SAStepGraph(_CounterStepGraph):
         return self.xp.clone()
 
 
-class VideoDPMStepGraph(_CounterStepGraph):
-    """The fused DPM-Solver++ loop of t2v/dpm_solver.py in the counter form: {forward(patch_major=True) - once for the
-    joint route, twice for cfg_split, the two chains forked onto a side stream as StepGraph._forward does -,
-    ops.cfg_dpmpp_step_patch(step=counter), ops.dpmpp_advance}.  The smooth-quant time range of a forward is host state
-    that a capture bakes in, so there is one capture per range the schedule visits (GraphedSampler._range_of), ALL taken
-    here, before the first replay; the warm-up passes move x, xm, t, the counter and the history, which are reset
-    afterwards.  ``solver``: a t2v.dpm_solver.VideoDPMSolverPP; ``t_vals``: the model-input time of every call."""
+class _RangedStepGraph(_CounterStepGraph):
+    """What the STDiT one-graph loops share.  The smooth-quant time range of a forward is host state that a capture bakes
+    in, so there is one capture per range the schedule visits (GraphedSampler._range_of), ALL taken in the constructor,
+    before the first replay; the warm-up passes move x, xm, t, the counter and whatever else the step keeps, which are
+    reset afterwards (``_clear`` for the subclass's own buffers).  ``t_vals``: the model-input time of every call, which a
+    QuantModel also receives as ``timestep_id``; ``_forward(serial)`` reads the one being captured from ``self.t_id``.
+    ``split``: two forwards of n samples (the second chain forked onto ``self.side``) instead of one joint forward."""
 
-    def __init__(self, solver, x, rows, t_vals, warmup: int = 2):
+    def __init__(self, net, kwargs, x, rows, t_vals, model_dtype, warmup, split):
         from .qdiff.models.quant_model import QuantModel
-        self.solver, self.patch = solver, tuple(solver.net.patch_size)
-        self.side = torch.cuda.Stream() if solver.cfg_split else None
-        self.hist = torch.zeros((3, x.numel()), dtype=torch.float32, device=x.device)
-        ranged = GraphedSampler(solver.net, None, None, None) if isinstance(solver.net, QuantModel) else None
+        self.side = torch.cuda.Stream() if split else None
+        ranged = GraphedSampler(net, None, None, None) if isinstance(net, QuantModel) else None
         self.range_of = [0 if ranged is None else ranged._range_of(t) for t in t_vals]
         self.t_id = t_vals[0]
-        kwargs = dict(solver.model_kwargs, timestep_id=t_vals[0])
         # the first pass on ONE stream: it packs weights and fills the module-level caches (StepGraph)
-        super().__init__(solver.net.forward, kwargs, x, rows, t_vals[0], solver.model_input_dtype, warmup,
-                         copies=1 if solver.cfg_split else 2, first=lambda: self._forward(serial=True))
+        super().__init__(net.forward, dict(kwargs, timestep_id=t_vals[0]), x, rows, t_vals[0], model_dtype, warmup,
+                         copies=1 if split else 2, first=lambda: self._forward(serial=True))
         self.graphs = {self.range_of[0]: self.graph}
         for k, r in enumerate(self.range_of):
             if r not in self.graphs:
                 self.t_id = t_vals[k]
                 self.graphs[r] = self._capture_step(warmup, first=lambda: self._forward(serial=True))
-        self.hist.zero_()
+        self._clear()
         self._reset(x)
+
+    def _clear(self):
+        pass
+
+    def _select(self, k):
+        self.graph = self.graphs[self.range_of[k]]
+
+
+class VideoDPMStepGraph(_RangedStepGraph):
+    """The fused DPM-Solver++ loop of t2v/dpm_solver.py in the counter form: {forward(patch_major=True) - once for the
+    joint route, twice for cfg_split, the two chains forked onto a side stream as StepGraph._forward does -,
+    ops.cfg_dpmpp_step_patch(step=counter), ops.dpmpp_advance}, one capture per smooth-quant time range
+    (_RangedStepGraph).  ``solver``: a t2v.dpm_solver.VideoDPMSolverPP; ``t_vals``: the model-input time of every call."""
+
+    def __init__(self, solver, x, rows, t_vals, warmup: int = 2):
+        self.solver, self.patch = solver, tuple(solver.net.patch_size)
+        self.hist = torch.zeros((3, x.numel()), dtype=torch.float32, device=x.device)
+        super().__init__(solver.net, solver.model_kwargs, x, rows, t_vals, solver.model_input_dtype, warmup,
+                         solver.cfg_split)
+
+    def _clear(self):
+        self.hist.zero_()
 
     def _forward(self, serial=False):
         return self.solver._forward_patch(self.xm, self.t, self.t_id, side=None if serial else self.side)
@@ -438,11 +457,53 @@ class VideoDPMStepGraph(_CounterStepGraph):
         ops.cfg_dpmpp_step_patch(eps[0], eps[1], self.x, self.hist, self.rows, 0, self.patch, step=self.step, x_out=self.x,
                                  x_model=self.xm)
 
-    def _select(self, k):
-        self.graph = self.graphs[self.range_of[k]]
-
     @torch.no_grad()
     def run(self, x, step_callback=None):
         self._loop(x, before=self._select,
                    after=None if step_callback is None else lambda k: step_callback(k + 1, self.x.clone()))
+        return self.x.clone()
+
+
+class VideoDDIMStepGraph(_RangedStepGraph):
+    """The fused DDIM loop of t2v/iddpm.py in the counter form: {forward(patch_major=True) - once for the joint route,
+    twice for cfg_split -, ops.cfg_ddim_step_patch(step=counter), ops.dpmpp_advance}, one capture per smooth-quant time
+    range (_RangedStepGraph).  PTQD's ``ks`` rides in the table.  ``sampler``: a t2v.iddpm.IDDPM; ``model_args``: what
+    ddim_sample_loop takes.  A model with ``timestep_wise_mp`` is refused: the host switches it between steps."""
+
+    def __init__(self, sampler, model, x, model_args, ks=None, warmup: int = 2):
+        from ._lib import VQError
+        from .t2v.iddpm import _accepts_timestep_id
+        if getattr(model, "timestep_wise_mp", False):
+            raise VQError("VideoDDIMStepGraph: timestep_wise_mp switches the model on the host between steps; "
+                          "use ddim_sample_loop(fused=True)")
+        n = x.shape[0]
+        y = model_args["y"]
+        self.model, self.patch = model, tuple(model.patch_size)
+        self.split = bool(getattr(model, "cfg_split", False))
+        self.texts = (y[:n], y[n:]) if self.split else torch.cat([y[:n], y[n:]], 0)
+        self.kw = {k: v for k, v in model_args.items() if k != "y"}
+        self.takes_id = _accepts_timestep_id(model)
+        self.indices = list(range(sampler.num_timesteps))[::-1]
+        t_vals = [sampler.timestep_map[i] for i in self.indices]
+        super().__init__(model, self.kw, x, sampler.ddim_rows(sampler.cfg_scale, ks), t_vals,
+                         getattr(model, "dtype", torch.float32), warmup, self.split)
+
+    def _forward(self, serial=False):
+        from .t2v.iddpm import patch_forward_pair
+        kw = dict(self.kw, timestep_id=self.t_id) if self.takes_id else self.kw
+        return patch_forward_pair(self.model, self.xm, self.t, self.texts, self.split, kw,
+                                  side=None if serial else self.side)
+
+    def _step(self, eps):
+        from . import ops
+        if not ops.cfg_ddim_step_patch_ok(eps[0], eps[1], self.x, self.patch):
+            self._refuse_output("vq_cfg_ddim_step_patch")
+        ops.cfg_ddim_step_patch(eps[0], eps[1], self.x, self.rows, 0, self.patch, step=self.step, x_out=self.x,
+                                x_model=self.xm)
+
+    @torch.no_grad()
+    def run(self, x, step_callback=None):
+        """``step_callback(i, x)`` with the loop index of ddim_sample_loop (num_timesteps - 1 down to 0)."""
+        self._loop(x, before=self._select,
+                   after=None if step_callback is None else lambda k: step_callback(self.indices[k], self.x.clone()))
         return self.x.clone()

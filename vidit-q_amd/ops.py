@@ -1191,16 +1191,17 @@ def _patch_geometry(eps_u, eps_c, x, patch):
     return n, Cc, int(es[2]) // P, T, H, W, int(eps_u.stride()[0])
 
 
-def cfg_dpmpp_step_patch_ok(eps_u, eps_c, x, patch) -> bool:
-    """Whether vq_cfg_dpmpp_step_patch takes the two model outputs and the latent (include/viditq.h), asked before the
-    launch from shapes, strides and addresses: GPU tensors, fp32 x, fp16 / fp32 eps and patch extents of 1 or 2 (VQ_EUNSUP),
-    positive extents (VQ_EINVAL), and VQ_ESHAPE: the layout, C <= C_out, ld_eps >= T*H*W*C_out and the pitch and the base
-    addresses on the elements of an access (4 channels x 2 along w when C == 4, C_out % 4 == 0 and W % 2 == 0, else 1 x 1)."""
-    if not (eps_u.is_cuda and eps_c.is_cuda and x.is_cuda):
+def _patch_ok(eps_a, eps_b, x, patch) -> bool:
+    """The refusals of a patch-major entry point (include/viditq.h) that depend on the two model outputs and the latent,
+    asked before the launch from shapes, strides and addresses: GPU tensors, fp32 x, fp16 / fp32 eps and patch extents of 1
+    or 2 (VQ_EUNSUP), positive extents (VQ_EINVAL), and VQ_ESHAPE: the layout, C <= C_out, ld_eps >= T*H*W*C_out and the
+    pitch and the base addresses on the elements of an access (4 channels x 2 along w when C == 4, C_out % 4 == 0 and
+    W % 2 == 0, else 1 x 1)."""
+    if not (eps_a.is_cuda and eps_b.is_cuda and x.is_cuda):
         return False
-    if x.dtype != torch.float32 or eps_u.dtype not in (torch.float16, torch.float32):
+    if x.dtype != torch.float32 or eps_a.dtype not in (torch.float16, torch.float32):
         return False
-    geo = _patch_geometry(eps_u, eps_c, x, patch)
+    geo = _patch_geometry(eps_a, eps_b, x, patch)
     if geo is None or any(int(p) not in (1, 2) for p in patch):
         return False
     n, Cc, Co, T, H, W, ld = geo
@@ -1208,31 +1209,29 @@ def cfg_dpmpp_step_patch_ok(eps_u, eps_c, x, patch) -> bool:
         return False
     wide = Cc == 4 and Co % 4 == 0 and W % 2 == 0
     VC, VW = (4, 2) if wide else (1, 1)
-    ea = eps_u.element_size() * VC
-    return ld % VC == 0 and eps_u.data_ptr() % ea == 0 and eps_c.data_ptr() % ea == 0 and x.data_ptr() % (4 * VW) == 0
+    ea = eps_a.element_size() * VC
+    return ld % VC == 0 and eps_a.data_ptr() % ea == 0 and eps_b.data_ptr() % ea == 0 and x.data_ptr() % (4 * VW) == 0
 
 
-def cfg_dpmpp_step_patch(eps_u: torch.Tensor, eps_c: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, coef: torch.Tensor,
-                         row: int, patch, step: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None,
-                         x_model: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """One call of the DPM-Solver++ step of cfg_dpmpp_step on the patch-major model output (vq_cfg_dpmpp_step_patch):
-    ``eps_u`` / ``eps_c`` the uncond / cond outputs of final_layer [n, tokens, p_t*p_h*p_w*C_out] (fp16 / fp32, sample pitch
-    free; the two halves of one joint output, or the outputs of two forwards), ``x`` [n, C, T, H, W] fp32, ``patch``
-    (p_t, p_h, p_w); hist, coef, row and step as for cfg_dpmpp_step.  All arithmetic is fp32.  Returns x_out (may be ``x``
-    itself); ``x_model`` [n or 2n, C, T, H, W] (fp16 / fp32) receives it once or twice."""
-    for t, name in ((eps_u, "eps_u"), (eps_c, "eps_c"), (x, "x"), (hist, "hist"), (coef, "coef")):
+def _patch_front(eps_a, eps_b, names, x, aux, coef, row_len, refuse, patch, step, x_out, x_model):
+    """What both patch-major wrappers do before their launch: GPU tensors, fp32 x / ``aux`` (name -> tensor) / coef,
+    fp16 / fp32 eps, the geometry, coef rows of ``row_len`` floats and the solver's own clause ``refuse`` = (bad, message),
+    the counter, x_out (allocated when None) and x_model.  Returns (n, C, C_out, T, H, W, ld_eps, p_t, p_h, p_w, x_out,
+    xm_f16, xm_copies)."""
+    for t, name in ((eps_a, names[0]), (eps_b, names[1]), (x, "x"), *((v, k) for k, v in aux.items()), (coef, "coef")):
         if not t.is_cuda:
             raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % name)
     _req(x, torch.float32, "x")
-    _req(hist, torch.float32, "hist")
+    for k, v in aux.items():
+        _req(v, torch.float32, k)
     _req(coef, torch.float32, "coef")
-    if eps_u.dtype not in (torch.float16, torch.float32):
-        raise VQError("eps must be float16 or float32, got %s" % eps_u.dtype)
-    geo = _patch_geometry(eps_u, eps_c, x, patch)
+    if eps_a.dtype not in (torch.float16, torch.float32):
+        raise VQError("eps must be float16 or float32, got %s" % eps_a.dtype)
+    geo = _patch_geometry(eps_a, eps_b, x, patch)
     if geo is None:
-        raise VQError("eps_u / eps_c must be [n, tokens, p_t*p_h*p_w*C_out] with equal strides for x [n, C, T, H, W]")
-    if hist.numel() != 3 * x.numel() or coef.dim() != 2 or coef.shape[1] != _lib.DPMPP_ROW:
-        raise VQError("hist must hold 3 x %d fp32 and coef rows of %d floats" % (x.numel(), _lib.DPMPP_ROW))
+        raise VQError("%s / %s must be [n, tokens, p_t*p_h*p_w*C_out] with equal strides for x [n, C, T, H, W]" % names)
+    if refuse[0] or coef.dim() != 2 or coef.shape[1] != row_len:
+        raise VQError(refuse[1])
     if step is not None:
         _req(step, torch.int32, "step")
     if x_out is None:
@@ -1247,18 +1246,58 @@ def cfg_dpmpp_step_patch(eps_u: torch.Tensor, eps_c: torch.Tensor, x: torch.Tens
         copies = x_model.numel() // x.numel()
         assert x_model.numel() == copies * x.numel()
         xm16 = int(x_model.dtype == torch.float16)
-    n, Cc, Co, T, H, W, ld = geo
-    pt, ph, pw = (int(p) for p in patch)
+    return (*geo, *(int(p) for p in patch), x_out, xm16, copies)
+
+
+def cfg_dpmpp_step_patch_ok(eps_u, eps_c, x, patch) -> bool:
+    """Whether vq_cfg_dpmpp_step_patch takes the two model outputs and the latent (_patch_ok)."""
+    return _patch_ok(eps_u, eps_c, x, patch)
+
+
+def cfg_dpmpp_step_patch(eps_u: torch.Tensor, eps_c: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, coef: torch.Tensor,
+                         row: int, patch, step: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None,
+                         x_model: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One call of the DPM-Solver++ step of cfg_dpmpp_step on the patch-major model output (vq_cfg_dpmpp_step_patch):
+    ``eps_u`` / ``eps_c`` the uncond / cond outputs of final_layer [n, tokens, p_t*p_h*p_w*C_out] (fp16 / fp32, sample pitch
+    free; the two halves of one joint output, or the outputs of two forwards), ``x`` [n, C, T, H, W] fp32, ``patch``
+    (p_t, p_h, p_w); hist, coef, row and step as for cfg_dpmpp_step.  All arithmetic is fp32.  Returns x_out (may be ``x``
+    itself); ``x_model`` [n or 2n, C, T, H, W] (fp16 / fp32) receives it once or twice."""
+    n, Cc, Co, T, H, W, ld, pt, ph, pw, x_out, xm16, copies = _patch_front(
+        eps_u, eps_c, ("eps_u", "eps_c"), x, {"hist": hist}, coef, _lib.DPMPP_ROW,
+        (hist.numel() != 3 * x.numel(), "hist must hold 3 x %d fp32 and coef rows of %d floats" % (x.numel(), _lib.DPMPP_ROW)),
+        patch, step, x_out, x_model)
     check(_L().vq_cfg_dpmpp_step_patch(_p(eps_u), _p(eps_c), _p(x), _p(hist), _p(coef), _p(step), _p(x_out), _p(x_model), n,
                                        Cc, Co, T, H, W, pt, ph, pw, ld, int(row), coef.shape[0],
                                        int(eps_u.dtype == torch.float16), xm16, copies, _stream()), "vq_cfg_dpmpp_step_patch")
     return x_out
 
 
+def cfg_ddim_step_patch_ok(eps_c, eps_u, x, patch) -> bool:
+    """Whether vq_cfg_ddim_step_patch takes the two model outputs and the latent (_patch_ok)."""
+    return _patch_ok(eps_c, eps_u, x, patch)
+
+
+def cfg_ddim_step_patch(eps_c: torch.Tensor, eps_u: torch.Tensor, x: torch.Tensor, rows: torch.Tensor, row: int, patch,
+                        step: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None,
+                        x_model: Optional[torch.Tensor] = None, guided: int = 3) -> torch.Tensor:
+    """One call of the DDIM(eta = 0) step of cfg_ddim_step on the patch-major model output (vq_cfg_ddim_step_patch):
+    ``eps_c`` / ``eps_u`` the cond / uncond outputs of final_layer [n, tokens, p_t*p_h*p_w*C_out] (fp16 / fp32, sample pitch
+    free; the two halves of one joint output, or the outputs of two forwards), ``x`` [n, C, T, H, W] fp32, ``rows``
+    [n_rows, DDIM_ROW] fp32 on the device (IDDPM.ddim_rows); the row is ``row`` plus the device counter ``step`` (int32, one
+    element) when given.  Guidance on the channels below ``guided``.  Bit for bit cfg_ddim_step on the unpatchified fp32
+    tensor.  Returns x_out (may be ``x`` itself); ``x_model`` [n or 2n, C, T, H, W] (fp16 / fp32) receives it once or twice."""
+    n, Cc, Co, T, H, W, ld, pt, ph, pw, x_out, xm16, copies = _patch_front(
+        eps_c, eps_u, ("eps_c", "eps_u"), x, {}, rows, _lib.DDIM_ROW,
+        (int(guided) < 0, "guided must be >= 0 and rows must have %d floats" % _lib.DDIM_ROW), patch, step, x_out, x_model)
+    check(_L().vq_cfg_ddim_step_patch(_p(eps_c), _p(eps_u), _p(x), _p(rows), _p(step), _p(x_out), _p(x_model), n, Cc, Co, T,
+                                      H, W, pt, ph, pw, ld, int(guided), int(row), rows.shape[0],
+                                      int(eps_c.dtype == torch.float16), xm16, copies, _stream()), "vq_cfg_ddim_step_patch")
+    return x_out
+
+
 def dpmpp_advance(step: torch.Tensor, coef: torch.Tensor, t_out: torch.Tensor) -> None:
     """t_out[:] = the counter's row's next model-input time, then the counter moves on (saturating at the last row):
-    vq_dpmpp_advance, enqueued after cfg_dpmpp_step(step=counter) or cfg_ddpm_step(step=counter) (T_NEXT is the same
-    column in both row layouts)."""
+    vq_dpmpp_advance, enqueued after a table-driven step(step=counter) (T_NEXT is the same column in every row layout)."""
     _req(step, torch.int32, "step")
     _req(coef, torch.float32, "coef")
     _req(t_out, torch.float32, "t_out")

@@ -26,7 +26,7 @@ from functools import partial
 import torch
 
 from ..t2i.dpm_solver import DPMSolverPP, _switch
-from .iddpm import _accepts_timestep_id, model_forward_pair
+from .iddpm import _accepts_timestep_id, model_forward_pair, patch_forward_pair
 
 _T2V_DPM_FUSED = _switch("VQ_T2V_DPM_FUSED", False)   # the patch-major step behind each model call
 
@@ -78,20 +78,9 @@ class VideoDPMSolverPP(DPMSolverPP):
         kw = {k: v for k, v in self.model_kwargs.items() if k != "timestep_id"}
         if self._takes_id:
             kw["timestep_id"] = t_val
-        net = self.net
         if not self.cfg_split:
-            n = xm.shape[0] // 2
-            out = net.forward(xm, t, self._joint_text(), patch_major=True, **kw)
-            return out[:n], out[n:]
-        if side is None:
-            eps_c = net.forward(xm, t, self.condition, patch_major=True, **kw)
-            return net.forward(xm, t, self.uncondition, patch_major=True, **kw), eps_c
-        cur = torch.cuda.current_stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            eps_u = net.forward(xm, t, self.uncondition, patch_major=True, **kw)
-        eps_c = net.forward(xm, t, self.condition, patch_major=True, **kw)
-        cur.wait_stream(side)
+            return patch_forward_pair(self.net, xm, t, self._joint_text(), False, kw)
+        eps_c, eps_u = patch_forward_pair(self.net, xm, t, (self.condition, self.uncondition), True, kw, side=side)
         return eps_u, eps_c
 
     def _eager_eps(self, pair):

@@ -15,15 +15,27 @@ As-released behaviours kept (SURVEY A.4-5): guidance on 3 of the 4 eps channels;
 is the first half of the duplicated batch; PTQD ``1/(1+k)`` with k looked up by (999-t)//50 -
 ``ks`` is an explicit optional argument here (default 0) because the reference's file
 (./t2v/rebuttal_files/k_for_each_timestep.pth) is not shipped.
+
+The fused route (``fused=True`` or VQ_T2V_DDIM_FUSED=1, off by default): per step ``forward(patch_major=True)`` once
+(joint) or twice (``cfg_split``) and one ops.cfg_ddim_step_patch, which reads final_layer's output where the model left
+it - no unpatchify copy, no fp32 cast, no ``torch.full`` / ``torch.cat`` on the host - takes its scalars (PTQD's 1 + k
+among them) from a device table (``ddim_rows``) and writes the next forward's input in the model's dtype.  Bit-identical
+to the eager expressions on the same device.  ``step_graph`` is its one-graph form (graph.VideoDDIMStepGraph).
 """
 from __future__ import annotations
 
+import inspect
+import os
 from typing import Optional
 
 import numpy as np
 import torch
 
-from .. import ops
+from .. import _lib, ops
+
+# DESIGN 8 item 10b: the patch-major step behind each forward.  Read once, here (t2i imports this module: its _switch
+# cannot be imported from here)
+_T2V_DDIM_FUSED = os.environ.get("VQ_T2V_DDIM_FUSED", "0") != "0"
 
 
 def get_key_for_value(dict_ranges, value):
@@ -132,6 +144,7 @@ class IDDPM:
         self.sqrt_recip_alphas_cumprod = np.sqrt(1.0 / self.alphas_cumprod)
         self.sqrt_recipm1_alphas_cumprod = np.sqrt(1.0 / self.alphas_cumprod - 1)
         self.cfg_scale = cfg_scale
+        self._tables = {}                        # fused_loop.device_table: (cfg, ks, device, n) -> table on the device
 
     # ------------------------------------------------------------------ one DDIM step
     def ddim_step(self, x, cond_out, uncond_out, i: int, cfg_scale: float, k: float = 0.0, out=None):
@@ -142,12 +155,30 @@ class IDDPM:
         return ops.cfg_ddim_step(cond_out.contiguous(), uncond_out.contiguous(), x.contiguous(), cfg_scale, 1.0 + k,
                                  float(A), float(Bc), float(abp), out=out)
 
+    def ddim_rows(self, cfg_scale: float, ks=None) -> torch.Tensor:
+        """The coefficient table of ops.cfg_ddim_step_patch, fp32 [num_timesteps, DDIM_ROW] in LOOP order (row 0 is the
+        first step, the highest t): per row the np.float32 scalars ``ddim_step`` passes for that step - cfg, 1 + k with
+        ``ks`` looked up as in the loop, A, Bc, abar_prev - and, in the slot every row layout shares, the model-input
+        time of the NEXT forward (the last row repeats its own)."""
+        rows = np.zeros((self.num_timesteps, _lib.DDIM_ROW), dtype=np.float32)
+        order = list(range(self.num_timesteps))[::-1]
+        for r, i in enumerate(order):
+            t_id = self.timestep_map[i]
+            k = 0.0 if ks is None else float(ks[(999 - t_id) // 50])
+            rows[r, _lib.DDIM_CFG] = np.float32(cfg_scale)
+            rows[r, _lib.DDIM_ONE_PLUS_K] = np.float32(1.0 + k)
+            rows[r, _lib.DDIM_A] = np.float32(self.sqrt_recip_alphas_cumprod[i])
+            rows[r, _lib.DDIM_BC] = np.float32(self.sqrt_recipm1_alphas_cumprod[i])
+            rows[r, _lib.DDIM_ABAR_PREV] = np.float32(self.alphas_cumprod_prev[i])
+            rows[r, _lib.DDIM_T_NEXT] = np.float32(self.timestep_map[order[min(r + 1, len(order) - 1)]])
+        return torch.from_numpy(rows)
+
     # ------------------------------------------------------------------ full loop
     @torch.no_grad()
     def sample(self, model, text_encoder, sampler_type, z_size, prompts, device, return_trajectory=False,
                additional_args=None, init_noise=None, ks: Optional[torch.Tensor] = None, generator=None,
-               progress=False):
-        """iddpm/__init__.py:53-132.  Returns the n kept samples [n, *z_size] fp32."""
+               progress=False, fused=None):
+        """iddpm/__init__.py:53-132.  Returns the n kept samples [n, *z_size] fp32.  ``fused``: ddim_sample_loop's."""
         if sampler_type != "ddim":
             raise NotImplementedError("only sampler_type='ddim' works in the reference (SURVEY A.4-5)")
         n = len(prompts)
@@ -172,13 +203,17 @@ class IDDPM:
             for k_, v_ in additional_args.items():
                 if k_ not in ("precompute_text_embeds", "batch_ids"):
                     model_args[k_] = v_
-        return self.ddim_sample_loop(model, z, model_args, ks=ks, progress=progress)
+        return self.ddim_sample_loop(model, z, model_args, ks=ks, progress=progress, fused=fused)
 
     @torch.no_grad()
-    def ddim_sample_loop(self, model, z, model_args, ks=None, progress=False, step_callback=None, graphed=False):
+    def ddim_sample_loop(self, model, z, model_args, ks=None, progress=False, step_callback=None, graphed=False,
+                         fused=None):
         """x: the kept half only (both halves evolve identically in the reference: :161-162).
         ``graphed``: replay the two forward-samples of a step from a HIP graph (one graph per smooth-quant
-        time-range and mixed-precision key, graph.GraphedSampler); needs ``cfg_split`` and a QuantModel."""
+        time-range and mixed-precision key, graph.GraphedSampler); needs ``cfg_split`` and a QuantModel.
+        ``fused``: the patch-major forwards and ops.cfg_ddim_step_patch per step (None reads the VQ_T2V_DDIM_FUSED
+        switch); CPU tensors, a model whose forward takes no ``patch_major`` and a model output the entry point
+        refuses run the eager expressions, the last from the forward already made."""
         x = z.float().contiguous()
         n = x.shape[0]
         y, mask = model_args["y"], model_args.get("mask")
@@ -193,10 +228,17 @@ class IDDPM:
             from ..graph import GraphedSampler
             assert cfg_split and _accepts_timestep_id(model) and not extra, "graphed sampling: cfg_split QuantModel"
             gs = GraphedSampler(model, y_cond, y_uncond, mask)
+        first = None
+        if (_T2V_DDIM_FUSED if fused is None else fused) and gs is None and x.is_cuda and takes_patch_major(model):
+            x_f, first = self._ddim_fused(model, x, y_cond, y_uncond, mask, extra, cfg_split, ks, mp, step_callback)
+            if x_f is not None:
+                return x_f
         for i in indices:
             t_id = self.timestep_map[i]
             key = mp.apply(i) if mp is not None else None
-            if gs is not None:
+            if first is not None:                          # the refused output of the fused route: not computed again
+                (cond, uncond), first = first, None
+            elif gs is not None:
                 cond, uncond = gs.forward_pair(x, t_id, key)
             else:
                 t = torch.full((n,), t_id, device=x.device, dtype=torch.long)
@@ -207,6 +249,85 @@ class IDDPM:
             if step_callback is not None:
                 step_callback(i, x)
         return x
+
+    def _ddim_fused(self, model, x, y_cond, y_uncond, mask, extra, cfg_split, ks, mp, step_callback):
+        """The loop above with the patch-major forwards and step.  Returns (x, None), or (None, (cond, uncond)) - the first
+        step's model outputs as the eager step takes them - when ops.cfg_ddim_step_patch_ok refuses them."""
+        from ..t2i.fused_loop import device_table, fused_loop
+        n = x.shape[0]
+        copies = 1 if cfg_split else 2
+        patch = tuple(model.patch_size)
+        texts = (y_cond, y_uncond) if cfg_split else torch.cat([y_cond, y_uncond], 0)
+        takes_id = _accepts_timestep_id(model)
+        x = x.clone()                                      # the step writes in place; the caller's latent stays
+        xm = torch.cat([x] * copies).to(getattr(model, "dtype", torch.float32))
+        indices = list(range(self.num_timesteps))[::-1]
+        t = torch.full((copies * n,), float(self.timestep_map[indices[0]]), dtype=torch.float32, device=x.device)
+
+        def forward(xm, t):
+            i = indices[call[0]]
+            call[0] += 1
+            if mp is not None:
+                mp.apply(i)
+            kw = dict(extra, mask=mask)
+            if takes_id:
+                kw["timestep_id"] = self.timestep_map[i]
+            return patch_forward_pair(model, xm, t[:copies * n], texts, cfg_split, kw)
+
+        def table(eps, x):
+            if not ops.cfg_ddim_step_patch_ok(eps[0], eps[1], x, patch):
+                return None
+            key = (float(self.cfg_scale), None if ks is None else tuple(float(v) for v in ks), str(x.device), n)
+            return device_table(self._tables, key, lambda: self.ddim_rows(self.cfg_scale, ks), x.device, n)
+
+        def step(k, eps, x, rows):
+            ops.cfg_ddim_step_patch(eps[0], eps[1], x, rows, k, patch, x_out=x, x_model=xm)
+            if step_callback is not None:
+                step_callback(indices[k], x)
+            return x
+
+        call = [0]
+        x_f, eps0 = fused_loop(self.num_timesteps, x, xm, t, forward, table, step)
+        if x_f is not None:
+            return x_f, None
+        return None, tuple(model.unpatchify(e).to(torch.float32) for e in eps0)
+
+    def step_graph(self, model, x, model_args, ks=None, warmup=2):
+        """The counter form of the fused loop: {forward(s), patch-major step, counter advance} captured as HIP graphs - one
+        per smooth-quant time range the schedule visits - and replayed ``num_timesteps`` times; ``.run(x)`` samples from a
+        start latent [n, ...].  PTQD's ``ks`` rides in the table."""
+        from ..graph import VideoDDIMStepGraph
+        return VideoDDIMStepGraph(self, model, x, model_args, ks=ks, warmup=warmup)
+
+
+def takes_patch_major(model) -> bool:
+    """Whether ``model.forward`` (a QuantModel's wrapped model's) has the ``patch_major`` argument of STDiT.forward."""
+    target = getattr(model, "model", model) if _accepts_timestep_id(model) else model
+    try:
+        return "patch_major" in inspect.signature(target.forward).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+def patch_forward_pair(model, xm, t, texts, cfg_split, kw, side=None):
+    """The patch-major forwards of one denoising step, (first, second) in the order of ``texts``.  Joint: ``texts`` is the
+    joint text of 2n samples and the result the two halves of ONE forward of ``xm`` [2n, ...].  ``cfg_split``: ``texts``
+    is a pair and each gets a forward of ``xm`` [n, ...], the first and then the second - the second's chain on the stream
+    ``side`` when one is given (a capture forks it as graph.StepGraph does).  ``kw``: mask, timestep_id and the rest."""
+    if not cfg_split:
+        n = xm.shape[0] // 2
+        out = model.forward(xm, t, texts, patch_major=True, **kw)
+        return out[:n], out[n:]
+    if side is None:
+        first = model.forward(xm, t, texts[0], patch_major=True, **kw)
+        return first, model.forward(xm, t, texts[1], patch_major=True, **kw)
+    cur = torch.cuda.current_stream()
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        second = model.forward(xm, t, texts[1], patch_major=True, **kw)
+    first = model.forward(xm, t, texts[0], patch_major=True, **kw)
+    cur.wait_stream(side)
+    return first, second
 
 
 def model_forward_pair(model, x, t, y_cond, y_uncond, mask, cfg_split, t_id, extra):
