@@ -193,20 +193,69 @@ def test_attention_entry_points_reject_pointers_off_16_bytes_without_gpu():
         assert lib.vq_attn_temporal_rowquant(*a) == -2, pos
 
 
-def test_product_ops_refuse_cpu_tensors():
+def test_product_ops_refuse_cpu_tensors(monkeypatch):
     """No CPU / eager fallback anywhere in the operator layer: every wrapper of viditq_amd.ops raises VQError on a CPU
-    tensor instead of computing something else."""
+    tensor instead of computing something else - before it reaches the library (``_lib.load`` fails the test).  Exhaustive
+    by construction: every public function of ``ops`` (enumerated as tests/helpers.py::trace_ops does) has a case here, is
+    a predicate over tensors that answers False, or stands on the list of functions that take no tensor to launch on."""
+    import types
     import pytest
     import torch
     import viditq_amd  # noqa: F401
-    from viditq_amd import ops
+    from viditq_amd import _lib, ops
+
+    def reached(*a, **k):
+        raise AssertionError("a CPU tensor got as far as the library")
+    monkeypatch.setattr(_lib, "load", reached)
 
     def h(*s):
         return torch.zeros(*s, dtype=torch.float16)
 
     def f(*s):
         return torch.ones(*s, dtype=torch.float32)
+
+    def i32(*s):
+        return torch.zeros(*s, dtype=torch.int32)
+    qa = ops.QAct(torch.zeros(4, 128, dtype=torch.int8), f(4), i32(4), i32(4), 64, 8)
+    pw = ops.PackedWeight(torch.zeros(8, 128, dtype=torch.int8), f(8), i32(8), i32(8), 8, 64, 128, 8)
+    q64 = h(64, 64)                                                     # temporal attention: B 1, T 16, S 4, H 4, D 16
+    x, eps = f(1, 4, 2, 2), f(2, 4, 2, 2)                               # a latent and its (uncond | cond) model output
+    x5, eps5 = f(1, 4, 1, 2, 2), f(1, 1, 32)                            # patch-major: patch (1, 2, 2), C_out 8
+    tensor_free = {"pad128", "packed_shapes", "new_status", "stack_packed", "shader_clock_ghz", "rowquant_multi_shared_ok",
+                   "rowquant_static_ok", "gemm_rowquant_static_ok", "attn_temporal_shared_ok", "attn_temporal_static_ok",
+                   "attn_fwd_static_ok"}
+    # the step predicates take tensors and mirror the entry points' refusals: for a CPU tensor the answer is no
+    predicates = {
+        "cfg_dpmpp_step_ok": lambda: ops.cfg_dpmpp_step_ok(eps, x),
+        "cfg_ddpm_step_ok": lambda: ops.cfg_ddpm_step_ok(f(2, 8, 2, 2), x),
+        "cfg_sa_step_ok": lambda: ops.cfg_sa_step_ok(eps, x),
+        "cfg_dpmpp_step_patch_ok": lambda: ops.cfg_dpmpp_step_patch_ok(eps5, eps5, x5, (1, 2, 2)),
+        "cfg_ddim_step_patch_ok": lambda: ops.cfg_ddim_step_patch_ok(eps5, eps5, x5, (1, 2, 2)),
+    }
+    for name, call in predicates.items():
+        assert call() is False, name
     cases = {
+        "act_scale_momentum": lambda: ops.act_scale_momentum(h(1, 4, 64), f(64), 0.9),
+        "rowquant_multi_shared": lambda: ops.rowquant_multi_shared(h(2, 4, 64), [f(64)]),
+        "rowquant_static": lambda: ops.rowquant_static(h(1, 4, 64), [f(1)], [f(1)]),
+        "gemm_i8": lambda: ops.gemm_i8(qa, pw),
+        "gemm_i8_rowquant_static": lambda: ops.gemm_i8_rowquant_static(qa, pw, None, f(1), f(1), 8),
+        "gemm_i8_cross_attn": lambda: ops.gemm_i8_cross_attn(qa, pw, None, h(4, 8), h(4, 8), h(4, 8), 1, 4, 4, 1, 8, 32, 8, 32,
+                                                             8),
+        "gemm_i8_batched": lambda: ops.gemm_i8_batched(qa, ops.stack_packed([pw], [None])),
+        "gemm_i8_grouped": lambda: ops.gemm_i8_grouped([qa, qa], [pw, pw]),
+        "attn_temporal_rowquant_shared": lambda: ops.attn_temporal_rowquant_shared(q64, q64, q64, 1, 16, 4, 4, 16, 64),
+        "attn_temporal_long": lambda: ops.attn_temporal_long(q64, q64, q64, 1, 16, 4, 4, 16, 64, quant=True),
+        "attn_temporal_rowquant_static": lambda: ops.attn_temporal_rowquant_static(q64, q64, q64, 1, 16, 4, 4, 16, 64, f(1),
+                                                                                   f(1)),
+        "attn_fwd_rowquant_static": lambda: ops.attn_fwd_rowquant_static(h(1, 4, 72), h(1, 4, 72), h(1, 4, 72), 1, 4, 4, 1, 72,
+                                                                         288, 72, 288, 72, f(1), f(1)),
+        "cfg_dpmpp_step": lambda: ops.cfg_dpmpp_step(eps, x, f(3, 16), f(1, _lib.DPMPP_ROW), 0),
+        "cfg_dpmpp_step_patch": lambda: ops.cfg_dpmpp_step_patch(eps5, eps5, x5, f(3, 16), f(1, _lib.DPMPP_ROW), 0, (1, 2, 2)),
+        "cfg_ddim_step_patch": lambda: ops.cfg_ddim_step_patch(eps5, eps5, x5, f(1, _lib.DDIM_ROW), 0, (1, 2, 2)),
+        "dpmpp_advance": lambda: ops.dpmpp_advance(i32(1), f(1, _lib.DPMPP_ROW), f(1)),
+        "cfg_ddpm_step": lambda: ops.cfg_ddpm_step(f(2, 8, 2, 2), x, f(1, 4, 2, 2), f(1, _lib.DDPM_ROW), 0),
+        "cfg_sa_step": lambda: ops.cfg_sa_step(eps, x, f(1, 4, 2, 2), f(2, 16), f(2, 16), f(1, _lib.SA_ROW), 0),
         "rowquant": lambda: ops.rowquant(h(1, 4, 64)),
         "rowquant_multi": lambda: ops.rowquant_multi(h(1, 4, 64), [f(64)]),
         "gelu_rowquant": lambda: ops.gelu_rowquant(h(1, 4, 64)),
@@ -235,3 +284,9 @@ def test_product_ops_refuse_cpu_tensors():
         with pytest.raises(ops.VQError):
             call()
         assert name in dir(ops)
+    public = {name for name, fn in vars(ops).items()
+              if not name.startswith("_") and isinstance(fn, types.FunctionType) and fn.__module__ == ops.__name__}
+    assert not (set(cases) & tensor_free) and not (set(cases) & set(predicates)) and not (set(predicates) & tensor_free)
+    listed = set(cases) | set(predicates) | tensor_free
+    assert public - listed == set(), "ops functions without a CPU-tensor case: %s" % sorted(public - listed)
+    assert listed - public == set(), "listed but not a public function of ops: %s" % sorted(listed - public)

@@ -7,6 +7,7 @@ never synchronises.  There is no fallback path: a missing library or a CPU tenso
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -28,9 +29,18 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
-def _req(t: torch.Tensor, dtype, name: str):
+# --------------------------------------------------------------------------- operand checks
+# One copy of each check, allocation and pointer table of the wrappers below.  All private: tests/helpers.py::trace_ops
+# records every call of a public function of this module, the calls one public function makes to another included
+# (pad128, smooth_rcp, packed_shapes), so a helper never calls pad128 - its caller passes Kp in.
+def _req_gpu(t: torch.Tensor, name: str):
     if not t.is_cuda:
         raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % name)
+    return t
+
+
+def _req(t: torch.Tensor, dtype, name: str):
+    _req_gpu(t, name)
     if t.dtype != dtype:
         raise VQError("%s must be %s, got %s" % (name, dtype, t.dtype))
     if not t.is_contiguous():
@@ -38,15 +48,48 @@ def _req(t: torch.Tensor, dtype, name: str):
     return t
 
 
+def _req_opt(t: Optional[torch.Tensor], dtype, name: str):
+    """_req of an operand that may be absent."""
+    return None if t is None else _req(t, dtype, name)
+
+
 def _req_rows(t: torch.Tensor, dtype, name: str):
     """As _req, for an operand whose rows may be strided: only the last dimension has to be dense."""
-    if not t.is_cuda:
-        raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % name)
+    _req_gpu(t, name)
     if t.dtype != dtype:
         raise VQError("%s must be %s, got %s" % (name, dtype, t.dtype))
     if t.stride(-1) != 1:
         raise VQError("%s must be contiguous in its last dimension" % name)
     return t
+
+
+def _req_f16(*pairs):
+    """(tensor, name) pairs of strided fp16 views: the kernel takes their pitches, so only the device and the type."""
+    for t, n in pairs:
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise VQError("%s must be a GPU fp16 tensor" % n)
+
+
+def _flat_f32(t: torch.Tensor, name: str):
+    """A calibrated grid term (delta or zp, any shape) as the dense fp32 vector the kernels read."""
+    return _req(t.reshape(-1).contiguous(), torch.float32, name)
+
+
+def _tensorwise_grid(delta: torch.Tensor, zp: torch.Tensor, who: str):
+    """(delta, zp) of wrapper ``who``, which takes one value of each."""
+    if delta.numel() != 1 or zp.numel() != 1:
+        raise VQError("%s: a tensor-wise grid (one delta, one zero point)" % who)
+    return delta, zp
+
+
+def _attn_scale(D: int, scale: Optional[float]) -> float:
+    return float(D) ** -0.5 if scale is None else float(scale)
+
+
+def _ptr_array(vals, n=3):
+    """A NULL-padded table of ``n`` device addresses.  The caller holds it until the C call has returned."""
+    arr = (C.c_void_p * n)(*[C.c_void_p(v) if v is not None else None for v in list(vals) + [None] * (n - len(vals))])
+    return arr
 
 
 def pad128(k: int) -> int:
@@ -89,6 +132,50 @@ class PackedWeight:
         return [self.wq, self.sw, self.zw, self.cs]
 
 
+def _qact_empty(rows: int, Kp: int, K: int, n_bits: int, device, want_zp: bool = False) -> QAct:
+    """The outputs of one quantizer launch, unwritten."""
+    xq = torch.empty((rows, Kp), dtype=torch.int8, device=device)
+    sx = torch.empty(rows, dtype=torch.float32, device=device)
+    zx = torch.empty(rows, dtype=torch.int32, device=device)
+    R = torch.empty(rows, dtype=torch.int32, device=device)
+    return QAct(xq, sx, zx, R, K, n_bits, torch.empty(rows, dtype=torch.float32, device=device) if want_zp else None)
+
+
+def _qact_ptrs(q: QAct):
+    """xq, sx, zx, R: the order every entry point takes the four tensors of one QAct."""
+    return q.xq.data_ptr(), q.sx.data_ptr(), q.zx.data_ptr(), q.R.data_ptr()
+
+
+def _weight_ptrs(w):
+    """wq, sw, zw, cs of a PackedWeight or a PackedStack."""
+    return w.wq.data_ptr(), w.sw.data_ptr(), w.zw.data_ptr(), w.cs.data_ptr()
+
+
+def _tables(*lists):
+    """One pointer table (_ptr_array) per list of up to three optional tensors."""
+    return [_ptr_array([_p(t) for t in ts]) for ts in lists]
+
+
+def _qact_tables(qs: Sequence[QAct]):
+    """The xq / sx / zx / R tables of up to three QActs, in the order every multi-output entry point takes them."""
+    return _tables(*([getattr(q, f) for q in qs] for f in ("xq", "sx", "zx", "R")))
+
+
+def _void(tables):
+    return [C.cast(t, C.c_void_p) for t in tables]
+
+
+def _req_gemm_gpu(a: QAct, w):
+    """The operands of a GEMM are on the GPU (the codes stand for the rest: one allocation makes them all)."""
+    _req_gpu(a.xq, "a.xq")
+    _req_gpu(w.wq, "w.wq")
+
+
+def _check_k(a: QAct, w):
+    if a.K != w.K or a.Kp != w.Kp:
+        raise VQError("K mismatch: activation %d/%d weight %d/%d" % (a.K, a.Kp, w.K, w.Kp))
+
+
 def new_status(device) -> torch.Tensor:
     return torch.zeros(1, dtype=torch.int32, device=device)
 
@@ -117,7 +204,6 @@ def smooth_rcp(s: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     bad = torch.zeros(1, dtype=torch.int32, device=s.device)
     check(_L().vq_smooth_reciprocal(_p(s), _p(r), s.numel(), _p(bad), _stream()), "vq_smooth_reciprocal")
     out = r if int(bad.item()) == 0 else None
-    import weakref
     # entries of dead vectors go on every insert; a LIVE entry is never evicted (its reciprocal may be referenced by
     # address from a captured graph) - only replaced when its vector was modified in place, which moves the epoch
     for k in [k for k, v in _RCP_CACHE.items() if v[0]() is None]:
@@ -126,6 +212,19 @@ def smooth_rcp(s: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         PACK_EPOCH[0] += 1
     _RCP_CACHE[key] = (weakref.ref(s), s._version, out)
     return out
+
+
+_NO_RCP = object()
+
+
+def _rcp_or_none(s: Optional[torch.Tensor]):
+    """The gate of the fused attention / GEMM + quantizer wrappers: the reciprocal of their smoothing vector (None without
+    a vector), or _NO_RCP when it has no exact reciprocal form - the wrapper then returns None before it allocates or
+    launches anything, and its caller keeps the two launches."""
+    if s is None:
+        return None
+    r = smooth_rcp(s)
+    return _NO_RCP if r is None else r
 
 
 def act_scale_momentum(x: torch.Tensor, act_scale: torch.Tensor, momentum: float, scratch: Optional[torch.Tensor] = None,
@@ -174,13 +273,7 @@ def rowquant(x: torch.Tensor, n_bits: int = 8, s: Optional[torch.Tensor] = None,
     assert x.dim() == 3
     B, n_tok, Cc = x.shape
     Kp = pad128(Cc)
-    rows = B * n_tok
-    dev = x.device
-    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
-    sx = torch.empty(rows, dtype=torch.float32, device=dev)
-    zx = torch.empty(rows, dtype=torch.int32, device=dev)
-    R = torch.empty(rows, dtype=torch.int32, device=dev)
-    zpf = torch.empty(rows, dtype=torch.float32, device=dev) if want_zp else None
+    out = _qact_empty(B * n_tok, Kp, Cc, n_bits, x.device, want_zp)
     if s is not None:
         _req(s, torch.float32, "s")
         assert s.numel() == Cc
@@ -190,14 +283,13 @@ def rowquant(x: torch.Tensor, n_bits: int = 8, s: Optional[torch.Tensor] = None,
         n_add = add_rows.shape[0]
     n_param = 0
     if delta is not None:
-        delta = _req(delta.reshape(-1).contiguous(), torch.float32, "delta")
-        zp = _req(zp.reshape(-1).contiguous(), torch.float32, "zp")
+        delta, zp = _flat_f32(delta, "delta"), _flat_f32(zp, "zp")
         n_param = delta.numel()
     s_rcp = smooth_rcp(s) if fast_div else None
-    check(_L().vq_rowquant(_p(x), _p(add_rows), n_add, add_div, _p(s), _p(s_rcp), _p(xq), _p(sx), _p(zx), _p(R), _p(zpf),
+    check(_L().vq_rowquant(_p(x), _p(add_rows), n_add, add_div, _p(s), _p(s_rcp), *_qact_ptrs(out), _p(out.zpf),
                            _p(delta), _p(zp), n_param, B, n_tok, Cc, Kp, n_bits, _p(status), _stream()),
           "vq_rowquant")
-    return QAct(xq, sx, zx, R, Cc, n_bits, zpf)
+    return out
 
 
 def rowquant_multi(x: torch.Tensor, smooth: Sequence[torch.Tensor], n_bits: int = 8,
@@ -211,14 +303,10 @@ def rowquant_multi(x: torch.Tensor, smooth: Sequence[torch.Tensor], n_bits: int 
     G = len(smooth)
     if B != 1 or G > 3 or any(r is None for r in rcps) or Kp != Cc or Cc % 128 or not (768 <= Cc <= 1280) or n_tok < 2:
         return [rowquant(x, n_bits=n_bits, s=sm, status=status) for sm in smooth]
-    dev = x.device
-    outs = [QAct(torch.empty((n_tok, Kp), dtype=torch.int8, device=dev), torch.empty(n_tok, dtype=torch.float32, device=dev),
-                 torch.empty(n_tok, dtype=torch.int32, device=dev), torch.empty(n_tok, dtype=torch.int32, device=dev),
-                 Cc, n_bits) for _ in range(G)]
-    keep = [_ptr_array([_p(sm) for sm in smooth]), _ptr_array([_p(r) for r in rcps])] + \
-           [_ptr_array([getattr(o, f).data_ptr() for o in outs]) for f in ("xq", "sx", "zx", "R")]
-    check(_L().vq_rowquant_smooth_multi(_p(x), G, *[C.cast(k, C.c_void_p) for k in keep], n_tok, Cc, Kp, n_bits,
-                                        _p(status), _stream()), "vq_rowquant_smooth_multi")
+    outs = [_qact_empty(n_tok, Kp, Cc, n_bits, x.device) for _ in range(G)]
+    keep = _tables(smooth, rcps) + _qact_tables(outs)
+    check(_L().vq_rowquant_smooth_multi(_p(x), G, *_void(keep), n_tok, Cc, Kp, n_bits, _p(status), _stream()),
+          "vq_rowquant_smooth_multi")
     return outs
 
 
@@ -264,15 +352,10 @@ def rowquant_multi_shared(x: torch.Tensor, smooth: Sequence[torch.Tensor], n_bit
         _req(scale, torch.float32, "scale")
         if shift.numel() != B * Cc or scale.numel() != B * Cc:
             raise VQError("rowquant_multi_shared: shift / scale must be [B, C]")
-    rows, dev = B * n_tok, x.device
-    outs = [QAct(torch.empty((rows, Kp), dtype=torch.int8, device=dev), torch.empty(rows, dtype=torch.float32, device=dev),
-                 torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
-                 Cc, n_bits) for _ in range(G)]
-    keep = [_ptr_array([_p(sm) for sm in smooth]), _ptr_array([_p(r) for r in rcps])] + \
-           [_ptr_array([getattr(o, f).data_ptr() for o in outs]) for f in ("xq", "sx", "zx", "R")]
-    check(_L().vq_rowquant_smooth_multi_shared(_p(x), _p(shift), _p(scale), float(eps), G,
-                                               *[C.cast(k, C.c_void_p) for k in keep], B, n_tok, Cc, Kp, n_bits, _p(status),
-                                               _stream()), "vq_rowquant_smooth_multi_shared")
+    outs = [_qact_empty(B * n_tok, Kp, Cc, n_bits, x.device) for _ in range(G)]
+    keep = _tables(smooth, rcps) + _qact_tables(outs)
+    check(_L().vq_rowquant_smooth_multi_shared(_p(x), _p(shift), _p(scale), float(eps), G, *_void(keep), B, n_tok, Cc, Kp,
+                                               n_bits, _p(status), _stream()), "vq_rowquant_smooth_multi_shared")
     return outs
 
 
@@ -303,10 +386,8 @@ def rowquant_static(x: torch.Tensor, delta: Sequence[torch.Tensor], zp: Sequence
     n_out = len(delta)
     assert len(zp) == n_out and 1 <= n_out <= 3
     Kp = pad128(Cc) if Kp is None else int(Kp)
-    rows = B * n_tok
-    dev = x.device
-    ds = [_req(d.reshape(-1).contiguous(), torch.float32, "delta") for d in delta]
-    zs = [_req(z.reshape(-1).contiguous(), torch.float32, "zp") for z in zp]
+    ds = [_flat_f32(d, "delta") for d in delta]
+    zs = [_flat_f32(z, "zp") for z in zp]
     n_param = ds[0].numel()
     assert all(d.numel() == n_param for d in ds) and all(z.numel() == n_param for z in zs)
     smooth = [None] * n_out if smooth is None else list(smooth)
@@ -328,17 +409,11 @@ def rowquant_static(x: torch.Tensor, delta: Sequence[torch.Tensor], zp: Sequence
         assert shift.numel() == B * Cc and scale.numel() == B * Cc
     elif want_xm:
         raise VQError("rowquant_static: xm exists behind LayerNorm + modulate only")
-    outs = [QAct(torch.empty((rows, Kp), dtype=torch.int8, device=dev), torch.empty(rows, dtype=torch.float32, device=dev),
-                 torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
-                 Cc, n_bits) for _ in range(n_out)]
+    outs = [_qact_empty(B * n_tok, Kp, Cc, n_bits, x.device) for _ in range(n_out)]
     xm = torch.empty_like(x) if want_xm else None
-    keep = [_ptr_array([_p(sm) for sm in smooth]), _ptr_array([_p(r) for r in rcps]),
-            _ptr_array([_p(d) for d in ds]), _ptr_array([_p(z) for z in zs])] + \
-           [_ptr_array([getattr(o, f).data_ptr() for o in outs]) for f in ("xq", "sx", "zx", "R")]
-    kp = [C.cast(k, C.c_void_p) for k in keep]
-    check(_L().vq_rowquant_static(_p(x), _p(add_rows), n_add, add_div, _p(shift), _p(scale), float(eps), n_out, kp[0], kp[1],
-                                  kp[2], kp[3], n_param, kp[4], kp[5], kp[6], kp[7], _p(xm), B, n_tok, Cc, Kp, n_bits,
-                                  _stream()), "vq_rowquant_static")
+    grid, codes = _tables(smooth, rcps, ds, zs), _qact_tables(outs)
+    check(_L().vq_rowquant_static(_p(x), _p(add_rows), n_add, add_div, _p(shift), _p(scale), float(eps), n_out, *_void(grid),
+                                  n_param, *_void(codes), _p(xm), B, n_tok, Cc, Kp, n_bits, _stream()), "vq_rowquant_static")
     return (outs, xm) if want_xm else outs
 
 
@@ -349,18 +424,12 @@ def gelu_rowquant(x: torch.Tensor, n_bits: int = 8, s: Optional[torch.Tensor] = 
     _req(x, torch.float16, "x")
     B, n_tok, Cc = x.shape
     Kp = pad128(Cc)
-    dev = x.device
-    rows = B * n_tok
-    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
-    sx = torch.empty(rows, dtype=torch.float32, device=dev)
-    zx = torch.empty(rows, dtype=torch.int32, device=dev)
-    R = torch.empty(rows, dtype=torch.int32, device=dev)
-    if s is not None:
-        _req(s, torch.float32, "s")
+    out = _qact_empty(B * n_tok, Kp, Cc, n_bits, x.device)
+    _req_opt(s, torch.float32, "s")
     s_rcp = smooth_rcp(s) if fast_div else None
-    check(_L().vq_gelu_rowquant(_p(x), _p(s), _p(s_rcp), _p(xq), _p(sx), _p(zx), _p(R), B, n_tok, Cc, Kp, n_bits,
-                                _p(status), _stream()), "vq_gelu_rowquant")
-    return QAct(xq, sx, zx, R, Cc, n_bits, None)
+    check(_L().vq_gelu_rowquant(_p(x), _p(s), _p(s_rcp), *_qact_ptrs(out), B, n_tok, Cc, Kp, n_bits, _p(status), _stream()),
+          "vq_gelu_rowquant")
+    return out
 
 
 def ln_modulate_rowquant(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, eps: float = 1e-6,
@@ -374,36 +443,15 @@ def ln_modulate_rowquant(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tens
     assert shift.numel() == B * Cc and scale.numel() == B * Cc
     n_out = len(smooth)
     Kp = pad128(Cc)
-    rows = B * n_tok
-    dev = x.device
-    outs: List[QAct] = []
-    for _ in range(n_out):
-        outs.append(QAct(torch.empty((rows, Kp), dtype=torch.int8, device=dev),
-                         torch.empty(rows, dtype=torch.float32, device=dev),
-                         torch.empty(rows, dtype=torch.int32, device=dev),
-                         torch.empty(rows, dtype=torch.int32, device=dev), Cc, n_bits))
-    arr = C.c_void_p * 3
-
-    def mk(vals):
-        vals = list(vals) + [None] * (3 - len(vals))
-        return arr(*[C.c_void_p(v) if v is not None else None for v in vals])
-
+    outs = [_qact_empty(B * n_tok, Kp, Cc, n_bits, x.device) for _ in range(n_out)]
     for sm in smooth:
         if sm is not None:
             _req(sm, torch.float32, "smooth")
-    s_arr = mk([_p(sm) for sm in smooth])
     rcps = [smooth_rcp(sm) if fast_div else None for sm in smooth]     # kept alive until the launch is enqueued
-    r_arr = mk([_p(r) for r in rcps])
-    xq_arr = mk([o.xq.data_ptr() for o in outs])
-    sx_arr = mk([o.sx.data_ptr() for o in outs])
-    zx_arr = mk([o.zx.data_ptr() for o in outs])
-    R_arr = mk([o.R.data_ptr() for o in outs])
+    keep = _tables(smooth, rcps) + _qact_tables(outs)
     xm = torch.empty_like(x) if want_xm else None
-    check(_L().vq_ln_modulate_rowquant(_p(x), _p(shift), _p(scale), float(eps), n_out,
-                                       C.cast(s_arr, C.c_void_p), C.cast(r_arr, C.c_void_p), C.cast(xq_arr, C.c_void_p),
-                                       C.cast(sx_arr, C.c_void_p), C.cast(zx_arr, C.c_void_p),
-                                       C.cast(R_arr, C.c_void_p), _p(xm), B, n_tok, Cc, Kp, n_bits,
-                                       _p(status), _stream()), "vq_ln_modulate_rowquant")
+    check(_L().vq_ln_modulate_rowquant(_p(x), _p(shift), _p(scale), float(eps), n_out, *_void(keep), _p(xm), B, n_tok, Cc, Kp,
+                                       n_bits, _p(status), _stream()), "vq_ln_modulate_rowquant")
     return (outs, xm) if want_xm else outs
 
 
@@ -423,8 +471,7 @@ def fakequant_act(x: torch.Tensor, n_bits: int = 8, delta: Optional[torch.Tensor
         check(_L().vq_fakequant_act(_p(x), _p(out), _p(codes), _p(d_out), _p(z_out), None, None, 0, B, n_tok, Cc,
                                     n_bits, 0, _p(scratch), _p(status), _stream()), "vq_fakequant_act")
         return out, codes, d_out, z_out
-    d = _req(delta.reshape(-1).contiguous(), torch.float32, "delta")
-    z = _req(zp.reshape(-1).contiguous(), torch.float32, "zp")
+    d, z = _flat_f32(delta, "delta"), _flat_f32(zp, "zp")
     assert d.numel() == z.numel() and d.numel() in (1, n_tok)
     check(_L().vq_fakequant_act(_p(x), _p(out), _p(codes), None, None, _p(d), _p(z), d.numel(), B, n_tok, Cc,
                                 n_bits, 1, None, _p(status), _stream()), "vq_fakequant_act")
@@ -442,8 +489,7 @@ def epsfill_fixup(flag: torch.Tensor, x: torch.Tensor, s: Optional[torch.Tensor]
     L = x.shape[-2]
     assert x.shape[-1] == C and x.numel() == L * C and out.numel() == nb * L * N
     assert x.is_contiguous() and wdq.is_contiguous() and out.is_contiguous()
-    if s is not None:
-        _req(s, torch.float32, "s")
+    _req_opt(s, torch.float32, "s")
     if bias is not None:
         _req(bias, torch.float16, "bias")
         assert bias.numel() == nb * N and bias.is_contiguous()
@@ -460,8 +506,7 @@ def weight_minmax(W: torch.Tensor, n_bits: int, s: Optional[torch.Tensor] = None
     N, K = W.shape
     delta = torch.empty(N, dtype=torch.float32, device=W.device)
     zp = torch.empty(N, dtype=torch.float32, device=W.device)
-    if s is not None:
-        _req(s, torch.float32, "s")
+    _req_opt(s, torch.float32, "s")
     check(_L().vq_weight_minmax(_p(W), _p(s), _p(delta), _p(zp), N, K, n_bits, int(force_eps), _p(status),
                                 _stream()), "vq_weight_minmax")
     return delta, zp
@@ -482,8 +527,7 @@ def pack_weight(W: torch.Tensor, delta: torch.Tensor, zp: torch.Tensor, n_bits: 
     N, K = W.shape
     Kp = pad128(K)
     dev = W.device
-    d = _req(delta.reshape(-1).contiguous(), torch.float32, "delta")
-    z = _req(zp.reshape(-1).contiguous(), torch.float32, "zp")
+    d, z = _flat_f32(delta, "delta"), _flat_f32(zp, "zp")
     assert d.numel() == N and z.numel() == N
     if out is not None:
         wq, sw, zw, cs = out
@@ -496,8 +540,7 @@ def pack_weight(W: torch.Tensor, delta: torch.Tensor, zp: torch.Tensor, n_bits: 
         sw = torch.empty(N, dtype=torch.float32, device=dev)
         zw = torch.empty(N, dtype=torch.int32, device=dev)
         cs = torch.empty(N, dtype=torch.int32, device=dev)
-    if s is not None:
-        _req(s, torch.float32, "s")
+    _req_opt(s, torch.float32, "s")
     check(_L().vq_pack_weight(_p(W), _p(s), _p(d), _p(z), _p(wq), _p(sw), _p(zw), _p(cs), N, K, Kp, n_bits,
                               _stream()), "vq_pack_weight")
     return PackedWeight(wq, sw, zw, cs, N, K, Kp, n_bits)
@@ -513,12 +556,24 @@ GEMM_TIMING = None
 DEFAULT_GEMM_VARIANT = -1
 
 
+def _timing_begin():
+    """The event pair of one GEMM_TIMING bracket, the first recorded on the launch stream."""
+    e0, e1 = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    e0.record()
+    return e0, e1
+
+
+def _timing_end(timing: list, events, int8_ops: float, nbytes: int):
+    events[1].record()
+    timing.append((events[0], events[1], int8_ops, nbytes))
+
+
 def gemm_i8(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
             epilogue: int = EPI_NONE, resid: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
             rows_per_gate: int = 0, variant: int = -1) -> torch.Tensor:
     """out[M, N] fp16 = dequant(int8 MFMA(a, w)) + bias, with the fused epilogue."""
-    if a.K != w.K or a.Kp != w.Kp:
-        raise VQError("K mismatch: activation %d/%d weight %d/%d" % (a.K, a.Kp, w.K, w.Kp))
+    _req_gemm_gpu(a, w)
+    _check_k(a, w)
     M, N = a.rows, w.N
     if out is None:
         out = torch.empty((M, N), dtype=torch.float16, device=a.xq.device)
@@ -527,28 +582,21 @@ def gemm_i8(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor] = None, out: 
             raise VQError("out must be a GPU fp16 2-D tensor with unit column stride")
         assert out.shape[0] == M and out.shape[1] >= N
     ldo = out.stride(0)
-    if bias is not None:
-        _req(bias, torch.float32, "bias")
+    _req_opt(bias, torch.float32, "bias")
     if resid is not None:
         if not resid.is_cuda or resid.dtype != torch.float16 or resid.dim() != 2 or resid.stride(1) != 1:
             raise VQError("resid must be a GPU fp16 2-D tensor with unit column stride")
         assert resid.stride(0) == ldo and resid.shape[0] == M
-    if gate is not None:
-        _req(gate, torch.float32, "gate")
+    _req_opt(gate, torch.float32, "gate")
     if variant < 0:
         variant = DEFAULT_GEMM_VARIANT
     timing = GEMM_TIMING
-    if timing is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().vq_gemm_i8(_p(a.xq), _p(a.sx), _p(a.zx), _p(a.R), _p(w.wq), _p(w.sw), _p(w.zw), _p(w.cs),
-                          _p(bias), _p(out), ldo, _p(resid), _p(gate), rows_per_gate, M, N, a.K, a.Kp,
-                          w.n_bits, epilogue, variant, _stream()), "vq_gemm_i8")
-    if timing is not None:
-        e1.record()
+    events = None if timing is None else _timing_begin()
+    check(_L().vq_gemm_i8(*_qact_ptrs(a), *_weight_ptrs(w), _p(bias), _p(out), ldo, _p(resid), _p(gate), rows_per_gate,
+                          M, N, a.K, a.Kp, w.n_bits, epilogue, variant, _stream()), "vq_gemm_i8")
+    if events is not None:
         wbytes = N * a.K // 2 if w.n_bits <= 4 else N * a.K
-        timing.append((e0, e1, 2.0 * M * N * a.K, M * a.K + wbytes + 2 * M * N * (2 if resid is not None else 1)))
+        _timing_end(timing, events, 2.0 * M * N * a.K, M * a.K + wbytes + 2 * M * N * (2 if resid is not None else 1))
     return out
 
 
@@ -574,48 +622,31 @@ def gemm_i8_rowquant_static(a: QAct, w: PackedWeight, bias: Optional[torch.Tenso
     returns, bit for bit.  ``s``: the consuming Linear's smoothing vector [N]; None is returned (the caller keeps the two
     launches) when its reciprocal form is not available.  A launch the entry point refuses raises: ask
     :func:`gemm_rowquant_static_ok` first."""
-    for t, n in ((a.xq, "a.xq"), (w.wq, "w.wq")):
-        if not t.is_cuda:
-            raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % n)
-    s_rcp = None
+    _req_gemm_gpu(a, w)
     if s is not None:
         _req(s, torch.float32, "s")
         if s.numel() != w.N:
             raise VQError("s must hold one entry per output column")
-        s_rcp = smooth_rcp(s)
-        if s_rcp is None:
-            return None
-    if a.K != w.K or a.Kp != w.Kp:
-        raise VQError("K mismatch: activation %d/%d weight %d/%d" % (a.K, a.Kp, w.K, w.Kp))
-    delta = _req(delta.reshape(-1).contiguous(), torch.float32, "delta")
-    zp = _req(zp.reshape(-1).contiguous(), torch.float32, "zp")
-    if delta.numel() != 1 or zp.numel() != 1:
-        raise VQError("gemm_i8_rowquant_static: a tensor-wise grid (one delta, one zero point)")
-    if bias is not None:
-        _req(bias, torch.float32, "bias")
+    s_rcp = _rcp_or_none(s)
+    if s_rcp is _NO_RCP:
+        return None
+    _check_k(a, w)
+    delta, zp = _tensorwise_grid(_flat_f32(delta, "delta"), _flat_f32(zp, "zp"), "gemm_i8_rowquant_static")
+    _req_opt(bias, torch.float32, "bias")
     M, N = a.rows, w.N
     Kp_out = pad128(N)
-    dev = a.xq.device
-    xq = torch.empty((M, Kp_out), dtype=torch.int8, device=dev)
-    sx = torch.empty(M, dtype=torch.float32, device=dev)
-    zx = torch.empty(M, dtype=torch.int32, device=dev)
-    R = torch.empty(M, dtype=torch.int32, device=dev)
+    out = _qact_empty(M, Kp_out, N, n_bits, a.xq.device)
     if variant < 0:
         variant = DEFAULT_GEMM_VARIANT
     timing = GEMM_TIMING
-    if timing is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_L().vq_gemm_i8_rowquant_static(_p(a.xq), _p(a.sx), _p(a.zx), _p(a.R), _p(w.wq), _p(w.sw), _p(w.zw), _p(w.cs),
-                                          _p(bias), _p(s), _p(s_rcp), _p(delta), _p(zp), _p(xq), _p(sx), _p(zx), _p(R),
-                                          M, N, a.K, a.Kp, Kp_out, w.n_bits, n_bits, variant, _stream()),
+    events = None if timing is None else _timing_begin()
+    check(_L().vq_gemm_i8_rowquant_static(*_qact_ptrs(a), *_weight_ptrs(w), _p(bias), _p(s), _p(s_rcp), _p(delta), _p(zp),
+                                          *_qact_ptrs(out), M, N, a.K, a.Kp, Kp_out, w.n_bits, n_bits, variant, _stream()),
           "vq_gemm_i8_rowquant_static")
-    if timing is not None:
-        e1.record()
+    if events is not None:
         # fused byte model: both operands, the codes (pad columns included) and the three row terms; no fp16 matrix
-        timing.append((e0, e1, 2.0 * M * N * a.K, M * a.K + N * a.K + M * Kp_out + 12 * M))
-    return QAct(xq, sx, zx, R, N, n_bits)
+        _timing_end(timing, events, 2.0 * M * N * a.K, M * a.K + N * a.K + M * Kp_out + 12 * M)
+    return out
 
 
 def gemm_i8_cross_attn(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor], k: torch.Tensor, v: torch.Tensor,
@@ -625,23 +656,14 @@ def gemm_i8_cross_attn(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor], k
     """cross_attn.q_linear's GEMM and cross attention against the prompt's <= 128 keys in ONE launch that never writes q:
     ``o`` is, bit for bit, what ``attn_fwd(gemm_i8(a, w, bias), k, v, o, n_seq, Lq, Lk, H, D, Lq * N, N, ...)`` writes.
     Shapes the entry point refuses (include/viditq.h) raise: callers choose the route before they launch."""
-    for t, n in ((a.xq, "a.xq"), (w.wq, "w.wq")):
-        if not t.is_cuda:
-            raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % n)
-    for t, n in ((k, "k"), (v, "v"), (o, "o")):
-        if not t.is_cuda or t.dtype != torch.float16:
-            raise VQError("%s must be a GPU fp16 tensor" % n)
-    if a.K != w.K or a.Kp != w.Kp:
-        raise VQError("K mismatch: activation %d/%d weight %d/%d" % (a.K, a.Kp, w.K, w.Kp))
-    if bias is not None:
-        _req(bias, torch.float32, "bias")
-    if kv_off is not None:
-        _req(kv_off, torch.int32, "kv_off")
-    scale = float(D) ** -0.5 if scale is None else float(scale)
-    check(_L().vq_gemm_i8_cross_attn(_p(a.xq), _p(a.sx), _p(a.zx), _p(a.R), _p(w.wq), _p(w.sw), _p(w.zw), _p(w.cs), _p(bias),
-                                     _p(k), _p(v), _p(o), a.rows, w.N, a.K, a.Kp, w.n_bits, n_seq, Lq, Lk, H, D,
-                                     kv_seq_stride, kv_tok_stride, o_seq_stride, o_tok_stride, _p(kv_off), scale, _stream()),
-          "vq_gemm_i8_cross_attn")
+    _req_gemm_gpu(a, w)
+    _req_f16((k, "k"), (v, "v"), (o, "o"))
+    _check_k(a, w)
+    _req_opt(bias, torch.float32, "bias")
+    _req_opt(kv_off, torch.int32, "kv_off")
+    check(_L().vq_gemm_i8_cross_attn(*_qact_ptrs(a), *_weight_ptrs(w), _p(bias), _p(k), _p(v), _p(o), a.rows, w.N, a.K, a.Kp,
+                                     w.n_bits, n_seq, Lq, Lk, H, D, kv_seq_stride, kv_tok_stride, o_seq_stride, o_tok_stride,
+                                     _p(kv_off), _attn_scale(D, scale), _stream()), "vq_gemm_i8_cross_attn")
     return o
 
 
@@ -654,12 +676,12 @@ def gemm_i8_stamped(a: QAct, w: PackedWeight, bias: Optional[torch.Tensor] = Non
     M, N = a.rows, w.N
     if not a.xq.is_cuda:
         raise VQError("gemm_i8_stamped needs GPU tensors")
+    _req_gpu(w.wq, "w.wq")
     out = torch.empty((M, N), dtype=torch.float16, device=a.xq.device)
     tiles = ((M + 255) // 256) * ((N + 287) // 288)
     stamps = torch.zeros((tiles, 8, 10), dtype=torch.int64, device=a.xq.device)
-    check(_L().vq_gemm_i8_stamped(_p(a.xq), _p(a.sx), _p(a.zx), _p(a.R), _p(w.wq), _p(w.sw), _p(w.zw), _p(w.cs), _p(bias),
-                                  _p(out), out.stride(0), M, N, a.K, a.Kp, _p(stamps), stamps.numel(), _stream()),
-          "vq_gemm_i8_stamped")
+    check(_L().vq_gemm_i8_stamped(*_qact_ptrs(a), *_weight_ptrs(w), _p(bias), _p(out), out.stride(0), M, N, a.K, a.Kp,
+                                  _p(stamps), stamps.numel(), _stream()), "vq_gemm_i8_stamped")
     return out, stamps
 
 
@@ -677,7 +699,6 @@ def shader_clock_ghz(stamps: torch.Tensor) -> dict:
             "phase_cycles": {n: float(v) for n, v in zip(names, ph)}}
 
 
-# --------------------------------------------------------------------------- attention
 @dataclass
 class PackedStack:
     """nbatch PackedWeights of identical shape stacked for vq_gemm_i8_batched (+ their fp32 biases)."""
@@ -707,20 +728,14 @@ def stack_packed(pws: Sequence[PackedWeight], biases: Sequence[Optional[torch.Te
 
 def gemm_i8_batched(a: QAct, w: PackedStack, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[b] [M, N] fp16 for every stacked weight set b, all from the same quantized activation ``a``."""
-    if a.K != w.K or a.Kp != w.Kp:
-        raise VQError("K mismatch: activation %d/%d weight %d/%d" % (a.K, a.Kp, w.K, w.Kp))
+    _req_gemm_gpu(a, w)
+    _check_k(a, w)
     M = a.rows
     if out is None:
         out = torch.empty((w.nbatch, M, w.N), dtype=torch.float16, device=a.xq.device)
-    check(_L().vq_gemm_i8_batched(_p(a.xq), _p(a.sx), _p(a.zx), _p(a.R), _p(w.wq), _p(w.sw), _p(w.zw), _p(w.cs),
-                                  _p(w.bias), _p(out), w.nbatch, M, w.N, a.K, a.Kp, w.n_bits, _stream()),
-          "vq_gemm_i8_batched")
+    check(_L().vq_gemm_i8_batched(*_qact_ptrs(a), *_weight_ptrs(w), _p(w.bias), _p(out), w.nbatch, M, w.N, a.K, a.Kp,
+                                  w.n_bits, _stream()), "vq_gemm_i8_batched")
     return out
-
-
-def _ptr_array(vals, n=3):
-    arr = (C.c_void_p * n)(*[C.c_void_p(v) if v is not None else None for v in list(vals) + [None] * (n - len(vals))])
-    return arr
 
 
 def gemm_i8_grouped(acts: Sequence[QAct], ws: Sequence[PackedWeight], biases: Optional[Sequence] = None,
@@ -730,6 +745,7 @@ def gemm_i8_grouped(acts: Sequence[QAct], ws: Sequence[PackedWeight], biases: Op
     assert 1 <= G <= 3 and len(ws) == G
     a0, w0 = acts[0], ws[0]
     for a, w in zip(acts, ws):
+        _req_gemm_gpu(a, w)
         if (a.K, a.Kp, a.rows) != (a0.K, a0.Kp, a0.rows) or (w.N, w.K, w.Kp, w.n_bits) != (w0.N, w0.K, w0.Kp, w0.n_bits) \
                 or a.K != w.K or a.Kp != w.Kp:
             raise VQError("grouped GEMM needs one shape for every group")
@@ -738,36 +754,52 @@ def gemm_i8_grouped(acts: Sequence[QAct], ws: Sequence[PackedWeight], biases: Op
         out = torch.empty((M, G * N), dtype=torch.float16, device=a0.xq.device)
     assert out.dtype == torch.float16 and out.stride(-1) == 1 and out.shape[-1] >= G * N
     bs = [None] * G if biases is None else [None if b is None else _req(b, torch.float32, "bias") for b in biases]
-    keep = [_ptr_array([_p(getattr(a, f)) for a in acts]) for f in ("xq", "sx", "zx", "R")] + \
-           [_ptr_array([_p(getattr(w, f)) for w in ws]) for f in ("wq", "sw", "zw", "cs")] + [_ptr_array([_p(b) for b in bs])]
-    check(_L().vq_gemm_i8_grouped(G, *[C.cast(k, C.c_void_p) for k in keep], _p(out), out.stride(0), M, N, a0.K, a0.Kp,
-                                  w0.n_bits, _stream()), "vq_gemm_i8_grouped")
+    keep = _qact_tables(acts) + _tables(*([getattr(w, f) for w in ws] for f in ("wq", "sw", "zw", "cs")), bs)
+    check(_L().vq_gemm_i8_grouped(G, *_void(keep), _p(out), out.stride(0), M, N, a0.K, a0.Kp, w0.n_bits, _stream()),
+          "vq_gemm_i8_grouped")
     return out
 
 
+# --------------------------------------------------------------------------- attention
 def attn_fwd(q, k, v, o, n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride,
              o_seq_stride, o_tok_stride, kv_off: Optional[torch.Tensor] = None, scale: Optional[float] = None):
     """Flash attention over strided fp16 views (pointers are the tensors' data_ptr())."""
-    for t, n in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
-        if not t.is_cuda or t.dtype != torch.float16:
-            raise VQError("%s must be a GPU fp16 tensor" % n)
-    if kv_off is not None:
-        _req(kv_off, torch.int32, "kv_off")
-    scale = float(D) ** -0.5 if scale is None else float(scale)
+    _req_f16((q, "q"), (k, "k"), (v, "v"), (o, "o"))
+    _req_opt(kv_off, torch.int32, "kv_off")
     check(_L().vq_attn_fwd(_p(q), _p(k), _p(v), _p(o), n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_stride,
-                           kv_seq_stride, kv_tok_stride, o_seq_stride, o_tok_stride, _p(kv_off), scale, _stream()),
-          "vq_attn_fwd")
+                           kv_seq_stride, kv_tok_stride, o_seq_stride, o_tok_stride, _p(kv_off), _attn_scale(D, scale),
+                           _stream()), "vq_attn_fwd")
     return o
 
 
 def attn_temporal(q, k, v, o, B, T, S, H, D, ld_in, ld_out, scale: Optional[float] = None):
-    for t, n in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
-        if not t.is_cuda or t.dtype != torch.float16:
-            raise VQError("%s must be a GPU fp16 tensor" % n)
-    scale = float(D) ** -0.5 if scale is None else float(scale)
-    check(_L().vq_attn_temporal(_p(q), _p(k), _p(v), _p(o), B, T, S, H, D, ld_in, ld_out, scale, _stream()),
+    _req_f16((q, "q"), (k, "k"), (v, "v"), (o, "o"))
+    check(_L().vq_attn_temporal(_p(q), _p(k), _p(v), _p(o), B, T, S, H, D, ld_in, ld_out, _attn_scale(D, scale), _stream()),
           "vq_attn_temporal")
     return o
+
+
+def _check_o(o: Optional[torch.Tensor], rows: int, Cc: int, who: Optional[str], strided: bool = False):
+    """The optional fp16 output of an attention + quantizer form, by each wrapper's own rule: a dense [rows, Cc] matrix, else
+    a VQError in the name of ``who`` (an assertion for who = None); ``strided``: a view with pitches of its own, of which
+    only the device and the type are asked."""
+    if o is None:
+        return
+    if strided:
+        _req_f16((o, "o"))
+        return
+    _req(o, torch.float16, "o")
+    if who is None:
+        assert o.shape == (rows, Cc)
+    elif o.shape != (rows, Cc):
+        raise VQError("%s: o must be [B*T*S, H*D]" % who)
+
+
+def _attn_qact(q, o, rows, Cc, Kp, n_bits, D, scale, who, strided=False):
+    """What the five attention + quantizer wrappers share once their own rules have passed and Kp is known: the check of the
+    optional fp16 output (_check_o), the quantizer's outputs on q's device and the softmax scale.  -> (QAct, scale)"""
+    _check_o(o, rows, Cc, who, strided)
+    return _qact_empty(rows, Kp, Cc, n_bits, q.device), _attn_scale(D, scale)
 
 
 def attn_temporal_rowquant(q, k, v, B, T, S, H, D, ld_in, scale: Optional[float] = None,
@@ -777,31 +809,18 @@ def attn_temporal_rowquant(q, k, v, B, T, S, H, D, ld_in, scale: Optional[float]
     forward: per-token scales are shared over the batch otherwise).  Returns what
     ``rowquant(attn_temporal(...).view(1, T*S, H*D), s=s)`` returns, bit for bit.  ``s``: the consuming Linear's
     smoothing vector; None is returned (caller runs the two kernels) when its reciprocal form is not available."""
-    s_rcp = None
-    if s is not None:
-        s_rcp = smooth_rcp(s)
-        if s_rcp is None:
-            return None
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if not t.is_cuda or t.dtype != torch.float16:
-            raise VQError("%s must be a GPU fp16 tensor" % n)
+    s_rcp = _rcp_or_none(s)
+    if s_rcp is _NO_RCP:
+        return None
+    _req_f16((q, "q"), (k, "k"), (v, "v"))
     if B != 1:
         raise VQError("attn_temporal_rowquant: per-token scales are shared over the batch; B must be 1")
     Cc = H * D
     Kp = pad128(Cc)
-    rows = B * T * S
-    dev = q.device
-    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
-    sx = torch.empty(rows, dtype=torch.float32, device=dev)
-    zx = torch.empty(rows, dtype=torch.int32, device=dev)
-    R = torch.empty(rows, dtype=torch.int32, device=dev)
-    scale = float(D) ** -0.5 if scale is None else float(scale)
-    if o is not None:
-        _req(o, torch.float16, "o")
-        assert o.shape == (rows, Cc)
-    check(_L().vq_attn_temporal_rowquant(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(xq), _p(sx), _p(zx), _p(R), _p(status),
-                                         _p(o), B, T, S, H, D, ld_in, Kp, scale, _stream()), "vq_attn_temporal_rowquant")
-    return QAct(xq, sx, zx, R, Cc, 8)
+    out, scale = _attn_qact(q, o, B * T * S, Cc, Kp, 8, D, scale, None)
+    check(_L().vq_attn_temporal_rowquant(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), *_qact_ptrs(out), _p(status), _p(o),
+                                         B, T, S, H, D, ld_in, Kp, scale, _stream()), "vq_attn_temporal_rowquant")
+    return out
 
 
 def attn_temporal_shared_ok(B: int, T: int, H: int, D: int, Kp: int, n_bits: int) -> bool:
@@ -826,31 +845,17 @@ def attn_temporal_rowquant_shared(q, k, v, B, T, S, H, D, ld_in, n_bits: int = 8
     ``rowquant(o.view(B, T*S, H*D), n_bits=n_bits, s=s)`` returns for the kernel's own fp16 output ``o`` (also written when
     given, [B*T*S, H*D]), bit for bit.  ``s``: the consuming Linear's smoothing vector; None is returned (caller runs the
     two kernels) when its reciprocal form is not available."""
-    s_rcp = None
-    if s is not None:
-        s_rcp = smooth_rcp(s)
-        if s_rcp is None:
-            return None
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if not t.is_cuda or t.dtype != torch.float16:
-            raise VQError("%s must be a GPU fp16 tensor" % n)
+    s_rcp = _rcp_or_none(s)
+    if s_rcp is _NO_RCP:
+        return None
+    _req_f16((q, "q"), (k, "k"), (v, "v"))
     Cc = H * D
     Kp = pad128(Cc)
-    rows = B * T * S
-    dev = q.device
-    if o is not None:
-        _req(o, torch.float16, "o")
-        if o.shape != (rows, Cc):
-            raise VQError("attn_temporal_rowquant_shared: o must be [B*T*S, H*D]")
-    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
-    sx = torch.empty(rows, dtype=torch.float32, device=dev)
-    zx = torch.empty(rows, dtype=torch.int32, device=dev)
-    R = torch.empty(rows, dtype=torch.int32, device=dev)
-    scale = float(D) ** -0.5 if scale is None else float(scale)
-    check(_L().vq_attn_temporal_rowquant_shared(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(xq), _p(sx), _p(zx), _p(R),
-                                                _p(status), _p(o), B, T, S, H, D, ld_in, Kp, n_bits, scale, _stream()),
+    out, scale = _attn_qact(q, o, B * T * S, Cc, Kp, n_bits, D, scale, "attn_temporal_rowquant_shared")
+    check(_L().vq_attn_temporal_rowquant_shared(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), *_qact_ptrs(out), _p(status), _p(o),
+                                                B, T, S, H, D, ld_in, Kp, n_bits, scale, _stream()),
           "vq_attn_temporal_rowquant_shared")
-    return QAct(xq, sx, zx, R, Cc, n_bits)
+    return out
 
 
 def attn_temporal_long(q, k, v, B, T, S, H, D, ld_in, o: Optional[torch.Tensor] = None, quant: bool = False,
@@ -861,18 +866,13 @@ def attn_temporal_long(q, k, v, B, T, S, H, D, ld_in, o: Optional[torch.Tensor] 
     ``quant=True`` (B == 1): returns the ``QAct`` of the consuming Linear's per-token 8-bit quantizer (behind its
     smoothing vector ``s``), bit-identical to ``rowquant`` of the fp16 output, and also writes ``o`` when given; None when
     ``s`` has no exact reciprocal form (the caller then runs attention and the quantizer separately)."""
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if not t.is_cuda or t.dtype != torch.float16:
-            raise VQError("%s must be a GPU fp16 tensor" % n)
+    _req_f16((q, "q"), (k, "k"), (v, "v"))
     Cc = H * D
     rows = B * T * S
-    if o is not None:
-        _req(o, torch.float16, "o")
-        if o.shape != (rows, Cc):
-            raise VQError("attn_temporal_long: o must be [B*T*S, H*D]")
-    elif not quant:
+    if o is None and not quant:
         raise VQError("attn_temporal_long: o is required without quant")
-    scale = float(D) ** -0.5 if scale is None else float(scale)
+    _check_o(o, rows, Cc, "attn_temporal_long")
+    scale = _attn_scale(D, scale)
     ld_out = o.stride(0) if o is not None else 0
     if not quant:
         check(_L().vq_attn_temporal_long(_p(q), _p(k), _p(v), None, None, None, None, None, None, None, _p(o), B, T, S,
@@ -880,20 +880,14 @@ def attn_temporal_long(q, k, v, B, T, S, H, D, ld_in, o: Optional[torch.Tensor] 
         return o
     if B != 1:
         raise VQError("attn_temporal_long: per-token scales are shared over the batch; B must be 1")
-    s_rcp = None
-    if s is not None:
-        s_rcp = smooth_rcp(s)
-        if s_rcp is None:
-            return None
+    s_rcp = _rcp_or_none(s)
+    if s_rcp is _NO_RCP:
+        return None
     Kp = pad128(Cc)
-    dev = q.device
-    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
-    sx = torch.empty(rows, dtype=torch.float32, device=dev)
-    zx = torch.empty(rows, dtype=torch.int32, device=dev)
-    R = torch.empty(rows, dtype=torch.int32, device=dev)
-    check(_L().vq_attn_temporal_long(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(xq), _p(sx), _p(zx), _p(R), _p(status),
-                                     _p(o), B, T, S, H, D, ld_in, ld_out, Kp, scale, _stream()), "vq_attn_temporal_long")
-    return QAct(xq, sx, zx, R, Cc, 8)
+    out, scale = _attn_qact(q, None, rows, Cc, Kp, 8, D, scale, None)      # o and the scale: settled above, for both forms
+    check(_L().vq_attn_temporal_long(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), *_qact_ptrs(out), _p(status), _p(o),
+                                     B, T, S, H, D, ld_in, ld_out, Kp, scale, _stream()), "vq_attn_temporal_long")
+    return out
 
 
 ATTN_HEAD_DIMS = (16, 32, 64, 72)     # head dims the attention kernels are compiled for (csrc/vq_common.h)
@@ -916,37 +910,19 @@ def attn_temporal_rowquant_static(q, k, v, B, T, S, H, D, ld_in, delta: torch.Te
     ``rowquant(o.view(B, T*S, H*D), n_bits, s=s, delta=delta, zp=zp)`` returns for the kernel's own fp16 output ``o``
     (also written when given, [B*T*S, H*D]), bit for bit.  ``s``: the consuming Linear's smoothing vector; None is
     returned (caller runs the two kernels) when its reciprocal form is not available."""
-    s_rcp = None
-    if s is not None:
-        s_rcp = smooth_rcp(s)
-        if s_rcp is None:
-            return None
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if not t.is_cuda or t.dtype != torch.float16:
-            raise VQError("%s must be a GPU fp16 tensor" % n)
-    delta = _req(delta.reshape(-1).contiguous(), torch.float32, "delta")
-    zp = _req(zp.reshape(-1).contiguous(), torch.float32, "zp")
-    if delta.numel() != 1 or zp.numel() != 1:
-        raise VQError("attn_temporal_rowquant_static: a tensor-wise grid (one delta, one zero point)")
+    s_rcp = _rcp_or_none(s)
+    if s_rcp is _NO_RCP:
+        return None
+    _req_f16((q, "q"), (k, "k"), (v, "v"))
+    delta, zp = _tensorwise_grid(_flat_f32(delta, "delta"), _flat_f32(zp, "zp"), "attn_temporal_rowquant_static")
     Cc = H * D
     Kp = pad128(Cc)
-    rows = B * T * S
-    dev = q.device
-    ld_out = Cc
-    if o is not None:
-        _req(o, torch.float16, "o")
-        if o.shape != (rows, Cc):
-            raise VQError("attn_temporal_rowquant_static: o must be [B*T*S, H*D]")
-        ld_out = o.stride(0)
-    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
-    sx = torch.empty(rows, dtype=torch.float32, device=dev)
-    zx = torch.empty(rows, dtype=torch.int32, device=dev)
-    R = torch.empty(rows, dtype=torch.int32, device=dev)
-    scale = float(D) ** -0.5 if scale is None else float(scale)
-    check(_L().vq_attn_temporal_rowquant_static(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(delta), _p(zp), _p(xq), _p(sx),
-                                                _p(zx), _p(R), _p(o), B, T, S, H, D, ld_in, ld_out, Kp, n_bits, scale,
-                                                _stream()), "vq_attn_temporal_rowquant_static")
-    return QAct(xq, sx, zx, R, Cc, n_bits)
+    out, scale = _attn_qact(q, o, B * T * S, Cc, Kp, n_bits, D, scale, "attn_temporal_rowquant_static")
+    ld_out = Cc if o is None else o.stride(0)
+    check(_L().vq_attn_temporal_rowquant_static(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(delta), _p(zp), *_qact_ptrs(out),
+                                                _p(o), B, T, S, H, D, ld_in, ld_out, Kp, n_bits, scale, _stream()),
+          "vq_attn_temporal_rowquant_static")
+    return out
 
 
 # routes of vq_attn_fwd_route (VQ_ATTN_K_* of include/viditq.h) whose kernel has a static-grid form
@@ -984,36 +960,20 @@ def attn_fwd_rowquant_static(q, k, v, n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_s
     strides; bit-identical to attn_fwd's), bit for bit.  ``s``: the consuming Linear's smoothing vector; None is returned
     (caller runs the two kernels) when its reciprocal form is not available.  A launch the entry point refuses raises:
     ask :func:`attn_fwd_static_ok` first."""
-    s_rcp = None
-    if s is not None:
-        s_rcp = smooth_rcp(s)
-        if s_rcp is None:
-            return None
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if not t.is_cuda or t.dtype != torch.float16:
-            raise VQError("%s must be a GPU fp16 tensor" % n)
-    if kv_off is not None:
-        _req(kv_off, torch.int32, "kv_off")
-    delta = _req(delta.reshape(-1).contiguous(), torch.float32, "delta")
-    zp = _req(zp.reshape(-1).contiguous(), torch.float32, "zp")
-    if delta.numel() != 1 or zp.numel() != 1:
-        raise VQError("attn_fwd_rowquant_static: a tensor-wise grid (one delta, one zero point)")
-    if o is not None and (not o.is_cuda or o.dtype != torch.float16):
-        raise VQError("o must be a GPU fp16 tensor")
+    s_rcp = _rcp_or_none(s)
+    if s_rcp is _NO_RCP:
+        return None
+    _req_f16((q, "q"), (k, "k"), (v, "v"))
+    _req_opt(kv_off, torch.int32, "kv_off")
+    delta, zp = _tensorwise_grid(_flat_f32(delta, "delta"), _flat_f32(zp, "zp"), "attn_fwd_rowquant_static")
     Cc = H * D
     Kp = pad128(Cc) if Kp is None else Kp
-    rows = n_seq * Lq
-    dev = q.device
-    xq = torch.empty((rows, Kp), dtype=torch.int8, device=dev)
-    sx = torch.empty(rows, dtype=torch.float32, device=dev)
-    zx = torch.empty(rows, dtype=torch.int32, device=dev)
-    R = torch.empty(rows, dtype=torch.int32, device=dev)
-    scale = float(D) ** -0.5 if scale is None else float(scale)
-    check(_L().vq_attn_fwd_rowquant_static(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(delta), _p(zp), _p(xq), _p(sx), _p(zx),
-                                           _p(R), _p(o), n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_stride, kv_seq_stride,
-                                           kv_tok_stride, o_seq_stride, o_tok_stride, _p(kv_off), Kp, n_bits, scale,
-                                           _stream()), "vq_attn_fwd_rowquant_static")
-    return QAct(xq, sx, zx, R, Cc, n_bits)
+    out, scale = _attn_qact(q, o, n_seq * Lq, Cc, Kp, n_bits, D, scale, None, strided=True)
+    check(_L().vq_attn_fwd_rowquant_static(_p(q), _p(k), _p(v), _p(s), _p(s_rcp), _p(delta), _p(zp), *_qact_ptrs(out), _p(o),
+                                           n_seq, Lq, Lk, H, D, q_seq_stride, q_tok_stride, kv_seq_stride, kv_tok_stride,
+                                           o_seq_stride, o_tok_stride, _p(kv_off), Kp, n_bits, scale, _stream()),
+          "vq_attn_fwd_rowquant_static")
+    return out
 
 
 # --------------------------------------------------------------------------- misc
@@ -1121,8 +1081,7 @@ def _step_front(eps, x, aux, aux_name, coef, elem_mult, layout, refuse, step, x_
     eps, the geometry (else the solver's ``layout`` message), the solver's own clause ``refuse`` = (bad, message), the
     counter, x_out (allocated when None) and x_model.  Returns (n, C, inner, ld_eps, x_out, xm_f16)."""
     for t, name in ((eps, "eps"), (x, "x"), (aux, aux_name), (coef, "coef")):
-        if not t.is_cuda:
-            raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % name)
+        _req_gpu(t, name)
     _req(x, torch.float32, "x")
     _req(aux, torch.float32, aux_name)
     _req(coef, torch.float32, "coef")
@@ -1133,8 +1092,7 @@ def _step_front(eps, x, aux, aux_name, coef, elem_mult, layout, refuse, step, x_
         raise VQError("eps must be %s for x [n, C, ...], dense within a batch element" % layout)
     if refuse[0]:
         raise VQError(refuse[1])
-    if step is not None:
-        _req(step, torch.int32, "step")
+    _req_opt(step, torch.int32, "step")
     if x_out is None:
         x_out = torch.empty_like(x)
     else:
@@ -1219,8 +1177,7 @@ def _patch_front(eps_a, eps_b, names, x, aux, coef, row_len, refuse, patch, step
     the counter, x_out (allocated when None) and x_model.  Returns (n, C, C_out, T, H, W, ld_eps, p_t, p_h, p_w, x_out,
     xm_f16, xm_copies)."""
     for t, name in ((eps_a, names[0]), (eps_b, names[1]), (x, "x"), *((v, k) for k, v in aux.items()), (coef, "coef")):
-        if not t.is_cuda:
-            raise VQError("%s must be a GPU tensor (no CPU fallback in the product path)" % name)
+        _req_gpu(t, name)
     _req(x, torch.float32, "x")
     for k, v in aux.items():
         _req(v, torch.float32, k)
@@ -1232,8 +1189,7 @@ def _patch_front(eps_a, eps_b, names, x, aux, coef, row_len, refuse, patch, step
         raise VQError("%s / %s must be [n, tokens, p_t*p_h*p_w*C_out] with equal strides for x [n, C, T, H, W]" % names)
     if refuse[0] or coef.dim() != 2 or coef.shape[1] != row_len:
         raise VQError(refuse[1])
-    if step is not None:
-        _req(step, torch.int32, "step")
+    _req_opt(step, torch.int32, "step")
     if x_out is None:
         x_out = torch.empty_like(x)
     else:
