@@ -16,8 +16,10 @@ row term R, zero padding and the status word are compared exactly.  Rows the ora
 and must raise VQ_ST_EPSFILL (the kernels leave the refill to vq_epsfill_fixup, so no codes are compared there);
 test_quant_rows_cpu.py shows that no bit-exact launch holds such a row.
 
-vq_gelu_rowquant and vq_ln_modulate_rowquant compute their quantizer input on the GPU, so ties cannot be placed; they
-run Q3 / Q5 / Q6 under the relations (and bounds) of test_kernels_gpu.py."""
+vq_gelu_rowquant and vq_ln_modulate_rowquant compute their quantizer input on the GPU, so exact ties cannot be placed
+here; they run Q3 / Q5 / Q6 under the relations (and bounds) of test_kernels_gpu.py.  Their quantizer input itself is
+pinned elsewhere: the GELU value at every call site over all finite fp16 inputs by test_gelu_rowquant_exact_gpu.py
+(gelu_cases.py), LayerNorm + modulate by test_ln_modulate_exact_gpu.py (ln_cases.py)."""
 import os
 import subprocess
 import sys
