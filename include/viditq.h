@@ -497,6 +497,33 @@ int vq_attn_fwd_rowquant_static(const void* q, const void* k, const void* v, con
                                 long o_seq_stride, long o_tok_stride, const int32_t* kv_off,
                                 int Kp, int n_bits, float scale, void* stream);
 
+/* ---- PixArt-Sigma key / value compression and q / k LayerNorm ----------------------------------------------------
+ * AttentionKVCompress between its qkv Linear and the attention (PixArt_blocks.py:99-124 downsample_2d, 135-146 forward),
+ * one launch on the q | k | v buffer where the GEMM left it: qkv [B * H * W, ld] fp16, q at column 0, k at C, v at 2 C.
+ * k_out, v_out: dense [B * Lk, C] fp16.  mode:
+ *   VQ_KVC_CONV       Lk = (H / sr)(W / sr); token (b, i, j), channel c:
+ *                     sr_b[c] + sum_{di, dj < sr} sr_w[c, di, dj] * x[b, (i sr + di) W + j sr + dj, c] in fp32 on the fp16
+ *                     inputs (sr_w [C, sr, sr] as the depthwise Conv2d holds it), then the affine LayerNorm norm_w / norm_b /
+ *                     norm_eps over the C channels in fp32, rounded to fp16 ONCE.  The same sr_* / norm_* serve k and v.
+ *   VQ_KVC_PICK       'uniform' and 'ave' (the same tokens for an integer factor): the token at row i sr, column j sr, copied.
+ *   VQ_KVC_PICK_FLAT  'uniform_every': Lk = H W / sr, every sr-th token of the flat sequence, copied.
+ * kn_w / kn_b (both or neither; qk_norm): every INPUT k row first gets the affine LayerNorm k_norm in fp32, rounded to
+ * fp16 - the rounding point of the torch route and of the reference's fp16 mode - and then enters the convolution or
+ * the pick.  v never gets it.  qn_w / qn_b (both or neither): the affine LayerNorm q_norm over the q columns of every
+ * row, IN PLACE in qkv (fp32, rounded to fp16 once); without them the q columns are neither read nor written.  Every
+ * LayerNorm is two-pass (mean, then centred sum of squares).  sr_* / norm_* are read by VQ_KVC_CONV only (nullable
+ * otherwise).  All vectors fp32 [C].
+ * VQ_EINVAL: qkv / k_out / v_out null; a non-positive B, H, W, C, sr or ld; one of a w / b pair without the other;
+ * VQ_KVC_CONV without sr_w, sr_b, norm_w or norm_b; 2 B H W beyond int32.  VQ_ESHAPE: C % 8, ld % 8, ld < 3 C; H % sr or
+ * W % sr (VQ_KVC_PICK_FLAT: H W % sr); a pointer not 16-byte aligned.  VQ_EUNSUP: an unknown mode; sr outside {2, 4};
+ * C > 2048.  All before any HIP call or dereference. */
+#define VQ_KVC_CONV 0
+#define VQ_KVC_PICK 1
+#define VQ_KVC_PICK_FLAT 2
+int vq_kv_compress(void* qkv, long ld, const float* sr_w, const float* sr_b, const float* norm_w, const float* norm_b,
+                   float norm_eps, const float* kn_w, const float* kn_b, float kn_eps, const float* qn_w, const float* qn_b,
+                   float qn_eps, void* k_out, void* v_out, int B, int H, int W, int C, int sr, int mode, void* stream);
+
 /* ---- small fused elementwise helpers ---------------------------------------
  * mod[j, b, c] = table[j, c] + t0[b, j*C + c]  (stdit.py:100-102), fp32 out, chunk-major. */
 int vq_adaln_table(const void* table, const void* t0, float* mod, int B, int J, int C, void* stream);

@@ -55,6 +55,7 @@ SIGNATURES = {
     "vq_attn_temporal_long": (_i, [_vp] * 11 + [_i] * 5 + [_l, _l, _i, _f, _vp]),
     "vq_attn_temporal_rowquant_static": (_i, [_vp] * 12 + [_i] * 5 + [_l, _l, _i, _i, _f, _vp]),
     "vq_attn_fwd_rowquant_static": (_i, [_vp] * 12 + [_i] * 5 + [_l] * 6 + [_vp, _i, _i, _f, _vp]),
+    "vq_kv_compress": (_i, [_vp, _l] + [_vp] * 4 + [_f, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp] + [_i] * 6 + [_vp]),
     "vq_adaln_table": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "vq_linear_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _vp]),
     "vq_cfg_ddim_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
@@ -82,6 +83,9 @@ SA_T_NEXT = 14
 DDIM_ROW = 16
 (DDIM_CFG, DDIM_ONE_PLUS_K, DDIM_A, DDIM_BC, DDIM_ABAR_PREV) = range(5)
 DDIM_T_NEXT = 14
+
+# vq_kv_compress modes (include/viditq.h, VQ_KVC_*)
+KVC_CONV, KVC_PICK, KVC_PICK_FLAT = 0, 1, 2
 
 _lib = None
 

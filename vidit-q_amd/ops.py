@@ -1319,3 +1319,8 @@ def cfg_sa_step(eps: torch.Tensor, x: torch.Tensor, xp: torch.Tensor, hist: torc
                               _p(x_model), n, Cc, inner, ld, int(row), coef.shape[0], int(eps.dtype == torch.float16), xm16,
                               _stream()), "vq_cfg_sa_step")
     return x_out, xp_out
+
+
+# --------------------------------------------------------------------------- key / value compression (PixArt-Sigma)
+# vq_kv_compress's wrapper and its route predicate, defined in ops_kv.py on this module's operand checks
+from .ops_kv import kv_compress, kv_compress_ok  # noqa: E402,F401

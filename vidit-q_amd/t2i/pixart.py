@@ -12,7 +12,8 @@ Block = STDiT block without the temporal branch (PixArtMS.py:71-79); the fused r
 t2v/stdit.py behind this model's own front end: LN+modulate+quant -> fused-qkv int8 GEMM -> flash attention over N tokens
 (4096 at 1024^2) -> proj GEMM (+gate, +residual) [attn_proj_stage] -> varlen cross attention [cross_stage] -> MLP [mlp_stage];
 the route rules and switches are stdit's as well (fused_rules, takes_fused).  kv-compression (sr_ratio > 1) and
-qk_norm are not used by the quantized configs; they are implemented (round 6) with their FP parts as torch ops around the HIP attention.
+qk_norm are not used by the quantized configs; their FP parts run as one HIP launch (ops.kv_compress, VQ_KV_COMPRESS_HIP, default
+off) or as torch ops around the HIP attention.
 """
 from __future__ import annotations
 
@@ -29,7 +30,9 @@ from ..qdiff.models.quant_layer import QuantLayer
 from ..t2v.stdit import (CaptionEmbedder, Mlp, fp_edge_linear, MultiHeadCrossAttention, T2IFinalLayer, TimestepEmbedder,
                          approx_gelu, attn_proj_stage, cross_stage, fused_rules, fwd_attn_quantized_static,
                          get_1d_sincos_pos_embed_from_grid, ln_quant, mlp_stage, prompt_kv_exact_fill, seq_offsets, t2i_modulate,
-                         takes_fused)
+                         takes_fused, _switch)
+
+_KV_COMPRESS_HIP = _switch("VQ_KV_COMPRESS_HIP", False)   # key / value compression + q / k LayerNorm in one HIP launch
 
 
 def get_2d_sincos_pos_embed(embed_dim, grid_size, pe_interpolation=1.0, base_size=16):
@@ -92,7 +95,8 @@ class AttentionKVCompress(nn.Module):
     image axis, ``qk_norm``: LayerNorm over all ``dim`` channels (affine) before the heads are split.  No released quantized
     config turns these on; they are here so that a PixArt checkpoint trained with them loads and runs (round 6).
     The attention itself is the HIP kernel with Lq = N queries and Lk = N / sr^2 keys; the LayerNorms, the token picks and
-    the depthwise convolution of 'conv' are torch ops on the fp16 q | k | v buffer (they are FP in the reference as well)."""
+    the depthwise convolution of 'conv' are one HIP launch on the fp16 q | k | v buffer (:meth:`kv_compress_hip`) or, by
+    default, torch ops on it (they are FP in the reference as well)."""
 
     SAMPLINGS = (None, "conv", "ave", "uniform", "uniform_every")
 
@@ -148,12 +152,53 @@ class AttentionKVCompress(nn.Module):
             g = self._norm_fp32(self.norm, g).to(tns.dtype)
         return g.reshape(B, int(H / sr) * int(W / sr), C).contiguous()
 
+    def _param_f32(self, p_):
+        """The dense fp32 vector ops.kv_compress reads for parameter ``p_``: the parameter itself when it is one, else a
+        copy made once per (parameter, in-place version, storage) - no conversion launch per forward, and an address a
+        captured graph may keep (a replaced copy moves ops.PACK_EPOCH, which drops such graphs)."""
+        t_ = p_.detach()
+        if t_.dtype == torch.float32 and t_.is_contiguous():
+            return t_
+        cache = self.__dict__.setdefault("_f32_cache", {})
+        key, stamp = id(p_), (p_._version, t_.data_ptr(), t_.device)
+        ent = cache.get(key)
+        if ent is None or ent[0] != stamp:
+            if ent is not None:
+                ops.PACK_EPOCH[0] += 1
+            ent = cache[key] = (stamp, t_.float().contiguous(), p_)      # (p_ held: its id stays its own)
+        return ent[1]
+
+    def kv_compress_hip(self, qkv, N, H, W) -> bool:
+        """Whether :meth:`attend` takes the one-launch HIP route (ops.kv_compress) for this q | k | v buffer: the switch, fp16
+        on the GPU, a shape the kernel takes, and no quantized ``attn.sr`` (that case raises in the torch sequence)."""
+        if not _KV_COMPRESS_HIP or self.sr_ratio <= 1 or self.sampling is None:
+            return False
+        if not qkv.is_cuda or qkv.dtype != torch.float16 or qkv.dim() != 2 or qkv.stride(1) != 1 or H * W != N:
+            return False
+        if self.sampling == "conv" and isinstance(self.sr, QuantLayer) and any(self.sr.get_quant_state()):
+            return False
+        return ops.kv_compress_ok(self.num_heads * self.head_dim, H, W, self.sr_ratio, self.sampling, qkv.stride(0))
+
     def attend(self, qkv, B, N, HW=None):
         """qkv [B*N, 3C] fp16 (q | k | v column blocks) -> [B*N, C] fp16."""
         if self.plain:
             return self.core.spatial(qkv, B, N)
         C = self.num_heads * self.head_dim
         H, W = HW if HW is not None else (int(N ** 0.5), int(N ** 0.5))
+        if self.kv_compress_hip(qkv, N, H, W):                 # one launch; q (normalised in place) is read where it lies
+            f32 = self._param_f32
+
+            def ln3(ln):
+                return None if isinstance(ln, nn.Identity) else (f32(ln.weight), f32(ln.bias), ln.eps)
+            conv = self.sampling == "conv"
+            k2, v2 = ops.kv_compress(qkv, B, H, W, C, self.sr_ratio, self.sampling, f32(self.sr.weight) if conv else None,
+                                     f32(self.sr.bias) if conv else None, ln3(self.norm) if conv else None,
+                                     ln3(self.k_norm), ln3(self.q_norm))
+            Lk, ld = k2.shape[0] // B, qkv.stride(0)
+            out = torch.empty((B * N, C), dtype=torch.float16, device=qkv.device)
+            ops.attn_fwd(qkv, k2, v2, out, B, N, Lk, self.num_heads, self.head_dim, N * ld, ld, Lk * C, C, N * C, C,
+                         scale=self.scale)
+            return out
         q3 = self._norm_fp32(self.q_norm, qkv[:, :C].reshape(B, N, C)).contiguous()
         k3 = self._norm_fp32(self.k_norm, qkv[:, C:2 * C].reshape(B, N, C))
         k3 = self.downsample_2d(k3, H, W).contiguous()
