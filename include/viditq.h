@@ -140,6 +140,32 @@ int vq_rowquant_smooth_multi_shared(const void* x, const float* shift, const flo
                                     int32_t* const* zx, int32_t* const* R, int B, int n_tok, int C, int Kp, int n_bits,
                                     int32_t* status, void* stream);
 
+/* Batched forwards of 3 to 16 samples: x [B, n_tok, C] fp16 -> n_out (1..3) per-token dynamic quantizers from ONE pass
+ * over the rows, the grid of a token shared by its B rows (base_quantizer.py:177-189; dynamic_quantizer.py:16-45), outputs
+ * indexed by row = sample * n_tok + token with the shared step replicated, as vq_rowquant writes them.  For B < 3 use
+ * vq_rowquant, vq_gelu_rowquant, vq_ln_modulate_rowquant and vq_rowquant_smooth_multi_shared.  Input arm, one of:
+ *   plain (act = 0, shift = scale = NULL): output j is vq_rowquant(x, s[j], B), bit for bit;
+ *   act = 1: nn.GELU(approximate="tanh") rounded to fp16 in front of the quantizer (layers/blocks.py:27, fc1 -> fc2), one
+ *   output, as vq_gelu_rowquant computes it;
+ *   LayerNorm(ln_eps, no affine) + (1 + scale[b]) * y + shift[b] (shift / scale fp32 [B, C], both set; stdit.py:100-103,
+ *   124), quantized in fp32; xm_out (nullable, [B*n_tok, C] fp16) receives the modulated activation.
+ * Lane map: B waves of one workgroup take the B rows of a token, each row in the wave map (16-byte chunks, chunk i of lane
+ * l at column 8 l + 512 i: LayerNorm sums in that order) and exchange min / max through LDS once; max(1, 16 / B) tokens
+ * per workgroup.  Division: u / s[j] in the reciprocal form when s_rcp[j] (vq_smooth_reciprocal, 0 bad channels) is
+ * given, the IEEE division when only s[j] is, u itself when s[j] is NULL - the same quotient bit for bit (quant_layer.py:140).
+ * s, s_rcp (each nullable as a whole or per entry), xq, sx, zx, R are HOST arrays of n_out device pointers.
+ * Errors, each before any device call or dereference of a device pointer, checked in this order:
+ *   1. VQ_EINVAL: a null x or output table or entry, exactly one of shift / scale, act outside {0, 1}, act = 1 with shift,
+ *      xm_out without shift, n_out < 1, a non-positive B, n_tok or C;
+ *   2. VQ_ESHAPE for C % 8, Kp % 128 or Kp < C and VQ_EUNSUP for n_bits outside 2..8; then VQ_ESHAPE for x, shift, scale,
+ *      xm_out, s[j], s_rcp[j] or xq[j] off 16 bytes;
+ *   3. VQ_ESHAPE for B > 16;
+ *   4. VQ_EUNSUP for B < 3, Kp > 4608, n_out > 3, n_out > 1 with act = 1, or the LayerNorm arm with Kp > 1536. */
+int vq_rowquant_batch(const void* x, const float* shift, const float* scale, float ln_eps, int act, int n_out,
+                      const float* const* s, const float* const* s_rcp, int8_t* const* xq, float* const* sx,
+                      int32_t* const* zx, int32_t* const* R, void* xm_out, int B, int n_tok, int C, int Kp,
+                      int n_bits, int32_t* status, void* stream);
+
 /* One pass over x [B, n_tok, C] fp16 -> n_out (1..3) quantized copies on STATIC calibrated grids: ActQuantizer.forward
  * after init_done (qdiff/quantizer/base_quantizer.py:129-144) for Linears that share an input (q / k / v), with what
  * precedes them in a block in the same pass.  Input arm, one of:

@@ -31,6 +31,7 @@ SIGNATURES = {
     "vq_smooth_reciprocal": (_i, [_vp, _vp, _i, _vp, _vp]),
     "vq_rowquant_smooth_multi": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "vq_rowquant_smooth_multi_shared": (_i, [_vp, _vp, _vp, _f, _i] + [_vp] * 6 + [_i] * 5 + [_vp, _vp]),
+    "vq_rowquant_batch": (_i, [_vp, _vp, _vp, _f, _i, _i] + [_vp] * 7 + [_i] * 5 + [_vp, _vp]),
     "vq_rowquant_static": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                 _i, _i, _i, _i, _i, _vp]),
     "vq_act_scale_momentum": (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp]),

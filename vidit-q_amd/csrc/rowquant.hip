@@ -16,13 +16,6 @@
 #define RQ_WAVES 4
 #define RQ_THREADS (RQ_WAVES * 64)
 
-// the shape and code-width check of the quantizer entry points: rows of C channels padded to Kp, codes of n_bits
-static int rq_check_shape(int C, int Kp, int n_bits) {
-    if (C % 8 != 0 || Kp % 128 != 0 || Kp < C) return VQ_ESHAPE;
-    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
-    return VQ_OK;
-}
-
 __device__ __forceinline__ void store_codes8(int8_t* dst, const int q[8]) {
     uint32_t lo = (uint32_t)(q[0] & 0xff) | ((uint32_t)(q[1] & 0xff) << 8) | ((uint32_t)(q[2] & 0xff) << 16) |
                   ((uint32_t)(q[3] & 0xff) << 24);
@@ -575,8 +568,6 @@ extern "C" int vq_rowquant_smooth_multi(const void* x, int n_out, const float* c
         return VQ_EUNSUP;
     return vq_check_launch();
 }
-
-static bool rq_off16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
 
 extern "C" int vq_rowquant_smooth_multi_shared(const void* x, const float* shift, const float* scale, float ln_eps, int n_out,
                                                const float* const* s, const float* const* s_rcp, int8_t* const* xq,

@@ -37,6 +37,15 @@ bool vq_rowquant_static_one(const half_t* x, const half_t* add_rows, int n_add, 
                             int8_t* xq, float* sx, int32_t* zx, int32_t* R, const float* delta, const float* zp, int n_param,
                             int B, int n_tok, int C, int Kp, int n_bits, hipStream_t st, int* rc);
 
+// the shape and code-width check of the quantizer entry points (rowquant.hip, rowquant_batch.hip): rows of C channels padded
+// to Kp, codes of n_bits; and a pointer that 16-byte accesses cannot take
+static int rq_check_shape(int C, int Kp, int n_bits) {
+    if (C % 8 != 0 || Kp % 128 != 0 || Kp < C) return VQ_ESHAPE;
+    if (n_bits < 2 || n_bits > 8) return VQ_EUNSUP;
+    return VQ_OK;
+}
+static bool rq_off16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+
 // up to three quantized outputs of one input (kernel argument)
 struct LnqOut {
     const float* s[3];     // smoothing vector of output j, or null

@@ -1324,3 +1324,5 @@ def cfg_sa_step(eps: torch.Tensor, x: torch.Tensor, xp: torch.Tensor, hist: torc
 # --------------------------------------------------------------------------- key / value compression (PixArt-Sigma)
 # vq_kv_compress's wrapper and its route predicate, defined in ops_kv.py on this module's operand checks
 from .ops_kv import kv_compress, kv_compress_ok  # noqa: E402,F401
+from .ops_batch import (gelu_rowquant_batch, ln_modulate_rowquant_batch, rowquant_batch,  # noqa: E402,F401
+                        rowquant_batch_ok)

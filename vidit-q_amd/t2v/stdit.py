@@ -357,6 +357,7 @@ _STATIC_GEMM_QUANT = _switch("VQ_STATIC_GEMM_QUANT", False)
 _RUNNING_SMOOTH_DEVICE = _switch("VQ_RUNNING_SMOOTH_DEVICE", False)   # a running statistic on mlp.fc2, on the device
 EXACT_KV_EPS_FILL = _switch("VQ_EXACT_KV_EPS_FILL", True)             # the reference's global eps fill of the prompt's K / V
 _CROSS_Q_FUSED = _switch("VQ_CROSS_Q_FUSED", True)                    # cross attention inside q_linear's GEMM (q never written)
+_BATCH_QUANT = _switch("VQ_BATCH_QUANT", False)                       # one-pass dynamic quantizers of a batched forward, 3 <= B <= 16
 
 
 # ---- what a quantizer is, asked in one place each
@@ -377,6 +378,23 @@ def _smooth_joint(layers, svs, B, add_rows=False) -> bool:
     smoothing vectors ``svs``: the switch, a joint forward, no added rows, dynamic quantizers of one bit width and a vector
     on every Linear.  (The shape and the reciprocals are the launch's own: it answers None and the caller falls through.)"""
     return _SMOOTH_JOINT and B == 2 and not add_rows and all(s is not None for s in svs) and _same_dynamic(layers)
+
+
+def _batch_quant(layers, B, C, n_out=1, act=0, ln=False, add_rows=False) -> bool:
+    """Whether ONE launch of vq_rowquant_batch (ops.rowquant_batch / gelu_rowquant_batch / ln_modulate_rowquant_batch) serves
+    the quantizers of ``layers`` (which share an input [B, n, C]): the switch, a batch of 3 to 16, no added rows, dynamic
+    quantizers of one bit width, no running statistic, and nothing the entry point would refuse.  No launch."""
+    return _BATCH_QUANT and 3 <= B <= 16 and not add_rows and _same_dynamic(layers) and not any(
+        getattr(l, "smooth_quant_running_stat", False) for l in layers) and ops.rowquant_batch_ok(
+        B, C, ops.pad128(C), layers[0].act_quantizer.n_bits, n_out, act, ln)
+
+
+def quantize_input(layer, x3, s):
+    """``layer``'s input codes of x3 [B, n, C] behind its smoothing vector ``s``: the batched one-pass launch where it
+    applies (_batch_quant), else the layer's own quantizer."""
+    if _batch_quant((layer,), x3.shape[0], x3.shape[-1]):
+        return ops.rowquant_batch(x3, layer.act_quantizer.n_bits, [s], status=layer.status)[0]
+    return layer.quantize_input(x3, s)
 
 
 def _static_attn_quant(proj, T, H, D) -> bool:
@@ -482,13 +500,16 @@ def ln_quant(x3, shift, scale, layers, svs, status):
     modulated fp16 activation and every layer quantizes it on ITS calibrated (delta, zero_point)
     (base_quantizer.py:129-144) - never a silently substituted dynamic grid."""
     l0 = layers[0]
+    smooth = [None] if all(s is None for s in svs) else list(svs)
+    if _batch_quant(layers, x3.shape[0], x3.shape[-1], len(smooth), ln=True):
+        return ops.ln_modulate_rowquant_batch(x3, shift, scale, 1e-6, smooth=smooth, n_bits=l0.act_quantizer.n_bits,
+                                              status=status)
     if len(layers) > 1 and _smooth_joint(layers, svs, x3.shape[0]):    # (one output, fc1: the pair kernel below)
         qas = ops.rowquant_multi_shared(x3, svs, n_bits=l0.act_quantizer.n_bits, status=status, shift=shift, scale=scale,
                                         eps=1e-6)
         if qas is not None:
             return qas
     if all(isinstance(l.act_quantizer, DynamicActQuantizer) for l in layers):
-        smooth = [None] if all(s is None for s in svs) else list(svs)
         return ops.ln_modulate_rowquant(x3, shift, scale, 1e-6, smooth=smooth, n_bits=l0.act_quantizer.n_bits,
                                         status=status)
     if _static_one_pass(layers, x3.shape[-1], ln=True):
@@ -505,6 +526,9 @@ def temporal_qkv_codes(att, x3, svs, tpe2, B, S):
     0), behind their smoothing vectors ``svs``: one QAct when the three share it, else three."""
     layers = (att.q, att.k, att.v)
     aq, st = att.q.act_quantizer, att.q.status
+    smooth = [None] if all(s is None for s in svs) else list(svs)
+    if _batch_quant(layers, B, x3.shape[-1], len(smooth), add_rows=tpe2 is not None):
+        return ops.rowquant_batch(x3, aq.n_bits, smooth, status=st)
     if _smooth_joint(layers, svs, B, add_rows=tpe2 is not None):
         # a joint forward's three smoothed copies from one pass (None: refused, today's launches below)
         qas = ops.rowquant_multi_shared(x3, svs, n_bits=aq.n_bits, status=st)
@@ -556,7 +580,7 @@ def attn_proj_stage(proj, r, x2, B, N, fused, plain, att_o, gate=None):
     qa = fused(sv)
     if qa is None:
         att_o = plain(att_o)
-        qa = proj.quantize_input(att_o.view(B, N, -1), sv)
+        qa = quantize_input(proj, att_o.view(B, N, -1), sv)
     proj_into_resid(proj, r, qa, x2, gate, N)
     return att_o
 
@@ -603,11 +627,11 @@ def cross_stage(ca, r, x2, x3, B, N, y_lens, prompt_kv, att_o):
             def fused_q(o):
                 if o is None:
                     o = torch.empty((B * N, C), dtype=torch.float16, device=x3.device)
-                return ops.gemm_i8_cross_attn(ql.quantize_input(x3, sv), ql.packed_weight(_range_of(ql, r), sv), ql.bias_f32(),
+                return ops.gemm_i8_cross_attn(quantize_input(ql, x3, sv), ql.packed_weight(_range_of(ql, r), sv), ql.bias_f32(),
                                               kv, kv[:, C:], o, B, N, bound, core.num_heads, core.head_dim, 0, kv.stride(0),
                                               N * o.stride(0), o.stride(0), kv_off=y_lens, scale=core.scale)
             return attn_proj_stage(ca.proj, r, x2, B, N, lambda s: None, fused_q, att_o)
-    q = ops.gemm_i8(ql.quantize_input(x3, sv), ql.packed_weight(_range_of(ql, r), sv), bias=ql.bias_f32())
+    q = ops.gemm_i8(quantize_input(ql, x3, sv), ql.packed_weight(_range_of(ql, r), sv), bias=ql.bias_f32())
     if kv is None:
         kv = prompt_kv()
     return attn_proj_stage(
@@ -633,10 +657,14 @@ def mlp_stage(mlp, r, x2, x3, B, N, shift, scale, gate, status):
     s2 = _svec(fc2)
     qa2 = mlp_quantized_static(fc1, fc2, qa, pw1, s2)
     if qa2 is None:
+        batch = _GELU_QUANT and _batch_quant((fc2,), B, fc2.in_features, act=1)       # (decided before fc1's GEMM, like one_pass)
         one_pass = _GELU_QUANT and fc2.gelu_one_pass_ok(B, fc2.in_features, s2)
-        h = ops.gemm_i8(qa, pw1, bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass else ops.EPI_GELU)
+        h = ops.gemm_i8(qa, pw1, bias=fc1.bias_f32(), epilogue=ops.EPI_NONE if one_pass or batch else ops.EPI_GELU)
         h3 = h.view(B, N, -1)
-        qa2 = fc2.quantize_gelu_input(h3, s2) if one_pass else fc2.quantize_input(h3, s2)
+        if batch:
+            qa2 = ops.gelu_rowquant_batch(h3, fc2.act_quantizer.n_bits, s2, status=fc2.status)
+        else:
+            qa2 = fc2.quantize_gelu_input(h3, s2) if one_pass else fc2.quantize_input(h3, s2)
     return proj_into_resid(fc2, r, qa2, x2, gate, N)
 
 
