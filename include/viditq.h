@@ -785,6 +785,44 @@ int vq_cfg_sa_step(const void* eps, const float* x, const float* xp, float* hist
                    const int32_t* step, float* x_out, float* xp_out, void* x_model, int n, int C, int inner, long ld_eps,
                    int row, int n_rows, int eps_f16, int xm_f16, void* stream);
 
+/* The three PixArt steps above - vq_cfg_dpmpp_step, vq_cfg_ddpm_step, vq_cfg_sa_step - reading the model output where
+ * final_layer left it (PixArt.forward / PixArtMS.forward with patch_major=True) instead of the unpatchified copy and its
+ * chunk(2, dim=1)[0] view.
+ *   eps: the joint output of ONE forward, [2n, N_h*N_w, p*p*C_out] with N_h = H/p, N_w = W/p (H != W is served), sample
+ *        pitch ld_eps elements, fp32 (eps_f16 = 0) or fp16 (1); the halves in the order of the dense sibling: (uncond |
+ *        cond) for DPM-Solver++ and SA-Solver, (cond | uncond) for IDDPM.
+ *   latent element (b, c, h, w) is read from token (h/p)*N_w + w/p at column ((h%p)*p + w%p)*C_out + c: the index map of
+ *        PixArt.unpatchify / PixArtMS.unpatchify.
+ *   Channels read: 0 .. C-1 of both halves for DPM-Solver++ and SA-Solver - the learned-sigma channels C .. C_out-1 never.
+ *        IDDPM: cond's 0 .. 2C-1 (C .. 2C-1 is the variance v) and uncond's channels below `guided` (in the wide form
+ *        below, the 4-channel group that holds one of them); uncond's variance channels never.  The pitch padding never.
+ * Everything else - x, hist, xp, noise, x_out, x0_out, xp_out (dense fp32 [n, C, H, W]; the slot layouts of hist and of the
+ * SA noise ring), x_model ([2n, C, H, W] fp16 / fp32, both halves written), the coefficient rows, row / n_rows / step,
+ * guided, the aliasing that is allowed - is the dense sibling's, and so is the arithmetic, operation for operation, the
+ * fp16 roundings of an fp16 eps included (vq_cfg_dpmpp_step_patch, the STDiT entry, widens to fp32 first and computes
+ * something else): the result is bit for bit the dense sibling's on unpatchify(eps) ([:, :C] for DPM-Solver++ / SA).
+ * Work split: a lane owns one (token, h % p) pair - p cells of p*C_out neighbouring columns, and per channel p neighbouring
+ * w; the 64 lanes of a wave are 64 neighbouring tokens of one token row; a workgroup is 64 tokens x p x (4 / p) token rows;
+ * the grid is (64-token strips, groups of 4 / p token rows, n).  No LDS, no division.
+ * Access form.  Wide: C == 4, C_out % 4 == 0, ld_eps % 4 == 0, eps on 4 of its elements, and x / hist / xp / noise / x_out /
+ * x0_out / xp_out / x_model on p of theirs: one eps access is the 4 channels of a cell (8 bytes fp16, 16 bytes fp32), one
+ * dense access the p values of a channel (8 bytes for p = 2; 4 bytes of an fp16 x_model).  Every other accepted call - any
+ * other C or C_out, an odd ld_eps, an address that is only on its own element - moves one element per access.
+ * Refusals, in this order, all before any HIP call or dereference.  VQ_EINVAL: the dense sibling's nulls and ranges (H, W, p,
+ * C_out <= 0 in place of inner).  VQ_ESHAPE: C > C_out (IDDPM: 2C > C_out), H % p or W % p != 0, ld_eps < H*W*C_out; guided > C
+ * (IDDPM); n or H/p above 65535 (grid extents); eps, x_model, a dense operand, coef or step off its own element type.
+ * VQ_EUNSUP: p outside {1, 2}, eps_f16 or xm_f16 outside {0, 1}. */
+int vq_cfg_dpmpp_step_patch2d(const void* eps, const float* x, float* hist, const float* coef, const int32_t* step,
+                              float* x_out, void* x_model, int n, int C, int C_out, int H, int W, int p, long ld_eps,
+                              int row, int n_rows, int eps_f16, int xm_f16, void* stream);
+int vq_cfg_ddpm_step_patch2d(const void* eps, const float* x, const float* noise, const float* coef, const int32_t* step,
+                             float* x_out, float* x0_out, void* x_model, int n, int C, int C_out, int H, int W, int p,
+                             long ld_eps, int guided, int row, int n_rows, int eps_f16, int xm_f16, void* stream);
+int vq_cfg_sa_step_patch2d(const void* eps, const float* x, const float* xp, float* hist, const float* noise,
+                           const float* coef, const int32_t* step, float* x_out, float* xp_out, void* x_model, int n, int C,
+                           int C_out, int H, int W, int p, long ld_eps, int row, int n_rows, int eps_f16, int xm_f16,
+                           void* stream);
+
 /* ---- floating-point Linears at the edges of a forward -------------------------------------
  * out[m, n] = act_out( sum_k act_in(x[m, k]) * w[n, k] + bias[n] ): fp16 operands and result, fp32 accumulation (MFMA),
  * act: 0 none, 1 SiLU, 2 GELU(tanh).  Replaces F.linear of the layers the reference's FP lists keep out of quantization

@@ -66,6 +66,9 @@ SIGNATURES = {
     "vq_cfg_ddim_step_patch": (_i, [_vp] * 7 + [_i] * 9 + [_l] + [_i] * 6 + [_vp]),
     "vq_cfg_ddpm_step": (_i, [_vp] * 8 + [_i, _i, _i, _l, _i, _i, _i, _i, _i, _vp]),
     "vq_cfg_sa_step": (_i, [_vp] * 10 + [_i, _i, _i, _l, _i, _i, _i, _i, _vp]),
+    "vq_cfg_dpmpp_step_patch2d": (_i, [_vp] * 7 + [_i] * 6 + [_l] + [_i] * 4 + [_vp]),
+    "vq_cfg_ddpm_step_patch2d": (_i, [_vp] * 8 + [_i] * 6 + [_l] + [_i] * 5 + [_vp]),
+    "vq_cfg_sa_step_patch2d": (_i, [_vp] * 10 + [_i] * 6 + [_l] + [_i] * 4 + [_vp]),
 }
 
 # the coefficient row of vq_cfg_dpmpp_step (include/viditq.h, VQ_DPMPP_*)

@@ -364,16 +364,25 @@ static inline int vq_log2_patch(int p) { return p == 1 ? 0 : (p == 2 ? 1 : -1); 
 // of an access: ``f32`` is the null-terminated list of the dense fp32 operands, of which an optional one may only stand
 // last), VQ_EUNSUP (a patch extent outside {1, 2}, a flag outside {0, 1}, xm_copies outside {1, 2}).  Sets the geometry,
 // the access form and the grid, and returns VQ_OK when the launch may go ahead.
+// The first two clauses, which every patch-major entry point has (patch_check here, patch2d_check further down): the
+// nulls and ranges, then the shapes and the pitch.  ``C_read``: the channels of a patch position an entry point reads.
+static int patch_shapes(bool einval, const void* eps_u, const void* eps_c, const float* coef, int n, int C_read, int C_out,
+                        int T, int H, int W, int p_t, int p_h, int p_w, long ld_eps, int row, int n_rows) {
+    if (einval || !eps_u || !eps_c || !coef || n <= 0 || C_read <= 0 || C_out <= 0 || T <= 0 || H <= 0 || W <= 0 || p_t <= 0 ||
+        p_h <= 0 || p_w <= 0 || row < 0 || n_rows <= 0 || row >= n_rows)
+        return VQ_EINVAL;
+    if (C_read > C_out || T % p_t || H % p_h || W % p_w) return VQ_ESHAPE;
+    // one sample of the model output: T*H*W positions (tokens x patch positions) of C_out columns each
+    if (ld_eps < (long)T * H * W * C_out) return VQ_ESHAPE;
+    return VQ_OK;
+}
+
 static int patch_check(bool einval, const void* eps_u, const void* eps_c, const void* const* f32, const float* coef,
                        const int32_t* step, const void* x_model, int n, int C, int C_out, int T, int H, int W, int p_t,
                        int p_h, int p_w, long ld_eps, int row, int n_rows, int eps_f16, int xm_f16, int xm_copies,
                        patch_geo* g_out, bool* wide_out, dim3* grid_out) {
-    if (einval || !eps_u || !eps_c || !coef || n <= 0 || C <= 0 || C_out <= 0 || T <= 0 || H <= 0 || W <= 0 || p_t <= 0 ||
-        p_h <= 0 || p_w <= 0 || row < 0 || n_rows <= 0 || row >= n_rows)
-        return VQ_EINVAL;
-    if (C > C_out || T % p_t || H % p_h || W % p_w) return VQ_ESHAPE;
-    // one sample of the model output: T*H*W positions (tokens x patch positions) of C_out columns each
-    if (ld_eps < (long)T * H * W * C_out) return VQ_ESHAPE;
+    const int rc = patch_shapes(einval, eps_u, eps_c, coef, n, C, C_out, T, H, W, p_t, p_h, p_w, ld_eps, row, n_rows);
+    if (rc != VQ_OK) return rc;
     const bool wide = *wide_out = C == 4 && C_out % 4 == 0 && W % 2 == 0;
     const int VC = wide ? 4 : 1, VW = wide ? 2 : 1;
     const size_t e_sz = eps_f16 == 1 ? 2 : 4, m_sz = xm_f16 == 1 ? 2 : 4;     // (a flag outside {0, 1} is refused below)
@@ -546,50 +555,68 @@ extern "C" int vq_dpmpp_advance(int32_t* step, const float* coef, int n_rows, fl
 // of the duplicated batch.  Row layout and contract: include/viditq.h (vq_cfg_ddpm_step).  As above nothing is contracted
 // and an fp16 model output gets the fp16 roundings of the eager tensors: c - u, cfg * (.), u + (.), v + 1, (.) * 0.5 and
 // 1 - frac; whatever meets a coefficient is fp32.  exp is the library expf.
+// The coefficient row of an IDDPM launch, read once per thread.
+struct ddpm_row {
+    float cfg, A, B, c1, c2, min_log, max_log, nonzero;
+    bool clip;
+};
+
+__device__ __forceinline__ ddpm_row ddpm_load_row(const float* __restrict__ coef, int k) {
+    const float* r = coef + (long)k * VQ_DDPM_ROW;
+    ddpm_row R;
+    R.cfg = r[VQ_DDPM_CFG], R.A = r[VQ_DDPM_A], R.B = r[VQ_DDPM_B], R.c1 = r[VQ_DDPM_C1], R.c2 = r[VQ_DDPM_C2];
+    R.min_log = r[VQ_DDPM_MIN_LOG], R.max_log = r[VQ_DDPM_MAX_LOG], R.nonzero = r[VQ_DDPM_NONZERO];
+    R.clip = r[VQ_DDPM_CLIP] != 0.0f;
+    return R;
+}
+
+// Guidance (when ``guide``; u is not used otherwise), the learned-range variance, x0 and the posterior sample of one
+// element (the body both IDDPM kernels share).  T: the model output's type.  Returns out; x0 receives pred_xstart.
+template <typename T>
+__device__ __forceinline__ float ddpm_element(const ddpm_row& R, float c, float u, float v, float xv, float z, bool guide,
+                                              float& x0) {
+#pragma clang fp contract(off)
+    const float e = guide ? step_guide<T>(c, u, R.cfg) : c;
+    const T v1 = (T)(v + 1.0f);
+    const float frac = (float)(T)((float)v1 * 0.5f);
+    const float rest = (float)(T)(1.0f - frac);
+    const float lmax = frac * R.max_log;
+    const float lmin = rest * R.min_log;
+    const float lv = lmax + lmin;
+    const float ax = R.A * xv;
+    const float be = R.B * e;
+    float p0 = ax - be;
+    if (R.clip) p0 = p0 < -1.0f ? -1.0f : (p0 > 1.0f ? 1.0f : p0);              // a NaN stays one, as torch.clamp leaves it
+    x0 = p0;
+    const float m1 = R.c1 * p0;
+    const float m2 = R.c2 * xv;
+    const float mean = m1 + m2;
+    const float h = 0.5f * lv;
+    const float s = expf(h);
+    const float ns = R.nonzero * s;
+    const float nz = ns * z;
+    return mean + nz;
+}
+
 template <typename T, int V>
 __global__ __launch_bounds__(256) void cfg_ddpm_kernel(const T* __restrict__ eps, const float* x,
                                                        const float* __restrict__ noise, const float* __restrict__ coef,
                                                        const int32_t* __restrict__ step, float* xo, float* x0o, void* xm,
                                                        int xm_f16, int n, long inner, long CI, long ld_eps, int guided,
                                                        int row, int n_rows) {
-#pragma clang fp contract(off)
-    const float* r = coef + (long)step_row(row, step, n_rows) * VQ_DDPM_ROW;
-    const float cfg = r[VQ_DDPM_CFG], A = r[VQ_DDPM_A], B = r[VQ_DDPM_B], c1 = r[VQ_DDPM_C1], c2 = r[VQ_DDPM_C2];
-    const float min_log = r[VQ_DDPM_MIN_LOG], max_log = r[VQ_DDPM_MAX_LOG], nonzero = r[VQ_DDPM_NONZERO];
-    const bool clip = r[VQ_DDPM_CLIP] != 0.0f;
+    const ddpm_row R = ddpm_load_row(coef, step_row(row, step, n_rows));
     const long total = (long)n * CI;
     for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V; i < total; i += (long)gridDim.x * blockDim.x * V) {
         const long bi = i / CI, ri = i - bi * CI;
         const bool guide = ri / inner < guided;                  // V == 4 has inner % 4 == 0: a group lies in one channel
-        float c[V], u[V], v[V], xv[V], z[V], x0[V], out[V];
+        float c[V], u[V] = {}, v[V], xv[V], z[V], x0[V], out[V];
         dpm_load<T, V>(eps + bi * ld_eps + ri, c);
         dpm_load<T, V>(eps + bi * ld_eps + CI + ri, v);
         if (guide) dpm_load<T, V>(eps + (bi + n) * ld_eps + ri, u);
         dpm_load<float, V>(x + i, xv);
         dpm_load<float, V>(noise + i, z);
 #pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const float e = guide ? step_guide<T>(c[j], u[j], cfg) : c[j];
-            const T v1 = (T)(v[j] + 1.0f);
-            const float frac = (float)(T)((float)v1 * 0.5f);
-            const float rest = (float)(T)(1.0f - frac);
-            const float lmax = frac * max_log;
-            const float lmin = rest * min_log;
-            const float lv = lmax + lmin;
-            const float ax = A * xv[j];
-            const float be = B * e;
-            float p0 = ax - be;
-            if (clip) p0 = p0 < -1.0f ? -1.0f : (p0 > 1.0f ? 1.0f : p0);      // a NaN stays one, as torch.clamp leaves it
-            x0[j] = p0;
-            const float m1 = c1 * p0;
-            const float m2 = c2 * xv[j];
-            const float mean = m1 + m2;
-            const float h = 0.5f * lv;
-            const float s = expf(h);
-            const float ns = nonzero * s;
-            const float nz = ns * z[j];
-            out[j] = mean + nz;
-        }
+        for (int j = 0; j < V; ++j) out[j] = ddpm_element<T>(R, c[j], u[j], v[j], xv[j], z[j], guide, x0[j]);
         dpm_store<float, V>(xo + i, out);
         if (x0o) dpm_store<float, V>(x0o + i, x0);
         step_store_model<V>(xm, xm_f16, i, total, out);
@@ -621,18 +648,68 @@ extern "C" int vq_cfg_ddpm_step(const void* eps, const float* x, const float* no
 // (vq_cfg_sa_step).  As above nothing is contracted; the guidance is rounded in the model output's type, sigma_t * e is an
 // fp32 product (sigma_t is a one-element fp32 tensor in the eager path, which promotes) and the division by alpha_t is the
 // correctly rounded fp32 division of a tensor / tensor division.  There is no transcendental.
+// The coefficient row of an SA-Solver launch, read once per thread.
+struct sa_row {
+    int oc, op;
+    float cfg, sigma, alpha, cx, cg0, cg1, cn, px, pg0, pg1, pn;
+};
+
+__device__ __forceinline__ sa_row sa_load_row(const float* __restrict__ coef, int k) {
+    const float* r = coef + (long)k * VQ_SA_ROW;
+    sa_row R;
+    R.oc = (int)r[VQ_SA_OC], R.op = (int)r[VQ_SA_OP];
+    R.cfg = r[VQ_SA_CFG], R.sigma = r[VQ_SA_SIGMA], R.alpha = r[VQ_SA_ALPHA];
+    R.cx = r[VQ_SA_CX], R.cg0 = r[VQ_SA_CG0], R.cg1 = r[VQ_SA_CG1], R.cn = r[VQ_SA_CN];
+    R.px = r[VQ_SA_PX], R.pg0 = r[VQ_SA_PG0], R.pg1 = r[VQ_SA_PG1], R.pn = r[VQ_SA_PN];
+    return R;
+}
+
+// Guidance, x0, the corrector and the next predictor of one element (the body both SA-Solver kernels share).  T: the
+// model output's type.  m1 is read when an order is 2, zc when oc >= 1, zp when op >= 1.  Returns xq; m0 receives m_k, xc
+// the corrected sample.
+template <typename T>
+__device__ __forceinline__ float sa_element(const sa_row& R, float c, float u, float xv, float pv, float m1, float zc,
+                                            float zp, float& m0, float& xc) {
+#pragma clang fp contract(off)
+    const float e = step_guide<T>(c, u, R.cfg);
+    const float se = R.sigma * e;
+    const float t = pv - se;
+    const float m = __fdiv_rn(t, R.alpha);
+    m0 = m;
+    float v = xv;
+    if (R.oc >= 1) {
+        float g = R.cg0 * m;
+        if (R.oc == 2) {
+            const float g1 = R.cg1 * m1;
+            g = g + g1;
+        }
+        const float a = R.cx * v;
+        const float ag = a + g;
+        const float nz = R.cn * zc;
+        v = ag + nz;
+    }
+    xc = v;
+    if (R.op >= 1) {
+        float q = R.pg0 * m;
+        if (R.op == 2) {
+            const float q1 = R.pg1 * m1;
+            q = q + q1;
+        }
+        const float a = R.px * v;
+        const float aq = a + q;
+        const float nz = R.pn * zp;
+        v = aq + nz;
+    }
+    return v;
+}
+
 template <typename T, int V>
 __global__ __launch_bounds__(256) void cfg_sa_kernel(const T* __restrict__ eps, const float* x, const float* xp, float* hist,
                                                      const float* __restrict__ noise, const float* __restrict__ coef,
                                                      const int32_t* __restrict__ step, float* xo, float* xpo, void* xm,
                                                      int xm_f16, int n, long CI, long ld_eps, int row, int n_rows) {
-#pragma clang fp contract(off)
     const int k = step_row(row, step, n_rows);
-    const float* r = coef + (long)k * VQ_SA_ROW;
-    const int oc = (int)r[VQ_SA_OC], op = (int)r[VQ_SA_OP];
-    const float cfg = r[VQ_SA_CFG], sigma = r[VQ_SA_SIGMA], alpha = r[VQ_SA_ALPHA];
-    const float cx = r[VQ_SA_CX], cg0 = r[VQ_SA_CG0], cg1 = r[VQ_SA_CG1], cn = r[VQ_SA_CN];
-    const float px = r[VQ_SA_PX], pg0 = r[VQ_SA_PG0], pg1 = r[VQ_SA_PG1], pn = r[VQ_SA_PN];
+    const sa_row R = sa_load_row(coef, k);
     const long total = (long)n * CI;
     float* h0 = hist + (long)(k % 2) * total;                    // written: m_k
     const float* h1 = hist + (long)((k + 1) % 2) * total;        // m_{k-1}
@@ -640,47 +717,16 @@ __global__ __launch_bounds__(256) void cfg_sa_kernel(const T* __restrict__ eps, 
     const float* z1 = noise + (long)((k + 1) % 2) * total;       // the draw of loop step k + 1 (predictor)
     for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V; i < total; i += (long)gridDim.x * blockDim.x * V) {
         const long bi = i / CI, ri = i - bi * CI;
-        float u[V], c[V], xv[V], pv[V], m1[V], zc[V], zp[V], m0[V], xc[V], xq[V];
+        float u[V], c[V], xv[V], pv[V], m1[V] = {}, zc[V] = {}, zp[V] = {}, m0[V], xc[V], xq[V];
         dpm_load<T, V>(eps + bi * ld_eps + ri, u);
         dpm_load<T, V>(eps + (bi + n) * ld_eps + ri, c);
         dpm_load<float, V>(x + i, xv);
         dpm_load<float, V>(xp + i, pv);
-        if (oc == 2 || op == 2) dpm_load<float, V>(h1 + i, m1);
-        if (oc >= 1) dpm_load<float, V>(z0 + i, zc);
-        if (op >= 1) dpm_load<float, V>(z1 + i, zp);
+        if (R.oc == 2 || R.op == 2) dpm_load<float, V>(h1 + i, m1);
+        if (R.oc >= 1) dpm_load<float, V>(z0 + i, zc);
+        if (R.op >= 1) dpm_load<float, V>(z1 + i, zp);
 #pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const float e = step_guide<T>(c[j], u[j], cfg);
-            const float se = sigma * e;
-            const float t = pv[j] - se;
-            const float m = __fdiv_rn(t, alpha);
-            m0[j] = m;
-            float v = xv[j];
-            if (oc >= 1) {
-                float g = cg0 * m;
-                if (oc == 2) {
-                    const float g1 = cg1 * m1[j];
-                    g = g + g1;
-                }
-                const float a = cx * v;
-                const float ag = a + g;
-                const float nz = cn * zc[j];
-                v = ag + nz;
-            }
-            xc[j] = v;
-            if (op >= 1) {
-                float q = pg0 * m;
-                if (op == 2) {
-                    const float q1 = pg1 * m1[j];
-                    q = q + q1;
-                }
-                const float a = px * v;
-                const float aq = a + q;
-                const float nz = pn * zp[j];
-                v = aq + nz;
-            }
-            xq[j] = v;
-        }
+        for (int j = 0; j < V; ++j) xq[j] = sa_element<T>(R, c[j], u[j], xv[j], pv[j], m1[j], zc[j], zp[j], m0[j], xc[j]);
         dpm_store<float, V>(h0 + i, m0);
         dpm_store<float, V>(xo + i, xc);
         dpm_store<float, V>(xpo + i, xq);
@@ -701,5 +747,245 @@ extern "C" int vq_cfg_sa_step(const void* eps, const float* x, const float* xp, 
         typedef decltype(t) T;
         hipLaunchKernelGGL((cfg_sa_kernel<T, decltype(v)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)eps, x,
                            xp, hist, noise, coef, step, x_out, xp_out, x_model, xm_f16, n, CI, ld_eps, row, n_rows);
+    });
+}
+
+// ---- the three PixArt steps reading final_layer's patch-major output (no unpatchify copy, no chunk) -----------------
+// eps: the joint output of ONE forward, [2n, N_h*N_w tokens, p*p*C_out columns], sample pitch ld_eps; latent element
+// (b, c, h, w) is at token (h/p)*N_w + w/p, column ((h%p)*p + w%p)*C_out + c (PixArt.unpatchify / PixArtMS.unpatchify).
+// The arithmetic is the dense kernels' own (dpmpp_element<T>, ddpm_element<T>, sa_element<T> with T the model output's
+// type), so the fp16 roundings of an fp16 output are kept: the STDiT patch kernels above widen first and do not serve.
+//
+// Work split (contract: include/viditq.h, vq_cfg_dpmpp_step_patch2d).  A lane owns one (token, h % p) pair: the p cells
+// (h % p, 0 .. p-1) of its token, which are p * C_out neighbouring columns, and per channel the p neighbouring w they hold.
+// threadIdx.x walks 64 neighbouring tokens of one token row, so a wave reads 64 cell rows 64-token-columns apart and
+// writes 64 * p neighbouring floats of one latent row per channel; threadIdx.y is h % p and threadIdx.z a token row, 256
+// threads in all.  The grid is (64-token strips, groups of 4 / p token rows, samples): no index is divided, no LDS.
+// VC = 4 (C == 4): one access per cell holds the four channels, and the dense streams move the p values of a channel in
+// one access.  VC = 1: one element per access, any C.
+template <int VC, int LP, typename F>
+__device__ __forceinline__ void patch2d_walk(const patch_geo& g, F item) {
+    constexpr int P = 1 << LP, VW = VC == 4 ? P : 1;
+    const int Nw = g.W >> LP, Nh = g.H >> LP;
+    const int tw = blockIdx.x * 64 + threadIdx.x, th = blockIdx.y * blockDim.z + threadIdx.z, hp = threadIdx.y;
+    if (tw >= Nw || th >= Nh) return;
+    const long b = blockIdx.z, HW = (long)g.H * g.W;
+    // cell (h % p, 0), channel 0 of this lane's token in sample b; dense (b, 0, h, w0)
+    const long e0 = b * g.ld_eps + (((long)th * Nw + tw) * (P * P) + hp * P) * g.C_out;
+    const long i0 = b * g.C * HW + (long)(th * P + hp) * g.W + tw * P;
+    for (int c0 = 0; c0 < g.C; c0 += VC) {
+#pragma unroll
+        for (int j0 = 0; j0 < P; j0 += VW) {
+            long e[VW];
+#pragma unroll
+            for (int j = 0; j < VW; ++j) e[j] = e0 + (long)(j0 + j) * g.C_out + c0;
+            item(c0, e, i0 + c0 * HW + j0);                      // channel c0 + cc of the item is at i + cc * H*W
+        }
+    }
+}
+
+// x_out may alias x: an element is read and written by the same lane.
+template <typename T, int VC, int LP>
+__global__ __launch_bounds__(256) void cfg_dpmpp_patch2d_kernel(const T* __restrict__ eps, const float* x, float* hist,
+                                                                const float* __restrict__ coef,
+                                                                const int32_t* __restrict__ step, float* xo, void* xm,
+                                                                int xm_f16, int n, patch_geo g, int row, int n_rows) {
+    constexpr int VW = VC == 4 ? 1 << LP : 1;
+    const int k = step_row(row, step, n_rows);
+    const dpmpp_row R = dpmpp_load_row(coef, k);
+    const long HW = (long)g.H * g.W, total = (long)n * g.C * HW;
+    const T* eps_c = eps + (long)n * g.ld_eps;                   // (uncond | cond)
+    float* h0 = hist + (long)(k % 3) * total;                    // written: m_k
+    const float* h1 = hist + (long)((k + 2) % 3) * total;        // m_{k-1}
+    const float* h2 = hist + (long)((k + 1) % 3) * total;        // m_{k-2}
+    patch2d_walk<VC, LP>(g, [&](int, const long (&e)[VW], long i0) {
+        float u[VW][VC], c[VW][VC];
+        patch_load<T, VC, VW>(eps, eps_c, e, u, c);
+#pragma unroll
+        for (int cc = 0; cc < VC; ++cc) {
+            const long i = i0 + cc * HW;
+            float xv[VW], m1[VW] = {}, m2[VW] = {}, m0[VW], out[VW];
+            dpm_load<float, VW>(x + i, xv);
+            if (R.order >= 2) dpm_load<float, VW>(h1 + i, m1);
+            if (R.order >= 3) dpm_load<float, VW>(h2 + i, m2);
+#pragma unroll
+            for (int j = 0; j < VW; ++j) out[j] = dpmpp_element<T>(R, c[j][cc], u[j][cc], xv[j], m1[j], m2[j], m0[j]);
+            dpm_store<float, VW>(h0 + i, m0);
+            dpm_store<float, VW>(xo + i, out);
+            step_store_model<VW>(xm, xm_f16, i, total, out);
+        }
+    });
+}
+
+template <typename T, int VC, int LP>
+__global__ __launch_bounds__(256) void cfg_ddpm_patch2d_kernel(const T* __restrict__ eps, const float* x,
+                                                               const float* __restrict__ noise,
+                                                               const float* __restrict__ coef,
+                                                               const int32_t* __restrict__ step, float* xo, float* x0o,
+                                                               void* xm, int xm_f16, int n, patch_geo g, int guided, int row,
+                                                               int n_rows) {
+    constexpr int VW = VC == 4 ? 1 << LP : 1;
+    const ddpm_row R = ddpm_load_row(coef, step_row(row, step, n_rows));
+    const long HW = (long)g.H * g.W, total = (long)n * g.C * HW;
+    const T* eps_u = eps + (long)n * g.ld_eps;                   // (cond | uncond)
+    patch2d_walk<VC, LP>(g, [&](int c0, const long (&e)[VW], long i0) {
+        float c[VW][VC], u[VW][VC] = {}, v[VW][VC];
+#pragma unroll
+        for (int j = 0; j < VW; ++j) {
+            dpm_load<T, VC>(eps + e[j], c[j]);
+            dpm_load<T, VC>(eps + e[j] + g.C, v[j]);             // cond's variance channels C .. 2C-1
+            if (c0 < guided) dpm_load<T, VC>(eps_u + e[j], u[j]);
+        }
+#pragma unroll
+        for (int cc = 0; cc < VC; ++cc) {
+            const long i = i0 + cc * HW;
+            float xv[VW], z[VW], x0[VW], out[VW];
+            dpm_load<float, VW>(x + i, xv);
+            dpm_load<float, VW>(noise + i, z);
+#pragma unroll
+            for (int j = 0; j < VW; ++j)
+                out[j] = ddpm_element<T>(R, c[j][cc], u[j][cc], v[j][cc], xv[j], z[j], c0 + cc < guided, x0[j]);
+            dpm_store<float, VW>(xo + i, out);
+            if (x0o) dpm_store<float, VW>(x0o + i, x0);
+            step_store_model<VW>(xm, xm_f16, i, total, out);
+        }
+    });
+}
+
+// x_out may alias x and xp_out may alias xp.
+template <typename T, int VC, int LP>
+__global__ __launch_bounds__(256) void cfg_sa_patch2d_kernel(const T* __restrict__ eps, const float* x, const float* xp,
+                                                             float* hist, const float* __restrict__ noise,
+                                                             const float* __restrict__ coef,
+                                                             const int32_t* __restrict__ step, float* xo, float* xpo, void* xm,
+                                                             int xm_f16, int n, patch_geo g, int row, int n_rows) {
+    constexpr int VW = VC == 4 ? 1 << LP : 1;
+    const int k = step_row(row, step, n_rows);
+    const sa_row R = sa_load_row(coef, k);
+    const long HW = (long)g.H * g.W, total = (long)n * g.C * HW;
+    const T* eps_c = eps + (long)n * g.ld_eps;                   // (uncond | cond)
+    float* h0 = hist + (long)(k % 2) * total;                    // written: m_k
+    const float* h1 = hist + (long)((k + 1) % 2) * total;        // m_{k-1}
+    const float* z0 = noise + (long)(k % 2) * total;             // the draw of loop step k (corrector)
+    const float* z1 = noise + (long)((k + 1) % 2) * total;       // the draw of loop step k + 1 (predictor)
+    patch2d_walk<VC, LP>(g, [&](int, const long (&e)[VW], long i0) {
+        float u[VW][VC], c[VW][VC];
+        patch_load<T, VC, VW>(eps, eps_c, e, u, c);
+#pragma unroll
+        for (int cc = 0; cc < VC; ++cc) {
+            const long i = i0 + cc * HW;
+            float xv[VW], pv[VW], m1[VW] = {}, zc[VW] = {}, zp[VW] = {}, m0[VW], xc[VW], xq[VW];
+            dpm_load<float, VW>(x + i, xv);
+            dpm_load<float, VW>(xp + i, pv);
+            if (R.oc == 2 || R.op == 2) dpm_load<float, VW>(h1 + i, m1);
+            if (R.oc >= 1) dpm_load<float, VW>(z0 + i, zc);
+            if (R.op >= 1) dpm_load<float, VW>(z1 + i, zp);
+#pragma unroll
+            for (int j = 0; j < VW; ++j)
+                xq[j] = sa_element<T>(R, c[j][cc], u[j][cc], xv[j], pv[j], m1[j], zc[j], zp[j], m0[j], xc[j]);
+            dpm_store<float, VW>(h0 + i, m0);
+            dpm_store<float, VW>(xo + i, xc);
+            dpm_store<float, VW>(xpo + i, xq);
+            step_store_model<VW>(xm, xm_f16, i, total, xq);
+        }
+    });
+}
+
+// The refusals of the patch2d entry points, in the order include/viditq.h documents: patch_shapes' two clauses (``einval``:
+// the solver's own nulls and ranges; ``C_read``: C, or 2C where the variance channels are read), then VQ_ESHAPE (``eshape``:
+// the solver's clause; a grid extent past 65535; an address off its own element type: ``f32`` is the null-terminated list of
+// the dense fp32 operands, of which an optional one may only stand last), then VQ_EUNSUP (p outside {1, 2}, a flag outside
+// {0, 1}).  Sets the geometry, log2 p, the access form - wide when the shape allows it AND every address is on the bytes of
+// its wide access, else one element per access - and the launch extents, and returns VQ_OK when the launch may go ahead.
+static int patch2d_check(bool einval, bool eshape, int C_read, const void* eps, const void* const* f32, const float* coef,
+                         const int32_t* step, const void* x_model, int n, int C, int C_out, int H, int W, int p, long ld_eps,
+                         int row, int n_rows, int eps_f16, int xm_f16, patch_geo* g_out, int* lp_out, bool* wide_out,
+                         dim3* grid_out, dim3* block_out) {
+    const int rc = patch_shapes(einval, eps, eps, coef, n, C_read, C_out, 1, H, W, 1, p, p, ld_eps, row, n_rows);
+    if (rc != VQ_OK) return rc;
+    const long rows_y = H / p, strips = ((long)(W / p) + 63) / 64;
+    if (eshape || n > 65535 || rows_y > 65535) return VQ_ESHAPE;
+    const size_t e_sz = eps_f16 == 1 ? 2 : 4, m_sz = xm_f16 == 1 ? 2 : 4;     // (a flag outside {0, 1} is refused below)
+    const int VW = p == 2 ? 2 : 1;
+    bool own = vq_aligned(eps, e_sz) && vq_aligned(x_model, m_sz) && vq_aligned(coef, 4) && vq_aligned(step, 4);
+    bool wide = C == 4 && C_out % 4 == 0 && ld_eps % 4 == 0 && vq_aligned(eps, e_sz * 4) && vq_aligned(x_model, m_sz * VW);
+    for (; *f32; ++f32) own = own && vq_aligned(*f32, 4), wide = wide && vq_aligned(*f32, 4 * VW);
+    if (!own) return VQ_ESHAPE;
+    const int lp = *lp_out = vq_log2_patch(p);
+    if (lp < 0 || eps_f16 < 0 || eps_f16 > 1 || xm_f16 < 0 || xm_f16 > 1) return VQ_EUNSUP;
+    patch_geo& g = *g_out;
+    g.C = C, g.C_out = C_out, g.T = 1, g.H = H, g.W = W, g.lt = 0, g.lh = g.lw = lp, g.ld_eps = ld_eps;
+    *wide_out = wide;
+    const int rows_z = 4 >> lp;                                  // token rows of a workgroup: 64 x p x (4 / p) threads
+    *block_out = dim3(64, p, rows_z);
+    *grid_out = dim3((unsigned)strips, (unsigned)((rows_y + rows_z - 1) / rows_z), (unsigned)n);
+    return VQ_OK;
+}
+
+// One launch of a patch2d kernel template: ``launch(T(), VC, LP)`` is called once, with the model output's type as a value
+// and the access form and log2 p as integral constants (patch_launch picks the first two).
+template <typename F>
+static int patch2d_launch(bool wide, int lp, int eps_f16, F launch) {
+    return patch_launch(wide, eps_f16, [&](auto t, auto vc, auto) {
+        if (lp) launch(t, vc, std::integral_constant<int, 1>()); else launch(t, vc, std::integral_constant<int, 0>());
+    });
+}
+
+extern "C" int vq_cfg_dpmpp_step_patch2d(const void* eps, const float* x, float* hist, const float* coef, const int32_t* step,
+                                         float* x_out, void* x_model, int n, int C, int C_out, int H, int W, int p, long ld_eps,
+                                         int row, int n_rows, int eps_f16, int xm_f16, void* stream) {
+    const void* const f32[] = {x, hist, x_out, nullptr};
+    patch_geo g;
+    int lp;
+    bool wide;
+    dim3 grid, block;
+    const int rc = patch2d_check(!x || !hist || !x_out, false, C, eps, f32, coef, step, x_model, n, C, C_out, H, W, p, ld_eps,
+                                 row, n_rows, eps_f16, xm_f16, &g, &lp, &wide, &grid, &block);
+    if (rc != VQ_OK) return rc;
+    return patch2d_launch(wide, lp, eps_f16, [&](auto t, auto vc, auto l) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((cfg_dpmpp_patch2d_kernel<T, decltype(vc)::value, decltype(l)::value>), grid, block, 0,
+                           (hipStream_t)stream, (const T*)eps, x, hist, coef, step, x_out, x_model, xm_f16, n, g, row, n_rows);
+    });
+}
+
+extern "C" int vq_cfg_ddpm_step_patch2d(const void* eps, const float* x, const float* noise, const float* coef,
+                                        const int32_t* step, float* x_out, float* x0_out, void* x_model, int n, int C,
+                                        int C_out, int H, int W, int p, long ld_eps, int guided, int row, int n_rows,
+                                        int eps_f16, int xm_f16, void* stream) {
+    const void* const f32[] = {x, noise, x_out, x0_out, nullptr};                 // (x0_out is optional: last)
+    patch_geo g;
+    int lp;
+    bool wide;
+    dim3 grid, block;
+    const int rc = patch2d_check(!x || !noise || !x_out || guided < 0 || C > (1 << 30), guided > C, 2 * C, eps, f32,
+                                 coef, step, x_model, n, C, C_out, H, W, p, ld_eps, row, n_rows, eps_f16, xm_f16, &g, &lp,
+                                 &wide, &grid, &block);
+    if (rc != VQ_OK) return rc;
+    return patch2d_launch(wide, lp, eps_f16, [&](auto t, auto vc, auto l) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((cfg_ddpm_patch2d_kernel<T, decltype(vc)::value, decltype(l)::value>), grid, block, 0,
+                           (hipStream_t)stream, (const T*)eps, x, noise, coef, step, x_out, x0_out, x_model, xm_f16, n, g,
+                           guided, row, n_rows);
+    });
+}
+
+extern "C" int vq_cfg_sa_step_patch2d(const void* eps, const float* x, const float* xp, float* hist, const float* noise,
+                                      const float* coef, const int32_t* step, float* x_out, float* xp_out, void* x_model,
+                                      int n, int C, int C_out, int H, int W, int p, long ld_eps, int row, int n_rows,
+                                      int eps_f16, int xm_f16, void* stream) {
+    const void* const f32[] = {x, xp, hist, noise, x_out, xp_out, nullptr};
+    patch_geo g;
+    int lp;
+    bool wide;
+    dim3 grid, block;
+    const int rc = patch2d_check(!x || !xp || !hist || !noise || !x_out || !xp_out, false, C, eps, f32, coef, step, x_model, n,
+                                 C, C_out, H, W, p, ld_eps, row, n_rows, eps_f16, xm_f16, &g, &lp, &wide, &grid, &block);
+    if (rc != VQ_OK) return rc;
+    return patch2d_launch(wide, lp, eps_f16, [&](auto t, auto vc, auto l) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((cfg_sa_patch2d_kernel<T, decltype(vc)::value, decltype(l)::value>), grid, block, 0,
+                           (hipStream_t)stream, (const T*)eps, x, xp, hist, noise, coef, step, x_out, xp_out, x_model, xm_f16,
+                           n, g, row, n_rows);
     });
 }

@@ -306,18 +306,21 @@ class DPMStepGraph(_CounterStepGraph):
     whose x0 history is one more device buffer."""
 
     def __init__(self, fn, text, kwargs, x, rows, t_first: float, model_dtype=torch.float32, warmup: int = 2):
+        from . import ops
+        from .t2i.fused_loop import StepRoute
         self.fn, self.text, self.kwargs = fn, text, kwargs
+        self.route = StepRoute(fn, (ops.cfg_dpmpp_step_ok, ops.cfg_dpmpp_step),
+                               (ops.cfg_dpmpp_step_patch2d_ok, ops.cfg_dpmpp_step_patch2d))
         self.hist = torch.zeros((3, x.numel()), dtype=torch.float32, device=x.device)
         super().__init__(fn, kwargs, x, rows, t_first, model_dtype, warmup)
 
     def _forward(self):
-        return self.fn(self.xm, self.t, self.text, **self.kwargs)
+        return self.route.forward(lambda **pm: self.fn(self.xm, self.t, self.text, **self.kwargs, **pm), self.x)
 
     def _step(self, eps):
-        from . import ops
-        if not ops.cfg_dpmpp_step_ok(eps, self.x):
+        if not self.route.ok(eps, self.x):
             self._refuse_output("vq_cfg_dpmpp_step")
-        ops.cfg_dpmpp_step(eps, self.x, self.hist, self.rows, 0, step=self.step, x_out=self.x, x_model=self.xm)
+        self.route.step(eps, self.x, self.hist, self.rows, 0, step=self.step, x_out=self.x, x_model=self.xm)
 
     @torch.no_grad()
     def run(self, x, step_callback=None):
@@ -332,20 +335,23 @@ class DDPMStepGraph(_CounterStepGraph):
 
     def __init__(self, fn, y, mask, kwargs, x, rows, t_first: float, model_dtype=torch.float32, guided: int = 3,
                  warmup: int = 2):
+        from . import ops
+        from .t2i.fused_loop import StepRoute
         self.fn, self.y, self.mask, self.kwargs, self.guided = fn, y, mask, kwargs, guided
+        self.route = StepRoute(fn, (ops.cfg_ddpm_step_ok, ops.cfg_ddpm_step),
+                               (ops.cfg_ddpm_step_patch2d_ok, ops.cfg_ddpm_step_patch2d))
         self.x0 = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
         self.noise = torch.zeros((2 * x.shape[0],) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
         super().__init__(fn, kwargs, x, rows, t_first, model_dtype, warmup)
 
     def _forward(self):
-        return self.fn(self.xm, self.t, self.y, self.mask, **self.kwargs)
+        return self.route.forward(lambda **pm: self.fn(self.xm, self.t, self.y, self.mask, **self.kwargs, **pm), self.x)
 
     def _step(self, eps):
-        from . import ops
-        if not ops.cfg_ddpm_step_ok(eps, self.x):
+        if not self.route.ok(eps, self.x):
             self._refuse_output("vq_cfg_ddpm_step")
-        ops.cfg_ddpm_step(eps, self.x, self.noise[:self.x.shape[0]], self.rows, 0, step=self.step, x_out=self.x,
-                          x0_out=self.x0, x_model=self.xm, guided=self.guided)
+        self.route.step(eps, self.x, self.noise[:self.x.shape[0]], self.rows, 0, step=self.step, x_out=self.x,
+                        x0_out=self.x0, x_model=self.xm, guided=self.guided)
 
     @torch.no_grad()
     def run(self, x, noise_steps=None, generator=None, step_callback=None):
@@ -369,20 +375,23 @@ class SAStepGraph(_CounterStepGraph):
     from ``noise_steps`` or with the draw the eager-launched loop makes - so a replay is bit-identical to that loop."""
 
     def __init__(self, fn, text, kwargs, x, rows, t_first: float, model_dtype=torch.float32, warmup: int = 2):
+        from . import ops
+        from .t2i.fused_loop import StepRoute
         self.fn, self.text, self.kwargs = fn, text, kwargs
+        self.route = StepRoute(fn, (ops.cfg_sa_step_ok, ops.cfg_sa_step),
+                               (ops.cfg_sa_step_patch2d_ok, ops.cfg_sa_step_patch2d))
         self.hist = torch.zeros((2, x.numel()), dtype=torch.float32, device=x.device)
         self.noise = torch.zeros((2,) + tuple(x.shape), dtype=torch.float32, device=x.device)
         self.xp = x.float().contiguous().clone()
         super().__init__(fn, kwargs, x, rows, t_first, model_dtype, warmup)
 
     def _forward(self):
-        return self.fn(self.xm, self.t, self.text, **self.kwargs)
+        return self.route.forward(lambda **pm: self.fn(self.xm, self.t, self.text, **self.kwargs, **pm), self.x)
 
     def _step(self, eps):
-        from . import ops
-        if not ops.cfg_sa_step_ok(eps, self.x):
+        if not self.route.ok(eps, self.x):
             self._refuse_output("vq_cfg_sa_step")
-        ops.cfg_sa_step(eps, self.x, self.xp, self.hist, self.noise, self.rows, 0, step=self.step, x_out=self.x,
+        self.route.step(eps, self.x, self.xp, self.hist, self.noise, self.rows, 0, step=self.step, x_out=self.x,
                         xp_out=self.xp, x_model=self.xm)
 
     @torch.no_grad()

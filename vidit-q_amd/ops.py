@@ -1076,10 +1076,11 @@ def _step_ok(eps, x, elem_mult) -> bool:
             and x.data_ptr() % (4 * V) == 0)
 
 
-def _step_front(eps, x, aux, aux_name, coef, elem_mult, layout, refuse, step, x_out, x_model):
-    """What both step wrappers do before their launch: GPU tensors, fp32 x / ``aux`` (hist or noise) / coef, fp16 / fp32
-    eps, the geometry (else the solver's ``layout`` message), the solver's own clause ``refuse`` = (bad, message), the
-    counter, x_out (allocated when None) and x_model.  Returns (n, C, inner, ld_eps, x_out, xm_f16)."""
+def _step_front(eps, x, aux, aux_name, coef, elem_mult, layout, refuse, step, x_out, x_model, geometry=None):
+    """What the step wrappers do before their launch: GPU tensors, fp32 x / ``aux`` (hist or noise) / coef, fp16 / fp32
+    eps, the geometry (``geometry``, by default _step_geometry; else the solver's ``layout`` message), the solver's own
+    clause ``refuse`` = (bad, message), the counter, x_out (allocated when None) and x_model.  Returns (*geometry, x_out,
+    xm_f16): (n, C, inner, ld_eps, x_out, xm_f16) by default."""
     for t, name in ((eps, "eps"), (x, "x"), (aux, aux_name), (coef, "coef")):
         _req_gpu(t, name)
     _req(x, torch.float32, "x")
@@ -1087,7 +1088,7 @@ def _step_front(eps, x, aux, aux_name, coef, elem_mult, layout, refuse, step, x_
     _req(coef, torch.float32, "coef")
     if eps.dtype not in (torch.float16, torch.float32):
         raise VQError("eps must be float16 or float32, got %s" % eps.dtype)
-    geo = _step_geometry(eps, x, elem_mult)
+    geo = (geometry or _step_geometry)(eps, x, elem_mult)
     if geo is None:
         raise VQError("eps must be %s for x [n, C, ...], dense within a batch element" % layout)
     if refuse[0]:
@@ -1324,5 +1325,8 @@ def cfg_sa_step(eps: torch.Tensor, x: torch.Tensor, xp: torch.Tensor, hist: torc
 # --------------------------------------------------------------------------- key / value compression (PixArt-Sigma)
 # vq_kv_compress's wrapper and its route predicate, defined in ops_kv.py on this module's operand checks
 from .ops_kv import kv_compress, kv_compress_ok  # noqa: E402,F401
+# the three t2i steps on the patch-major model output (vq_cfg_*_step_patch2d), defined in ops_patch2d.py on _step_front
+from .ops_patch2d import (cfg_ddpm_step_patch2d, cfg_ddpm_step_patch2d_ok, cfg_dpmpp_step_patch2d,  # noqa: E402,F401
+                          cfg_dpmpp_step_patch2d_ok, cfg_sa_step_patch2d, cfg_sa_step_patch2d_ok)
 from .ops_batch import (gelu_rowquant_batch, ln_modulate_rowquant_batch, rowquant_batch,  # noqa: E402,F401
                         rowquant_batch_ok)

@@ -417,8 +417,10 @@ class DPMSolverPP(GuidedModel):
         (None, eps) when the first model output is not one the kernel takes (ops.cfg_dpmpp_step_ok): the caller goes on
         eagerly from it."""
         from .. import ops
-        from .fused_loop import device_table, fused_loop
+        from .fused_loop import StepRoute, device_table, fused_loop
         n, steps, order = x.shape[0], args[0], args[1]
+        route = StepRoute(self.model, (ops.cfg_dpmpp_step_ok, ops.cfg_dpmpp_step),
+                          (ops.cfg_dpmpp_step_patch2d_ok, ops.cfg_dpmpp_step_patch2d))
         x = x.float().contiguous() if x.dtype != torch.float32 or not x.is_contiguous() else x
         xm = torch.cat([x, x]).to(self.model_input_dtype)
         hist = torch.empty((3, x.numel()), dtype=torch.float32, device=x.device)
@@ -426,19 +428,20 @@ class DPMSolverPP(GuidedModel):
         t = torch.full((2 * n,), self._t_val(ts[0]), dtype=torch.float32, device=x.device)
 
         def table(eps, x):
-            if not ops.cfg_dpmpp_step_ok(eps, x):
+            if not route.ok(eps, x):
                 return None
             return device_table(self._tables, (args, self.cfg_scale, str(x.device), n),
                                 lambda: self.multistep_rows(*args), x.device, n)
 
         def step(k, eps, x, rows):
             # a fresh x_out per step: what a step_callback was handed is never written again
-            x = ops.cfg_dpmpp_step(eps, x, hist, rows, k, x_model=xm)
+            x = route.step(eps, x, hist, rows, k, x_model=xm)
             if step_callback is not None and k + 1 >= order:
                 step_callback(k + 1, x)
             return x
 
-        return fused_loop(steps, x, xm, t, lambda xm, t: self.model(xm, t, text, **self.model_kwargs), table, step)
+        return fused_loop(steps, x, xm, t, lambda xm, t: route.forward(
+            lambda **kw: self.model(xm, t, text, **self.model_kwargs, **kw), x), table, step)
 
     def step_graph(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type="time_uniform", lower_order_final=True,
                    solver_type="dpmsolver"):

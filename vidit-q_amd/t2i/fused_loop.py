@@ -3,6 +3,40 @@ SASolver._pec_fused): the
 device coefficient table and the loop that puts one fused launch behind each model call."""
 from __future__ import annotations
 
+import inspect
+
+from ..t2v.iddpm import takes_patch_major
+from .dpm_solver import _switch
+
+# DESIGN 8 item 10c: the fused loops and their step graphs run forward(patch_major=True) + the patch2d step (opt-in)
+_T2I_PATCH_MAJOR = _switch("VQ_T2I_PATCH_MAJOR", False)
+
+
+class StepRoute:
+    """Which step a fused loop, or its step graph, puts behind the model callable ``fn``: ``ok`` / ``step`` are the dense
+    pair (ops.cfg_*_step_ok, ops.cfg_*_step), and ``forward`` calls the model as before - unless VQ_T2I_PATCH_MAJOR=1 and
+    ``fn`` is a bound method that takes ``patch_major`` of a net whose forward does (a PixArt net's forward_with_dpmsolver
+    or forward): then the model is called with ``patch_major=True`` and the pair is the patch2d one, which has the
+    dense pair's signatures."""
+
+    def __init__(self, fn, dense, patch2d):
+        self._dense = dense
+        self.kw, (self.ok, self.step) = {}, dense
+        net = getattr(fn, "__self__", None)
+        if _T2I_PATCH_MAJOR and net is not None and takes_patch_major(net) \
+                and "patch_major" in inspect.signature(fn).parameters:
+            self.kw, (self.ok, self.step) = {"patch_major": True}, patch2d
+
+    def forward(self, call, x):
+        """The model output ``call(**kw)`` for the latent ``x``.  A patch-major output is shown to the patch2d predicate:
+        one it refuses puts the route back on the dense step for good, and that forward is made again, densely."""
+        eps = call(**self.kw)
+        if self.kw and not self.ok(eps, x):
+            self.kw, (self.ok, self.step) = {}, self._dense
+            eps = call()
+        return eps
+
+
 
 def device_table(cache: dict, key, build_rows, dev, n):
     """(coefficient table, its T_NEXT column - the model-input time of the forward that follows each row - as

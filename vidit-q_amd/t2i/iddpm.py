@@ -235,8 +235,10 @@ class SpacedDiffusion:
         """The loop with one launch behind each model call (fused_loop).  Returns (x, None), or (None, model output) when
         the first model output is not one the kernel takes (ops.cfg_ddpm_step_ok): the caller goes on eagerly from it."""
         from .. import ops
-        from .fused_loop import device_table, fused_loop
+        from .fused_loop import StepRoute, device_table, fused_loop
         n = img.shape[0] // 2
+        route = StepRoute(net.forward, (ops.cfg_ddpm_step_ok, ops.cfg_ddpm_step),
+                          (ops.cfg_ddpm_step_patch2d_ok, ops.cfg_ddpm_step_patch2d))
         y, cfg_scale, mask, kw = self._split_kwargs(model_kwargs)
         x = img[:n].contiguous()
         xm = torch.cat([x, x]).to(self.model_input_dtype)
@@ -245,7 +247,7 @@ class SpacedDiffusion:
         t = torch.full((2 * n,), float(self.timestep_map[-1]), dtype=torch.float32, device=x.device)
 
         def table(eps, x):
-            if not ops.cfg_ddpm_step_ok(eps, x):
+            if not route.ok(eps, x):
                 return None
             return device_table(self._tables, (float(cfg_scale), bool(clip_denoised), str(x.device), n),
                                 lambda: self.step_rows(cfg_scale, clip_denoised), x.device, n)
@@ -256,12 +258,13 @@ class SpacedDiffusion:
                 img.shape, generator=generator, device=x.device, dtype=torch.float32)
             x0 = torch.empty_like(x) if step_callback is not None else None
             # a fresh x_out per step: what a step_callback was handed is never written again
-            x = ops.cfg_ddpm_step(eps, x, z[:n], rows, k, x0_out=x0, x_model=xm, guided=GUIDED)
+            x = route.step(eps, x, z[:n], rows, k, x0_out=x0, x_model=xm, guided=GUIDED)
             if step_callback is not None:
                 step_callback(self.num_timesteps - 1 - k, x, x0)
             return x
 
-        return fused_loop(self.num_timesteps, x, xm, t, lambda xm, t: net.forward(xm, t, y, mask, **kw), table, step)
+        return fused_loop(self.num_timesteps, x, xm, t, lambda xm, t: route.forward(
+            lambda **pm: net.forward(xm, t, y, mask, **kw, **pm), x), table, step)
 
     def p_sample_graph(self, model, noise, clip_denoised=True, model_kwargs=None):
         """The counter form of the fused loop: {forward, fused step, counter advance} captured once as a HIP graph and

@@ -395,10 +395,14 @@ class _PixArtBase(nn.Module):
                 x = block(x, y, t0, y_lens, HW=(self.h, self.w))
         return x
 
-    def forward_with_cfg(self, x, timestep, y, cfg_scale, mask=None, **kwargs):
-        """PixArt.py:183-196: one batched (cond | uncond) forward, guidance on the first three channels."""
+    def forward_with_cfg(self, x, timestep, y, cfg_scale, mask=None, patch_major=False, **kwargs):
+        """PixArt.py:183-196: one batched (cond | uncond) forward, guidance on the first three channels.  ``patch_major``:
+        final_layer's (cond | uncond) output as ``forward(patch_major=True)`` leaves it, unguided - the guidance is the step
+        kernel's (ops.cfg_ddpm_step_patch2d)."""
         half = x[: len(x) // 2]
         combined = torch.cat([half, half], dim=0)
+        if patch_major:
+            return self.forward(combined, timestep, y, mask, patch_major=True, **kwargs)
         return self.guide_cfg(self.forward(combined, timestep, y, mask, **kwargs), cfg_scale)
 
     @staticmethod
@@ -433,8 +437,9 @@ class PixArt(_PixArtBase):
                                      pe_interpolation=self.pe_interpolation, base_size=self.base_size)
         self.pos_embed.data.copy_(torch.from_numpy(pe).float().unsqueeze(0))      # PixArt.py:224-229
 
-    def forward(self, x, timestep, y, mask=None, data_info=None, **kwargs):
-        """PixArt.py:143-173."""
+    def forward(self, x, timestep, y, mask=None, data_info=None, patch_major=False, **kwargs):
+        """PixArt.py:143-173.  ``patch_major``: return final_layer's output [B, h*w, p*p*out_channels] as it is, in the
+        model's dtype (``unpatchify`` of it is the default result); ``self.h`` / ``self.w`` are set either way."""
         x = x.to(self.dtype)
         timestep = timestep.to(self.dtype)
         y = y.to(self.dtype)
@@ -449,10 +454,14 @@ class PixArt(_PixArtBase):
         y, y_lens = self._select(y, mask, C)
         x = self._run_blocks(x, y, t0, y_lens)
         x = self.final_layer(x, t)
-        return self.unpatchify(x)
+        return x if patch_major else self.unpatchify(x)
 
-    def forward_with_dpmsolver(self, x, timestep, y, mask=None, **kwargs):
-        """PixArt.py:175-181: DPM-Solver needs no variance prediction."""
+    def forward_with_dpmsolver(self, x, timestep, y, mask=None, patch_major=False, **kwargs):
+        """PixArt.py:175-181: DPM-Solver needs no variance prediction.  ``patch_major``: final_layer's whole output as
+        ``forward(patch_major=True)`` leaves it - the step kernels (ops.cfg_dpmpp_step_patch2d, ops.cfg_sa_step_patch2d)
+        read the first C channels of a patch position."""
+        if patch_major:
+            return self.forward(x, timestep, y, mask, patch_major=True)
         return self.forward(x, timestep, y, mask).chunk(2, dim=1)[0]
 
     def unpatchify(self, x):
@@ -497,8 +506,8 @@ class PixArtMS(_PixArtBase):
             self._pe_cache[key] = pe
         return pe
 
-    def forward(self, x, timestep, y, mask=None, data_info=None, **kwargs):
-        """PixArtMS.py:165-211."""
+    def forward(self, x, timestep, y, mask=None, data_info=None, patch_major=False, **kwargs):
+        """PixArtMS.py:165-211.  ``patch_major``: as PixArt.forward."""
         bs = x.shape[0]
         x = x.to(self.dtype)
         timestep = timestep.to(self.dtype)
@@ -517,10 +526,12 @@ class PixArtMS(_PixArtBase):
         y, y_lens = self._select(y, mask, C)
         x = self._run_blocks(x, y, t0, y_lens)
         x = self.final_layer(x, t)
-        return self.unpatchify(x)
+        return x if patch_major else self.unpatchify(x)
 
-    def forward_with_dpmsolver(self, x, timestep, y, data_info=None, **kwargs):
-        """PixArtMS.py:213-218: DPM-Solver needs no variance prediction."""
+    def forward_with_dpmsolver(self, x, timestep, y, data_info=None, patch_major=False, **kwargs):
+        """PixArtMS.py:213-218: DPM-Solver needs no variance prediction.  ``patch_major``: as PixArt.forward_with_dpmsolver."""
+        if patch_major:
+            return self.forward(x, timestep, y, data_info=data_info, patch_major=True, **kwargs)
         return self.forward(x, timestep, y, data_info=data_info, **kwargs).chunk(2, dim=1)[0]
 
     def unpatchify(self, x):

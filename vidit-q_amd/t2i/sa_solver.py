@@ -357,8 +357,10 @@ class SASolver(GuidedModel):
         intermediates, None), or (None, None, eps) when the first model output is not one the kernel takes
         (ops.cfg_sa_step_ok): the caller goes on eagerly from it."""
         from .. import ops
-        from .fused_loop import device_table, fused_loop
+        from .fused_loop import StepRoute, device_table, fused_loop
         n, steps = x.shape[0], args[0]
+        route = StepRoute(self.model, (ops.cfg_sa_step_ok, ops.cfg_sa_step),
+                          (ops.cfg_sa_step_patch2d_ok, ops.cfg_sa_step_patch2d))
         x = x.float().contiguous() if x.dtype != torch.float32 or not x.is_contiguous() else x
         xm = torch.cat([x, x]).to(self.model_input_dtype)
         hist = torch.empty((2, x.numel()), dtype=torch.float32, device=x.device)
@@ -372,7 +374,7 @@ class SASolver(GuidedModel):
         state = dict(xp=x, mid=[x])
 
         def table(eps, x):
-            if not ops.cfg_sa_step_ok(eps, x):
+            if not route.ok(eps, x):
                 return None
             return device_table(self._tables, (args, taus, self.cfg_scale, str(x.device), n),
                                 lambda: self.pec_rows(tau, *args), x.device, n)
@@ -381,14 +383,15 @@ class SASolver(GuidedModel):
             # the draw of loop step k + 1, from the eager route's RNG stream, into the slot the predictor reads
             self._draw(x, noise_steps, generator, k + 1, out=ring[(k + 1) % 2])
             # a fresh x_out where the intermediates are kept: what was handed out is never written again
-            x, state["xp"] = ops.cfg_sa_step(eps, x, state["xp"], hist, ring, rows, k,
-                                             x_out=None if return_intermediate or k == 0 else x,
-                                             xp_out=None if k == 0 else state["xp"], x_model=xm)
+            x, state["xp"] = route.step(eps, x, state["xp"], hist, ring, rows, k,
+                                        x_out=None if return_intermediate or k == 0 else x,
+                                        xp_out=None if k == 0 else state["xp"], x_model=xm)
             if k > 0:
                 state["mid"].append(x)
             return x
 
-        x_c, eps0 = fused_loop(steps, x, xm, t, lambda xm, t: self.model(xm, t, text, **self.model_kwargs), table, step)
+        x_c, eps0 = fused_loop(steps, x, xm, t, lambda xm, t: route.forward(
+            lambda **kw: self.model(xm, t, text, **self.model_kwargs, **kw), x), table, step)
         if x_c is None:
             return None, None, eps0
         return state["xp"], state["mid"] + [state["xp"]], None
