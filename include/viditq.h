@@ -836,6 +836,25 @@ int vq_cfg_sa_step_patch2d(const void* eps, const float* x, const float* xp, flo
 int vq_linear_f16(const void* x, const void* w, const void* bias, void* out, int M, int N, int K, long ldx, long ldw,
                   long ldo, int act_in, int act_out, void* stream);
 
+/* ---- T2IFinalLayer in one launch: LayerNorm + modulate + Linear (csrc/final_layer.hip) ----------------------------
+ * Replaces T2IFinalLayer.forward (t2v/opensora/models/layers/blocks.py:393-397: norm_final, t2i_modulate, linear) with the
+ * t2i_modulate expression x * (1 + scale) + shift (blocks.py:51-52) - today vq_ln_modulate_rowquant taken for its fp16
+ * by-product followed by vq_linear_f16 - without the codes, the row terms and the round trip of the modulated activation:
+ *   out[r, n] = fp16( sum_k xm[r, k] * w[n, k] + bias[n] ),
+ *   xm[r, k]  = fp16( ((x[r, k] - mu_r) * rstd_r) * (1 + scale[b, k]) + shift[b, k] ),  b = r / rows_per_sample.
+ * x [M, C] fp16, row pitch ldx; shift, scale [M / rows_per_sample, C] fp32, dense, as vq_adaln_table writes them; w
+ * [N_out, C] fp16, row pitch ldw; bias [N_out] fp16 or NULL; out [M, N_out] fp16, dense (the patch-major buffer the step
+ * kernels read).  Rounding points: the LayerNorm (no affine) is two-pass in fp32 - mean, then the centred sum of squares,
+ * rstd = 1 / sqrt(var + ln_eps) correctly rounded; 1 + scale, the product and the sum with shift in fp32; xm rounded to
+ * fp16 ONCE, where the two-launch route rounds it; fp32 accumulation (MFMA) of fp16 products, bias added in fp32, one
+ * rounding to fp16.  Refusals, in this order, before any HIP call or dereference:
+ *   1. VQ_EINVAL: x, shift, scale, w or out null;  2. VQ_EINVAL: M, rows_per_sample, C, N_out, ldx or ldw not positive;
+ *   3. VQ_EINVAL: M % rows_per_sample != 0;  4. VQ_ESHAPE: C % 32 != 0, C > 1536, N_out % 16 != 0 or N_out > 64;
+ *   5. VQ_ESHAPE: ldx % 8, ldw % 8, ldx < C or ldw < C;  6. VQ_ESHAPE: x, shift, scale, w, out or a non-null bias not
+ *   16-byte aligned. */
+int vq_final_layer_f16(const void* x, const float* shift, const float* scale, float ln_eps, const void* w, const void* bias,
+                       void* out, int M, int rows_per_sample, int C, int N_out, long ldx, long ldw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,10 +71,9 @@ def get_2d_sincos_pos_embed(embed_dim, grid_size, scale=1.0, base_size=None):
 
 
 # --------------------------------------------------------------------------- small modules
-def fp_edge_linear(layer, x, act_in=0, act_out=0):
-    """One of the Linears the FP lists keep in floating point (embedders, t_block, final layer: SURVEY 8 row F4), through
-    the HIP kernel vq_linear_f16 with its neighbouring activation fused - when it is a Linear in FP state on fp16 GPU
-    tensors; returns None otherwise (quantized by a non-default FP list, CPU, fp32: the caller takes the module path)."""
+def fp_edge_operands(layer, x):
+    """(weight, bias) of ``layer`` when fp_edge_linear serves it on ``x`` - a Linear in FP state on fp16 GPU tensors that
+    nothing observes - else None (quantized by a non-default FP list, CPU, fp32, autograd, hooks, a full-size problem)."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float16):
         return None
     if isinstance(layer, nn.Linear):
@@ -106,7 +105,17 @@ def fp_edge_linear(layer, x, act_in=0, act_out=0):
     M = x.numel() // x.shape[-1]
     if not (M <= 640 or w.shape[0] <= 64 or w.shape[1] <= 32):
         return None
-    return ops.linear_f16(x.contiguous(), w.detach(), None if b is None else b.detach(), act_in=act_in, act_out=act_out)
+    return w.detach(), None if b is None else b.detach()
+
+
+def fp_edge_linear(layer, x, act_in=0, act_out=0):
+    """One of the Linears the FP lists keep in floating point (embedders, t_block, final layer: SURVEY 8 row F4), through
+    the HIP kernel vq_linear_f16 with its neighbouring activation fused - when it is a Linear in FP state on fp16 GPU
+    tensors; returns None otherwise (fp_edge_operands: the caller takes the module path)."""
+    wb = fp_edge_operands(layer, x)
+    if wb is None:
+        return None
+    return ops.linear_f16(x.contiguous(), wb[0], wb[1], act_in=act_in, act_out=act_out)
 
 
 class Mlp(nn.Module):
@@ -228,6 +237,15 @@ class T2IFinalLayer(nn.Module):
             # LayerNorm + modulate in ONE pass of the fused kernel (its modulated fp16 output; the quantized codes it
             # also produces are not used here) instead of a LayerNorm and two broadcast elementwise launches
             mod = ops.adaln_table(self.scale_shift_table.detach(), torch.cat([t, t], dim=1).to(torch.float16).contiguous())
+            if _FINAL_FUSED:
+                # LayerNorm + modulate + Linear in ONE launch (csrc/final_layer.hip) when the Linear is one
+                # fp_edge_linear serves and the entry point takes the shape; anything else keeps the two launches below
+                wb = fp_edge_operands(self.linear, x)
+                xc = x.contiguous()
+                if wb is not None and wb[0].stride(1) == 1 and ops.final_layer_f16_ok(
+                        xc.shape[0] * xc.shape[1], xc.shape[1], xc.shape[2], wb[0].shape[0], xc.shape[2], wb[0].stride(0)) \
+                        and not any(v is not None and v.data_ptr() % 16 for v in (xc, wb[0], wb[1])):
+                    return ops.final_layer_f16(xc, mod[0], mod[1], 1e-6, wb[0], wb[1])
             _, xm = ops.ln_modulate_rowquant(x.contiguous(), mod[0], mod[1], 1e-6, want_xm=True)
             o = fp_edge_linear(self.linear, xm)                              # FP under the t2v list; quantized in t2i
             return o if o is not None else self.linear(xm)
@@ -350,6 +368,7 @@ _ATTN_QUANT = _switch("VQ_ATTN_QUANT", True)
 _GELU_QUANT = _switch("VQ_GELU_QUANT", True)                          # GELU inside fc2's quantizer pass
 _STATIC_FUSED = True                                                  # one-pass quantizers of static grids (no variable)
 _ATTN_QUANT_JOINT = _switch("VQ_ATTN_QUANT_JOINT", False)             # the same for B = 2 and 2..7 bits
+_FINAL_FUSED = _switch("VQ_FINAL_FUSED", False)                       # final_layer's LayerNorm + modulate + Linear in one launch
 _SMOOTH_JOINT = _switch("VQ_SMOOTH_JOINT", False)                     # a joint forward's smoothed q | k | v codes in one pass
 _STATIC_ATTN_QUANT = _switch("VQ_STATIC_ATTN_QUANT", False)           # temporal attention + proj's static quantizer
 _STATIC_FWD_ATTN_QUANT = _switch("VQ_STATIC_FWD_ATTN_QUANT", False)   # spatial / cross attention + proj's static quantizer
