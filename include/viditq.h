@@ -855,6 +855,28 @@ int vq_linear_f16(const void* x, const void* w, const void* bias, void* out, int
 int vq_final_layer_f16(const void* x, const float* shift, const float* scale, float ln_eps, const void* w, const void* bias,
                        void* out, int M, int rows_per_sample, int C, int N_out, long ldx, long ldw, void* stream);
 
+/* ---- patch embedding in one launch: gather + Linear + position-embedding add (csrc/patch_embed.hip) ----------------
+ * Replaces PatchEmbed3D.forward (t2v/opensora/models/layers/blocks.py:66-105: Conv3d with kernel == stride, flatten,
+ * transpose) and PixArt's PatchEmbed (t2i/diffusion/model/nets/PixArtMS.py / timm PatchEmbed: Conv2d, flatten, transpose)
+ * together with the "+ pos_embed" line of the three forwards (stdit.py STDiT.forward, PixArt.py PixArt.forward,
+ * PixArtMS.py PixArtMS.forward) - today a permuted copy of the latent, its cast, vq_linear_f16 and a torch add.  For token
+ * n = (t, i, j) of sample b, row-major over (D / pt, H / ph, W / pw), and channel c:
+ *   a[b, n, c]   = fp16( sum_k fp16(x[b, ci, t pt + dt, i ph + dh, j pw + dw]) * w[c, k] + bias[c] ),
+ *                  k = ((ci pt + dt) ph + dh) pw + dw              (the flatten order of the Conv weight)
+ *   out[b, n, c] = pos ? fp16( float(a) + float(pos[n % pos_rows, c]) ) : a.
+ * x [B, Cin, D, H, W] dense, fp16 (x_f32 = 0) or fp32 (x_f32 = 1; rounded to fp16 as it is loaded); a 2-D latent is D = pt
+ * = 1.  w [C, K] fp16, row pitch ldw; bias [C] fp16 or NULL; pos [pos_rows, C] fp16, dense, or NULL (STDiT: its [S, C]
+ * spatial table, PixArt: its [N, C] table); out [B N, C] fp16, dense.  Rounding points: fp32 accumulation (one
+ * v_mfma_f32_16x16x32_f16 per 16 x 16 tile, k >= K zero-filled: the placement of vq_linear_f16 with K <= 32), bias added in
+ * fp32, ONE rounding to fp16 (a); then the fp32 sum of the two fp16 values a and pos, rounded once - torch's fp16 add.
+ * Refusals, in this order, before any HIP call or dereference:
+ *   1. VQ_EINVAL: x, w or out null;  2. VQ_EINVAL: B, Cin, D, H, W, pt, ph, pw, C or ldw not positive, or pos given with
+ *   pos_rows not positive;  3. VQ_ESHAPE: D % pt, H % ph or W % pw != 0; K = Cin pt ph pw with K % 8 != 0 or K > 32;
+ *   C % 16 != 0 or C > 1536; pos given with N % pos_rows != 0; B Cin D H W >= 2^31;  4. VQ_ESHAPE: ldw % 8 != 0 or ldw < K;
+ *   5. VQ_ESHAPE: x, w, out, a non-null bias or a non-null pos not 16-byte aligned;  6. VQ_EUNSUP: x_f32 not 0 or 1. */
+int vq_patch_embed_f16(const void* x, int x_f32, const void* w, const void* bias, const void* pos, void* out, int B, int Cin,
+                       int D, int H, int W, int pt, int ph, int pw, int C, int pos_rows, long ldw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1332,3 +1332,5 @@ from .ops_batch import (gelu_rowquant_batch, ln_modulate_rowquant_batch, rowquan
                         rowquant_batch_ok)
 # vq_final_layer_f16's wrapper and its route predicate, defined in ops_final.py on this module's operand checks
 from .ops_final import final_layer_f16, final_layer_f16_ok  # noqa: E402,F401
+# vq_patch_embed_f16's wrapper and its route predicate, defined in ops_patch_embed.py on this module's operand checks
+from .ops_patch_embed import patch_embed_f16, patch_embed_f16_ok  # noqa: E402,F401

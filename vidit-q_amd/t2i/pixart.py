@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..qdiff.models.quant_block import QuantAttention
 from ..qdiff.models.quant_layer import QuantLayer
-from ..t2v.stdit import (CaptionEmbedder, Mlp, fp_edge_linear, MultiHeadCrossAttention, T2IFinalLayer, TimestepEmbedder,
+from ..t2v.stdit import (CaptionEmbedder, Mlp, fp_edge_linear, patch_embed_fused, MultiHeadCrossAttention, T2IFinalLayer, TimestepEmbedder,
                          approx_gelu, attn_proj_stage, cross_stage, fused_rules, fwd_attn_quantized_static,
                          get_1d_sincos_pos_embed_from_grid, ln_quant, mlp_stage, prompt_kv_exact_fill, seq_offsets, t2i_modulate,
                          takes_fused, _switch)
@@ -440,12 +440,12 @@ class PixArt(_PixArtBase):
     def forward(self, x, timestep, y, mask=None, data_info=None, patch_major=False, **kwargs):
         """PixArt.py:143-173.  ``patch_major``: return final_layer's output [B, h*w, p*p*out_channels] as it is, in the
         model's dtype (``unpatchify`` of it is the default result); ``self.h`` / ``self.w`` are set either way."""
-        x = x.to(self.dtype)
         timestep = timestep.to(self.dtype)
         y = y.to(self.dtype)
         C = self.hidden_size
         self.h, self.w = x.shape[-2] // self.patch_size, x.shape[-1] // self.patch_size
-        x = self.x_embedder(x) + self.pos_embed.to(self.dtype)
+        xe = patch_embed_fused(self.x_embedder, x, self.pos_embed, self.dtype)           # one launch (DESIGN 8 item 10e) or None
+        x = self.x_embedder(x.to(self.dtype)) + self.pos_embed.to(self.dtype) if xe is None else xe
         t = self.t_embedder(timestep, dtype=x.dtype)
         t0 = fp_edge_linear(self.t_block[1], t, act_in=ops.ACT_SILU)        # SiLU, Linear in one launch (FP edge kernel)
         if t0 is None:
@@ -509,12 +509,12 @@ class PixArtMS(_PixArtBase):
     def forward(self, x, timestep, y, mask=None, data_info=None, patch_major=False, **kwargs):
         """PixArtMS.py:165-211.  ``patch_major``: as PixArt.forward."""
         bs = x.shape[0]
-        x = x.to(self.dtype)
         timestep = timestep.to(self.dtype)
         y = y.to(self.dtype)
         C = self.hidden_size
         self.h, self.w = x.shape[-2] // self.patch_size, x.shape[-1] // self.patch_size
-        x = self.x_embedder(x) + self._pos_embed(x.device, self.dtype)
+        xe = patch_embed_fused(self.x_embedder, x, self._pos_embed(x.device, self.dtype), self.dtype)
+        x = self.x_embedder(x.to(self.dtype)) + self._pos_embed(x.device, self.dtype) if xe is None else xe
         t = self.t_embedder(timestep, dtype=x.dtype)
         if self.micro_conditioning:
             c_size, ar = data_info["img_hw"].to(self.dtype), data_info["aspect_ratio"].to(self.dtype)

@@ -71,6 +71,22 @@ def get_2d_sincos_pos_embed(embed_dim, grid_size, scale=1.0, base_size=None):
 
 
 # --------------------------------------------------------------------------- small modules
+def unobserved(layer, x, w, b):
+    """Whether a forward-only kernel may stand in for ``layer(x)`` (operands w, b): it by-passes the module's __call__, so
+    anything autograd or a hook would observe keeps the module path (round-4 advisor finding: the graph was silently cut
+    and forward hooks skipped)."""
+    if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad)):
+        return False
+    if getattr(layer, "_forward_hooks", None) or getattr(layer, "_forward_pre_hooks", None) or getattr(
+            layer, "_backward_hooks", None) or getattr(layer, "_backward_pre_hooks", None):
+        return False
+    # hooks registered for EVERY module (torch.nn.modules.module.register_module_forward_hook and friends: calibration /
+    # observer tooling) see the module path only - round-5 advisor
+    gm = torch.nn.modules.module
+    return not (getattr(gm, "_global_forward_hooks", None) or getattr(gm, "_global_forward_pre_hooks", None) or getattr(
+        gm, "_global_backward_hooks", None) or getattr(gm, "_global_backward_pre_hooks", None))
+
+
 def fp_edge_operands(layer, x):
     """(weight, bias) of ``layer`` when fp_edge_linear serves it on ``x`` - a Linear in FP state on fp16 GPU tensors that
     nothing observes - else None (quantized by a non-default FP list, CPU, fp32, autograd, hooks, a full-size problem)."""
@@ -86,18 +102,7 @@ def fp_edge_operands(layer, x):
         w, b = layer.org_weight, layer.org_bias
     if w.dtype != torch.float16 or w.numel() == 0 or w.shape[1] % 8 or w.shape[0] % 4 or (b is not None and b.dtype != torch.float16):
         return None
-    # the kernel is forward-only and by-passes the module's __call__: anything autograd or a hook would observe keeps the
-    # module path (round-4 advisor finding: the graph was silently cut and forward hooks skipped)
-    if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad)):
-        return None
-    if getattr(layer, "_forward_hooks", None) or getattr(layer, "_forward_pre_hooks", None) or getattr(
-            layer, "_backward_hooks", None) or getattr(layer, "_backward_pre_hooks", None):
-        return None
-    # hooks registered for EVERY module (torch.nn.modules.module.register_module_forward_hook and friends: calibration /
-    # observer tooling) see the module path only - round-5 advisor
-    gm = torch.nn.modules.module
-    if getattr(gm, "_global_forward_hooks", None) or getattr(gm, "_global_forward_pre_hooks", None) or getattr(
-            gm, "_global_backward_hooks", None) or getattr(gm, "_global_backward_pre_hooks", None):
+    if not unobserved(layer, x, w, b):
         return None
     # the edge kernel is built for SKINNY problems (one 16 x 16 output tile per workgroup, no operand reuse): few rows, few
     # columns or a short contraction.  A full-size FP Linear (16384 x 4608 x 1152: the block MLP of an FP calibration
@@ -116,6 +121,40 @@ def fp_edge_linear(layer, x, act_in=0, act_out=0):
     if wb is None:
         return None
     return ops.linear_f16(x.contiguous(), wb[0], wb[1], act_in=act_in, act_out=act_out)
+
+
+def patch_embed_fused(embedder, x, pos, dtype):
+    """``embedder(x.to(dtype)) + pos`` of STDiT.forward, PixArt.forward and PixArtMS.forward as ONE HIP
+    launch (ops.patch_embed_f16: gather + Linear + position add, bit for bit today's launches) - under VQ_PATCH_EMBED_FUSED,
+    for a dense fp32 / fp16 GPU latent that needs no padding, ``embedder.proj`` in FP state with fp16 operands that
+    nothing observes, ``pos`` [1, H/ph * W/pw, C] in the model's dtype and a shape the entry point takes.  None otherwise:
+    the caller runs its own lines."""
+    if not _PATCH_EMBED_FUSED or dtype != torch.float16:
+        return None
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in (torch.float16, torch.float32) and x.is_contiguous()):
+        return None
+    proj, patch = embedder.proj, tuple(embedder.patch_size)
+    if x.dim() != len(patch) + 2 or getattr(proj, "weight_quant", False) or getattr(proj, "act_quant", False) or getattr(
+            proj, "smooth_quant", False):
+        return None
+    w = getattr(proj, "org_weight", None)
+    w = proj.weight if w is None else w
+    b = getattr(proj, "org_bias", None) if hasattr(proj, "org_weight") else proj.bias
+    if w.dtype != torch.float16 or not w.is_contiguous() or (b is not None and (b.dtype != torch.float16 or not b.is_contiguous())):
+        return None
+    if not (unobserved(proj, x, w, b) and unobserved(embedder, x, w, b)):
+        return None
+    Cc = w.shape[0]
+    patch3, (D, H, W) = (1,) * (3 - len(patch)) + patch, (1,) * (5 - x.dim()) + tuple(x.shape[2:])
+    if not ops.patch_embed_f16_ok(x.shape[0], x.shape[1], D, H, W, patch3, Cc, pos.numel() // Cc, w[0].numel()):
+        return None
+    if not (pos.is_cuda and pos.dtype == dtype and pos.is_contiguous() and not pos.requires_grad and pos.shape[-1] == Cc and
+            pos.numel() == (H // patch3[1]) * (W // patch3[2]) * Cc):
+        return None
+    w2, b = w.detach().reshape(Cc, -1), None if b is None else b.detach()
+    if any(v is not None and v.data_ptr() % 16 for v in (x, w2, b, pos)):
+        return None
+    return ops.patch_embed_f16(x, w2, b, pos, patch3)
 
 
 class Mlp(nn.Module):
@@ -369,6 +408,7 @@ _GELU_QUANT = _switch("VQ_GELU_QUANT", True)
 _STATIC_FUSED = True                                                  # one-pass quantizers of static grids (no variable)
 _ATTN_QUANT_JOINT = _switch("VQ_ATTN_QUANT_JOINT", False)             # the same for B = 2 and 2..7 bits
 _FINAL_FUSED = _switch("VQ_FINAL_FUSED", False)                       # final_layer's LayerNorm + modulate + Linear in one launch
+_PATCH_EMBED_FUSED = _switch("VQ_PATCH_EMBED_FUSED", False)           # patch gather + Linear + position add in one launch
 _SMOOTH_JOINT = _switch("VQ_SMOOTH_JOINT", False)                     # a joint forward's smoothed q | k | v codes in one pass
 _STATIC_ATTN_QUANT = _switch("VQ_STATIC_ATTN_QUANT", False)           # temporal attention + proj's static quantizer
 _STATIC_FWD_ATTN_QUANT = _switch("VQ_STATIC_FWD_ATTN_QUANT", False)   # spatial / cross attention + proj's static quantizer
@@ -1050,13 +1090,16 @@ class STDiT(nn.Module):
     def forward(self, x, timestep, y, mask=None, patch_major=False):
         """``patch_major``: return final_layer's output [B, N_t*N_h*N_w, p_t*p_h*p_w*out_channels] as it is, in the model's
         dtype (no unpatchify copy, no cast): what ops.cfg_dpmpp_step_patch reads."""
-        x = x.to(self.dtype)
         timestep = timestep.to(self.dtype)
         C = self.hidden_size
-        x = self.x_embedder(x)
         B = x.shape[0]
-        x = x.reshape(B, self.num_temporal, self.num_spatial, C) + self.pos_embed
-        x = x.reshape(B, self.num_patches, C).contiguous()
+        xe = patch_embed_fused(self.x_embedder, x, self.pos_embed, self.dtype)
+        if xe is None:
+            x = self.x_embedder(x.to(self.dtype))
+            x = x.reshape(B, self.num_temporal, self.num_spatial, C) + self.pos_embed
+            x = x.reshape(B, self.num_patches, C).contiguous()
+        else:
+            x = xe
         t = self.t_embedder(timestep, dtype=x.dtype)
         t0 = fp_edge_linear(self.t_block[1], t, act_in=ops.ACT_SILU)        # SiLU, Linear in one launch
         if t0 is None:
