@@ -855,6 +855,31 @@ int vq_linear_f16(const void* x, const void* w, const void* bias, void* out, int
 int vq_final_layer_f16(const void* x, const float* shift, const float* scale, float ln_eps, const void* w, const void* bias,
                        void* out, int M, int rows_per_sample, int C, int N_out, long ldx, long ldw, void* stream);
 
+/* ---- T2IFinalLayer with a quantized Linear in one launch (csrc/final_layer_i8.hip) ---------------------------------
+ * LayerNorm + modulate as vq_final_layer_f16, then the Linear's DYNAMIC per-token quantizer and the int8 Linear on a
+ * PackedWeight (vq_pack_weight) - today vq_ln_modulate_rowquant taken for its fp16 by-product, vq_rowquant and vq_gemm_i8.
+ * Per row r, sample b = r / rows_per_sample, token n = r % rows_per_sample, B = M / rows_per_sample:
+ *   xm[r, k] = fp16( ((x[r, k] - mu_r) * rstd_r) * (1 + scale[b, k]) + shift[b, k] )   (the rounding points above),
+ *   q[r, k]  = xm[r, k] / s[k]: RN(1 / s) given in s_rcp -> the reciprocal form of vq_rowquant's smooth arm, s alone -> the
+ *              correctly rounded division, s null -> xm itself,
+ *   (delta, zp) of token n: min-max grid of n_bits over the channels of q of ALL B samples of the token (min clamped to
+ *              <= 0, max to >= 0; delta < 1e-6 raises VQ_ST_EPSFILL in *status), codes = clamp(rint(q / delta) + zp),
+ *   out[r, j] = fp16( sx sw[j] (acc - zw[j] R - zx cs[j]) + bias[j] ) with acc the int32 sum of code x weight products and
+ *              sx, zx, R the row terms a QAct carries (never written; nor are the codes or xm).
+ * x [M, C] fp16, row pitch ldx; shift, scale [B, C] fp32; s, s_rcp [C] fp32 or NULL; wq [N_out, Kp] int8 (w_bits > 4) or
+ * [N_out, Kp / 2] nibbles, sw, zw, cs [N_out]; bias [N_out] fp32 or NULL; out [M, N_out] fp16, dense; status one int32 or
+ * NULL.  The int32 sums are exact, so out does not depend on how the launch splits a row.  Served: C % 32 == 0, C <= 1536,
+ * Kp == C rounded up to 128, N_out % 16 == 0, N_out <= 64, B in {1, 2, 4, 8, 16}, n_bits and w_bits 2 .. 8.  Refusals, in
+ * this order, before any HIP call or dereference:
+ *   1. VQ_EINVAL: x, shift, scale, wq, sw, zw, cs or out null, or s_rcp without s;  2. VQ_EINVAL: M, rows_per_sample, C,
+ *   Kp, N_out or ldx not positive;  3. VQ_EINVAL: M % rows_per_sample != 0;  4. VQ_ESHAPE: the shapes served, B included;
+ *   5. VQ_ESHAPE: ldx % 8 or ldx < C;  6. VQ_EUNSUP: n_bits or w_bits outside 2 .. 8;  7. VQ_ESHAPE: a non-null pointer
+ *   not 16-byte aligned. */
+int vq_final_layer_i8(const void* x, const float* shift, const float* scale, float ln_eps, const float* s, const float* s_rcp,
+                      const void* wq, const float* sw, const int* zw, const int* cs, const float* bias, void* out,
+                      int* status, int M, int rows_per_sample, int C, int Kp, int N_out, long ldx, int n_bits, int w_bits,
+                      void* stream);
+
 /* ---- patch embedding in one launch: gather + Linear + position-embedding add (csrc/patch_embed.hip) ----------------
  * Replaces PatchEmbed3D.forward (t2v/opensora/models/layers/blocks.py:66-105: Conv3d with kernel == stride, flatten,
  * transpose) and PixArt's PatchEmbed (t2i/diffusion/model/nets/PixArtMS.py / timm PatchEmbed: Conv2d, flatten, transpose)

@@ -11,6 +11,10 @@ modulation vectors once.
 
     python tools/final_layer_time.py [--alternate 3] [--out profiles/final_layer/times.json]
 
+--i8: the quantized arm instead - the one launch of ops.final_layer_i8 against the three it replaces
+(ops.ln_modulate_rowquant for xm, ops.rowquant, ops.gemm_i8) at M = B x rows in {1024, 4096, 8192, 16384}, C 1152 -> 32,
+for the joint forward B = 2, 8-bit and 4-bit weights, measured the same way.
+
 Exit status 1 when the one launch is slower than the pair at any shape in any alternation (the flip criterion of
 DESIGN.md section 8).
 """
@@ -28,18 +32,25 @@ from static_quant_time import graph_time  # noqa: E402
 from viditq_amd import ops  # noqa: E402
 
 SHAPES = [(16384, 1152, 32), (32768, 1152, 32), (4096, 1152, 32), (1024, 1152, 32)]
+SHAPES_I8 = [(1024, 1152, 32), (4096, 1152, 32), (8192, 1152, 32), (16384, 1152, 32)]
 
 
-def one(dev, M, C, N, alternate):
+def rotating(dev, B, M, C):
+    """x(): the next of enough [B, M / B, C] token matrices that no launch finds its rows in L2 / MALL"""
     n_buf = max(2, min(12, (1 << 30) // (M * C * 2)))
-    bufs = [(torch.randn(1, M, C, device=dev) * 1.5 + 0.3).half() for _ in range(n_buf)]
-    shift, scale = [torch.randn(1, C, device=dev) * 0.3 for _ in range(2)]
-    w, b = (torch.randn(N, C, device=dev) / C ** 0.5).half(), (torch.randn(N, device=dev) * 0.1).half()
+    bufs = [(torch.randn(B, M // B, C, device=dev) * 1.5 + 0.3).half() for _ in range(n_buf)]
     i = [0]
 
     def x():
         i[0] = (i[0] + 1) % n_buf
         return bufs[i[0]]
+    return x
+
+
+def one(dev, M, C, N, alternate):
+    x = rotating(dev, 1, M, C)
+    shift, scale = [torch.randn(1, C, device=dev) * 0.3 for _ in range(2)]
+    w, b = (torch.randn(N, C, device=dev) / C ** 0.5).half(), (torch.randn(N, device=dev) * 0.1).half()
 
     def old():
         return ops.linear_f16(ops.ln_modulate_rowquant(x(), shift, scale, 1e-6, want_xm=True)[1], w, b)
@@ -49,8 +60,31 @@ def one(dev, M, C, N, alternate):
     def new():
         return ops.final_layer_f16(x(), shift, scale, 1e-6, w, b)
 
-    n = 8
     mb = (M * C * 2 + M * N * 2 + N * C * 2 + 2 * C * 4) / 1e6
+    return alternations("M %5d, C %d, N_out %d" % (M, C, N), mb, old, new, alternate)
+
+
+def one_i8(dev, M, C, N, w_bits, alternate, B=2):
+    x = rotating(dev, B, M, C)
+    shift, scale = [torch.randn(B, C, device=dev) * 0.3 for _ in range(2)]
+    w, b = (torch.randn(N, C, device=dev) / C ** 0.5).half(), torch.randn(N, device=dev) * 0.1
+    pw = ops.pack_weight(w, *ops.weight_minmax(w, w_bits), w_bits)
+
+    def old():
+        xm = ops.ln_modulate_rowquant(x(), shift, scale, 1e-6, want_xm=True)[1]
+        return ops.gemm_i8(ops.rowquant(xm, n_bits=8), pw, b)
+
+    assert ops.final_layer_i8_ok(M, M // B, C, pw.Kp, N, C, 8, w_bits)
+
+    def new():
+        return ops.final_layer_i8(x(), shift, scale, 1e-6, pw, b)
+
+    mb = (M * C * 2 + M * N * 2 + pw.wq.numel() + 2 * B * C * 4) / 1e6
+    return alternations("M %5d, C %d, N_out %d, B %d, W%d" % (M, C, N, B, w_bits), mb, old, new, alternate)
+
+
+def alternations(name, mb, old, new, alternate):
+    n = 8
     keep = [graph_time(old, n=n)[1], graph_time(new, n=n)[1]]                # warm-up of both routes
     t_old, t_new = [], []
     for _ in range(alternate):
@@ -59,8 +93,7 @@ def one(dev, M, C, N, alternate):
     del keep
     ba, bb = min(t_old), min(t_new)
     ok = all(tn <= to for to, tn in zip(t_old, t_new))
-    name = "M %5d, C %d, N_out %d" % (M, C, N)
-    print("%-26s pair %s -> best %.1f us | one launch %s -> best %.1f us (%.2f TB/s of %.1f MB) | %s" % (
+    print("%-34s parent launches %s -> best %.1f us | one launch %s -> best %.1f us (%.2f TB/s of %.1f MB) | %s" % (
         name, ["%.1f" % t for t in t_old], ba, ["%.1f" % t for t in t_new], bb, mb / bb, mb, "not slower" if ok else "SLOWER"),
         flush=True)
     return dict(shape=name, MB=round(mb, 1), pair_us=[round(t, 1) for t in t_old], fused_us=[round(t, 1) for t in t_new],
@@ -78,6 +111,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--alternate", type=int, default=3)
+    ap.add_argument("--i8", action="store_true", help="the quantized arm: ops.final_layer_i8 against its three launches")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("final_layer_time.py needs a GPU: a CPU run gives no time")
@@ -92,8 +126,9 @@ def main():
     rec = dict(device=torch.cuda.get_device_name(0), clock_mhz=_read(torch.cuda.clock_rate), power_mw=_read(torch.cuda.power_draw),
                copy_us=round(copy_us, 1), copy_TBps=round(copy_tbs, 2), shapes=[])
     with torch.no_grad():
-        for M, C, N in SHAPES:
-            rec["shapes"].append(one(dev, M, C, N, args.alternate))
+        runs = [(one_i8, (M, C, N, wb)) for wb in (8, 4) for M, C, N in SHAPES_I8] if args.i8 else [(one, s) for s in SHAPES]
+        for fn, shape in runs:
+            rec["shapes"].append(fn(dev, *shape, args.alternate))
             if args.out:
                 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
                 with open(args.out, "w") as f:

@@ -60,6 +60,7 @@ SIGNATURES = {
     "vq_adaln_table": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "vq_linear_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _i, _vp]),
     "vq_final_layer_f16": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp]),
+    "vq_final_layer_i8": (_i, [_vp, _vp, _vp, _f] + [_vp] * 9 + [_i] * 5 + [_l, _i, _i, _vp]),
     "vq_patch_embed_f16": (_i, [_vp, _i, _vp, _vp, _vp, _vp] + [_i] * 10 + [_l, _vp]),
     "vq_cfg_ddim_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
     "vq_cfg_dpmpp_step": (_i, [_vp] * 7 + [_i, _i, _i, _l, _i, _i, _i, _i, _vp]),

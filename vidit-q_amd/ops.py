@@ -1330,7 +1330,9 @@ from .ops_patch2d import (cfg_ddpm_step_patch2d, cfg_ddpm_step_patch2d_ok, cfg_d
                           cfg_dpmpp_step_patch2d_ok, cfg_sa_step_patch2d, cfg_sa_step_patch2d_ok)
 from .ops_batch import (gelu_rowquant_batch, ln_modulate_rowquant_batch, rowquant_batch,  # noqa: E402,F401
                         rowquant_batch_ok)
-# vq_final_layer_f16's wrapper and its route predicate, defined in ops_final.py on this module's operand checks
-from .ops_final import final_layer_f16, final_layer_f16_ok  # noqa: E402,F401
+# the wrappers of vq_final_layer_f16 / vq_final_layer_i8 and their route predicates, defined in ops_final.py on this
+# module's operand checks
+from .ops_final import (final_layer_f16, final_layer_f16_ok, final_layer_i8,  # noqa: E402,F401
+                        final_layer_i8_ok)
 # vq_patch_embed_f16's wrapper and its route predicate, defined in ops_patch_embed.py on this module's operand checks
 from .ops_patch_embed import patch_embed_f16, patch_embed_f16_ok  # noqa: E402,F401

@@ -113,6 +113,31 @@ def fp_edge_operands(layer, x):
     return w.detach(), None if b is None else b.detach()
 
 
+def final_quant_operands(layer, x):
+    """(packed weight, fp32 bias, smoothing vector, n_bits) of ``layer`` when ops.final_layer_i8 serves it behind
+    final_layer's LayerNorm + modulate of ``x`` [B, n_tok, C] fp16 (contiguous, on the GPU) - a QuantLayer on the integer
+    route with a dynamic per-token activation quantizer, no running statistic, a smoothing vector (if any) that does not
+    depend on the live input, nothing observing it, and a launch the entry point takes - else None."""
+    if not (isinstance(layer, QuantLayer) and type(layer).forward is QuantLayer.forward and
+            type(layer)._token_view is QuantLayer._token_view):
+        return None                                          # (a subclass with a forward or a token view of its own)
+    if not (layer.int_route_ok() and isinstance(layer.act_quantizer, DynamicActQuantizer)):
+        return None
+    if getattr(layer, "smooth_quant_running_stat", False) or getattr(layer, "channel_wise_scale_type", None) == "dynamic":
+        return None
+    if not unobserved(layer, x, layer.weight, layer.bias):
+        return None
+    r, alpha = layer._range_and_alpha()
+    s = layer.smooth_vector(r, alpha)
+    pw, bias, n_bits = layer.packed_weight(r, s), layer.bias_f32(), layer.act_quantizer.n_bits
+    if pw.K != x.shape[2] or not ops.final_layer_i8_ok(x.shape[0] * x.shape[1], x.shape[1], pw.K, pw.Kp, pw.N, x.shape[2],
+                                                       n_bits, pw.n_bits):
+        return None
+    if any(v is not None and v.data_ptr() % 16 for v in (x, s, bias, layer.status, *pw.tensors())):
+        return None
+    return pw, bias, s, n_bits
+
+
 def fp_edge_linear(layer, x, act_in=0, act_out=0):
     """One of the Linears the FP lists keep in floating point (embedders, t_block, final layer: SURVEY 8 row F4), through
     the HIP kernel vq_linear_f16 with its neighbouring activation fused - when it is a Linear in FP state on fp16 GPU
@@ -285,6 +310,14 @@ class T2IFinalLayer(nn.Module):
                         xc.shape[0] * xc.shape[1], xc.shape[1], xc.shape[2], wb[0].shape[0], xc.shape[2], wb[0].stride(0)) \
                         and not any(v is not None and v.data_ptr() % 16 for v in (xc, wb[0], wb[1])):
                     return ops.final_layer_f16(xc, mod[0], mod[1], 1e-6, wb[0], wb[1])
+            if _FINAL_QUANT_FUSED:
+                # the same for a QUANTIZED Linear (PixArt's plans): quantizer and int8 Linear in the launch too
+                # (csrc/final_layer_i8.hip); anything final_quant_operands does not serve keeps the three launches below
+                xc, layer = x.contiguous(), self.linear
+                q = final_quant_operands(layer, xc)
+                if q is not None:
+                    o = ops.final_layer_i8(xc, mod[0], mod[1], 1e-6, q[0], q[1], q[2], q[3], layer.status)
+                    return layer.activation_function(o)      # (x is fp16: QuantLayer.forward's cast is the identity)
             _, xm = ops.ln_modulate_rowquant(x.contiguous(), mod[0], mod[1], 1e-6, want_xm=True)
             o = fp_edge_linear(self.linear, xm)                              # FP under the t2v list; quantized in t2i
             return o if o is not None else self.linear(xm)
@@ -408,7 +441,8 @@ _GELU_QUANT = _switch("VQ_GELU_QUANT", True)
 _STATIC_FUSED = True                                                  # one-pass quantizers of static grids (no variable)
 _ATTN_QUANT_JOINT = _switch("VQ_ATTN_QUANT_JOINT", False)             # the same for B = 2 and 2..7 bits
 _FINAL_FUSED = _switch("VQ_FINAL_FUSED", False)                       # final_layer's LayerNorm + modulate + Linear in one launch
-_PATCH_EMBED_FUSED = _switch("VQ_PATCH_EMBED_FUSED", False)           # patch gather + Linear + position add in one launch
+_FINAL_QUANT_FUSED = _switch("VQ_FINAL_QUANT_FUSED", False)           # the same with a quantized Linear: + quantizer + int8 Linear
+_PATCH_EMBED_FUSED = _switch("VQ_PATCH_EMBED_FUSED", False)          # patch gather + Linear + position add in one launch
 _SMOOTH_JOINT = _switch("VQ_SMOOTH_JOINT", False)                     # a joint forward's smoothed q | k | v codes in one pass
 _STATIC_ATTN_QUANT = _switch("VQ_STATIC_ATTN_QUANT", False)           # temporal attention + proj's static quantizer
 _STATIC_FWD_ATTN_QUANT = _switch("VQ_STATIC_FWD_ATTN_QUANT", False)   # spatial / cross attention + proj's static quantizer
